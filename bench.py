@@ -30,7 +30,14 @@ ranks sharing whatever GPUs are visible (rank -> device rank % device_count):
 a functional dry run of the N > 1 path on a 1-GPU box, not a scaling number
 (`config.dry_run`).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+Prints ONE JSON line (rank 0). A plain run (`--gpus N --steps K --warmup W`)
+sets up, warms up, times the K steps and prints the contract fields (metric,
+value, unit, ms_per_step, ...) and a small `config`; before it,
+`--dump-outputs DIR` writes the grid the timed steps built (dump_outputs).
+With `--full` the line also holds
+  cold_pass_frames_per_s, drop_in
+                one pass over the stream into an empty grid; the reference's
+                call shapes (two calls or one call per frame, host-fed batch).
   roofline      dominant kernel (FrameStepKernel): SURVEY 8(d) algorithmic
                 bytes / HIP-event kernel time (`frac`), counter-measured fabric
                 bytes / the same time (`frac_hbm`: FETCH_SIZE x2 + WRITE_SIZE,
@@ -99,6 +106,12 @@ def valu_fractions(insts, simd_cycles):
     return per * VALU_CYCLES_PER_INST, [per * VALU_FULL, per * VALU_HALF]
 N_XCD = 8
 KERNEL = "FrameStepKernel"
+METRIC = ("RGB-D frames/s, TSDF integrate with known poses (configs[1]: touch "
+          "+ activate + integrate into an 8 mm / 16^3 VoxelBlockGrid); the ICP "
+          "+ integrate + ray-cast loop (configs[2]) is in loop_frames_per_s "
+          "(its first tracked frame untimed as warm-up; the whole run in "
+          "loop_frames_per_s_with_first_frame)")
+DUMP_BLOCKS = 384         # blocks of the grid written by --dump-outputs
 
 
 def parse():
@@ -186,6 +199,17 @@ def parse():
     ap.add_argument("--no-configs4", action="store_true",
                     help="skip the configs[4] leg (4 mm voxels, > 500 k "
                          "blocks, ICP on 2 x 1 M points)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: cold pass, drop-in "
+                         "call shapes, the other multi-GPU scheme, roofline "
+                         "and live counters, ICP legs, configs[4], CPU "
+                         "baseline, bench_detail.json (the --no-* switches "
+                         "above thin it out). Without it a run sets up, "
+                         "warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the grid they built "
+                         "as DIR/<name>.npy (float32 / float64; see "
+                         "dump_outputs)")
     return ap.parse_args()
 
 
@@ -1041,6 +1065,48 @@ def pin_to_gpu_numa_node(device_index):
         return None
 
 
+# ---------------------------------------------------------------------------
+# --dump-outputs: what the timed path hands its caller
+
+
+def dump_sample(n_blocks, n_sample=DUMP_BLOCKS, seed=0):
+    """Positions, in key order, of the blocks whose voxels are written: a
+    fixed, seeded sample of the active blocks (all of them when few)."""
+    rng = np.random.default_rng(seed)
+    return np.sort(rng.choice(n_blocks, size=min(n_sample, n_blocks),
+                              replace=False))
+
+
+def dump_outputs(g, out_dir):
+    """The grid after the last timed step, as a caller of integrate_frames
+    receives it: `block_keys` = every active block's key (sorted; buffer
+    slots are handed out concurrently, so their order is not stable), and for
+    a seeded sample of DUMP_BLOCKS of those blocks (`sample_block_keys`) each
+    attribute's voxels ({n, 16, 16, 16, channels}, float32; about 31 MB with
+    colour). Returns the names written."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    hm = g.hashmap()
+    buf = hm.active_buf_indices().long()
+    keys = hm.key_tensor()[buf].cpu().numpy().astype(np.int64)
+    order = np.lexsort((keys[:, 2], keys[:, 1], keys[:, 0]))
+    keys, buf = keys[order], buf[torch.from_numpy(order).to(buf.device)]
+    pick = dump_sample(len(keys))
+    idx = buf[torch.from_numpy(pick).to(buf.device)]
+    arrays = {"block_keys": keys.astype(np.float64),
+              "sample_block_keys": keys[pick].astype(np.float64)}
+    for name in g.attr_names:
+        t = g.attribute(name)
+        if t.dtype == torch.uint16:  # gathered through its int16 view
+            t = t.view(torch.int16)[idx].to(torch.int32) & 0xFFFF
+        else:
+            t = t[idx]
+        arrays[name] = t.to(torch.float32).cpu().numpy()
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return sorted(arrays)
+
+
 def main():
     a = parse()
     if a.leg == "configs4-integrate":  # the run rocprofv3 wraps
@@ -1295,6 +1361,31 @@ def main():
     fps = total_frames / elapsed
 
     if a.pmc_inner:  # the run rocprofv3 wraps: nothing else to do
+        return
+    if a.dump_outputs and rank == 0:
+        dump_outputs(g, a.dump_outputs)
+    if not a.full:
+        # a plain run: the headline and nothing else (what follows is --full)
+        if rank == 0:
+            cfg = {"frames_per_step": a.batch, "block_count": a.block_count,
+                   "frames_per_launch": a.frames_per_launch,
+                   "timed_region_s": elapsed, "active_blocks": int(n_blocks),
+                   "merge_ms": merge_ms,
+                   "emulated_ranks_ms_per_step": emu_ranks_ms,
+                   "emulated_rank_of_world": [e_rank, e_world]
+                   if e_world != world else None}
+            line = {"metric": METRIC, "value": fps, "unit": "frames/s",
+                    "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+                    "ms_per_step": elapsed / a.steps * 1e3,
+                    "higher_is_better": True, "scaling": "strong",
+                    "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+                    "config": _r({k: v for k, v in cfg.items()
+                                  if v is not None})}
+            print(json.dumps(line), flush=True)
+        if dist is not None:
+            torch.cuda.synchronize()
+            comm.destroy()
+            dist.destroy_process_group()
         return
 
     # configs[1] taken literally: ONE pass over the 1000 frames into an EMPTY
@@ -1601,12 +1692,7 @@ def main():
                      "exchange inside the timed region: all-to-all of block "
                      "IDs + voxel rows to the owning rank, folded in there")
     out = {
-        "metric": "RGB-D frames/s, TSDF integrate with known poses "
-                  "(configs[1]: touch + activate + integrate into an 8 mm / "
-                  "16^3 VoxelBlockGrid); the ICP + integrate + ray-cast loop "
-                  "(configs[2]) is in loop_frames_per_s (its first tracked "
-                  "frame untimed as warm-up; the whole run in "
-                  "loop_frames_per_s_with_first_frame)",
+        "metric": METRIC,
         "loop_frames_per_s": None,  # filled from the configs[2] legs
         "value": fps, "unit": "frames/s", "n_gpus": world, "steps": a.steps,
         "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,

@@ -73,3 +73,37 @@ def test_driver_line_stays_under_6_kb():
     assert line["configs2"]["640x480"]["gpu_busy_frac"] > 0
     assert line["configs4"]["frames_per_s"] > 0
     assert "per_kernel" not in text and "note" not in line["roofline"]
+
+
+def test_plain_run_is_the_headline_alone_unless_full():
+    """`bench.py --gpus N --steps K --warmup W` times the steps and prints
+    the line; every other leg waits for --full. Outputs are written only when
+    --dump-outputs names a directory."""
+    bench = _bench()
+    import sys
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"]
+        a = bench.parse()
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "out"]
+        b = bench.parse()
+    finally:
+        sys.argv = argv
+    assert a.steps == 7 and a.warmup == 3
+    assert not a.full and a.dump_outputs is None
+    assert b.full and b.dump_outputs == "out"
+
+
+def test_dump_sample_is_fixed_sorted_and_bounded():
+    """The blocks --dump-outputs writes are the same from run to run for the
+    same grid: a seeded sample of at most DUMP_BLOCKS positions in key
+    order, all of them when the grid is smaller."""
+    bench = _bench()
+    import numpy as np
+    s = bench.dump_sample(5745)
+    assert np.array_equal(s, bench.dump_sample(5745))
+    assert len(s) == bench.DUMP_BLOCKS
+    assert np.all(np.diff(s) > 0) and s[0] >= 0 and s[-1] < 5745
+    assert np.array_equal(bench.dump_sample(10), np.arange(10))
+    # tsdf + weight + 3 colour channels of the sample, float32: under 64 MB
+    assert bench.DUMP_BLOCKS * 16 ** 3 * 5 * 4 < 64 << 20

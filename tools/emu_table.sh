@@ -11,7 +11,7 @@ set -u
 TAG=${1:-emu}; WORLDS=${2:-"2 4 8"}; FORMS=${3:-"0 1"}
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 O=gpurun_out/$TAG; mkdir -p "$O"
-B="python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-pmc --no-secondary --no-configs4"
+B="python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-pmc --no-secondary --no-configs4"
 libs="default"
 for d in _ab/*/; do
   n=$(basename "$d"); [ "$n" = r3lib ] && continue

@@ -10,7 +10,7 @@ ROOT=$PWD
 O=$ROOT/gpurun_out/${TAG}_final; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats -d "$O/bench" -o bench -- \
-  python "$ROOT/bench.py" --no-secondary --no-cpu-baseline --no-pmc > "$O/bench.json" 2> "$O/bench.err"
+  python "$ROOT/bench.py" --full --no-secondary --no-cpu-baseline --no-pmc > "$O/bench.json" 2> "$O/bench.err"
 timeout 300 rocprofv3 --kernel-trace --stats -d "$O/icp_slam_vga" -o vga -- \
   "$ROOT/examples/icp_slam" 60 640 480 > "$O/icp_slam_vga.json" 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats -d "$O/icp_slam_720p" -o hd -- \

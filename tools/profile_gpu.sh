@@ -11,7 +11,7 @@ SUM=$ROOT/gpurun_out/profiles_$TAG
 mkdir -p "$OUT" "$SUM"
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python $ROOT/bench.py --no-cpu-baseline $*"
+BENCH="python $ROOT/bench.py --full --no-cpu-baseline $*"
 echo "== kernel trace ==" 
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace -- $BENCH > "$OUT/trace.log" 2>&1
 tail -2 "$OUT/trace.log"

@@ -183,19 +183,50 @@ int main(int argc, char** argv) {
                 model, 3.0f, total, points, normals, colors, &written, stream));
     CHECK_HIP(hipStreamSynchronize(stream));
 
+    // ExtractTriangleMesh: count first (capacity < 0), then fetch; the
+    // triangle buffer holds 3 x the vertex capacity.
+    int64_t n_vertices = 0, n_triangles = 0;
+    CHECK_O3D(o3dmi_slam_model_extract_triangle_mesh(
+            model, 3.0f, -1, nullptr, nullptr, nullptr, nullptr, &n_vertices,
+            &n_triangles, stream));
+    float* mesh_vertices = DeviceAlloc<float>((size_t)n_vertices * 3);
+    float* mesh_normals = DeviceAlloc<float>((size_t)n_vertices * 3);
+    int32_t* mesh_triangles = DeviceAlloc<int32_t>((size_t)n_vertices * 9);
+    if (n_vertices > 0)
+        CHECK_O3D(o3dmi_slam_model_extract_triangle_mesh(
+                model, 3.0f, n_vertices, mesh_vertices, mesh_normals, nullptr,
+                mesh_triangles, &n_vertices, &n_triangles, stream));
+    std::vector<int32_t> tri_host((size_t)n_triangles * 3);
+    if (n_triangles > 0)
+        CHECK_HIP(hipMemcpy(tri_host.data(), mesh_triangles,
+                            tri_host.size() * sizeof(int32_t),
+                            hipMemcpyDeviceToHost));
+    bool mesh_ok = n_vertices > 0 && n_triangles > 0;
+    for (size_t i = 0; i + 2 < tri_host.size(); i += 3) {
+        const int32_t a = tri_host[i], b = tri_host[i + 1], c = tri_host[i + 2];
+        mesh_ok = mesh_ok && a >= 0 && b >= 0 && c >= 0 && a < n_vertices &&
+                  b < n_vertices && c < n_vertices && a != b && b != c &&
+                  a != c;
+    }
+
     std::printf(
             "{\"example\": \"dense_slam.cpp\", \"frames\": %d, \"width\": %d, "
             "\"height\": %d, \"frames_per_s\": %.1f, \"odometry_iterations\": %d, "
             "\"max_translation_error_m\": %.3g, \"max_rotation_error_rad\": %.3g, "
-            "\"frustum_blocks\": %lld, \"surface_points\": %lld}\n",
+            "\"frustum_blocks\": %lld, \"surface_points\": %lld, "
+            "\"mesh_vertices\": %lld, \"mesh_triangles\": %lld}\n",
             n_frames, cam.width, cam.height, n_frames / seconds, iterations,
             worst_translation, worst_angle,
             (long long)o3dmi_slam_model_frustum_block_count(model),
-            (long long)written);
+            (long long)written, (long long)n_vertices,
+            (long long)n_triangles);
 
     (void)hipFree(points);
     (void)hipFree(normals);
     (void)hipFree(colors);
+    (void)hipFree(mesh_vertices);
+    (void)hipFree(mesh_normals);
+    (void)hipFree(mesh_triangles);
     (void)hipFree(raycast_depth);
     (void)hipFree(raycast_color);
     CHECK_O3D(o3dmi_slam_model_destroy(model));
@@ -206,7 +237,7 @@ int main(int argc, char** argv) {
     (void)hipStreamDestroy(stream);
 
     const bool ok = worst_translation < 0.08 && worst_angle < 0.01745 &&
-                    written > 1000 && total == written;
+                    written > 1000 && total == written && mesh_ok;
     if (!ok) std::fprintf(stderr, "dense_slam: self-check FAILED\n");
     return ok ? 0 : 1;
 }

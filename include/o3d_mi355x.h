@@ -349,6 +349,28 @@ int o3dmi_vbg_extract_points(o3dmi_hash_t* block_hash,
                              float* normals_dev, float* colors_dev,
                              int64_t capacity, int64_t* total_out,
                              o3dmi_stream_t stream);
+/* ExtractTriangleMeshCUDA<tsdf_t, weight_t, color_t> (t/geometry/kernel/
+ * VoxelBlockGridImpl.h:1383-1783): marching cubes over the active blocks
+ * indices_dev[0..n_blocks), which must be ASCENDING and hold every block of
+ * the grid; same grid arguments as o3dmi_vbg_extract_points. Outputs:
+ * vertices / normals / colours {n,3} float32 (colors_dev may be NULL) and
+ * triangles {m,3} int32, each triangle's right-hand normal towards tsdf > 0.
+ * vertex_capacity < 0 only counts; otherwise the triangle capacity is
+ * 3 x vertex_capacity, and when either is too small (or the vertex count
+ * exceeds INT32_MAX) nothing is written and O3DMI_ERR_CAPACITY is returned.
+ * Order: vertices by (position in indices_dev, voxel, axis), triangles by
+ * (position, voxel, table order) -- deterministic. *n_vertices_out /
+ * *n_triangles_out = the mesh's counts (synchronises). Block resolution
+ * <= 32. */
+int o3dmi_vbg_extract_mesh(o3dmi_hash_t* block_hash, const int32_t* indices_dev,
+                           int64_t n_blocks, const float* tsdf_dev,
+                           const void* weight_dev, const void* color_dev,
+                           int grid_dtype, int resolution, float voxel_size,
+                           float weight_threshold, float* vertices_dev,
+                           float* normals_dev, float* colors_dev,
+                           int32_t* triangles_dev, int64_t vertex_capacity,
+                           int64_t* n_vertices_out, int64_t* n_triangles_out,
+                           o3dmi_stream_t stream);
 /* Ascending in-place sort of int32 indices (synchronises). */
 int o3dmi_sort_indices(int32_t* indices_dev, int64_t n, o3dmi_stream_t stream);
 

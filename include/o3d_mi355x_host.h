@@ -685,6 +685,23 @@ int o3dmi_vbg_extract_point_cloud(o3dmi_vbg_t* g, float weight_threshold,
                                   float* normals_dev, float* colors_dev,
                                   int64_t* total_out, o3dmi_stream_t stream);
 
+/* ExtractTriangleMesh (VoxelBlockGrid.cpp:436-471): marching cubes over
+ * every active block. vertex_capacity < 0 counts only (the reference's 2-pass
+ * mode); otherwise vertices / normals / colours hold vertex_capacity x 3
+ * floats and triangles 3 x vertex_capacity x 3 int32, and O3DMI_ERR_CAPACITY
+ * (nothing written) reports too small a capacity or more than INT32_MAX
+ * vertices. colors_dev may be NULL; colours are written when the grid has a
+ * "color" attribute. *n_vertices_out / *n_triangles_out = the mesh's counts
+ * (synchronises). Order: active blocks by ascending buffer index, then voxel,
+ * then axis (vertices) or table order (triangles). */
+int o3dmi_vbg_extract_triangle_mesh(o3dmi_vbg_t* g, float weight_threshold,
+                                    int64_t vertex_capacity,
+                                    float* vertices_dev, float* normals_dev,
+                                    float* colors_dev, int32_t* triangles_dev,
+                                    int64_t* n_vertices_out,
+                                    int64_t* n_triangles_out,
+                                    o3dmi_stream_t stream);
+
 /* ------------------------------------------------------------------------ */
 /* slam::Model (t/pipelines/slam/Model.h:24-137, Model.cpp:23-118)           */
 /* ------------------------------------------------------------------------ */
@@ -748,6 +765,13 @@ int o3dmi_slam_model_extract_point_cloud(o3dmi_slam_model_t* m,
                                          float* normals_dev, float* colors_dev,
                                          int64_t* total_out,
                                          o3dmi_stream_t stream);
+
+/* ExtractTriangleMesh (Model.cpp:113-116). */
+int o3dmi_slam_model_extract_triangle_mesh(
+        o3dmi_slam_model_t* m, float weight_threshold, int64_t vertex_capacity,
+        float* vertices_dev, float* normals_dev, float* colors_dev,
+        int32_t* triangles_dev, int64_t* n_vertices_out,
+        int64_t* n_triangles_out, o3dmi_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* NPZ interchange (t/io/NumpyIO.cpp) and VoxelBlockGrid::Save / Load        */

@@ -106,6 +106,9 @@ PROTOTYPES = {
     "o3dmi_vbg_extract_points": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i32,
                                         _i32, _f, _f, _vp, _vp, _vp, _i64,
                                         C.POINTER(_i64), _vp]),
+    "o3dmi_vbg_extract_mesh": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i32,
+                                      _i32, _f, _f, _vp, _vp, _vp, _vp, _i64,
+                                      C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "o3dmi_sort_indices": (_i32, [_vp, _i64, _vp]),
     "o3dmi_image_clip_transform": (_i32, [_vp, _i32, _i32, _i32, _f, _f, _f,
                                           _f, _vp, _vp]),
@@ -271,6 +274,9 @@ PROTOTYPES.update({
         [_f, _f, _f, _f, _f, _i32, _vp]),
     "o3dmi_vbg_extract_point_cloud": (_i32, [_vp, _f, _i64, _vp, _vp, _vp,
                                              C.POINTER(_i64), _vp]),
+    "o3dmi_vbg_extract_triangle_mesh": (_i32, [_vp, _f, _i64, _vp, _vp, _vp,
+                                               _vp, C.POINTER(_i64),
+                                               C.POINTER(_i64), _vp]),
     "o3dmi_slam_model_create": (_i32, [_f, _i32, _i64, _dp, _vp,
                                        C.POINTER(_vp)]),
     "o3dmi_slam_model_destroy": (_i32, [_vp]),
@@ -291,6 +297,9 @@ PROTOTYPES.update({
     "o3dmi_slam_model_extract_point_cloud": (_i32, [_vp, _f, _i64, _vp, _vp,
                                                     _vp, C.POINTER(_i64),
                                                     _vp]),
+    "o3dmi_slam_model_extract_triangle_mesh": (
+        _i32, [_vp, _f, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i64),
+               C.POINTER(_i64), _vp]),
     "o3dmi_npz_create": (_i32, [C.POINTER(_vp)]),
     "o3dmi_npz_destroy": (_i32, [_vp]),
     "o3dmi_npz_add": (_i32, [_vp, C.c_char_p, _i32, _i32, C.POINTER(_i64),

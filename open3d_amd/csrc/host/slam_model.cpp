@@ -224,4 +224,16 @@ int o3dmi_slam_model_extract_point_cloud(o3dmi_slam_model_t* m,
                                          total_out, stream);
 }
 
+int o3dmi_slam_model_extract_triangle_mesh(
+        o3dmi_slam_model_t* m, float weight_threshold, int64_t vertex_capacity,
+        float* vertices_dev, float* normals_dev, float* colors_dev,
+        int32_t* triangles_dev, int64_t* n_vertices_out,
+        int64_t* n_triangles_out, o3dmi_stream_t stream) {
+    O3DMI_REQUIRE(m != nullptr, "model is null");
+    return o3dmi_vbg_extract_triangle_mesh(
+            m->grid, weight_threshold, vertex_capacity, vertices_dev,
+            normals_dev, colors_dev, triangles_dev, n_vertices_out,
+            n_triangles_out, stream);
+}
+
 }  // extern "C"

@@ -2727,6 +2727,51 @@ int o3dmi_vbg_extract_point_cloud(o3dmi_vbg_t* g, float weight_threshold,
     return st;
 }
 
+int o3dmi_vbg_extract_triangle_mesh(o3dmi_vbg_t* g, float weight_threshold,
+                                    int64_t vertex_capacity,
+                                    float* vertices_dev, float* normals_dev,
+                                    float* colors_dev, int32_t* triangles_dev,
+                                    int64_t* n_vertices_out,
+                                    int64_t* n_triangles_out,
+                                    o3dmi_stream_t stream) {
+    O3DMI_REQUIRE(g && n_vertices_out && n_triangles_out, "null argument");
+    int ti = g->AttrIndex("tsdf"), wi = g->AttrIndex("weight"),
+        ci = g->AttrIndex("color");
+    if (ti < 0 || wi < 0) {
+        SetLastError(
+                "TSDF and/or weight not allocated in blocks, please implement "
+                "customized integration.");
+        return O3DMI_ERR_INVALID_ARG;
+    }
+    int grid_dtype;
+    int st = GridDtype(g, &grid_dtype);
+    if (st) return st;
+    // GetActiveIndices, sorted: the output order is a function of the grid
+    // state only, and the kernel finds a neighbour's position by bisection.
+    int32_t* active = nullptr;
+    const int64_t cap = o3dmi_hash_capacity(g->block_hashmap);
+    if ((st = PoolAlloc((void**)&active, sizeof(int32_t) * (size_t)cap)))
+        return st;
+    int64_t n = 0;
+    st = o3dmi_hash_active_indices(g->block_hashmap, active, stream, &n);
+    if (!st) st = o3dmi_sort_indices(active, n, stream);
+    if (!st)
+        st = o3dmi_vbg_extract_mesh(
+                g->block_hashmap, active, n,
+                (const float*)o3dmi_hash_value_buffer(g->block_hashmap, ti),
+                o3dmi_hash_value_buffer(g->block_hashmap, wi),
+                ci >= 0 ? o3dmi_hash_value_buffer(g->block_hashmap, ci)
+                        : nullptr,
+                grid_dtype, (int)g->block_resolution, g->voxel_size,
+                weight_threshold, vertices_dev, normals_dev,
+                ci >= 0 ? colors_dev : nullptr, triangles_dev, vertex_capacity,
+                n_vertices_out, n_triangles_out, stream);
+    // extract_mesh synchronised the stream (or failed before launching).
+    (void)hipStreamSynchronize((hipStream_t)stream);
+    PoolFree(active);
+    return st;
+}
+
 // SURVEY 8(e)(B), the payload step: every active block goes to the rank that
 // OWNS it (OwnerOf, the rule of the block-ownership scheme); the owner folds
 // the partial blocks of all ranks into one. Afterwards the grids of the ranks

@@ -87,6 +87,30 @@ def _extract(call, has_color, weight_threshold, estimated_point_number):
     return out
 
 
+def _extract_mesh(call, has_color, weight_threshold, estimated_vertex_number):
+    nv, nt = C.c_int64(0), C.c_int64(0)
+    cap = int(estimated_vertex_number)
+    if cap < 0:
+        _lib.check(call(C.c_float(weight_threshold), C.c_int64(-1), None, None,
+                        None, None, C.byref(nv), C.byref(nt), stream()),
+                   "extract_triangle_mesh")
+        cap = int(nv.value)
+    pos = torch.empty((cap, 3), dtype=torch.float32, device="cuda")
+    nrm = torch.empty((cap, 3), dtype=torch.float32, device="cuda")
+    col = torch.empty((cap, 3), dtype=torch.float32, device="cuda") \
+        if has_color else None
+    tri = torch.empty((3 * cap, 3), dtype=torch.int32, device="cuda")
+    _lib.check(call(C.c_float(weight_threshold), C.c_int64(cap), _lib.ptr(pos),
+                    _lib.ptr(nrm), _lib.ptr(col), _lib.ptr(tri), C.byref(nv),
+                    C.byref(nt), stream()), "extract_triangle_mesh")
+    n, m = int(nv.value), int(nt.value)
+    out = {"positions": pos[:n], "normals": nrm[:n]}
+    if col is not None:
+        out["colors"] = col[:n]
+    out["indices"] = tri[:m]
+    return out
+
+
 class FrameBatch:
     """Prepared arguments of VoxelBlockGrid.integrate_frames (prepare_frames)."""
     pass
@@ -552,6 +576,20 @@ class VoxelBlockGrid:
         return _extract(lambda *a: _lib.lib().o3dmi_vbg_extract_point_cloud(
             self._g, *a), "color" in self.attr_names, weight_threshold,
             estimated_point_number)
+
+    def extract_triangle_mesh(self, weight_threshold=3.0,
+                              estimated_vertex_number=-1):
+        """ExtractTriangleMesh (VoxelBlockGrid.cpp:436-471) -> dict(positions,
+        normals[, colors], indices) of device tensors: {N,3} float32 vertex
+        attributes (mesh.vertex.*) and {M,3} int32 triangles
+        (mesh.triangle.indices). A negative estimate runs the counting pass
+        first (the reference's 2-pass mode); otherwise the estimate caps the
+        vertices (and 3x it the triangles), a mesh that does not fit raises,
+        and only the rows written are returned."""
+        return _extract_mesh(
+            lambda *a: _lib.lib().o3dmi_vbg_extract_triangle_mesh(self._g, *a),
+            "color" in self.attr_names, weight_threshold,
+            estimated_vertex_number)
 
     def profile_begin(self, max_frames, stride=1):
         _lib.check(_lib.lib().o3dmi_vbg_profile_begin(

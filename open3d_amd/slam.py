@@ -181,3 +181,8 @@ class Model:
         return geometry._extract(
             lambda *a: _lib.lib().o3dmi_slam_model_extract_point_cloud(
                 self._m, *a), True, weight_threshold, estimated_number)
+
+    def extract_trianglemesh(self, weight_threshold=3.0, estimated_number=-1):
+        return geometry._extract_mesh(
+            lambda *a: _lib.lib().o3dmi_slam_model_extract_triangle_mesh(
+                self._m, *a), True, weight_threshold, estimated_number)

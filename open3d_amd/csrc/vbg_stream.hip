@@ -915,6 +915,17 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
         const int64_t block_base = (int64_t)block_idx * res3;
         if (!kLong && part == 0 && threadIdx.x == 0 && ip.prof_frame_blocks)
             frame_blocks += __popc(bits);
+        if constexpr (!kLong) {
+            // The group's items get the kLong form's issue priority by frame
+            // count as well (+1.1 % frames/s, profiles/r7_README.md): with
+            // the rounds' gathers overlapped, the many-frame items' VALU work
+            // is what the launch's tail waits for.
+            const int n_set = __popc(bits);
+            if (n_set >= 3 * ip.n_frames / 4) __builtin_amdgcn_s_setprio(3);
+            else if (n_set >= ip.n_frames / 2) __builtin_amdgcn_s_setprio(2);
+            else if (n_set >= ip.n_frames / 4) __builtin_amdgcn_s_setprio(1);
+            else __builtin_amdgcn_s_setprio(0);
+        }
         int opaque = 0;  // a zero the optimiser cannot see through
         asm volatile("" : "+s"(opaque));
 
@@ -1008,6 +1019,8 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
             // kRaw: upper half of the 8 colour bytes, bit offset of the pixel
             unsigned chi[kRaw && kColor ? kChunk : 1][kV];
             unsigned csh[kRaw && kColor ? kChunk : 1][kV];
+            // kRaw: the raw uint16 depth
+            uint16_t dr[kRaw ? kChunk : 1][kV];
             unsigned in_mask;  // kRaw: voxel projects into the image
             unsigned cbits;    // frames of the round that touch the block
         };
@@ -1114,9 +1127,8 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
                                    : 0u;
                         R.in_mask |= (in ? 1u : 0u) << (fk * kV + 2 * p + h);
                         PixelRec r;
-                        // .d holds the raw uint16 depth (converted below)
-                        r.d = __uint_as_float(
-                                (unsigned)*(U16G*)(dimg + 2u * pix));
+                        // (.d is set from R.dr below)
+                        R.dr[fk][2 * p + h] = *(U16G*)(dimg + 2u * pix);
                         r.rgba = 0u;
                         if constexpr (kColor) {
                             // the 3 bytes at 3 * pix out of ONE aligned 8-byte
@@ -1161,8 +1173,8 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
         auto convert_depth = [&](int fk, Round& R) {
 #pragma unroll
             for (int p = 0; p < kP; ++p) {
-                f2 a = f2{(float)__float_as_uint(R.rec[fk][2 * p].d),
-                          (float)__float_as_uint(R.rec[fk][2 * p + 1].d)};
+                f2 a = f2{(float)R.dr[kRaw ? fk : 0][2 * p],
+                          (float)R.dr[kRaw ? fk : 0][2 * p + 1]};
                 f2 q;
                 if (ip.depth_div_short) {
                     const f2 q0 = a * ip.inv_depth_scale;
@@ -1264,6 +1276,24 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
             }
         }
         };
+        // The end of a round: s_waitcnt vmcnt(0) (expcnt, lgkmcnt left at
+        // their maxima, 7 and 15). It costs nothing -- apply has already
+        // waited for every gather the round issued, since it reads each
+        // frame's records -- but without it the compiler's wait-count pass
+        // drains the vector memory queue at the top of EVERY frame's issue
+        // block: a frame's gathers sit behind a wave-uniform branch (cbits),
+        // and on the path that skips a frame the registers of the previous
+        // round's gathers (reused as this round's temporaries) may still be
+        // pending, so the pass waits vmcnt(0) before each frame's projection.
+        // The round's gathers then went out one frame at a time -- kChunk
+        // dependent round trips per round instead of one. With the explicit
+        // wait nothing is pending when a round starts and the colour records
+        // forms issue the round's 2 * kChunk gathers back to back
+        // (tests/test_integrate_round_isa.py checks the assembly; the
+        // colourless and raw forms still wait once or twice inside a round,
+        // where a pending single-register load is paired with a packed
+        // operand of the next frame: profiles/r7b_round_isa.txt).
+        auto round_drained = [] { __builtin_amdgcn_s_waitcnt(0x0F70); };
         if constexpr (kLong) {
 #pragma nounroll
             for (int c0 = 0; c0 < ip.n_frames; c0 += kChunk) {
@@ -1272,6 +1302,7 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
                 if (r.cbits == 0u) continue;  // wave-uniform
                 issue(c0, r);
                 apply(c0, r);
+                round_drained();
             }
         } else {
             // (kChunk frames at a time: a group of up to kMaxGroup frames is
@@ -1286,6 +1317,7 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
                 if (r.cbits == 0u) continue;  // wave-uniform
                 issue(c0, r);
                 apply(c0, r);
+                round_drained();
             }
         }
         if (touched) {
@@ -1351,9 +1383,10 @@ static_assert(sizeof(StepParams) <= 4096, "kernel arguments are limited to 4 KB"
 // Frames of a round of the raw / long form (the chunk launch of the sliced
 // path): a rank's share of a chunk is a few hundred blocks, about one round of
 // the chip, so a work item's chain of dependent memory round trips is what the
-// launch lasts -- twice the frames in flight per round halve the rounds; the
-// registers this costs (2 waves per SIMD allowed) are not needed for occupancy
-// there.
+// launch lasts -- one trip per round once the round's gathers are in flight
+// together (round_drained in IntegrateRoleWide; before round 7 the compiler
+// drained the queue between frames, a trip per FRAME, and the r4 / r4zg
+// measurements of this constant were taken in that state).
 #ifndef O3DMI_RAW_CHUNK
 #define O3DMI_RAW_CHUNK 4
 #endif
@@ -1387,7 +1420,9 @@ struct ChunkParams {
 // frame, the per-group role's registers and occupancy); true: raw images.
 // (Software-pipelined rounds -- the next round's gathers in flight during this
 // round's arithmetic -- cost two waves of occupancy and were 0-10 % slower:
-// profiles/r4p, dropped.)
+// profiles/r4p, dropped. Measured while the compiler still waited vmcnt(0)
+// between the frames of a round, so neither form had a round's gathers in
+// flight together; see round_drained in IntegrateRoleWide.)
 template <typename weight_t, typename color_t, bool kColor, int kDiv,
           bool kRaw>
 __global__ void __launch_bounds__(256, kRaw ? O3DMI_RAW_WAVES : 7)

@@ -582,6 +582,30 @@ int o3dmi_icp_colored_accumulate(
         double scaling_parameter, double shape_parameter, double* sums29_dev,
         o3dmi_stream_t stream);
 
+/* ComputeFPFHFeatureCUDA (t/pipelines/kernel/FeatureImpl.h:108-296), the
+ * kernel step of ComputeFPFHFeature after the neighbour search. Lists are
+ * either padded {n_rows, max_nn} (indices_dev, distance2_dev) with counts_dev
+ * {n_rows}, or CSR (row_splits_dev {n_rows + 1}, int64; counts_dev NULL).
+ * Position 0 of every list is skipped, as the reference does. Without a mask,
+ * row r is point r (n_rows == n_points) and fpfhs_dev gets {n_points, 33}.
+ * With mask_dev (uint8 {n_points}) and map_info_idx_to_point_idx_dev (int64
+ * {n_rows}: the point of each list row, holding every masked point and all
+ * its neighbours), fpfhs_dev gets one row per masked point in ascending point
+ * order (NonZero(mask)). *n_fpfh_out (optional) receives the row count. SPFH
+ * bins in float64, d2 weights, sums in the point dtype in list order; every
+ * output row is written (rows with count <= 1 are zero). Synchronises when a
+ * mask is given. */
+int o3dmi_fpfh_from_neighbors(const void* points_dev, const void* normals_dev,
+                              int64_t n_points, int dtype,
+                              const int32_t* indices_dev,
+                              const void* distance2_dev,
+                              const int32_t* counts_dev,
+                              const int64_t* row_splits_dev, int max_nn,
+                              int64_t n_rows, const uint8_t* mask_dev,
+                              const int64_t* map_info_idx_to_point_idx_dev,
+                              void* fpfhs_dev, int64_t* n_fpfh_out,
+                              o3dmi_stream_t stream);
+
 /* EstimateColorGradientsUsing{Hybrid,KNN}SearchCUDA after the search
  * (t/geometry/kernel/PointCloudImpl.h:1067-1290): per point, least squares of
  * the intensity over its neighbours projected on the tangent plane plus the

@@ -7,6 +7,8 @@
  *   (_ex: estimator choice)               (t/pipelines/registration/Registration.cpp:93-106,362-444)
  *   o3dmi_registration_evaluate,       <- EvaluateRegistration, GetInformationMatrix
  *   o3dmi_registration_information_matrix (Registration.cpp:64-91,446-486)
+ *   o3dmi_registration_compute_fpfh_feature, <- ComputeFPFHFeature, CorrespondencesFromFeatures
+ *   o3dmi_registration_correspondences_from_features (Feature.cpp:23-333)
  *   o3dmi_voxel_down_sample,           <- t::geometry::PointCloud::{VoxelDownSample, EstimateNormals,
  *   o3dmi_pointcloud_estimate_*           EstimateColorGradients} (t/geometry/PointCloud.cpp:496-567,856-1060)
  *   o3dmi_vbg_*                        <- t::geometry::VoxelBlockGrid (+ Save / Load)
@@ -266,6 +268,41 @@ int o3dmi_registration_information_matrix(
         int dtype, double max_correspondence_distance,
         const double* transformation, double* information36,
         o3dmi_stream_t stream);
+
+/* ComputeFPFHFeature (t/pipelines/registration/Feature.cpp:23-277): FPFH
+ * {rows, 33} of a cloud with normals. Hybrid search when both max_nn and
+ * radius are given, KNN search (k = min(max_nn, n)) for max_nn alone, radius
+ * search for radius alone. max_nn <= 3, radius <= 0, no normals or neither
+ * parameter: O3DMI_ERR_INVALID_ARG; max_nn > 128: O3DMI_ERR_UNSUPPORTED.
+ * indices_dev (int64, n_indices >= 0; NULL with n_indices < 0 = all points):
+ * one row per DISTINCT index in ascending order, as the reference's mask +
+ * NonZero; an index outside [0, n) is O3DMI_ERR_INVALID_ARG; none gives 0
+ * rows. fpfhs_dev must hold min(n_indices, n) rows (n without indices);
+ * *n_rows_out receives the row count. n must be below 2^27 (the grid index
+ * addresses its records by 32-bit byte offsets); larger clouds are
+ * O3DMI_ERR_INVALID_ARG. Synchronises. */
+int o3dmi_registration_compute_fpfh_feature(
+        const void* points_dev, const void* normals_dev, int64_t n, int dtype,
+        int has_max_nn, int max_nn, int has_radius, double radius,
+        const int64_t* indices_dev, int64_t n_indices, void* fpfhs_dev,
+        int64_t* n_rows_out, o3dmi_stream_t stream);
+
+/* CorrespondencesFromFeatures (Feature.cpp:279-333): for every source row i
+ * the target row j nearest in feature space, as int64 pairs (i, j) in
+ * ascending i. Distance: sum_k (a_k - b_k)^2 in float64 over k = 0..dim-1 in
+ * order (exact for Float32 and Float64 features); ties go to the lowest index
+ * (stricter than the reference's GEMM-based search). A NaN distance (NaN or
+ * inf in a feature) counts as +inf, so every row gets an index in range. With mutual_filter, only
+ * pairs whose target row has i as its own nearest source row are kept, unless
+ * they number <= mutual_consistency_ratio * n_source (float): then all
+ * n_source pairs are returned and *fell_back (optional) is set to 1 (the
+ * reference logs a warning). correspondences_dev holds {n_source, 2};
+ * *n_correspondences receives the rows written. Synchronises. */
+int o3dmi_registration_correspondences_from_features(
+        const void* source_dev, int64_t n_source, const void* target_dev,
+        int64_t n_target, int dim, int dtype, int mutual_filter,
+        float mutual_consistency_ratio, int64_t* correspondences_dev,
+        int64_t* n_correspondences, int* fell_back, o3dmi_stream_t stream);
 
 /* PointCloud::VoxelDownSample (t/geometry/PointCloud.cpp:496-567) for
  * positions (+ optional normals): mean per voxel in float32, voxel order =

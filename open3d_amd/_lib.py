@@ -213,6 +213,15 @@ PROTOTYPES.update({
     "o3dmi_icp_search_accumulate_p2point": (_i32, [_vp, _vp, _i64, _vp, _vp,
                                                    _vp]),
     "o3dmi_compute_rt_p2point": (_i32, [_dp, _dp, _dp]),
+    "o3dmi_fpfh_from_neighbors": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp,
+                                         _vp, _i32, _i64, _vp, _vp, _vp,
+                                         C.POINTER(_i64), _vp]),
+    "o3dmi_registration_compute_fpfh_feature": (
+        _i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _d, _vp, _i64, _vp,
+               C.POINTER(_i64), _vp]),
+    "o3dmi_registration_correspondences_from_features": (
+        _i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _f, _vp,
+               C.POINTER(_i64), C.POINTER(_i32), _vp]),
     "o3dmi_pointcloud_estimate_normals": (_i32, [_vp, _i64, _i32, _i32, _d,
                                                  _vp, _i32, _vp]),
     "o3dmi_voxel_down_sample": (_i32, [_vp, _vp, _i64, _i32, _d, _vp, _vp,

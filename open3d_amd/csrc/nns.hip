@@ -791,6 +791,62 @@ RadiusWriteKernel(NnsView<T> nv, const T* __restrict__ q, int64_t nq,
     }
 }
 
+// HybridSearch for max_knn up to kMaxWideKnn (internal: the FPFH operator,
+// whose default max_nn of 100 exceeds one wave's list). The floor rounds of
+// RadiusWriteKernel: each round selects the next <= 64 pairs above the last
+// one emitted. Rows w of `ids` (NULL: every row) are searched; row i =
+// ids[w] reads query i and writes output row i of width max_knn.
+constexpr int kMaxWideKnn = 128;
+
+template <typename T>
+__global__ void __launch_bounds__(kCoopBlock)
+HybridSearchWideKernel(NnsView<T> nv, const T* __restrict__ q,
+                       const int* __restrict__ ids, int64_t nq, int max_knn,
+                       int* __restrict__ idx_out, T* __restrict__ d2_out,
+                       int* __restrict__ cnt_out) {
+    extern __shared__ __align__(16) char coop_lds[];
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    WaveTopK<T> list;
+    list.Init(coop_lds);
+    for (int64_t w = wave; w < nq; w += n_waves) {
+        const int64_t i = ids ? (int64_t)ids[w] : w;
+        const T qq[3] = {q[3 * i + 0], q[3 * i + 1], q[3 * i + 2]};
+        long long cx, cy, cz;
+        CellOf(qq, nv.inv_cell, cx, cy, cz);
+        int* row_idx = idx_out + i * max_knn;
+        T* row_d2 = d2_out + i * max_knn;
+        FloorSink<T> sink;
+        sink.list = &list;
+        sink.floor_d = T(0);
+        sink.floor_i = -1;
+        sink.has_floor = false;
+        int at = 0;
+        while (at < max_knn) {
+            const int want = max_knn - at < kMaxKnn ? max_knn - at : kMaxKnn;
+            list.Reset(want);
+            GatherCells<T, true>(nv, qq, cx, cy, cz, cx - 1, cx + 1, cy - 1,
+                                 cy + 1, cz - 1, cz + 1, 0, sink);
+            list.Flush();
+            if (lane < list.nbest) {
+                row_idx[at + lane] = list.best_i;
+                row_d2[at + lane] = list.best_d;
+            }
+            at += list.nbest;
+            if (list.nbest < want) break;
+            sink.floor_d = list.kth_d;
+            sink.floor_i = list.kth_i;
+            sink.has_floor = true;
+        }
+        for (int j = at + lane; j < max_knn; j += 64) {
+            row_idx[j] = -1;
+            row_d2[j] = T(0);
+        }
+        if (lane == 0) cnt_out[i] = at;
+    }
+}
+
 // EstimateCovariancesUsingRadiusSearch (t/geometry/kernel/PointCloudImpl.h:
 // 641-689): every neighbour with d2 < r2, no cap. One wave per point, two
 // sweeps over the 27 cells: count + centroid, then the six cumulants about it
@@ -1504,6 +1560,43 @@ int o3dmi_nns_hybrid_search(const o3dmi_nns_t* nns, const void* queries_dev,
                            CoopLdsBytesPerWave<float>() * (kCoopBlock / 64), s,
                            MakeView<float>(nns), (const float*)queries_dev, q,
                            max_knn, idx_dev, (float*)dist2_dev, counts_dev);
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
+// Internal (FPFH operator): HybridSearch with 1 <= max_knn <= 128; rows of
+// `ids_dev` (NULL: all nq rows) only. idx / dist2 are {rows, max_knn} (padded
+// with -1 / 0), counts {rows}. The public o3dmi_nns_hybrid_search keeps its
+// limit of 64.
+int o3dmi_internal_nns_hybrid_search_wide(const o3dmi_nns_t* nns,
+                                          const void* queries_dev,
+                                          const int32_t* ids_dev, int64_t nq,
+                                          int max_knn, int32_t* idx_dev,
+                                          void* dist2_dev, int32_t* counts_dev,
+                                          o3dmi_stream_t stream) {
+    O3DMI_REQUIRE(nns != nullptr, "index is null");
+    O3DMI_REQUIRE(nq >= 0, "q < 0");
+    if (max_knn < 1 || max_knn > kMaxWideKnn) {
+        SetLastError("max_knn must be in [1, 128]");
+        return O3DMI_ERR_UNSUPPORTED;
+    }
+    if (nq == 0) return O3DMI_OK;
+    O3DMI_REQUIRE(queries_dev && idx_dev && dist2_dev && counts_dev,
+                  "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid(GridFor(nq, kCoopBlock / 64, kCUs * 16)), block(kCoopBlock);
+    if (nns->dtype == O3DMI_F64)
+        hipLaunchKernelGGL(HybridSearchWideKernel<double>, grid, block,
+                           CoopLdsBytesPerWave<double>() * (kCoopBlock / 64), s,
+                           MakeView<double>(nns), (const double*)queries_dev,
+                           ids_dev, nq, max_knn, idx_dev, (double*)dist2_dev,
+                           counts_dev);
+    else
+        hipLaunchKernelGGL(HybridSearchWideKernel<float>, grid, block,
+                           CoopLdsBytesPerWave<float>() * (kCoopBlock / 64), s,
+                           MakeView<float>(nns), (const float*)queries_dev,
+                           ids_dev, nq, max_knn, idx_dev, (float*)dist2_dev,
+                           counts_dev);
     O3DMI_HIP_CHECK(hipGetLastError());
     return O3DMI_OK;
 }

@@ -1,5 +1,6 @@
-"""Python mirror of open3d.t.pipelines.registration.{icp, multi_scale_icp}
-for the MI355X backend (point-to-plane and point-to-point estimators).
+"""Python mirror of open3d.t.pipelines.registration.{icp, multi_scale_icp,
+compute_fpfh_feature, correspondences_from_features} for the MI355X backend
+(point-to-plane and point-to-point estimators).
 
 Argument names / defaults follow the reference's binding
 (cpp/pybind/t/pipelines/registration/registration.cpp) and
@@ -436,3 +437,65 @@ def fixed_radius_search(points, queries, radius):
         return idx[:total], d2[:total], splits
     finally:
         L.o3dmi_nns_destroy(h)
+
+
+def compute_fpfh_feature(positions, normals, max_nn=100, radius=None,
+                         indices=None):
+    """t::pipelines::registration::ComputeFPFHFeature (Feature.cpp:23-277) ->
+    FPFH features {N,33} (with `indices`: one row per distinct index, in
+    ascending order). Hybrid search when max_nn and radius are given, KNN
+    search when radius is None (the default), radius search when max_nn is
+    None. max_nn is limited to 128."""
+    positions = require_cuda(positions, "positions")
+    if normals is None:
+        raise ValueError("The input point cloud has no normal.")
+    normals = require_cuda(normals, "normals")
+    if normals.dtype != positions.dtype or normals.shape != positions.shape:
+        raise ValueError("positions / normals mismatch")
+    n = positions.shape[0]
+    idx = None
+    n_idx = -1
+    rows = n
+    if indices is not None:
+        idx = torch.as_tensor(indices, dtype=torch.int64).reshape(-1)
+        idx = idx.to("cuda").contiguous()
+        n_idx = idx.shape[0]
+        rows = min(n_idx, n)
+    out = torch.zeros((max(rows, 1), 33), dtype=positions.dtype,
+                      device="cuda")
+    got = C.c_int64(0)
+    _lib.check(_lib.lib().o3dmi_registration_compute_fpfh_feature(
+        _lib.ptr(positions), _lib.ptr(normals), n,
+        TORCH_TO_O3DMI[positions.dtype], int(max_nn is not None),
+        int(max_nn if max_nn is not None else 0), int(radius is not None),
+        C.c_double(radius if radius is not None else 0.0), _lib.ptr(idx),
+        n_idx, _lib.ptr(out), C.byref(got), stream()),
+        "compute_fpfh_feature")
+    return out[:got.value]
+
+
+def correspondences_from_features(source_features, target_features,
+                                  mutual_filter=False,
+                                  mutual_consistency_ratio=0.1,
+                                  return_fallback=False):
+    """t::pipelines::registration::CorrespondencesFromFeatures
+    (Feature.cpp:279-333) -> int64 {K,2} pairs (source row, nearest target
+    row). Exact float64 distances, ties to the lowest index. With
+    return_fallback, also returns whether the mutual filter fell back to all
+    pairs (the reference only logs it)."""
+    src = require_cuda(source_features, "source_features")
+    tgt = require_cuda(target_features, "target_features")
+    if src.dtype != tgt.dtype or src.dim() != 2 or tgt.dim() != 2 or \
+            src.shape[1] != tgt.shape[1]:
+        raise ValueError("feature sets must be {N,D} and {M,D} of one dtype")
+    n = src.shape[0]
+    out = torch.empty((max(n, 1), 2), dtype=torch.int64, device="cuda")
+    k = C.c_int64(0)
+    fb = C.c_int(0)
+    _lib.check(_lib.lib().o3dmi_registration_correspondences_from_features(
+        _lib.ptr(src), n, _lib.ptr(tgt), tgt.shape[0], src.shape[1],
+        TORCH_TO_O3DMI[src.dtype], int(bool(mutual_filter)),
+        C.c_float(mutual_consistency_ratio), _lib.ptr(out), C.byref(k),
+        C.byref(fb), stream()), "correspondences_from_features")
+    res = out[:k.value]
+    return (res, bool(fb.value)) if return_fallback else res

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "o3d_mi355x.h"
 
@@ -21,6 +22,29 @@ void SetLastError(const std::string& msg);
 // work using the block has completed.
 int PoolAlloc(void** out, size_t bytes);
 void PoolFree(void* p);
+
+// The pooled scratch of one call. The destructor waits for the stream when it
+// holds anything, then returns every block to the pool.
+struct PoolScratch {
+    hipStream_t s;
+    std::vector<void*> blocks;
+    explicit PoolScratch(hipStream_t st) : s(st) {}
+    PoolScratch(const PoolScratch&) = delete;
+    PoolScratch& operator=(const PoolScratch&) = delete;
+    ~PoolScratch() {
+        if (!blocks.empty()) (void)hipStreamSynchronize(s);
+        for (void* p : blocks) PoolFree(p);
+    }
+    template <typename P>
+    int Alloc(P** out, size_t bytes) {
+        void* p = nullptr;
+        const int st = PoolAlloc(&p, bytes);
+        if (st) return st;
+        blocks.push_back(p);
+        *out = (P*)p;
+        return O3DMI_OK;
+    }
+};
 
 // Row gather / scatter by index (rows.hip): dst[r] = src[idx[r]] and
 // dst[idx[r]] = src[r] for rows of row_bytes bytes.

@@ -25,7 +25,6 @@
 
 #include <cmath>
 #include <cstring>
-#include <vector>
 
 #include "common.h"
 #include "scan.h"
@@ -469,26 +468,6 @@ int LaunchFpfh(const T* pts, const T* nrm, const T* dist2, Lists lists,
     return O3DMI_OK;
 }
 
-// Owns the scratch of one call; released once the stream has drained.
-struct Scratch {
-    hipStream_t s;
-    std::vector<void*> blocks;
-    explicit Scratch(hipStream_t st) : s(st) {}
-    ~Scratch() {
-        if (!blocks.empty()) (void)hipStreamSynchronize(s);
-        for (void* p : blocks) PoolFree(p);
-    }
-    template <typename P>
-    int Alloc(P** out, size_t bytes) {
-        void* p = nullptr;
-        const int st = PoolAlloc(&p, bytes > 0 ? bytes : 1);
-        if (st) return st;
-        blocks.push_back(p);
-        *out = (P*)p;
-        return O3DMI_OK;
-    }
-};
-
 
 // ---- helpers of the FPFH operator (csrc/host/feature.cpp) -------------------
 __global__ void MarkIndicesKernel(const int64_t* __restrict__ idx, int64_t m,
@@ -596,7 +575,7 @@ int o3dmi_internal_mask_nonzero(const uint8_t* mask_dev, int64_t n,
     hipStream_t s = (hipStream_t)stream;
     *count = 0;
     if (n == 0) return O3DMI_OK;
-    Scratch sc(s);
+    PoolScratch sc(s);
     int32_t* m32 = nullptr;
     int64_t* pos = nullptr;
     void* tmp = nullptr;
@@ -640,7 +619,7 @@ int o3dmi_internal_short_rows(const int32_t* counts_dev, int64_t n, int k,
 int o3dmi_internal_bounds(const void* points_dev, int64_t n, int dtype,
                           double* lo, double* hi, o3dmi_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
-    Scratch sc(s);
+    PoolScratch sc(s);
     unsigned long long* box = nullptr;
     int st;
     if ((st = sc.Alloc(&box, 64))) return st;
@@ -690,7 +669,7 @@ int o3dmi_fpfh_from_neighbors(const void* points_dev, const void* normals_dev,
     O3DMI_REQUIRE(n_rows == 0 || (indices_dev && distance2_dev),
                   "indices / distance2 are null");
     hipStream_t s = (hipStream_t)stream;
-    Scratch sc(s);
+    PoolScratch sc(s);
     const Lists lists{indices_dev, counts_dev, row_splits_dev, max_nn};
     const size_t esz = dtype == O3DMI_F64 ? 8 : 4;
     int st;
@@ -787,7 +766,7 @@ int o3dmi_internal_feature_nn1(const void* a_dev, int64_t na, const void* b_dev,
     if (slices < 1) slices = 1;
     const int64_t cols = ((col_tiles + slices - 1) / slices) * kNnTile;
     slices = (nb + cols - 1) / cols;
-    Scratch sc(s);
+    PoolScratch sc(s);
     double* pd = nullptr;
     int32_t* pi = nullptr;
     int st;

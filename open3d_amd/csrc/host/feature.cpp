@@ -57,25 +57,14 @@ namespace {
 
 constexpr int kMaxFpfhNn = 128;
 
-// Owns the scratch of one call; released once the stream has drained.
-struct Scratch {
-    hipStream_t s;
-    std::vector<void*> blocks;
+// The scratch and search indices of one call; released once the stream has
+// drained.
+struct SearchScratch : PoolScratch {
     std::vector<o3dmi_nns_t*> indices;
-    explicit Scratch(hipStream_t st) : s(st) {}
-    ~Scratch() {
+    explicit SearchScratch(hipStream_t st) : PoolScratch(st) {}
+    ~SearchScratch() {
         (void)hipStreamSynchronize(s);
         for (o3dmi_nns_t* x : indices) o3dmi_nns_destroy(x);
-        for (void* p : blocks) PoolFree(p);
-    }
-    template <typename P>
-    int Alloc(P** out, size_t bytes) {
-        void* p = nullptr;
-        const int st = PoolAlloc(&p, bytes > 0 ? bytes : 1);
-        if (st) return st;
-        blocks.push_back(p);
-        *out = (P*)p;
-        return O3DMI_OK;
     }
     int Index(const void* pts, int64_t n, int dtype, double radius,
               o3dmi_nns_t** out) {
@@ -106,7 +95,7 @@ struct Search {
     o3dmi_nns_t* index = nullptr;  // hybrid / radius
     double diag = 0, knn_r0 = 0;   // KNN
 
-    int Prepare(Scratch& sc) {
+    int Prepare(SearchScratch& sc) {
         if (radius > 0) return sc.Index(pts, n, dtype, radius, &index);
         double lo[3], hi[3];
         int st = o3dmi_internal_bounds(pts, n, dtype, lo, hi,
@@ -131,7 +120,7 @@ struct Search {
         return O3DMI_OK;
     }
 
-    int Run(Scratch& sc, const void* q, int64_t nq, NbLists* out) {
+    int Run(SearchScratch& sc, const void* q, int64_t nq, NbLists* out) {
         o3dmi_stream_t stream = (o3dmi_stream_t)sc.s;
         int st;
         if (radius > 0 && max_nn <= 0) {
@@ -249,7 +238,7 @@ int o3dmi_registration_compute_fpfh_feature(
     O3DMI_REQUIRE(points_dev && fpfhs_dev, "null argument");
     hipStream_t s = (hipStream_t)stream;
     const size_t esz = dtype == O3DMI_F64 ? 8 : 4;
-    Scratch sc(s);
+    SearchScratch sc(s);
     Search search{points_dev, n, dtype, esz, has_max_nn ? max_nn : 0,
                   has_radius ? radius : 0.0};
     int st = search.Prepare(sc);
@@ -340,7 +329,7 @@ int o3dmi_registration_correspondences_from_features(
     if (fell_back) *fell_back = 0;
     if (n_source == 0) return O3DMI_OK;
     O3DMI_REQUIRE(correspondences_dev != nullptr, "correspondences is null");
-    Scratch sc(s);
+    SearchScratch sc(s);
     int32_t* ij = nullptr;
     int32_t* ji = nullptr;
     int64_t* info = nullptr;

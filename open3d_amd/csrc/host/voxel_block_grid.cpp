@@ -231,35 +231,84 @@ int GridDtype(o3dmi_vbg* g, int* out) {
     return O3DMI_OK;
 }
 
+// The attributes the TSDF operators read: tsdf, weight and (ci >= 0) colour,
+// with the grid dtype of the (weight, colour) pair.
+struct TsdfAttrs {
+    int ti = -1, wi = -1, ci = -1;
+    int grid_dtype = O3DMI_F32;
+    float* tsdf = nullptr;
+    void* weight = nullptr;
+    void* color = nullptr;
+};
+
+int ResolveTsdf(o3dmi_vbg* g, TsdfAttrs* a) {
+    a->ti = g->AttrIndex("tsdf");
+    a->wi = g->AttrIndex("weight");
+    a->ci = g->AttrIndex("color");
+    if (a->ti < 0 || a->wi < 0) {
+        SetLastError(
+                "TSDF and/or weight not allocated in blocks, please implement "
+                "customized integration.");
+        return O3DMI_ERR_INVALID_ARG;
+    }
+    const int st = GridDtype(g, &a->grid_dtype);
+    if (st) return st;
+    a->tsdf = (float*)o3dmi_hash_value_buffer(g->block_hashmap, a->ti);
+    a->weight = o3dmi_hash_value_buffer(g->block_hashmap, a->wi);
+    a->color = a->ci >= 0 ? o3dmi_hash_value_buffer(g->block_hashmap, a->ci)
+                          : nullptr;
+    return O3DMI_OK;
+}
+
+// block_hashmap_->GetActiveIndices into the call's pooled scratch; ascending
+// when `sorted`, so that what is built from them is a function of the grid
+// state only.
+struct ActiveList {
+    int32_t* idx = nullptr;
+    int64_t n = 0;
+    int Fill(o3dmi_vbg* g, bool sorted, PoolScratch& scratch,
+             o3dmi_stream_t stream) {
+        const int64_t cap = o3dmi_hash_capacity(g->block_hashmap);
+        int st = scratch.Alloc(&idx, sizeof(int32_t) * (size_t)cap);
+        if (st) return st;
+        n = 0;
+        if ((st = o3dmi_hash_active_indices(g->block_hashmap, idx, stream, &n)))
+            return st;
+        return sorted ? o3dmi_sort_indices(idx, n, stream) : O3DMI_OK;
+    }
+};
+
+// ExtractPointCloud / ExtractTriangleMesh (VoxelBlockGrid.cpp:404-471): the
+// seam `extract` over the active blocks, sorted (the mesh seam finds a
+// neighbour's position by bisection). The seams synchronise the stream.
+template <typename F>
+int ExtractSurface(o3dmi_vbg* g, o3dmi_stream_t stream, F&& extract) {
+    TsdfAttrs at;
+    int st = ResolveTsdf(g, &at);
+    if (st) return st;
+    PoolScratch scratch((hipStream_t)stream);
+    ActiveList active;
+    if ((st = active.Fill(g, true, scratch, stream))) return st;
+    return extract(at, active);
+}
+
 int RunIntegrate(o3dmi_vbg* g, const int32_t* indices, int64_t n,
                  const int32_t* n_dev, const void* depth, int drows, int dcols,
                  const void* color, int crows, int ccols, int input_dtype,
                  const double* Kd, const double* Kc, const double* T,
                  float depth_scale, float depth_max, float trunc_mult,
                  o3dmi_stream_t stream) {
-    int ti = g->AttrIndex("tsdf"), wi = g->AttrIndex("weight"),
-        ci = g->AttrIndex("color");
-    if (ti < 0 || wi < 0) {
-        SetLastError(
-                "TSDF and/or weight not allocated in blocks, please implement "
-                "customized integration.");
-        return O3DMI_ERR_INVALID_ARG;
-    }
-    O3DMI_REQUIRE(g->attr_dtypes[(size_t)ti] == O3DMI_F32,
-                  "tsdf must be Float32");
-    int grid_dtype;
-    int st = GridDtype(g, &grid_dtype);
+    TsdfAttrs at;
+    const int st = ResolveTsdf(g, &at);
     if (st) return st;
+    O3DMI_REQUIRE(g->attr_dtypes[(size_t)at.ti] == O3DMI_F32,
+                  "tsdf must be Float32");
     bool integrate_color = color != nullptr && (int64_t)crows * ccols > 0;
-    void* cbuf = (ci >= 0 && integrate_color)
-                         ? o3dmi_hash_value_buffer(g->block_hashmap, ci)
-                         : nullptr;
     return o3dmi_vbg_integrate(
             depth, drows, dcols, integrate_color ? color : nullptr, crows,
             ccols, input_dtype, indices, n, n_dev,
-            o3dmi_hash_key_buffer(g->block_hashmap),
-            (float*)o3dmi_hash_value_buffer(g->block_hashmap, ti),
-            o3dmi_hash_value_buffer(g->block_hashmap, wi), cbuf, grid_dtype, Kd,
+            o3dmi_hash_key_buffer(g->block_hashmap), at.tsdf, at.weight,
+            integrate_color ? at.color : nullptr, at.grid_dtype, Kd,
             Kc ? Kc : Kd, T, (int)g->block_resolution, g->voxel_size,
             g->voxel_size * trunc_mult, depth_scale, depth_max, stream);
 }
@@ -2433,16 +2482,8 @@ int o3dmi_vbg_ray_cast_dev(o3dmi_vbg_t* g, const int32_t* block_coords_dev,
                            float trunc_voxel_multiplier,
                            int range_map_down_factor, o3dmi_stream_t stream) {
     O3DMI_REQUIRE(g && intrinsic && extrinsic, "null argument");
-    int ti = g->AttrIndex("tsdf"), wi = g->AttrIndex("weight"),
-        ci = g->AttrIndex("color");
-    if (ti < 0 || wi < 0) {
-        SetLastError(
-                "TSDF and/or weight not allocated in blocks, please implement "
-                "customized integration.");
-        return O3DMI_ERR_INVALID_ARG;
-    }
-    int grid_dtype;
-    int st = GridDtype(g, &grid_dtype);
+    TsdfAttrs at;
+    int st = ResolveTsdf(g, &at);
     if (st) return st;
     O3DMI_REQUIRE(range_map_down_factor > 0 && height >= range_map_down_factor &&
                           width >= range_map_down_factor,
@@ -2547,14 +2588,10 @@ int o3dmi_vbg_ray_cast_dev(o3dmi_vbg_t* g, const int32_t* block_coords_dev,
         g->own_range_clean = false;
         return st;
     }
-    const void* cbuf = (ci >= 0 && out_color)
-                               ? o3dmi_hash_value_buffer(g->block_hashmap, ci)
-                               : nullptr;
     st = o3dmi_vbg_raycast(
-            g->block_hashmap,
-            (const float*)o3dmi_hash_value_buffer(g->block_hashmap, ti),
-            o3dmi_hash_value_buffer(g->block_hashmap, wi), cbuf, grid_dtype,
-            range_map_dev, out_depth, out_vertex, out_color, out_normal,
+            g->block_hashmap, at.tsdf, at.weight,
+            out_color ? at.color : nullptr, at.grid_dtype, range_map_dev,
+            out_depth, out_vertex, out_color, out_normal,
             out_index, out_mask, out_ratio, out_ratio_dx, out_ratio_dy,
             out_ratio_dz, intrinsic, extrinsic, height, width,
             (int)g->block_resolution, g->voxel_size, depth_scale, depth_min,
@@ -2611,16 +2648,8 @@ int o3dmi_vbg_ray_cast_sharded(
         O3DMI_REQUIRE(g && range_map_dev && intrinsic && extrinsic &&
                               width > 0 && height > 0,
                       "bad argument");
-        int ti = g->AttrIndex("tsdf"), wi = g->AttrIndex("weight"),
-            ci = g->AttrIndex("color");
-        if (ti < 0 || wi < 0) {
-            SetLastError(
-                    "TSDF and/or weight not allocated in blocks, please "
-                    "implement customized integration.");
-            return O3DMI_ERR_INVALID_ARG;
-        }
-        int grid_dtype;
-        int st = GridDtype(g, &grid_dtype);
+        TsdfAttrs at;
+        int st = ResolveTsdf(g, &at);
         if (st) return st;
         // the range map is cheap (one pass over the frustum's block keys)
         // and replicated: every rank needs the cells of its band only, but
@@ -2651,15 +2680,9 @@ int o3dmi_vbg_ray_cast_sharded(
                 mp.staged = q;
                 q += (size_t)padded * width * mp.channels;
             }
-        const void* cbuf =
-                (ci >= 0 && out_color)
-                        ? o3dmi_hash_value_buffer(g->block_hashmap, ci)
-                        : nullptr;
         return o3dmi_vbg_raycast_rows(
-                g->block_hashmap,
-                (const float*)o3dmi_hash_value_buffer(g->block_hashmap, ti),
-                o3dmi_hash_value_buffer(g->block_hashmap, wi), cbuf,
-                grid_dtype, range_map_dev, maps[0].staged, maps[1].staged,
+                g->block_hashmap, at.tsdf, at.weight,
+                out_color ? at.color : nullptr, at.grid_dtype, range_map_dev, maps[0].staged, maps[1].staged,
                 maps[2].staged, maps[3].staged, nullptr, nullptr, nullptr,
                 nullptr, nullptr, nullptr, intrinsic, extrinsic, height, width,
                 r0, r1, (int)g->block_resolution, g->voxel_size, depth_scale,
@@ -2691,40 +2714,15 @@ int o3dmi_vbg_extract_point_cloud(o3dmi_vbg_t* g, float weight_threshold,
                                   float* normals_dev, float* colors_dev,
                                   int64_t* total_out, o3dmi_stream_t stream) {
     O3DMI_REQUIRE(g && total_out, "null argument");
-    int ti = g->AttrIndex("tsdf"), wi = g->AttrIndex("weight"),
-        ci = g->AttrIndex("color");
-    if (ti < 0 || wi < 0) {
-        SetLastError(
-                "TSDF and/or weight not allocated in blocks, please implement "
-                "customized integration.");
-        return O3DMI_ERR_INVALID_ARG;
-    }
-    int grid_dtype;
-    int st = GridDtype(g, &grid_dtype);
-    if (st) return st;
-    // block_hashmap_->GetActiveIndices(active_buf_indices), sorted so that the
-    // output order is a function of the grid state only.
-    int32_t* active = nullptr;
-    const int64_t cap = o3dmi_hash_capacity(g->block_hashmap);
-    if ((st = PoolAlloc((void**)&active, sizeof(int32_t) * (size_t)cap)))
-        return st;
-    int64_t n = 0;
-    st = o3dmi_hash_active_indices(g->block_hashmap, active, stream, &n);
-    if (!st) st = o3dmi_sort_indices(active, n, stream);
-    if (!st)
-        st = o3dmi_vbg_extract_points(
-                g->block_hashmap, active, n,
-                (const float*)o3dmi_hash_value_buffer(g->block_hashmap, ti),
-                o3dmi_hash_value_buffer(g->block_hashmap, wi),
-                ci >= 0 ? o3dmi_hash_value_buffer(g->block_hashmap, ci)
-                        : nullptr,
-                grid_dtype, (int)g->block_resolution, g->voxel_size,
-                weight_threshold, points_dev, normals_dev,
-                ci >= 0 ? colors_dev : nullptr, capacity, total_out, stream);
-    // extract_points synchronised the stream (or failed before launching).
-    (void)hipStreamSynchronize((hipStream_t)stream);
-    PoolFree(active);
-    return st;
+    return ExtractSurface(g, stream, [&](const TsdfAttrs& at,
+                                         const ActiveList& active) {
+        return o3dmi_vbg_extract_points(
+                g->block_hashmap, active.idx, active.n, at.tsdf, at.weight,
+                at.color, at.grid_dtype, (int)g->block_resolution,
+                g->voxel_size, weight_threshold, points_dev, normals_dev,
+                at.ci >= 0 ? colors_dev : nullptr, capacity, total_out,
+                stream);
+    });
 }
 
 int o3dmi_vbg_extract_triangle_mesh(o3dmi_vbg_t* g, float weight_threshold,
@@ -2735,41 +2733,15 @@ int o3dmi_vbg_extract_triangle_mesh(o3dmi_vbg_t* g, float weight_threshold,
                                     int64_t* n_triangles_out,
                                     o3dmi_stream_t stream) {
     O3DMI_REQUIRE(g && n_vertices_out && n_triangles_out, "null argument");
-    int ti = g->AttrIndex("tsdf"), wi = g->AttrIndex("weight"),
-        ci = g->AttrIndex("color");
-    if (ti < 0 || wi < 0) {
-        SetLastError(
-                "TSDF and/or weight not allocated in blocks, please implement "
-                "customized integration.");
-        return O3DMI_ERR_INVALID_ARG;
-    }
-    int grid_dtype;
-    int st = GridDtype(g, &grid_dtype);
-    if (st) return st;
-    // GetActiveIndices, sorted: the output order is a function of the grid
-    // state only, and the kernel finds a neighbour's position by bisection.
-    int32_t* active = nullptr;
-    const int64_t cap = o3dmi_hash_capacity(g->block_hashmap);
-    if ((st = PoolAlloc((void**)&active, sizeof(int32_t) * (size_t)cap)))
-        return st;
-    int64_t n = 0;
-    st = o3dmi_hash_active_indices(g->block_hashmap, active, stream, &n);
-    if (!st) st = o3dmi_sort_indices(active, n, stream);
-    if (!st)
-        st = o3dmi_vbg_extract_mesh(
-                g->block_hashmap, active, n,
-                (const float*)o3dmi_hash_value_buffer(g->block_hashmap, ti),
-                o3dmi_hash_value_buffer(g->block_hashmap, wi),
-                ci >= 0 ? o3dmi_hash_value_buffer(g->block_hashmap, ci)
-                        : nullptr,
-                grid_dtype, (int)g->block_resolution, g->voxel_size,
-                weight_threshold, vertices_dev, normals_dev,
-                ci >= 0 ? colors_dev : nullptr, triangles_dev, vertex_capacity,
-                n_vertices_out, n_triangles_out, stream);
-    // extract_mesh synchronised the stream (or failed before launching).
-    (void)hipStreamSynchronize((hipStream_t)stream);
-    PoolFree(active);
-    return st;
+    return ExtractSurface(g, stream, [&](const TsdfAttrs& at,
+                                         const ActiveList& active) {
+        return o3dmi_vbg_extract_mesh(
+                g->block_hashmap, active.idx, active.n, at.tsdf, at.weight,
+                at.color, at.grid_dtype, (int)g->block_resolution,
+                g->voxel_size, weight_threshold, vertices_dev, normals_dev,
+                at.ci >= 0 ? colors_dev : nullptr, triangles_dev,
+                vertex_capacity, n_vertices_out, n_triangles_out, stream);
+    });
 }
 
 // SURVEY 8(e)(B), the payload step: every active block goes to the rank that
@@ -2806,24 +2778,13 @@ int o3dmi_vbg_merge_frame_sharded(o3dmi_vbg_t* g, o3dmi_comm_t* comm,
         O3DMI_REQUIRE(row_bytes[i] % 16 == 0, "value rows must be 16-byte "
                                               "multiples");
     }
-    struct Scratch {
-        hipStream_t s;
-        std::vector<void*> p;
-        int Alloc(void** out, size_t bytes) {
-            int e = PoolAlloc(out, bytes ? bytes : 16);
-            if (!e) p.push_back(*out);
-            return e;
-        }
-        ~Scratch() {
-            (void)hipStreamSynchronize(s);
-            for (void* q : p) PoolFree(q);
-        }
-    } scratch{s, {}};
+    PoolScratch scratch(s);
     int st;
     // 1. ---------------------------------------------------------------------
     // (a function: run again after a Reserve, which renumbers the buffer
     // indices `grouped` holds)
-    int32_t *active = nullptr, *owner = nullptr, *grouped = nullptr;
+    ActiveList active;
+    int32_t *owner = nullptr, *grouped = nullptr;
     int* counters = nullptr;  // counts[world] | cursor[world]
     int64_t n = 0;
     const int* key_buffer = nullptr;
@@ -2832,24 +2793,20 @@ int o3dmi_vbg_merge_frame_sharded(o3dmi_vbg_t* g, o3dmi_comm_t* comm,
     auto group_by_owner = [&]() -> int {
         const int64_t cap = o3dmi_hash_capacity(g->block_hashmap);
         int e;
-        if ((e = scratch.Alloc((void**)&active, sizeof(int32_t) * (size_t)cap)) ||
-            (e = scratch.Alloc((void**)&owner, sizeof(int32_t) * (size_t)cap)) ||
-            (e = scratch.Alloc((void**)&grouped,
-                               sizeof(int32_t) * (size_t)cap)) ||
-            (e = scratch.Alloc((void**)&counters, sizeof(int) * 2 * kMaxWorld)))
-            return e;
         n = 0;
-        if ((e = o3dmi_hash_active_indices(g->block_hashmap, active, stream,
-                                           &n)))
+        if ((e = scratch.Alloc(&owner, sizeof(int32_t) * (size_t)cap)) ||
+            (e = scratch.Alloc(&grouped, sizeof(int32_t) * (size_t)cap)) ||
+            (e = scratch.Alloc(&counters, sizeof(int) * 2 * kMaxWorld)) ||
+            (e = active.Fill(g, true, scratch, stream)))
             return e;
-        if (n > 1 && (e = o3dmi_sort_indices(active, n, stream))) return e;
+        n = active.n;
         O3DMI_HIP_CHECK(hipMemsetAsync(counters, 0,
                                        sizeof(int) * 2 * kMaxWorld, s));
         key_buffer = (const int*)o3dmi_hash_key_buffer(g->block_hashmap);
         if (n > 0)
             hipLaunchKernelGGL(OwnerCountKernel, dim3(GridFor(n, kBlock)),
-                               dim3(kBlock), 0, s, active, n, key_buffer, world,
-                               owner, counters);
+                               dim3(kBlock), 0, s, active.idx, n, key_buffer,
+                               world, owner, counters);
         for (int r = 0; r < kMaxWorld; ++r) host_counts[r] = 0;
         O3DMI_HIP_CHECK(hipMemcpyAsync(host_counts, counters,
                                        sizeof(int) * world,
@@ -2862,7 +2819,7 @@ int o3dmi_vbg_merge_frame_sharded(o3dmi_vbg_t* g, o3dmi_comm_t* comm,
         }
         if (n > 0)
             hipLaunchKernelGGL(OwnerGroupKernel, dim3(GridFor(n, kBlock)),
-                               dim3(kBlock), 0, s, active, n, owner, off,
+                               dim3(kBlock), 0, s, active.idx, n, owner, off,
                                counters + kMaxWorld, grouped);
         O3DMI_HIP_CHECK(hipGetLastError());
         return O3DMI_OK;
@@ -2874,7 +2831,7 @@ int o3dmi_vbg_merge_frame_sharded(o3dmi_vbg_t* g, o3dmi_comm_t* comm,
     const int grouped_st = group_by_owner();
     // 2. ---------------------------------------------------------------------
     int64_t* matrix_dev = nullptr;  // [world][world]: row r = rank r's counts
-    if ((st = scratch.Alloc((void**)&matrix_dev,
+    if ((st = scratch.Alloc(&matrix_dev,
                             sizeof(int64_t) * (size_t)world * (world + 1))))
         return st;
     std::vector<int64_t> mine((size_t)world), matrix((size_t)world * world);
@@ -2931,8 +2888,8 @@ int o3dmi_vbg_merge_frame_sharded(o3dmi_vbg_t* g, o3dmi_comm_t* comm,
         char* send = nullptr;
         char* recv = nullptr;
         int e;
-        if ((e = scratch.Alloc((void**)&send, (size_t)(n * row))) ||
-            (e = scratch.Alloc((void**)&recv, (size_t)(recv_total * row))))
+        if ((e = scratch.Alloc(&send, (size_t)(n * row))) ||
+            (e = scratch.Alloc(&recv, (size_t)(recv_total * row))))
             return e;
         if ((e = GatherRows(src_rows, grouped, n, row, send, s))) return e;
         std::vector<int64_t> sb((size_t)world), so((size_t)world),
@@ -2959,7 +2916,7 @@ int o3dmi_vbg_merge_frame_sharded(o3dmi_vbg_t* g, o3dmi_comm_t* comm,
     // first(me)) and grouped[first(me) + count(me) .. n)
     {
         int32_t* gone_keys = nullptr;
-        if ((st = scratch.Alloc((void**)&gone_keys,
+        if ((st = scratch.Alloc(&gone_keys,
                                 sizeof(int32_t) * 3 * (size_t)(n ? n : 1))))
             return st;
         const int64_t head = off.v[me];
@@ -3017,19 +2974,7 @@ int o3dmi_vbg_allgather_owned_blocks(o3dmi_vbg_t* g, o3dmi_comm_t* comm,
     hipStream_t s = (hipStream_t)stream;
     const size_t n_attr = g->attr_names.size();
     const int64_t res = g->block_resolution;
-    struct Scratch {
-        hipStream_t s;
-        std::vector<void*> p;
-        int Alloc(void** out, size_t bytes) {
-            int e = PoolAlloc(out, bytes ? bytes : 16);
-            if (!e) p.push_back(*out);
-            return e;
-        }
-        ~Scratch() {
-            (void)hipStreamSynchronize(s);
-            for (void* q : p) PoolFree(q);
-        }
-    } scratch{s, {}};
+    PoolScratch scratch(s);
     int st;
     // (Rank-local failures do not leave the peers waiting: the status of the
     // count travels as a negative count, the status of the export is agreed
@@ -3039,7 +2984,7 @@ int o3dmi_vbg_allgather_owned_blocks(o3dmi_vbg_t* g, o3dmi_comm_t* comm,
             o3dmi_vbg_export_blocks(g, 0, nullptr, nullptr, &n, stream);
     if (count_st) n = -(int64_t)count_st;
     int64_t* counts_dev = nullptr;
-    if ((st = scratch.Alloc((void**)&counts_dev,
+    if ((st = scratch.Alloc(&counts_dev,
                             sizeof(int64_t) * (size_t)(world + 1))))
         return st;
     O3DMI_HIP_CHECK(hipMemcpyAsync(counts_dev + world, &n, sizeof(int64_t),
@@ -3076,8 +3021,8 @@ int o3dmi_vbg_allgather_owned_blocks(o3dmi_vbg_t* g, o3dmi_comm_t* comm,
     // one rank alone to run out of memory
     const auto export_mine = [&]() -> int {
         int e;
-        if ((e = scratch.Alloc((void**)&keys, (size_t)m * 12)) ||
-            (e = scratch.Alloc((void**)&all_keys, (size_t)m * 12 * world)))
+        if ((e = scratch.Alloc(&keys, (size_t)m * 12)) ||
+            (e = scratch.Alloc(&all_keys, (size_t)m * 12 * world)))
             return e;
         for (size_t i = 0; i < n_attr; ++i)
             if ((e = scratch.Alloc(&rows[i], (size_t)(m * row_bytes[i]))) ||
@@ -3124,22 +3069,11 @@ int o3dmi_vbg_save(o3dmi_vbg_t* g, const char* file_name,
                    o3dmi_stream_t stream) {
     O3DMI_REQUIRE(g && file_name, "null argument");
     hipStream_t s = (hipStream_t)stream;
-    const int64_t cap = o3dmi_hash_capacity(g->block_hashmap);
-    int32_t* active = nullptr;
-    int st = PoolAlloc((void**)&active, sizeof(int32_t) * (size_t)cap);
+    PoolScratch scratch(s);
+    ActiveList active;
+    int st = active.Fill(g, true, scratch, stream);
     if (st) return st;
-    struct Scratch {
-        hipStream_t s;
-        std::vector<void*> p;
-        ~Scratch() {
-            (void)hipStreamSynchronize(s);
-            for (void* q : p) PoolFree(q);
-        }
-    } scratch{s, {active}};
-    int64_t n = 0;
-    if ((st = o3dmi_hash_active_indices(g->block_hashmap, active, stream, &n)))
-        return st;
-    if ((st = o3dmi_sort_indices(active, n, stream))) return st;
+    const int64_t n = active.n;
 
     o3dmi_npz z;
     auto scalar = [&](const std::string& name, int dtype, const void* v,
@@ -3167,10 +3101,10 @@ int o3dmi_vbg_save(o3dmi_vbg_t* g, const char* file_name,
         a->data.resize((size_t)(n * row_bytes));
         if (n == 0) return O3DMI_OK;
         void* tmp = nullptr;
-        int e = PoolAlloc(&tmp, (size_t)(n * row_bytes));
-        if (e) return e;
-        scratch.p.push_back(tmp);
-        if ((e = GatherRows(src, active, n, row_bytes, tmp, s))) return e;
+        int e;
+        if ((e = scratch.Alloc(&tmp, (size_t)(n * row_bytes))) ||
+            (e = GatherRows(src, active.idx, n, row_bytes, tmp, s)))
+            return e;
         O3DMI_HIP_CHECK(hipMemcpyAsync(a->data.data(), tmp,
                                        (size_t)(n * row_bytes),
                                        hipMemcpyDeviceToHost, s));
@@ -3219,30 +3153,19 @@ int o3dmi_vbg_export_blocks(o3dmi_vbg_t* g, int64_t capacity,
     O3DMI_REQUIRE(keys_dev == nullptr || values_dev != nullptr,
                   "values_dev is null");
     hipStream_t s = (hipStream_t)stream;
-    const int64_t cap = o3dmi_hash_capacity(g->block_hashmap);
-    int32_t* active = nullptr;
-    int st = PoolAlloc((void**)&active, sizeof(int32_t) * (size_t)cap);
+    PoolScratch scratch(s);
+    ActiveList active;
+    int st = active.Fill(g, keys_dev != nullptr, scratch, stream);
     if (st) return st;
-    struct Scratch {
-        hipStream_t s;
-        void* p;
-        ~Scratch() {
-            (void)hipStreamSynchronize(s);
-            PoolFree(p);
-        }
-    } scratch{s, active};
-    int64_t n = 0;
-    if ((st = o3dmi_hash_active_indices(g->block_hashmap, active, stream, &n)))
-        return st;
+    const int64_t n = active.n;
     *n_out = n;
     if (!keys_dev || n == 0) return O3DMI_OK;
     if (n > capacity) {
         SetLastError("export_blocks: more active blocks than `capacity`");
         return O3DMI_ERR_CAPACITY;
     }
-    if ((st = o3dmi_sort_indices(active, n, stream))) return st;
-    if ((st = GatherRows(o3dmi_hash_key_buffer(g->block_hashmap), active, n, 12,
-                         keys_dev, s)))
+    if ((st = GatherRows(o3dmi_hash_key_buffer(g->block_hashmap), active.idx,
+                         n, 12, keys_dev, s)))
         return st;
     const int64_t res = g->block_resolution;
     for (size_t i = 0; i < g->attr_names.size(); ++i) {
@@ -3250,7 +3173,7 @@ int o3dmi_vbg_export_blocks(o3dmi_vbg_t* g, int64_t capacity,
         const int64_t row = res * res * res * g->attr_channels[i] *
                             DtypeSize(g->attr_dtypes[i]);
         if ((st = GatherRows(o3dmi_hash_value_buffer(g->block_hashmap, (int)i),
-                             active, n, row, values_dev[i], s)))
+                             active.idx, n, row, values_dev[i], s)))
             return st;
     }
     return O3DMI_OK;
@@ -3263,12 +3186,10 @@ int o3dmi_vbg_merge_blocks(o3dmi_vbg_t* g, const int32_t* keys_dev,
     O3DMI_REQUIRE(n >= 0, "n < 0");
     if (n == 0) return O3DMI_OK;
     O3DMI_REQUIRE(keys_dev && values_dev, "null argument");
-    const int ti = g->AttrIndex("tsdf"), wi = g->AttrIndex("weight"),
-              ci = g->AttrIndex("color");
-    if (ti < 0 || wi < 0) {
-        SetLastError("TSDF and/or weight not allocated in blocks");
-        return O3DMI_ERR_INVALID_ARG;
-    }
+    TsdfAttrs at;
+    int st = ResolveTsdf(g, &at);
+    if (st) return st;
+    const int ti = at.ti, wi = at.wi, ci = at.ci;
     O3DMI_REQUIRE(g->attr_dtypes[(size_t)ti] == O3DMI_F32,
                   "tsdf must be Float32");
     O3DMI_REQUIRE((int)g->attr_names.size() ==
@@ -3276,9 +3197,6 @@ int o3dmi_vbg_merge_blocks(o3dmi_vbg_t* g, const int32_t* keys_dev,
                   "merge_blocks handles the tsdf / weight / color attributes");
     O3DMI_REQUIRE(ci < 0 || g->attr_channels[(size_t)ci] == 3,
                   "color must have 3 channels");
-    int grid_dtype;
-    int st = GridDtype(g, &grid_dtype);
-    if (st) return st;
     O3DMI_REQUIRE(values_dev[ti] && values_dev[wi] &&
                           (ci < 0 || values_dev[ci]),
                   "values_dev[i] is null");
@@ -3291,27 +3209,25 @@ int o3dmi_vbg_merge_blocks(o3dmi_vbg_t* g, const int32_t* keys_dev,
     if ((st = o3dmi_hash_find(g->block_hashmap, keys_dev, n, nullptr,
                               g->scratch_buf_indices, nullptr, stream)))
         return st;
+    (void)ResolveTsdf(g, &at);  // again: a Reserve above moves the buffers
     const int64_t res = g->block_resolution;
     const int vpb = (int)(res * res * res);
     const int64_t total = n * vpb;
     const int block = 256;
     const int64_t want = (total + block - 1) / block;
     const int grid = (int)(want < 65536 ? want : 65536);
-    float* tsdf = (float*)o3dmi_hash_value_buffer(g->block_hashmap, ti);
-    void* weight = o3dmi_hash_value_buffer(g->block_hashmap, wi);
-    void* color = ci >= 0 ? o3dmi_hash_value_buffer(g->block_hashmap, ci)
-                          : nullptr;
     hipStream_t s = (hipStream_t)stream;
-    if (grid_dtype == O3DMI_F32)
+    if (at.grid_dtype == O3DMI_F32)
         MergeBlocksKernel<float><<<grid, block, 0, s>>>(
-                g->scratch_buf_indices, total, vpb, tsdf, (float*)weight,
-                (float*)color, (const float*)values_dev[ti],
+                g->scratch_buf_indices, total, vpb, at.tsdf, (float*)at.weight,
+                (float*)at.color, (const float*)values_dev[ti],
                 (const float*)values_dev[wi],
                 ci >= 0 ? (const float*)values_dev[ci] : nullptr);
     else
         MergeBlocksKernel<uint16_t><<<grid, block, 0, s>>>(
-                g->scratch_buf_indices, total, vpb, tsdf, (uint16_t*)weight,
-                (uint16_t*)color, (const float*)values_dev[ti],
+                g->scratch_buf_indices, total, vpb, at.tsdf,
+                (uint16_t*)at.weight, (uint16_t*)at.color,
+                (const float*)values_dev[ti],
                 (const uint16_t*)values_dev[wi],
                 ci >= 0 ? (const uint16_t*)values_dev[ci] : nullptr);
     O3DMI_HIP_CHECK(hipGetLastError());

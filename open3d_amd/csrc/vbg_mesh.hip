@@ -27,10 +27,12 @@
 //    triangle capacity writes nothing (the reference writes past its
 //    tensors);
 //  * 64-bit linear voxel indices.
+// The per-voxel arithmetic (neighbour lookup, normals, edge vertices) is
+// vbg_surface.h's, shared with vbg_extract.hip.
 
-#include "common.h"
 #include "mc_tables.h"
 #include "scan.h"
+#include "vbg_surface.h"
 
 namespace o3dmi {
 namespace {
@@ -46,16 +48,6 @@ constexpr unsigned char kCube = 4;  // the cube with its origin here is valid
 // Bit 31 of a voxel's first-vertex word: the voxel has a vertex on axis 0.
 constexpr unsigned kHas0 = 0x80000000u;
 
-__device__ __forceinline__ int Sgn(int x) { return (x > 0) - (x < 0); }
-
-// Block resolution: RT > 0 is a compile-time value (8, 16), 0 the run-time
-// one; divisions by a run-time value cost tens of instructions each.
-template <int RT>
-struct Res {
-    int r;
-    __device__ __forceinline__ int R() const { return RT > 0 ? RT : r; }
-};
-
 struct MeshArgs {
     const int32_t* indices;  // [n_blocks] active buffer indices, ascending
     int n_blocks;
@@ -70,89 +62,22 @@ struct MeshArgs {
     long long triangle_capacity;
 };
 
-// DeviceGetLinearIdx, VoxelBlockGridImpl.h:94-121; nb = LDS table of the 27
-// neighbour buffer indices (-1 = absent). xo, yo, zo in [-R, 2R).
-template <int RT>
-__device__ __forceinline__ long long LinearIdx(int xo, int yo, int zo,
-                                               Res<RT> rs, const int* nb) {
-    const int res = rs.R();
-    const int xn = (xo + res) % res;
-    const int yn = (yo + res) % res;
-    const int zn = (zo + res) % res;
-    const int nb_idx = (Sgn(xo - xn) + 1) + (Sgn(yo - yn) + 1) * 3 +
-                       (Sgn(zo - zn) + 1) * 9;
-    const int b = nb[nb_idx];
-    if (b < 0) return -1;
-    return ((((long long)b * res) + zn) * res + yn) * res + xn;
-}
-
-// DeviceGetNormal, :123-149: components are only overwritten when both
-// neighbours exist.
-template <int RT>
-__device__ __forceinline__ void GetNormal(const float* __restrict__ tsdf,
-                                          int xo, int yo, int zo, Res<RT> rs,
-                                          const int* nb, float* n) {
-    const long long vxp = LinearIdx(xo + 1, yo, zo, rs, nb);
-    const long long vxn = LinearIdx(xo - 1, yo, zo, rs, nb);
-    const long long vyp = LinearIdx(xo, yo + 1, zo, rs, nb);
-    const long long vyn = LinearIdx(xo, yo - 1, zo, rs, nb);
-    const long long vzp = LinearIdx(xo, yo, zo + 1, rs, nb);
-    const long long vzn = LinearIdx(xo, yo, zo - 1, rs, nb);
-    if (vxp >= 0 && vxn >= 0) n[0] = tsdf[vxp] - tsdf[vxn];
-    if (vyp >= 0 && vyn >= 0) n[1] = tsdf[vyp] - tsdf[vyn];
-    if (vzp >= 0 && vzn >= 0) n[2] = tsdf[vzp] - tsdf[vzn];
-}
-
-// Exclusive prefix of v over the workgroup; total = sum over the workgroup.
-__device__ __forceinline__ int BlockExclusiveScan(int v, int* wave_sums,
-                                                  int& total) {
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int y = __shfl_up(x, off, 64);
-        if (lane >= off) x += y;
-    }
-    if (lane == 63) wave_sums[wave] = x;
-    __syncthreads();
-    int wave_off = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < kMeshBlock / 64; ++k) {
-        const int s = wave_sums[k];
-        if (k < wave) wave_off += s;
-        total += s;
-    }
-    __syncthreads();
-    return wave_off + x - v;
-}
-
 // Halo index of voxel (x, y, z), each in [-1, R].
 __device__ __forceinline__ int H(int x, int y, int z, int s) {
     return ((z + 1) * s + (y + 1)) * s + (x + 1);
 }
 
-// The block's 27 neighbour buffer indices into nb, then the (R+2)^3 halo
-// cells into `cell`: kOk / kNeg per voxel, then kCube per cube origin in
+// LoadNeighbours (key into xyz_b, 27 neighbours into nb), then the (R+2)^3
+// halo cells into `cell`: kOk / kNeg per voxel, then kCube per cube origin in
 // [-1, R-1]^3. Ends with a barrier.
 template <typename weight_t, int RT>
 __device__ void LoadBlock(const HashView& hv, const MeshArgs& a, Res<RT> rs,
                           int block_idx, int* nb, unsigned char* cell,
                           int* xyz_b) {
-    const int res = rs.R();
+    const int res = rs.r;
     const int s = res + 2;
     const int s3 = s * s * s;
-    const int* key = hv.key_buffer + 3 * (long long)block_idx;
-    const int xb = key[0], yb = key[1], zb = key[2];
-    xyz_b[0] = xb, xyz_b[1] = yb, xyz_b[2] = zb;
-    if (threadIdx.x < 27) {
-        const int t = threadIdx.x;
-        const int dz = t / 9, dy = (t % 9) / 3, dx = t % 3;
-        nb[t] = (t == 13) ? block_idx
-                          : hv.Find(xb + dx - 1, yb + dy - 1, zb + dz - 1);
-    }
-    __syncthreads();
+    LoadNeighbours(hv, block_idx, nb, xyz_b);
     const weight_t* __restrict__ weight = (const weight_t*)a.weight;
     const float thr = a.weight_threshold;
     for (int h = threadIdx.x; h < s3; h += kMeshBlock) {
@@ -222,9 +147,8 @@ MeshCountKernel(HashView hv, MeshArgs a, int* __restrict__ vcount,
     __shared__ int nb[27];
     __shared__ int xyz_b[3];
     __shared__ int wave_sums[kMeshBlock / 64];
-    Res<RT> rs;
-    rs.r = a.resolution;
-    const int res = rs.R(), s = res + 2, res3 = res * res * res;
+    const Res<RT> rs(a.resolution);
+    const int res = rs.r, s = res + 2, res3 = res * res * res;
     LoadBlock<weight_t>(hv, a, rs, a.indices[blockIdx.x], nb, cell, xyz_b);
     int vt = 0, tt = 0;
 #pragma unroll 1
@@ -232,14 +156,15 @@ MeshCountKernel(HashView hv, MeshArgs a, int* __restrict__ vcount,
         const int v = v0 + threadIdx.x;
         int nv = 0, nt = 0;
         if (v < res3) {
-            const int x = v % res, y = (v / res) % res, z = v / (res * res);
+            int x, y, z;
+            rs.Voxel(v, x, y, z);
             nv = __popc(VertexFlags(cell, x, y, z, s));
             const int c = CubeCase(cell, x, y, z, s);
             nt = c < 0 ? 0 : mc::kTriCount[c];
         }
         int sv, st;
-        (void)BlockExclusiveScan(nv, wave_sums, sv);
-        (void)BlockExclusiveScan(nt, wave_sums, st);
+        (void)BlockExclusiveScan<kMeshBlock>(nv, wave_sums, sv);
+        (void)BlockExclusiveScan<kMeshBlock>(nt, wave_sums, st);
         vt += sv;
         tt += st;
     }
@@ -268,9 +193,8 @@ MeshVertexKernel(HashView hv, MeshArgs a, const long long* __restrict__ voff,
     __shared__ int xyz_b[3];
     __shared__ int wave_sums[kMeshBlock / 64];
     if (OverCapacity(a)) return;
-    Res<RT> rs;
-    rs.r = a.resolution;
-    const int res = rs.R(), s = res + 2, res3 = res * res * res;
+    const Res<RT> rs(a.resolution);
+    const int res = rs.r, s = res + 2, res3 = res * res * res;
     const int block_idx = a.indices[blockIdx.x];
     LoadBlock<weight_t>(hv, a, rs, block_idx, nb, cell, xyz_b);
     const float* __restrict__ tsdf = a.tsdf;
@@ -281,14 +205,12 @@ MeshVertexKernel(HashView hv, MeshArgs a, const long long* __restrict__ voff,
         const int voxel_idx = v0 + threadIdx.x;
         int flags = 0, xv = 0, yv = 0, zv = 0;
         if (voxel_idx < res3) {
-            xv = voxel_idx % res;
-            yv = (voxel_idx / res) % res;
-            zv = voxel_idx / (res * res);
+            rs.Voxel(voxel_idx, xv, yv, zv);
             flags = VertexFlags(cell, xv, yv, zv, s);
         }
         int chunk_total;
-        const int rank = BlockExclusiveScan(__popc(flags), wave_sums,
-                                            chunk_total);
+        const int rank = BlockExclusiveScan<kMeshBlock>(
+                __popc(flags), wave_sums, chunk_total);
         long long idx = base + rank;
         if (voxel_idx < res3)
             vf[voxel_idx] = (unsigned)idx | ((flags & 1) ? kHas0 : 0u);
@@ -297,45 +219,11 @@ MeshVertexKernel(HashView hv, MeshArgs a, const long long* __restrict__ voff,
             const float tsdf_o = tsdf[linear_idx];
             float no[3] = {0, 0, 0}, ne[3] = {0, 0, 0};
             GetNormal(tsdf, xv, yv, zv, rs, nb, no);
-            const int x = xyz_b[0] * res + xv;
-            const int y = xyz_b[1] * res + yv;
-            const int z = xyz_b[2] * res + zv;
-            // `ne` carries over between the axes of a voxel, as in the
-            // reference (it is never reset).
             for (int e = 0; e < 3; ++e) {
                 if (!(flags & (1 << e))) continue;
-                const long long linear_idx_e = LinearIdx(
-                        xv + (e == 0), yv + (e == 1), zv + (e == 2), rs, nb);
-                const float tsdf_e = tsdf[linear_idx_e];
-                const float ratio = (0 - tsdf_o) / (tsdf_e - tsdf_o);
-                float* p = vertices + 3 * idx;
-                p[0] = a.voxel_size * ((float)x + ratio * (float)(int)(e == 0));
-                p[1] = a.voxel_size * ((float)y + ratio * (float)(int)(e == 1));
-                p[2] = a.voxel_size * ((float)z + ratio * (float)(int)(e == 2));
-                GetNormal(tsdf, xv + (e == 0), yv + (e == 1), zv + (e == 2),
-                          rs, nb, ne);
-                const float nx = (1 - ratio) * no[0] + ratio * ne[0];
-                const float ny = (1 - ratio) * no[1] + ratio * ne[1];
-                const float nz = (1 - ratio) * no[2] + ratio * ne[2];
-                const float norm =
-                        (float)((double)sqrtf(nx * nx + ny * ny + nz * nz) +
-                                1e-5);
-                float* nn = normals + 3 * idx;
-                nn[0] = nx / norm;
-                nn[1] = ny / norm;
-                nn[2] = nz / norm;
-                if (color != nullptr && colors != nullptr) {
-                    const color_t* co = color + 3 * linear_idx;
-                    const color_t* ce = color + 3 * linear_idx_e;
-                    const float r_o = (float)co[0], g_o = (float)co[1],
-                                b_o = (float)co[2];
-                    const float r_e = (float)ce[0], g_e = (float)ce[1],
-                                b_e = (float)ce[2];
-                    float* c = colors + 3 * idx;
-                    c[0] = ((1 - ratio) * r_o + ratio * r_e) / 255.0f;
-                    c[1] = ((1 - ratio) * g_o + ratio * g_e) / 255.0f;
-                    c[2] = ((1 - ratio) * b_o + ratio * b_e) / 255.0f;
-                }
+                EdgeVertex(tsdf, color, rs, nb, xyz_b, xv, yv, zv, e,
+                           linear_idx, tsdf_o, no, ne, a.voxel_size, true, idx,
+                           vertices, normals, colors);
                 ++idx;
             }
         }
@@ -370,9 +258,8 @@ MeshTriangleKernel(HashView hv, MeshArgs a, const long long* __restrict__ toff,
     __shared__ int xyz_b[3];
     __shared__ int wave_sums[kMeshBlock / 64];
     if (OverCapacity(a)) return;
-    Res<RT> rs;
-    rs.r = a.resolution;
-    const int res = rs.R(), s = res + 2, res3 = res * res * res;
+    const Res<RT> rs(a.resolution);
+    const int res = rs.r, s = res + 2, res3 = res * res * res;
     LoadBlock<weight_t>(hv, a, rs, a.indices[blockIdx.x], nb, cell, xyz_b);
     if (threadIdx.x < 27)
         pos[threadIdx.x] = nb[threadIdx.x] < 0
@@ -385,14 +272,13 @@ MeshTriangleKernel(HashView hv, MeshArgs a, const long long* __restrict__ toff,
         const int v = v0 + threadIdx.x;
         int c = -1, xv = 0, yv = 0, zv = 0;
         if (v < res3) {
-            xv = v % res;
-            yv = (v / res) % res;
-            zv = v / (res * res);
+            rs.Voxel(v, xv, yv, zv);
             c = CubeCase(cell, xv, yv, zv, s);
         }
         const int nt = c < 0 ? 0 : mc::kTriCount[c];
         int chunk_total;
-        const int rank = BlockExclusiveScan(nt, wave_sums, chunk_total);
+        const int rank =
+                BlockExclusiveScan<kMeshBlock>(nt, wave_sums, chunk_total);
         int32_t* tri = triangles + 3 * (base + rank);
         for (int k = 0; k < 3 * nt; ++k) {
             const int j = mc::kTriTable[c][k];
@@ -441,19 +327,13 @@ extern "C" int o3dmi_vbg_extract_mesh(
         o3dmi_stream_t stream) {
     O3DMI_REQUIRE(block_hash && n_vertices_out && n_triangles_out,
                   "null argument");
-    O3DMI_REQUIRE(n_blocks >= 0 && n_blocks < (1ll << 31),
-                  "n_blocks out of range");
-    O3DMI_REQUIRE(resolution > 0 && resolution <= kMaxMeshRes,
-                  "ExtractTriangleMesh: block resolution must be in [1, 32]");
-    O3DMI_REQUIRE(grid_dtype == O3DMI_F32 || grid_dtype == O3DMI_U16,
-                  "Unsupported value data type combination. Expected (float, "
-                  "float) or (uint16, uint16)");
     *n_vertices_out = 0;
     *n_triangles_out = 0;
-    if (n_blocks == 0) return O3DMI_OK;
-    O3DMI_REQUIRE(indices_dev && tsdf_dev && weight_dev,
-                  "TSDF and/or weight not allocated in blocks, please implement "
-                  "customized integration.");
+    int st = CheckSurfaceArgs(
+            n_blocks, resolution, kMaxMeshRes,
+            "ExtractTriangleMesh: block resolution must be in [1, 32]",
+            grid_dtype, indices_dev, tsdf_dev, weight_dev);
+    if (st || n_blocks == 0) return st;
     const bool write = vertex_capacity > 0;
     if (write)
         O3DMI_REQUIRE(vertices_dev && normals_dev && triangles_dev,
@@ -467,17 +347,17 @@ extern "C" int o3dmi_vbg_extract_mesh(
     const size_t n = (size_t)n_blocks;
     const size_t fixed = 8 * (2 + 2 * n) + scan_bytes + 4 * (2 * n + 2);
     const size_t first_bytes = write ? 4 * ((size_t)n * res3 + 1) : 0;
-    char* scratch = nullptr;
-    int st = PoolAlloc((void**)&scratch, fixed + first_bytes);
-    if (st) return st;
-    long long* totals = (long long*)scratch;
+    PoolScratch scratch(s);
+    char* mem = nullptr;
+    if ((st = scratch.Alloc(&mem, fixed + first_bytes))) return st;
+    long long* totals = (long long*)mem;
     long long* voff = totals + 2;
     long long* toff = voff + n;
     void* scan_tmp = (void*)(toff + n);
     int* vcount = (int*)((char*)scan_tmp + scan_bytes);
     int* tcount = vcount + n;
     int* err = tcount + n;
-    unsigned* vfirst = (unsigned*)(scratch + fixed);
+    unsigned* vfirst = (unsigned*)(mem + fixed);
 
     MeshArgs a;
     a.indices = indices_dev;
@@ -498,26 +378,17 @@ extern "C" int o3dmi_vbg_extract_mesh(
     const HashView hv = block_hash->view;
     const bool f32 = grid_dtype == O3DMI_F32;
 
-#define O3DMI_MESH_RES(KERNEL_RT, ...)                                         \
-    do {                                                                       \
-        if (resolution == 16) KERNEL_RT(16, __VA_ARGS__);                      \
-        else if (resolution == 8) KERNEL_RT(8, __VA_ARGS__);                   \
-        else KERNEL_RT(0, __VA_ARGS__);                                        \
-    } while (0)
-#define O3DMI_COUNT(RT, WT)                                                    \
-    hipLaunchKernelGGL((MeshCountKernel<WT, RT>), grid, block, lds, s, hv, a,  \
-                       vcount, tcount)
-#define O3DMI_VERTEX(RT, WT)                                                   \
-    hipLaunchKernelGGL((MeshVertexKernel<WT, WT, RT>), grid, block, lds, s,    \
-                       hv, a, voff, vfirst, vertices_dev, normals_dev,         \
-                       colors_dev)
-#define O3DMI_TRIANGLE(RT, WT)                                                 \
-    hipLaunchKernelGGL((MeshTriangleKernel<WT, RT>), grid, block, lds, s, hv,  \
-                       a, toff, vfirst, triangles_dev, err)
     hipError_t e = hipMemsetAsync(err, 0, sizeof(int), s);
     if (e == hipSuccess) {
-        if (f32) O3DMI_MESH_RES(O3DMI_COUNT, float);
-        else O3DMI_MESH_RES(O3DMI_COUNT, uint16_t);
+        WithRes(resolution, [&](auto rt) {
+            constexpr int RT = decltype(rt)::value;
+            if (f32)
+                hipLaunchKernelGGL((MeshCountKernel<float, RT>), grid, block,
+                                   lds, s, hv, a, vcount, tcount);
+            else
+                hipLaunchKernelGGL((MeshCountKernel<uint16_t, RT>), grid,
+                                   block, lds, s, hv, a, vcount, tcount);
+        });
         st = PrefixSumAsync(vcount, n_blocks, false, (int64_t*)voff,
                             (int64_t*)totals, scan_tmp, s);
         if (!st)
@@ -525,18 +396,25 @@ extern "C" int o3dmi_vbg_extract_mesh(
                                 (int64_t*)(totals + 1), scan_tmp, s);
     }
     if (e == hipSuccess && !st && write) {
-        if (f32) {
-            O3DMI_MESH_RES(O3DMI_VERTEX, float);
-            O3DMI_MESH_RES(O3DMI_TRIANGLE, float);
-        } else {
-            O3DMI_MESH_RES(O3DMI_VERTEX, uint16_t);
-            O3DMI_MESH_RES(O3DMI_TRIANGLE, uint16_t);
-        }
+        WithRes(resolution, [&](auto rt) {
+            constexpr int RT = decltype(rt)::value;
+            if (f32) {
+                hipLaunchKernelGGL((MeshVertexKernel<float, float, RT>), grid,
+                                   block, lds, s, hv, a, voff, vfirst,
+                                   vertices_dev, normals_dev, colors_dev);
+                hipLaunchKernelGGL((MeshTriangleKernel<float, RT>), grid,
+                                   block, lds, s, hv, a, toff, vfirst,
+                                   triangles_dev, err);
+            } else {
+                hipLaunchKernelGGL((MeshVertexKernel<uint16_t, uint16_t, RT>),
+                                   grid, block, lds, s, hv, a, voff, vfirst,
+                                   vertices_dev, normals_dev, colors_dev);
+                hipLaunchKernelGGL((MeshTriangleKernel<uint16_t, RT>), grid,
+                                   block, lds, s, hv, a, toff, vfirst,
+                                   triangles_dev, err);
+            }
+        });
     }
-#undef O3DMI_TRIANGLE
-#undef O3DMI_VERTEX
-#undef O3DMI_COUNT
-#undef O3DMI_MESH_RES
     long long host[3] = {0, 0, 0};
     if (e == hipSuccess) e = hipGetLastError();
     if (e == hipSuccess && !st)
@@ -546,7 +424,6 @@ extern "C" int o3dmi_vbg_extract_mesh(
         e = hipMemcpyAsync(&host[2], err, sizeof(int), hipMemcpyDeviceToHost,
                            s);
     hipError_t e2 = hipStreamSynchronize(s);
-    PoolFree(scratch);
     if (st) return st;
     O3DMI_HIP_CHECK(e);
     O3DMI_HIP_CHECK(e2);

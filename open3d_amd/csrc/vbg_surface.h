@@ -53,7 +53,10 @@ void WithRes(int res, F&& f) {
 
 __device__ __forceinline__ int Sgn(int x) { return (x > 0) - (x < 0); }
 
-// DeviceGetLinearIdx, VoxelBlockGridImpl.h:94-121. xo, yo, zo in [-R, 2R).
+// DeviceGetLinearIdx, VoxelBlockGridImpl.h:94-121. xo, yo, zo in [-R, 2R],
+// and 2R only at R = 1: EdgeVertex's GetNormal at the edge's far end reads
+// offset R + 1. Offset 2R maps to voxel 0 of the +1 neighbour, not of the +2
+// one, as in the reference; the oracles keep that.
 template <int RT>
 __device__ __forceinline__ long long LinearIdx(int xo, int yo, int zo,
                                                Res<RT> rs, const int* nb) {

@@ -338,6 +338,61 @@ int64_t ref_extract_point_cloud(const int* indices, const int* nb_indices,
     return rc == 0 ? (int64_t)valid_size : -1;
 }
 
+// ExtractTriangleMeshCPU<...>, VoxelBlockGridImpl.h:1383-1783 (instantiations
+// VoxelBlockGridCPU.cpp). Arguments as ref_extract_point_cloud, plus
+// inv_block_indices {capacity} (-1 except inv[indices[i]] = i). The vertex
+// count is always counted (vertex_count = -1). Rows past the capacities are
+// not copied; *n_vertices / *n_triangles are the full counts. Output order is
+// the atomic counters' (sequential with ref_set_threads(1)).
+int ref_extract_triangle_mesh(const int* indices, const int* inv_indices,
+                              const int* nb_indices, const uint8_t* nb_masks,
+                              const int* block_keys, int64_t capacity,
+                              const float* tsdf, const void* weight,
+                              const void* color_buf, int grid_is_f32,
+                              int64_t n_blocks, int resolution,
+                              float voxel_size, float weight_threshold,
+                              float* vertices, float* normals, float* colors,
+                              int64_t vertex_capacity, int32_t* triangles,
+                              int64_t triangle_capacity, int64_t* n_vertices,
+                              int64_t* n_triangles) {
+    return Guard([&] {
+        const core::Dtype gdt = grid_is_f32 ? core::Float32 : core::UInt16;
+        const int64_t r = resolution;
+        Tensor idx = Wrap(indices, {n_blocks}, core::Int32);
+        Tensor inv = Wrap(inv_indices, {capacity}, core::Int32);
+        Tensor nbi = Wrap(nb_indices, {27, n_blocks, 1}, core::Int32);
+        Tensor nbm = Wrap(nb_masks, {27, n_blocks, 1}, core::Bool);
+        Tensor keys = Wrap(block_keys, {capacity, 3}, core::Int32);
+        t::geometry::TensorMap vm("tsdf");
+        vm["tsdf"] = Wrap(tsdf, {capacity, r, r, r, 1}, core::Float32);
+        vm["weight"] = Wrap(weight, {capacity, r, r, r, 1}, gdt);
+        if (color_buf) vm["color"] = Wrap(color_buf, {capacity, r, r, r, 3}, gdt);
+        Tensor v, t, n, c;
+        int vertex_count = -1;
+        if (grid_is_f32)
+            vg::ExtractTriangleMeshCPU<float, float, float>(
+                    idx, inv, nbi, nbm, keys, vm, v, t, n, c, resolution,
+                    voxel_size, weight_threshold, vertex_count);
+        else
+            vg::ExtractTriangleMeshCPU<float, uint16_t, uint16_t>(
+                    idx, inv, nbi, nbm, keys, vm, v, t, n, c, resolution,
+                    voxel_size, weight_threshold, vertex_count);
+        *n_vertices = vertex_count;
+        *n_triangles = t.GetLength();
+        const int64_t m = std::min<int64_t>(vertex_count, vertex_capacity);
+        if (vertices && m > 0)
+            std::memcpy(vertices, v.GetDataPtr<float>(), sizeof(float) * 3 * m);
+        if (normals && m > 0)
+            std::memcpy(normals, n.GetDataPtr<float>(), sizeof(float) * 3 * m);
+        if (colors && color_buf && m > 0)
+            std::memcpy(colors, c.GetDataPtr<float>(), sizeof(float) * 3 * m);
+        const int64_t k = std::min<int64_t>(*n_triangles, triangle_capacity);
+        if (triangles && k > 0)
+            std::memcpy(triangles, t.GetDataPtr<int32_t>(),
+                        sizeof(int32_t) * 3 * k);
+    });
+}
+
 // EstimatePointWiseRobustNormalizedCovarianceKernel (PointCloudImpl.h:512-585)
 // per point over given hybrid-search results, and
 // EstimateNormalsFromCovariancesCPU (:1011-1063). The search itself

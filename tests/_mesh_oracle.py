@@ -32,7 +32,8 @@ def extract_triangle_mesh(keys, active, tsdf, weight, color, res, voxel_size,
     """keys {cap,3} int32 (by buffer index), active = buffer indices,
     tsdf / weight {cap, R^3} (weight float32 or uint16), color {cap, R^3, 3}
     or None -> dict(positions, normals[, colors], indices, block_vertices,
-    block_triangles)."""
+    block_triangles, cube_triangles). cube_triangles: the triangle count of
+    every cube that has triangles, in output order."""
     if table is None:
         table = project_table()
     edge_owner, tri_table, tri_count, corners, edge_table = table
@@ -49,7 +50,8 @@ def extract_triangle_mesh(keys, active, tsdf, weight, color, res, voxel_size,
              "normals": np.zeros((0, 3), f32),
              "indices": np.zeros((0, 3), np.int32),
              "block_vertices": np.zeros(n, np.int64),
-             "block_triangles": np.zeros(n, np.int64)}
+             "block_triangles": np.zeros(n, np.int64),
+             "cube_triangles": np.zeros(0, np.int64)}
     if color is not None:
         empty["colors"] = np.zeros((0, 3), f32)
     if n == 0:
@@ -202,7 +204,8 @@ def extract_triangle_mesh(keys, active, tsdf, weight, color, res, voxel_size,
     out = {"positions": positions, "normals": normals,
            "indices": tris.astype(np.int32),
            "block_vertices": has.reshape(n, -1).sum(1).astype(np.int64),
-           "block_triangles": ntri.reshape(n, R3).sum(1).astype(np.int64)}
+           "block_triangles": ntri.reshape(n, R3).sum(1).astype(np.int64),
+           "cube_triangles": ntri[ntri > 0].astype(np.int64)}
     if colors is not None:
         out["colors"] = colors
     return out

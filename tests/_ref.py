@@ -554,3 +554,38 @@ def normals_from_covariances(cov, normals=None):
         _p(cov), C.c_int64(n), int(cov.dtype == np.float64), _p(out),
         int(has)), "normals_from_covariances")
     return out
+
+
+def extract_triangle_mesh(indices, nb_indices, nb_masks, block_keys, tsdf,
+                          weight, color_buf, resolution, voxel_size,
+                          weight_threshold):
+    """The reference's ExtractTriangleMeshCPU body, counting pass included:
+    (vertices, normals, colors|None, triangles). inv_block_indices is built
+    here as VoxelBlockGrid::ExtractTriangleMesh builds it. Output order is
+    sequential only under set_threads(1)."""
+    indices = np.ascontiguousarray(indices, dtype=np.int32)
+    nb_indices = np.ascontiguousarray(nb_indices, dtype=np.int32)
+    nb_masks = np.ascontiguousarray(nb_masks, dtype=np.uint8)
+    block_keys = np.ascontiguousarray(block_keys, dtype=np.int32)
+    n = indices.shape[0]
+    capacity = block_keys.shape[0]
+    inv = np.full(capacity, -1, np.int32)
+    inv[indices] = np.arange(n, dtype=np.int32)
+    grid_is_f32 = int(weight.dtype == np.float32)
+    vcap = n * resolution ** 3 * 3
+    tcap = 3 * vcap
+    pts = np.zeros((vcap, 3), np.float32)
+    nrm = np.zeros((vcap, 3), np.float32)
+    col = np.zeros((vcap, 3), np.float32) if color_buf is not None else None
+    tri = np.zeros((tcap, 3), np.int32)
+    nv, nt = C.c_int64(0), C.c_int64(0)
+    _check(lib().ref_extract_triangle_mesh(
+        _p(indices), _p(inv), _p(nb_indices), _p(nb_masks), _p(block_keys),
+        C.c_int64(capacity), _p(tsdf), _p(weight), _p(color_buf), grid_is_f32,
+        C.c_int64(n), int(resolution), C.c_float(voxel_size),
+        C.c_float(weight_threshold), _p(pts), _p(nrm), _p(col),
+        C.c_int64(vcap), _p(tri), C.c_int64(tcap), C.byref(nv), C.byref(nt)),
+        "ref_extract_triangle_mesh")
+    m, k = nv.value, nt.value
+    assert m <= vcap and k <= tcap
+    return pts[:m], nrm[:m], (None if col is None else col[:m]), tri[:k]

@@ -5,12 +5,21 @@ oracle/ref_shim/README.md). Bit-exact unless stated.
 Runs wherever libo3d_ref.so exists (built here from the reference sources; it
 travels to the GPU box as a prebuilt file). Skipped otherwise.
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 
+import _mesh_oracle as mo
 import _oracle as orc
 import _ref as ref
 import _scene as sc
+import _surface_grids as sg
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                                "golden"))
+import make_mc_golden as mk  # noqa: E402
 
 pytestmark = pytest.mark.skipif(not ref.available(),
                                 reason="oracle/_ref/libo3d_ref.so not built")
@@ -461,6 +470,125 @@ def test_extract_point_cloud_vs_reference_body(grid_f32, with_color):
     assert b8[3] == a[3]
     key = lambda p: sc.sort_rows(np.concatenate(p[:2], axis=1))
     assert np.array_equal(key(b8), key(a))
+
+
+def _synthetic_grid(res, grid_f32, with_color, seed=0, edge_values=False):
+    """_surface_grids.sphere_blocks laid out in an oracle hash map ->
+    (hashmap, tsdf, weight, color) as _integrated_grid returns them; the
+    capacity leaves rows unused."""
+    wd = np.float32 if grid_f32 else np.uint16
+    keys, t, w, c = sg.sphere_blocks(res, wd, with_color, seed=seed,
+                                     edge_values=edge_values,
+                                     thresholds=(1.0, 2.0))
+    cap = keys.shape[0] + 7
+    hm = orc.HashMap(cap)
+    buf, fresh = hm.activate(keys)
+    assert fresh.all()
+    r = res
+    tsdf = np.zeros((cap, r, r, r), np.float32)
+    wgt = np.zeros((cap, r, r, r), wd)
+    tsdf.reshape(cap, -1)[buf] = t
+    wgt.reshape(cap, -1)[buf] = w
+    col = None
+    if with_color:
+        col = np.zeros((cap, r, r, r, 3), wd)
+        col.reshape(cap, -1, 3)[buf] = c
+    return hm, tsdf, wgt, col
+
+
+@pytest.mark.parametrize("res,with_color,edge_values", [
+    (4, True, False),    # a run-time power of two
+    (5, False, True),    # any other run-time value; exact +-0 tsdf
+    (12, True, True)])
+@pytest.mark.parametrize("grid_f32", [False, True])
+def test_extract_point_cloud_vs_reference_body_other_resolutions(
+        res, with_color, edge_values, grid_f32):
+    """As above at the resolutions the kernel takes at run time, on
+    synthetic grids with absent neighbours and negative keys."""
+    hm, tsdf, wgt, col = _synthetic_grid(res, grid_f32, with_color,
+                                         edge_values=edge_values)
+    active = np.sort(hm.active_indices())
+    nbi, nbm = orc.buffer_radius_neighbors(hm, active)
+    assert not nbm.all()
+    ref.set_threads(1)
+    for thr in (0.0, 1.0, 2.0):
+        a = orc.extract_point_cloud(active, nbi, nbm, hm.key_buffer(), tsdf,
+                                    wgt, col, res, 0.01, thr)
+        b = ref.extract_point_cloud(active, nbi, nbm, hm.key_buffer(), tsdf,
+                                    wgt, col, res, 0.01, thr)
+        assert a[3] == b[3] and a[3] > 100
+        assert a[0].tobytes() == b[0].tobytes()
+        assert a[1].tobytes() == b[1].tobytes()
+        if with_color:
+            assert a[2].tobytes() == b[2].tobytes()
+
+
+# ---------------------------------------------------------------------------
+# ExtractTriangleMesh: the numpy restatement (tests/_mesh_oracle.py) against
+# the reference's ExtractTriangleMeshCPU body
+# ---------------------------------------------------------------------------
+def _assert_mesh_matches_reference_body(hm, tsdf, wgt, col, res, voxel, thr):
+    cap = tsdf.shape[0]
+    active = np.sort(hm.active_indices())
+    nbi, nbm = orc.buffer_radius_neighbors(hm, active)
+    want = mo.extract_triangle_mesh(
+        hm.key_buffer(), active, tsdf.reshape(cap, -1), wgt.reshape(cap, -1),
+        None if col is None else col.reshape(cap, -1, 3), res,
+        np.float32(voxel), thr)
+    ref.set_threads(1)  # sequential: the counters follow workload order
+    v, n, c, t = ref.extract_triangle_mesh(active, nbi, nbm, hm.key_buffer(),
+                                           tsdf, wgt, col, res, voxel, thr)
+    assert want["positions"].shape[0] == v.shape[0]
+    assert want["positions"].tobytes() == v.tobytes()
+    assert want["normals"].tobytes() == n.tobytes()
+    if col is not None:
+        assert want["colors"].tobytes() == c.tobytes()
+    T = want["indices"]
+    assert T.shape[0] == t.shape[0]
+    # Both emit triangles cube by cube in the same cube order, with the same
+    # count per cube; the tables triangulate a cube's polygon differently, so
+    # each cube's directed boundary edges are compared.
+    counts = want["cube_triangles"]
+    assert counts.sum() == T.shape[0]
+    ends = np.cumsum(counts)
+    for s, e in zip(ends - counts, ends):
+        assert np.array_equal(mk.boundary_edges(T[s:e]),
+                              mk.boundary_edges(t[s:e])), (s, e)
+    return T.shape[0]
+
+
+@pytest.mark.parametrize("grid_f32", [False, True])
+@pytest.mark.parametrize("with_color", [True, False])
+def test_extract_triangle_mesh_vs_reference_body(grid_f32, with_color):
+    hm, tsdf, wgt, col, res, voxel = _integrated_grid(grid_f32)
+    if not with_color:
+        col = None
+    for thr in (0.0, 1.0, 2.0):
+        nt = _assert_mesh_matches_reference_body(hm, tsdf, wgt, col, res,
+                                                 voxel, thr)
+        assert nt > 2000
+
+
+@pytest.mark.parametrize("res,with_color,edge_values", [
+    (1, True, False),
+    (3, False, True),
+    (5, True, True),
+    (12, False, False)])
+@pytest.mark.parametrize("grid_f32", [False, True])
+def test_extract_triangle_mesh_vs_reference_body_other_resolutions(
+        res, with_color, edge_values, grid_f32):
+    """Synthetic grids with absent neighbours and negative keys; at R = 1
+    the normal at an edge's far end reads offset 2R, which both fold into
+    the +1 neighbour."""
+    hm, tsdf, wgt, col = _synthetic_grid(res, grid_f32, with_color,
+                                         edge_values=edge_values)
+    if edge_values:
+        active = hm.active_indices()
+        assert sg.has_edge_values(tsdf[active], wgt[active], (1.0, 2.0))
+    for thr in (0.0, 1.0, 2.0):
+        nt = _assert_mesh_matches_reference_body(hm, tsdf, wgt, col, res,
+                                                 0.01, thr)
+        assert nt > 50
 
 
 # ---------------------------------------------------------------------------

@@ -754,29 +754,46 @@ def test_unique_block_coordinates_of_a_point_cloud_and_integrate_from_them():
     assert (out[10:].cpu().numpy() == -9).all()
 
 
-@pytest.mark.parametrize("res", [16, 8])
+@pytest.mark.parametrize("res", [16, 8, 1, 3, 5, 12, 32, 64])
 def test_voxel_indices_coordinates_and_flattened_indices(res):
     """GetVoxelIndices / GetVoxelCoordinates /
     GetVoxelCoordinatesAndFlattenedIndices (VoxelBlockGrid.cpp:130-211,
-    kernel VoxelBlockGridImpl.h:43-92) on a grid with integrated frames: the
+    kernel VoxelBlockGridImpl.h:43-92) on a grid with integrated frames (16,
+    8) or with random keys, negative ones included (other resolutions): the
     forms that take the active indices and the forms given buffer indices
     (repeated, unordered), against the oracle on the grid's own key tensor,
     bit for bit; the flattened indices address the voxels they name in the
     value tensor; a buffer index outside the map is refused."""
     _lib, geometry = _gpu()
-    g = _mk_grid(geometry, False, block_count=4096, res=res)
-    for k in (0, 7):
-        d, c, K, Ts = sc.frames(k, 1, 320, 240)
-        g.integrate_frame(torch.from_numpy(d[0]).cuda(),
-                          torch.from_numpy(c[0]).cuda(), K, K, Ts[0])
+    rng = np.random.default_rng(2)
+    if res in (16, 8):
+        g = _mk_grid(geometry, False, block_count=4096, res=res)
+        for k in (0, 7):
+            d, c, K, Ts = sc.frames(k, 1, 320, 240)
+            g.integrate_frame(torch.from_numpy(d[0]).cuda(),
+                              torch.from_numpy(c[0]).cuda(), K, K, Ts[0])
+        n_blocks = 50
+    else:
+        # a few hundred blocks at small R, a few at large R
+        n_blocks = max(4, min(400, (1 << 18) // res ** 3))
+        g = _mk_grid(geometry, True, block_count=n_blocks + 64,
+                     with_color=False, res=res)
+        kk = np.unique(rng.integers(-40, 40, (2 * n_blocks, 3)), axis=0)
+        kk = kk[rng.permutation(kk.shape[0])[:n_blocks]].astype(np.int32)
+        m = kk.shape[0] * res ** 3
+        g.merge_blocks(torch.from_numpy(kk).cuda(),
+                       [torch.rand(m, device="cuda"),
+                        torch.ones(m, device="cuda")])
     hm = g.hashmap()
     keys = hm.key_tensor().cpu().numpy()
     active = hm.active_buf_indices()
-    assert active.shape[0] > 50
+    if res in (16, 8):
+        assert active.shape[0] > n_blocks
+    else:
+        assert active.shape[0] == n_blocks
     voxel = sc.VOXEL
-    rng = np.random.default_rng(2)
-    picks = torch.from_numpy(
-        active.cpu().numpy()[rng.integers(0, active.shape[0], 37)]).cuda()
+    picks = torch.from_numpy(active.cpu().numpy()[rng.integers(
+        0, active.shape[0], 37 if res <= 16 else 5)]).cuda()
     act_sorted = np.sort(active.cpu().numpy())
     for buf in (None, picks, active[:1], active[:0]):
         vi = g.voxel_indices(buf)
@@ -895,12 +912,12 @@ def test_raycast_parity(grid_f32):
 
 
 def _raycast_case(res, width, height, down, weight_threshold, n_frames,
-                  grid_f32=False):
+                  grid_f32=False, block_count=8192):
     """Integrate n_frames, then EstimateRange + RayCast (depth / vertex /
     normal / colour) on both sides; returns (oracle maps, library maps)."""
     _lib, geometry = _gpu()
-    g = _mk_grid(geometry, grid_f32, res=res, block_count=8192)
-    og = OracleGrid(grid_f32, 8192, res=res)
+    g = _mk_grid(geometry, grid_f32, res=res, block_count=block_count)
+    og = OracleGrid(grid_f32, block_count, res=res)
     for k in range(300, 300 + 2 * n_frames, 2):
         d, c, K, Ts = sc.frames(k, 1, width, height)
         keys = og.integrate(d[0], c[0], K, Ts[0])
@@ -936,13 +953,16 @@ def _assert_maps(want, got):
     (16, 200, 148, 4, 0.9),  # tiles cut by the right and the lower border
     (8, 320, 240, 4, 0.9),   # the kernel taking the resolution at run time
     (16, 72, 40, 8, 0.5),    # 15 tiles: fewer than two per XCD
+    (12, 320, 240, 4, 0.9),  # a run-time resolution, not a power of two
+    (6, 200, 148, 4, 0.9),   # ... and integrated by the scalar path
 ])
 def test_raycast_partial_tiles_and_block_resolutions(res, width, height, down,
                                                      min_hit):
     """The ray cast's workgroup tile is 32 x 8 pixels and the second phase of
     its march is a wave-wide loop: pixels past the image border keep a lane
     but no ray. Every map against the oracle."""
-    want, got = _raycast_case(res, width, height, down, 1.0, 6)
+    want, got = _raycast_case(res, width, height, down, 1.0, 6,
+                              block_count=16384 if res < 8 else 8192)
     assert (want["depth"] > 0).mean() > min_hit
     _assert_maps(want, got)
 

@@ -1256,9 +1256,11 @@ int VdsTiledImpl(const VdsLevelJob* jobs, int n_jobs, hipStream_t s,
         most_buckets = (1 << d.bucket_bits) > most_buckets ? 1 << d.bucket_bits
                                                            : most_buckets;
     }
-    // the counts posted by this level's reduce launch: only if every job asks
-    // and none of them inserts into a next level (the error word is final)
-    bool post = true;
+    // the counts posted by this level's reduce launch: only if the caller
+    // learns of it (posted), every job asks and none of them inserts into a
+    // next level (the error word is final). A post nobody is told of would
+    // zero the chain's counts and error word before the caller's own post.
+    bool post = posted != nullptr;
     for (int q = 0; q < n_jobs; ++q)
         post = post && jobs[q].post.counts && jobs[q].post.mail_data &&
                jobs[q].post.mail_flag && jobs[q].post.n >= 1 &&
@@ -1508,8 +1510,10 @@ int VdsPairAsync(const VdsLevelJob* jobs, int n_jobs, int dtype,
         return dtype == O3DMI_F64
                        ? VdsTiledImpl<double>(jobs, n_jobs, s, posted)
                        : VdsTiledImpl<float>(jobs, n_jobs, s, posted);
+    // one call per cloud, none of which posts: the caller posts the counts
     for (int q = 0; q < n_jobs; ++q) {
-        const VdsLevelJob& J = jobs[q];
+        VdsLevelJob J = jobs[q];
+        J.post = VdsPost{};
         int st;
         if (J.n_max > 0 && J.n_max <= kTiledMaxPoints)
             st = dtype == O3DMI_F64 ? VdsTiledImpl<double>(&J, 1, s)

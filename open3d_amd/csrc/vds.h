@@ -73,9 +73,10 @@ struct VdsLevelJob {
     double next_voxel_size = 0;
     bool from_previous = false;
 };
-// *posted (optional): whether the jobs' VdsPost requests were carried out
-// (tiled form, every job of the call asking); if not, the caller posts with
-// PostCountsPairAsync as before.
+// *posted: whether the jobs' VdsPost requests were carried out (tiled form,
+// every cloud <= kTiledMaxPoints, every job of the call asking); if not, the
+// caller posts with PostCountsPairAsync as before. Without `posted` no post
+// is made, whatever the jobs carry: a post always reaches a caller who knows.
 int VdsPairAsync(const VdsLevelJob* jobs, int n_jobs, int dtype,
                  std::vector<void*>& scratch, hipStream_t s,
                  bool* posted = nullptr);

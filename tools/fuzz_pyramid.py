@@ -9,7 +9,12 @@ posting launch: O3DMI_VDS_UNPAIRED=1 O3DMI_VDS_NO_FUSE=1
 O3DMI_VDS_POST_LAUNCH=1). Every iteration's rmse, the final pose, fitness and
 the iteration count must be the same bits.
 
-  python tools/fuzz_pyramid.py [--cases 40] [--seed 1]
+--large: source and target sizes drawn independently from 700 000 ..
+1 500 000 points, about half the pairs straddling the tiled VoxelDownSample's
+2^20-point limit (one cloud tiled, the other on the sort form: one call per
+cloud), 1 to 5 scales, 12 cases by default.
+
+  python tools/fuzz_pyramid.py [--cases 40] [--seed 1] [--large]
 """
 import argparse
 import json
@@ -20,7 +25,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def emit(cases, seed):
+def emit(cases, seed, large):
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
@@ -28,20 +33,34 @@ def emit(cases, seed):
     rng = np.random.default_rng(seed)
     out = []
     for case in range(cases):
-        r = rng.random()
-        n = int(rng.integers(200, 5000)) if r < 0.3 else (
-            int(rng.integers(5000, 60000)) if r < 0.8 else
-            int(rng.integers(60000, 250000)))
+        if large:
+            ns = int(rng.integers(700_000, 1_500_001))
+            nt = int(rng.integers(700_000, 1_500_001))
+            n = max(ns, nt)
+        else:
+            r = rng.random()
+            n = int(rng.integers(200, 5000)) if r < 0.3 else (
+                int(rng.integers(5000, 60000)) if r < 0.8 else
+                int(rng.integers(60000, 250000)))
         dtype = np.float32 if rng.random() < 0.75 else np.float64
         n_scales = int(rng.integers(1, 6))
         v0 = float(rng.choice([0.02, 0.04, 0.08]))
         voxels = [v0 / (2 ** k) for k in range(n_scales)]
         if rng.random() < 0.3:
             voxels[-1] = -1.0          # the finest level is the input itself
-        p = syn.make_icp_pair(n, n, seed=int(rng.integers(1, 1 << 30)),
-                              dtype=dtype)
-        ns = int(rng.integers(n // 2 + 1, n + 1))
-        nt = int(rng.integers(n // 2 + 1, n + 1))
+        if large:
+            # device-resident sizes: buffers a little larger than the clouds
+            # (their capacities decide the form, and may straddle 2^20 when
+            # the live sizes do not)
+            p = syn.make_icp_pair(ns + int(rng.integers(0, 40_000)),
+                                  nt + int(rng.integers(0, 40_000)),
+                                  seed=int(rng.integers(1, 1 << 30)),
+                                  dtype=dtype)
+        else:
+            p = syn.make_icp_pair(n, n, seed=int(rng.integers(1, 1 << 30)),
+                                  dtype=dtype)
+            ns = int(rng.integers(n // 2 + 1, n + 1))
+            nt = int(rng.integers(n // 2 + 1, n + 1))
         src = torch.from_numpy(p["source"]).cuda()
         tgt = torch.from_numpy(p["target"]).cuda()
         nrm = torch.from_numpy(p["target_normals"]).cuda()
@@ -54,12 +73,14 @@ def emit(cases, seed):
                      use_dev)
         except Exception as e:   # (e.g. a singular system: the same either way)
             out.append([n, ns, nt, dtype.__name__, voxels, "error: %s" % e,
-                        -1, "", "", [repr(x["inlier_rmse"]) for x in log]])
+                        -1, "", "", [repr(x["inlier_rmse"]) for x in log],
+                        [repr(x["fitness"]) for x in log]])
             continue
         out.append([n, ns, nt, dtype.__name__, voxels,
                     r_.transformation.tobytes().hex(), r_.num_iterations,
                     repr(r_.fitness), repr(r_.inlier_rmse),
-                    [repr(e["inlier_rmse"]) for e in log]])
+                    [repr(e["inlier_rmse"]) for e in log],
+                    [repr(e["fitness"]) for e in log]])
     print(json.dumps(out))
 
 
@@ -76,12 +97,15 @@ def one(reg, torch, src, tgt, nrm, ns, nt, voxels, crit, md, log, use_dev):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--cases", type=int, default=40)
+    ap.add_argument("--cases", type=int, default=None)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--large", action="store_true")
     ap.add_argument("--emit", action="store_true")
     a = ap.parse_args()
+    if a.cases is None:
+        a.cases = 12 if a.large else 40
     if a.emit:
-        return emit(a.cases, a.seed)
+        return emit(a.cases, a.seed, a.large)
 
     def run(extra):
         env = dict(os.environ)
@@ -91,8 +115,8 @@ def main():
         env.update(extra)
         r = subprocess.run([sys.executable, os.path.abspath(__file__),
                             "--emit", "--cases", str(a.cases), "--seed",
-                            str(a.seed)], env=env, capture_output=True,
-                           text=True)
+                            str(a.seed)] + (["--large"] if a.large else []),
+                           env=env, capture_output=True, text=True)
         if r.returncode != 0:
             print(r.stderr[-3000:])
             sys.exit(2)
@@ -108,8 +132,15 @@ def main():
             bad += 1
             print("MISMATCH case %d: n %d ns %d nt %d %s voxels %s" %
                   (k, x[0], x[1], x[2], x[3], x[4]))
-    print("fuzz_pyramid: %d cases, %d mismatches; iterations %d..%d" %
-          (len(fast), bad, min(c[6] for c in fast), max(c[6] for c in fast)))
+    print("fuzz_pyramid%s: %d cases, %d mismatches; iterations %d..%d" %
+          (" --large" if a.large else "", len(fast), bad,
+           min(c[6] for c in fast), max(c[6] for c in fast)))
+    if a.large:
+        lim = 1 << 20
+        print("  pairs straddling 2^20: %d; both beyond: %d; both within: %d"
+              % (sum((c[1] > lim) != (c[2] > lim) for c in fast),
+                 sum(c[1] > lim and c[2] > lim for c in fast),
+                 sum(c[1] <= lim and c[2] <= lim for c in fast)))
     return 1 if bad else 0
 
 

@@ -1255,6 +1255,7 @@ static void MakeIntegArgs(o3dmi_vbg* g, const StreamCommon& c,
     ia->voxel_size = g->voxel_size;
     ia->sdf_trunc = g->voxel_size * c.trunc;
     ia->depth_max = c.depth_max;
+    ia->depth_scale = c.depth_scale;
     ia->zero_counter = g->ring_counters + ((grp.seq + 2) & 3);
     ia->size_host = (int*)g->stream_status;
     ia->status_stamp = grp.stamp;

@@ -64,7 +64,8 @@ struct alignas(16) ReadyEntry {
 
 // Per-pixel prepared record (u16 depth / u8 colour inputs).
 struct alignas(8) PixelRec {
-    float d;        // float(depth) / depth_scale
+    float d;        // float(depth) / depth_scale, -inf where that is <= 0 or
+                    // > depth_max (invalid: the integrate role skips it)
     unsigned rgba;  // r | g<<8 | b<<16 | (colour pixel in bounds)<<24
 };
 
@@ -94,7 +95,7 @@ struct FrameFrontArgs {
     const int* row_lut;
     bool depth_div_short;
     bool prep_identity;   // col_lut[u] == u and row_lut[v] == v everywhere
-    PixelRec* recs;       // {rows, cols} out, + 1 sentinel record {0, 0}
+    PixelRec* recs;       // {rows, cols} out, + 1 sentinel record {-inf, 0}
     FrameBlock* list;     // the group's list (shared by its frames)
     int64_t list_capacity;
     int* count;           // the group's count; 0 before the group's first frame
@@ -130,6 +131,7 @@ struct IntegrateStreamArgs {
     const double* depth_intrinsic;
     int resolution;
     float voxel_size, sdf_trunc, depth_max;
+    float depth_scale;    // the front roles' (integrate_checks.h)
     // bookkeeping done by workgroup 0 (any may be null):
     int* zero_counter;    // device int reset to 0 (a future group's count)
     int* size_host;       // host-mapped {heap_top, error flags, count, stamp}

@@ -24,7 +24,9 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 
+#include "integrate_checks.h"
 #include "stream_path.h"
 #include "sliced_path.h"
 #include "touch_device.h"
@@ -49,6 +51,16 @@ __device__ __forceinline__ float DivByConst(float a, float b, float y) {
     const float r = __builtin_fmaf(-b, q0, a);
     return __builtin_fmaf(r, y, q0);
 }
+// A prepared record's depth: the integrate lambda's two depth tests
+// (VoxelBlockGridImpl.h:263, `depth <= 0 || depth > depth_max` -> skip) are
+// taken here, once per pixel, and an invalid depth is stored as -inf. The integrate role's short
+// test then needs no depth compare of its own: -inf - z < -sdf_trunc
+// (integrate_checks.h DepthFoldPoseOk); its full test (IEEE-division forms,
+// chunk launch) reads -inf as invalid just like the depth itself.
+__device__ __forceinline__ float RecordDepth(float d, float depth_max) {
+    return (!(d <= 0) && !(d > depth_max)) ? d : -__builtin_inff();
+}
+
 struct PrepParams {
     Camera color_cam;  // colour intrinsics, identity extrinsic, scale 1
     int color_rows, color_cols;
@@ -373,7 +385,7 @@ __device__ __forceinline__ void FrontRole(const HashView& hv,
     // sentinel behind the image: what a voxel outside the image reads
     if (wg == n_touch_wg && threadIdx.x == 0) {
         PixelRec r;
-        r.d = 0.0f;
+        r.d = -__builtin_inff();
         r.rgba = 0u;
         recs[n_px] = r;
     }
@@ -432,7 +444,7 @@ __device__ __forceinline__ void FrontRole(const HashView& hv,
                                     ? DivByConst(df, p.depth_scale,
                                                  fp.inv_depth_scale)
                                     : df / p.depth_scale;
-                    w[2 * j] = __float_as_uint(d);
+                    w[2 * j] = __float_as_uint(RecordDepth(d, p.depth_max));
                     w[2 * j + 1] = rgba[j];
                 }
                 o[0] = make_uint4(w[0], w[1], w[2], w[3]);
@@ -506,10 +518,11 @@ __device__ __forceinline__ void FrontRole(const HashView& hv,
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 PixelRec r;
-                r.d = fp.depth_div_short
-                              ? DivByConst(df[k], p.depth_scale,
-                                           fp.inv_depth_scale)
-                              : df[k] / p.depth_scale;
+                r.d = RecordDepth(fp.depth_div_short
+                                          ? DivByConst(df[k], p.depth_scale,
+                                                       fp.inv_depth_scale)
+                                          : df[k] / p.depth_scale,
+                                  p.depth_max);
                 r.rgba = rgba[k];
                 if (first + k * step < n_px) recs[idx[k]] = r;
             }
@@ -521,7 +534,7 @@ __device__ __forceinline__ void FrontRole(const HashView& hv,
         const int vi = i / p.cols;
         const int ui = i - vi * p.cols;
         PixelRec r;
-        r.d = (float)depth[i] / p.depth_scale;
+        r.d = RecordDepth((float)depth[i] / p.depth_scale, p.depth_max);
         r.rgba = 0u;
         if (pp.with_color) {
             float x, y, z, uf, vf;
@@ -611,10 +624,8 @@ __device__ __forceinline__ float RcpSmallInt(float b) {
     return __builtin_fmaf(e, r0, r0);
 }
 
-// Lower bound of the magnitudes DivByConst handles itself; smaller inputs
-// (zeros, denormals and their neighbourhood, where the exact-residual argument
-// needs gradual underflow to cooperate) take the IEEE sequence.
-constexpr float kDivTiny = 1.0e-30f;
+// (kDivTiny, the lower bound of the magnitudes DivByConst handles itself:
+// integrate_checks.h)
 
 __device__ __forceinline__ float DivByConstGuarded(float a, float b, float y) {
     // wave-uniform branch: the IEEE sequence only when some lane needs it
@@ -766,6 +777,11 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
     using WVec = Vec<weight_t, kV, kV * sizeof(weight_t)>;
     using CVec = Vec<color_t, 3 * kV, kV * sizeof(color_t)>;
     constexpr bool kU16 = sizeof(weight_t) == 2;
+    // The frame stream's records form with the verified short divisions:
+    // the depth tests folded into the records and no underflow guard on
+    // sdf / sdf_trunc (the host launches the IEEE-division form instead when
+    // a proof of integrate_checks.h fails for the launch)
+    constexpr bool kFold = kDiv >= 2 && !kRaw && !kLong;
     float* __restrict__ tsdf_base = ip.tsdf;
     weight_t* __restrict__ weight_base = (weight_t*)ip.weight;
     color_t* __restrict__ color_base = (color_t*)ip.color;
@@ -994,6 +1010,36 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
                         cf[v][i] = (float)c12.v[3 * v + i];
             }
         }
+        // Facts of the whole work item, wave-uniform (one ballot each, kept
+        // in scalar registers; apply takes ONE scalar branch on them per
+        // round instead of paying vector instructions per voxel; kFold forms
+        // only -- the others keep today's update):
+        //   c_small -- every colour state of the wave is <= 255. Then
+        //     weight * c (weight <= 65535) + in (<= 255) is an integer below
+        //     2^24, exact in float32, and fma(weight, c, in) has the bits of
+        //     the separate multiply and add. The update keeps c <= 255 (the
+        //     truncated mean of values <= 255), so the fact holds for every
+        //     frame of the item. A state above 255 (loaded through the API)
+        //     keeps the multiply + add.
+        //   may_wrap -- some weight of the wave plus the group's frame count
+        //     reaches 65536: only then can the uint16 wrap below happen.
+        bool c_small = !(kColor && sizeof(color_t) == 2), may_wrap = true;
+        if constexpr (kU16 && kFold) {
+            float w_max = wf[0];
+#pragma unroll
+            for (int v = 1; v < kV; ++v) w_max = fmaxf(w_max, wf[v]);
+            may_wrap = __builtin_amdgcn_ballot_w64(
+                               w_max + (float)ip.n_frames >= 65536.0f) != 0ull;
+            if constexpr (kColor && sizeof(color_t) == 2) {
+                float c_max = cf[0][0];
+#pragma unroll
+                for (int v = 0; v < kV; ++v)
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) c_max = fmaxf(c_max, cf[v][i]);
+                c_small = __builtin_amdgcn_ballot_w64(c_max > 255.0f) == 0ull;
+            }
+        }
+        const bool short_item = kU16 && kFold && c_small && !may_wrap;
 
         // 2. projections + record requests of every frame.
         // Camera::RigidTransform (GeometryIndexer.h:62-78): x * scale, then
@@ -1191,24 +1237,14 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
                         ((R.in_mask >> (fk * kV + 2 * p + 1)) & 1u) ? q.y : 0.0f;
             }
         };
-        auto apply = [&](int c0, Round& R) {
-        // 3. frames applied in order (VoxelBlockGridImpl.h:258-302). The
-        // update of a voxel runs under the voxel's own predicate (an
-        // exec-masked region per voxel of the lane) instead of being computed
-        // for every lane and selected. Why: on gfx950 a v_cndmask, a v_cmp, a
-        // v_trunc or a conversion occupies the SIMD's issue for 4.3 cycles, a
-        // plain float32 multiply / add / fma for 2.4, and a PACKED float32
-        // instruction for 4.3 -- no cheaper than the two plain ones it
-        // replaces (profiles/r5b_valu_calibration.json). Rounds 2-4 ran this
-        // block as packed pairs with two selects per state value; the selects
-        // were a quarter of its cycles. A region whose predicate is false in
-        // every lane of the wave is jumped over (s_cbranch_execz): the
-        // wave-level "no voxel takes this frame" test of the packed form is
-        // implied. Same IEEE operations, operands and order: same bits.
-#pragma unroll
-        for (int fk = 0; fk < kChunk; ++fk) {
-            if (!((R.cbits >> fk) & 1u)) continue;  // wave-uniform
-            if constexpr (kRaw) convert_depth(fk, R);
+        // One frame's update of the lane's voxels (3. below). kShort: the
+        // work item's facts c_small and !may_wrap hold -- colour as one fma,
+        // no uint16 wrap test. The two forms are separate code behind ONE
+        // wave-uniform branch per round: behind a branch per voxel the
+        // compiler computes both colour forms and selects (v_cndmask); behind
+        // one per frame the step kernel needs 72 registers and spills.
+        auto update = [&](int fk, Round& R, auto short_form) {
+            constexpr bool kShort = decltype(short_form)::value;
 #pragma unroll
             for (int p = 0; p < kP; ++p) {
 #pragma unroll
@@ -1216,8 +1252,14 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
                     const float dh = R.rec[fk][2 * p + h].d;
                     const float zh = h ? R.zc[fk][p].y : R.zc[fk][p].x;
                     const float sh = dh - zh;
-                    const bool ok = !(dh <= 0) && !(dh > ip.depth_max) &&
-                                    !(zh <= 0) && !(sh < -ip.sdf_trunc);
+                    // kFold: the depth tests were taken by the prepare pass
+                    // (an invalid depth is -inf: sh = -inf < -sdf_trunc),
+                    // valid for launches whose poses the host checked
+                    const bool ok =
+                            kFold ? !(zh <= 0) && !(sh < -ip.sdf_trunc)
+                                  : !(dh <= 0) && !(dh > ip.depth_max) &&
+                                            !(zh <= 0) &&
+                                            !(sh < -ip.sdf_trunc);
                     if (!ok) continue;
                     touched = true;
                     // sh < trunc ? sh : trunc as ONE v_min_f32 (2.4 cycles
@@ -1230,9 +1272,10 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
                         : "=v"(cl)
                         : "s"(ip.sdf_trunc), "v"(sh));
                     // sdf / sdf_trunc: the verified short form, the IEEE
-                    // sequence in the underflow range
+                    // sequence in the underflow range (kFold: unreachable,
+                    // integrate_checks.h SdfDivGuardRedundant)
                     float sd;
-                    if (kDiv < 1 || fabsf(cl) < kDivTiny)
+                    if (kDiv < 1 || (!kFold && fabsf(cl) < kDivTiny))
                         sd = cl / ip.sdf_trunc;
                     else
                         sd = DivByConst(cl, ip.sdf_trunc, ip.inv_sdf_trunc);
@@ -1258,8 +1301,14 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
                             for (int i = 0; i < 3; ++i) {
                                 const float in =
                                         (float)((rg >> (8 * i)) & 0xffu);
-                                float c_new =
-                                        (weight * cf[vx][i] + in) * inv_wsum;
+                                float c_new;
+                                if constexpr (kShort)  // exact: c_small
+                                    c_new = __builtin_fmaf(weight, cf[vx][i],
+                                                           in) *
+                                            inv_wsum;
+                                else
+                                    c_new = (weight * cf[vx][i] + in) *
+                                            inv_wsum;
                                 if constexpr (sizeof(color_t) == 2)
                                     c_new = truncf(c_new);
                                 cf[vx][i] = c_new;
@@ -1267,14 +1316,40 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
                         }
                     }
                     wf[vx] = wsum;
-                    if constexpr (kU16) {
+                    if constexpr (kU16 && !kShort) {
                         // what the uint16 store keeps of 65536 (a branch that
                         // is taken once in 65536 frames, not a select)
                         if (wsum >= 65536.0f) wf[vx] = 0.0f;
                     }
                 }
             }
-        }
+        };
+        auto apply = [&](int c0, Round& R) {
+        // 3. frames applied in order (VoxelBlockGridImpl.h:258-302). The
+        // update of a voxel runs under the voxel's own predicate (an
+        // exec-masked region per voxel of the lane) instead of being computed
+        // for every lane and selected. Why: on gfx950 a v_cndmask, a v_cmp, a
+        // v_trunc or a conversion occupies the SIMD's issue for 4.3 cycles, a
+        // plain float32 multiply / add / fma for 2.4, and a PACKED float32
+        // instruction for 4.3 -- no cheaper than the two plain ones it
+        // replaces (profiles/r5b_valu_calibration.json). Rounds 2-4 ran this
+        // block as packed pairs with two selects per state value; the selects
+        // were a quarter of its cycles. A region whose predicate is false in
+        // every lane of the wave is jumped over (s_cbranch_execz): the
+        // wave-level "no voxel takes this frame" test of the packed form is
+        // implied. Same IEEE operations, operands and order: same bits.
+        auto frames = [&](auto short_form) {
+#pragma unroll
+            for (int fk = 0; fk < kChunk; ++fk) {
+                if (!((R.cbits >> fk) & 1u)) continue;  // wave-uniform
+                if constexpr (kRaw) convert_depth(fk, R);
+                update(fk, R, short_form);
+            }
+        };
+        if (short_item)  // wave-uniform
+            frames(std::true_type());
+        else
+            frames(std::false_type());
         };
         // The end of a round: s_waitcnt vmcnt(0) (expcnt, lgkmcnt left at
         // their maxima, 7 and 15). It costs nothing -- apply has already
@@ -1708,9 +1783,16 @@ int LaunchFrameStep(o3dmi_hash* bh, const FrameFrontArgs* fronts, int n_fronts,
         ip.n_frames = a->n_frames;
         ip.group_stamp = a->group_stamp;
         ip.touch_plane = a->touch_plane & 1;
+        // the short update of the kDiv = 2 form (IntegrateRoleWide, kFold)
+        // needs both proofs of integrate_checks.h for the whole launch: the
+        // poses are checked frame by frame, but one rejected pose sends the
+        // WHOLE group to the IEEE-division form (same bits, ~4 % slower)
+        bool fold = SdfDivGuardRedundant(a->depth_scale, a->sdf_trunc);
         for (int f = 0; f < a->n_frames; ++f) {
             const Camera cf = Camera::Make(a->depth_intrinsic, a->extrinsic[f],
                                            a->voxel_size);
+            fold = fold && DepthFoldPoseOk(cf.e, a->voxel_size, a->resolution,
+                                           a->sdf_trunc);
             if (f == 0) {
                 ip.cam0 = cf;
                 CanonicalPrincipalPoint(ip.cam0);
@@ -1730,6 +1812,8 @@ int LaunchFrameStep(o3dmi_hash* bh, const FrameFrontArgs* fronts, int n_fronts,
         ip.sdf_trunc = a->sdf_trunc;
         ip.depth_max = a->depth_max;
         fast_div = VerifyFastDivision(a->sdf_trunc, &ip.inv_sdf_trunc);
+        // otherwise the IEEE-division form: every per-voxel test, same bits
+        if (!fold) fast_div = 0;
         ip.list = a->list;
         ip.ready = a->ready;
         ip.count = a->count;

@@ -606,6 +606,98 @@ int o3dmi_fpfh_from_neighbors(const void* points_dev, const void* normals_dev,
                               void* fpfhs_dev, int64_t* n_fpfh_out,
                               o3dmi_stream_t stream);
 
+/* ---- RANSAC on correspondences: the two kernel steps --------------------
+ * The legacy (Eigen, float64) RegistrationRANSACBasedOnCorrespondence
+ * (pipelines/registration/Registration.cpp:212-380) has no tensor version and
+ * draws from one generator shared by TBB threads, so which hypotheses it sees
+ * depends on thread timing. This library fixes ONE reading -- the reference
+ * loop run by a single thread over a stateless sample stream -- and reproduces
+ * it exactly however the work is batched. The contract:
+ *
+ * 1. Samples. Draw j (0 <= j < ransac_n) of iteration i >= 0 is a pure
+ *    function of (seed, i, j), in uint64 arithmetic modulo 2^64:
+ *        z = seed + 0x9E3779B97F4A7C15 * (8 * i + j + 1)
+ *        z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9
+ *        z ^= z >> 27;  z *= 0x94D049BB133111EB
+ *        z ^= z >> 31
+ *        draw = (z * n_corres) >> 64        (high half of the 128-bit product)
+ *    Draws may repeat inside an iteration, as the reference's do.
+ * 2. Hypothesis. TransformationEstimationPointToPoint without scaling over the
+ *    ransac_n sampled pairs (3 <= ransac_n <= 8): points widened to float64,
+ *    means (sum in sample order / ransac_n), the centred 3x3 sum
+ *    sum (t - mean_t)(s - mean_s)^T in sample order, then the Jacobi routine
+ *    of o3dmi_compute_rt_p2point (one shared body). A sample whose second
+ *    singular value is not above 1e-12 of the first (repeated or collinear
+ *    pairs) is rejected like a failed check (the reference validates whatever
+ *    Eigen::umeyama returns for it).
+ * 3. Checks (CorrespondenceChecker.cpp:19-83) in the caller's order, each kind
+ *    at most once, float64 on the widened points: edge length (every pair
+ *    a < b of the sample fails when |s_a - s_b| < |t_a - t_b| * threshold or
+ *    |t_a - t_b| < |s_a - s_b| * threshold), distance (|t - T s| > threshold
+ *    fails), normal (n_t . R n_s < cos(threshold) fails; passes when either
+ *    cloud has no normals). A rejected iteration is not a validation.
+ * 4. Validation. fitness and inlier_rmse of iteration i are what
+ *    o3dmi_registration_evaluate(source, target, max_distance, T_i) defines:
+ *    T cast to the point dtype, points moved in the point dtype, nearest
+ *    target point with d2 < r2, lowest index on ties. The inlier count is that
+ *    call's count exactly; the d2 (point dtype) are summed in float64 in a
+ *    fixed order (per 256-point tile, then over tiles; no floating-point
+ *    atomics), so the sum repeats run to run and does not depend on the batch.
+ * 5. Best. RegistrationResult::IsBetterRANSACThan, strict (higher fitness;
+ *    equal fitness: lower inlier_rmse), scanning iterations in ascending i: on
+ *    a full tie the lower i stays.
+ * 6. Early exit. When iteration i becomes the best, the share of ALL given
+ *    correspondences with |T s - t|^2 < max_distance^2 (s moved as in 4, the
+ *    difference and its square sum in the point dtype) gives, in host float64,
+ *    k = log(1 - confidence) / log(1 - ratio^ransac_n)
+ *    (Registration.cpp:315-324): k < 0 leaves the bound alone, otherwise
+ *    est_k = min(est_k, ceil(k)). est_k starts at max_iteration; iteration i
+ *    takes part iff i < est_k as left by every iteration before it. Batches
+ *    run past the bound; what they computed there is discarded.
+ * 7. Result: see o3dmi_registration_ransac_correspondence (o3d_mi355x_host.h).
+ *
+ * o3dmi_ransac_hypotheses: iterations first_iteration .. first_iteration +
+ * count - 1, one lane each (rules 1-3). corres_dev int64 {n_corres, 2} (source
+ * row, target row); a pair outside [0, ns) x [0, nt) is never read and fails
+ * its iteration. source/target_normals_dev may be NULL. checker_types: 0 edge
+ * length, 1 distance, 2 normal; num_checkers <= 3. Outputs: samples_dev int64
+ * {count, ransac_n} (rows of corres_dev), transformations_dev float64
+ * {count, 16} row-major, pass_dev int32 {count} (1 = to be validated). */
+#define O3DMI_RANSAC_CHECK_EDGE_LENGTH 0
+#define O3DMI_RANSAC_CHECK_DISTANCE 1
+#define O3DMI_RANSAC_CHECK_NORMAL 2
+#define O3DMI_RANSAC_MAX_N 8
+int o3dmi_ransac_hypotheses(uint64_t seed, int64_t first_iteration,
+                            int64_t count, const void* source_dev, int64_t ns,
+                            const void* target_dev, int64_t nt,
+                            const void* source_normals_dev,
+                            const void* target_normals_dev, int dtype,
+                            const int64_t* corres_dev, int64_t n_corres,
+                            int ransac_n, int num_checkers,
+                            const int* checker_types,
+                            const double* checker_thresholds,
+                            int64_t* samples_dev, double* transformations_dev,
+                            int32_t* pass_dev, o3dmi_stream_t stream);
+
+/* Rules 4 and 6 for b given transformations in one pass over the source: a
+ * work item is (a few transformations, a tile of 256 source points); the tile
+ * is loaded once, the matrices are wave-uniform, every lane runs the k = 1
+ * search of `nns` (the target's index, radius = max_distance; target_dev are
+ * the same points in their original order). transformations_dev float64
+ * {b, 16}. Outputs {b}: counts_dev int64 (inliers), d2_sums_dev float64,
+ * corres_inliers_dev int64 (may be NULL with corres_dev). scratch_dev: device
+ * memory of o3dmi_ransac_score_scratch_bytes(ns, b) bytes (8-byte aligned) for
+ * the per-tile partials, the caller's until the queued work has run. Stream-
+ * ordered: queues its launches on `stream` and returns without waiting. */
+size_t o3dmi_ransac_score_scratch_bytes(int64_t ns, int64_t b);
+int o3dmi_ransac_score(const o3dmi_nns_t* nns, const void* source_dev,
+                       int64_t ns, const void* target_dev, int64_t nt,
+                       const double* transformations_dev, int64_t b,
+                       const int64_t* corres_dev, int64_t n_corres,
+                       int64_t* counts_dev, double* d2_sums_dev,
+                       int64_t* corres_inliers_dev, void* scratch_dev,
+                       o3dmi_stream_t stream);
+
 /* EstimateColorGradientsUsing{Hybrid,KNN}SearchCUDA after the search
  * (t/geometry/kernel/PointCloudImpl.h:1067-1290): per point, least squares of
  * the intensity over its neighbours projected on the tangent plane plus the

@@ -9,6 +9,8 @@
  *   o3dmi_registration_information_matrix (Registration.cpp:64-91,446-486)
  *   o3dmi_registration_compute_fpfh_feature, <- ComputeFPFHFeature, CorrespondencesFromFeatures
  *   o3dmi_registration_correspondences_from_features (Feature.cpp:23-333)
+ *   o3dmi_registration_ransac_correspondence, <- legacy RegistrationRANSACBasedOnCorrespondence /
+ *   o3dmi_registration_ransac_feature_matching   ...FeatureMatching (pipelines/registration/Registration.cpp:212-406)
  *   o3dmi_voxel_down_sample,           <- t::geometry::PointCloud::{VoxelDownSample, EstimateNormals,
  *   o3dmi_pointcloud_estimate_*           EstimateColorGradients} (t/geometry/PointCloud.cpp:496-567,856-1060)
  *   o3dmi_vbg_*                        <- t::geometry::VoxelBlockGrid (+ Save / Load)
@@ -303,6 +305,72 @@ int o3dmi_registration_correspondences_from_features(
         int64_t n_target, int dim, int dtype, int mutual_filter,
         float mutual_consistency_ratio, int64_t* correspondences_dev,
         int64_t* n_correspondences, int* fell_back, o3dmi_stream_t stream);
+
+/* RegistrationRANSACBasedOnCorrespondence / ...BasedOnFeatureMatching
+ * (legacy pipelines/registration/Registration.cpp:212-406; the one place where
+ * this library mirrors a legacy operator: there is no tensor version). The
+ * semantics are rules 1-6 of "RANSAC on correspondences" in o3d_mi355x.h: the
+ * reference loop run by ONE thread over a stateless sample stream, reproduced
+ * exactly whatever batch_size is. RANSACConvergenceCriteria defaults:
+ * max_iteration 100000, confidence 0.999. */
+typedef struct {
+    int num_checkers;            /* <= 3, each kind at most once, in order  */
+    int checker_types[3];        /* O3DMI_RANSAC_CHECK_*                     */
+    double checker_thresholds[3];/* similarity / distance / normal angle    */
+    int max_iteration;
+    double confidence;
+    uint64_t seed;
+    int batch_size;              /* hypotheses per launch; 0 = the library's
+                                    choice (adapts to the share that passes
+                                    the checks)                              */
+} o3dmi_ransac_options_t;
+
+/* What the reference only logs. */
+typedef struct {
+    int64_t best_iteration;        /* -1: none                               */
+    int64_t num_validations;       /* iterations that passed the checks and
+                                      took part                              */
+    int64_t final_iteration_bound; /* est_k when the loop ended              */
+    int64_t iterations_run;        /* hypotheses formed, incl. the discarded
+                                      tail of the last batch                 */
+    int64_t num_batches;
+} o3dmi_ransac_info_t;
+
+/* Rule 7. The fields of the best iteration come from calling
+ * o3dmi_registration_evaluate once more on T_best: result (transformation,
+ * fitness, inlier_rmse) and the optional correspondences_dev (int64[ns]) are
+ * bit for bit what that call returns. No iteration validated, or best fitness
+ * 0: identity and zeros (the reference's default-constructed result;
+ * correspondences_dev is then filled with -1). ransac_n < 3, fewer
+ * correspondences than ransac_n, max_iteration <= 0 or
+ * max_correspondence_distance <= 0 return that empty result with O3DMI_OK, as
+ * the reference. estimation other than O3DMI_ICP_POINT_TO_POINT, with_scaling
+ * or ransac_n > 8: O3DMI_ERR_UNSUPPORTED. A correspondence outside
+ * [0, ns) x [0, nt): O3DMI_ERR_INVALID_ARG. corres_dev int64 {n_corres, 2};
+ * normals may be NULL (the normal checker then passes). info may be NULL.
+ * Synchronises; per batch the host reads back only the per-survivor arrays. */
+int o3dmi_registration_ransac_correspondence(
+        const void* source_dev, int64_t ns, const void* target_dev, int64_t nt,
+        const void* source_normals_dev, const void* target_normals_dev,
+        int dtype, const int64_t* corres_dev, int64_t n_corres,
+        double max_correspondence_distance, int estimation, int with_scaling,
+        int ransac_n, const o3dmi_ransac_options_t* options,
+        int64_t* correspondences_dev, o3dmi_registration_result_t* result,
+        o3dmi_ransac_info_t* info, o3dmi_stream_t stream);
+
+/* = o3dmi_registration_correspondences_from_features(source_features,
+ * target_features, mutual_filter, mutual consistency ratio 0.1) + the call
+ * above. Features {ns, dim} / {nt, dim} of feature_dtype (Float32 / Float64),
+ * row r belonging to point r. */
+int o3dmi_registration_ransac_feature_matching(
+        const void* source_dev, int64_t ns, const void* target_dev, int64_t nt,
+        const void* source_normals_dev, const void* target_normals_dev,
+        int dtype, const void* source_features_dev,
+        const void* target_features_dev, int dim, int feature_dtype,
+        int mutual_filter, double max_correspondence_distance, int estimation,
+        int with_scaling, int ransac_n, const o3dmi_ransac_options_t* options,
+        int64_t* correspondences_dev, o3dmi_registration_result_t* result,
+        o3dmi_ransac_info_t* info, o3dmi_stream_t stream);
 
 /* PointCloud::VoxelDownSample (t/geometry/PointCloud.cpp:496-567) for
  * positions (+ optional normals): mean per voxel in float32, voxel order =

@@ -160,6 +160,19 @@ class OdometryResultC(C.Structure):
                 ("fitness", _d), ("num_iterations", _i32)]
 
 
+class RansacOptionsC(C.Structure):
+    _fields_ = [("num_checkers", _i32), ("checker_types", _i32 * 3),
+                ("checker_thresholds", _d * 3), ("max_iteration", _i32),
+                ("confidence", _d), ("seed", C.c_uint64),
+                ("batch_size", _i32)]
+
+
+class RansacInfoC(C.Structure):
+    _fields_ = [("best_iteration", _i64), ("num_validations", _i64),
+                ("final_iteration_bound", _i64), ("iterations_run", _i64),
+                ("num_batches", _i64)]
+
+
 class IcpAttributes(C.Structure):
     _fields_ = [("source_normals", _vp), ("source_colors", _vp),
                 ("target_colors", _vp), ("target_color_gradients", _vp),
@@ -222,6 +235,21 @@ PROTOTYPES.update({
     "o3dmi_registration_correspondences_from_features": (
         _i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _f, _vp,
                C.POINTER(_i64), C.POINTER(_i32), _vp]),
+    "o3dmi_ransac_hypotheses": (
+        _i32, [C.c_uint64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32,
+               _vp, _i64, _i32, _i32, C.POINTER(_i32), _dp, _vp, _vp, _vp,
+               _vp]),
+    "o3dmi_ransac_score_scratch_bytes": (C.c_size_t, [_i64, _i64]),
+    "o3dmi_ransac_score": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp,
+                                  _i64, _vp, _vp, _vp, _vp, _vp]),
+    "o3dmi_registration_ransac_correspondence": (
+        _i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _d, _i32,
+               _i32, _i32, C.POINTER(RansacOptionsC), _vp,
+               C.POINTER(RegistrationResultC), C.POINTER(RansacInfoC), _vp]),
+    "o3dmi_registration_ransac_feature_matching": (
+        _i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _i32,
+               _i32, _d, _i32, _i32, _i32, C.POINTER(RansacOptionsC), _vp,
+               C.POINTER(RegistrationResultC), C.POINTER(RansacInfoC), _vp]),
     "o3dmi_pointcloud_estimate_normals": (_i32, [_vp, _i64, _i32, _i32, _d,
                                                  _vp, _i32, _vp]),
     "o3dmi_voxel_down_sample": (_i32, [_vp, _vp, _i64, _i32, _d, _vp, _vp,

@@ -345,48 +345,6 @@ __global__ void GatherAttrKernel(const T* __restrict__ attr,
     }
 }
 
-// Nearest neighbour with d2 < r2 (strict), ties -> lowest original index.
-// Returns the position in the sorted array (or -1); idx/d2 by reference.
-// Distance arithmetic: nanoflann::L2_Adaptor::evalMetric for dim 3,
-// ((dx*dx) + dy*dy) + dz*dz with dx = query - point, in T.
-template <typename T>
-__device__ __forceinline__ int SearchNearest(const NnsView<T>& nv, const T* q,
-                                             int& best_idx, T& best_d2) {
-    long long cx, cy, cz;
-    CellOf(q, nv.inv_cell, cx, cy, cz);
-    int best_pos = -1;
-    best_idx = -1;
-    best_d2 = 0;
-    const T qx = q[0], qy = q[1], qz = q[2];
-    for (int dz = -1; dz <= 1; ++dz)
-        for (int dy = -1; dy <= 1; ++dy)
-            for (int dx = -1; dx <= 1; ++dx) {
-                unsigned b = HashCell(cx + dx, cy + dy, cz + dz) & nv.mask;
-                unsigned s, e;
-                BucketRange(nv, b, s, e);
-                for (unsigned j = s; j < e; ++j) {
-                    Rec4<T> p = nv.sorted[j];
-                    T result = T(0);
-                    const T d0 = qx - p.x;
-                    result += d0 * d0;
-                    const T d1 = qy - p.y;
-                    result += d1 * d1;
-                    const T d2 = qz - p.z;
-                    result += d2 * d2;
-                    if (result < nv.radius_squared) {
-                        int idx = RecIndex(p);
-                        if (best_pos < 0 || result < best_d2 ||
-                            (result == best_d2 && idx < best_idx)) {
-                            best_pos = (int)j;
-                            best_idx = idx;
-                            best_d2 = result;
-                        }
-                    }
-                }
-            }
-    return best_pos;
-}
-
 template <typename T>
 __global__ void HybridSearchK1Kernel(NnsView<T> nv, const T* __restrict__ q,
                                      int64_t nq, int* __restrict__ idx_out,

@@ -1,6 +1,8 @@
 """Python mirror of open3d.t.pipelines.registration.{icp, multi_scale_icp,
 compute_fpfh_feature, correspondences_from_features} for the MI355X backend
-(point-to-plane and point-to-point estimators).
+(point-to-plane and point-to-point estimators), and of the legacy
+open3d.pipelines.registration.registration_ransac_based_on_{correspondence,
+feature_matching} with their correspondence checkers.
 
 Argument names / defaults follow the reference's binding
 (cpp/pybind/t/pipelines/registration/registration.cpp) and
@@ -40,8 +42,13 @@ class TransformationEstimationPointToPlane:
 
 
 class TransformationEstimationPointToPoint:
-    """TransformationEstimation.h:76-118; no robust kernel, no normals."""
+    """TransformationEstimation.h:76-118; no robust kernel, no normals.
+    with_scaling (the legacy estimator's argument) is read by the RANSAC
+    functions only, which reject it."""
     kernel = RobustKernel()
+
+    def __init__(self, with_scaling=False):
+        self.with_scaling = with_scaling
 
 
 class TransformationEstimationSymmetric:
@@ -499,3 +506,161 @@ def correspondences_from_features(source_features, target_features,
         C.byref(fb), stream()), "correspondences_from_features")
     res = out[:k.value]
     return (res, bool(fb.value)) if return_fallback else res
+
+
+class RANSACConvergenceCriteria:
+    """Registration.h: max_iteration 100000, confidence 0.999."""
+    def __init__(self, max_iteration=100000, confidence=0.999):
+        self.max_iteration = max_iteration
+        self.confidence = confidence
+
+
+class CorrespondenceCheckerBasedOnEdgeLength:
+    """CorrespondenceChecker.cpp:19-40."""
+    kind = 0
+
+    def __init__(self, similarity_threshold=0.9):
+        self.similarity_threshold = similarity_threshold
+        self.threshold = similarity_threshold
+
+
+class CorrespondenceCheckerBasedOnDistance:
+    """CorrespondenceChecker.cpp:42-57."""
+    kind = 1
+
+    def __init__(self, distance_threshold):
+        self.distance_threshold = distance_threshold
+        self.threshold = distance_threshold
+
+
+class CorrespondenceCheckerBasedOnNormal:
+    """CorrespondenceChecker.cpp:59-83; passes when either cloud has no
+    normals."""
+    kind = 2
+
+    def __init__(self, normal_angle_threshold):
+        self.normal_angle_threshold = normal_angle_threshold
+        self.threshold = normal_angle_threshold
+
+
+def _ransac_options(checkers, criteria, seed, batch_size):
+    checkers = list(checkers or [])
+    if len(checkers) > 3:
+        raise ValueError("at most one checker of each kind")
+    criteria = criteria or RANSACConvergenceCriteria()
+    opt = _lib.RansacOptionsC()
+    opt.num_checkers = len(checkers)
+    for k, c in enumerate(checkers):
+        if not hasattr(c, "kind"):
+            raise ValueError("unsupported correspondence checker %r" % (c,))
+        opt.checker_types[k] = c.kind
+        opt.checker_thresholds[k] = float(c.threshold)
+    opt.max_iteration = int(criteria.max_iteration)
+    opt.confidence = float(criteria.confidence)
+    opt.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    opt.batch_size = int(batch_size)
+    return opt
+
+
+def _ransac_estimation(estimation_method):
+    est = estimation_method or TransformationEstimationPointToPoint()
+    code = (1 if isinstance(est, TransformationEstimationPointToPoint) else
+            2 if isinstance(est, TransformationEstimationSymmetric) else
+            3 if isinstance(est, TransformationEstimationForColoredICP) else 0)
+    return code, int(bool(getattr(est, "with_scaling", False)))
+
+
+def _ransac_normals(source, target, source_normals, target_normals):
+    sn = tn = None
+    if source_normals is not None:
+        sn = require_cuda(source_normals, "source_normals")
+        if sn.dtype != source.dtype or sn.shape != source.shape:
+            raise ValueError("source / source_normals mismatch")
+    if target_normals is not None:
+        tn = require_cuda(target_normals, "target_normals")
+        if tn.dtype != target.dtype or tn.shape != target.shape:
+            raise ValueError("target / target_normals mismatch")
+    return sn, tn
+
+
+def _ransac_result(res, info, corr):
+    out = RegistrationResult()
+    out.transformation = np.array(res.transformation[:]).reshape(4, 4)
+    out.inlier_rmse = res.inlier_rmse
+    out.fitness = res.fitness
+    out.correspondence_set = corr
+    out.best_iteration = info.best_iteration
+    out.num_validations = info.num_validations
+    out.final_iteration_bound = info.final_iteration_bound
+    out.iterations_run = info.iterations_run
+    out.num_batches = info.num_batches
+    return out
+
+
+def registration_ransac_based_on_correspondence(
+        source, target, corres, max_correspondence_distance,
+        estimation_method=None, ransac_n=3, checkers=(), criteria=None,
+        seed=0, source_normals=None, target_normals=None, batch_size=0):
+    """Legacy pipelines::registration::RegistrationRANSACBasedOnCorrespondence
+    (Registration.cpp:344-380) on device tensors: `corres` int64 {K,2} (source
+    row, target row). The reference loop as one thread runs it over a
+    stateless sample stream keyed by `seed` (rules 1-7 in o3d_mi355x.h); the
+    result does not depend on `batch_size` (0 = the library's choice). The
+    normals are read by CorrespondenceCheckerBasedOnNormal only. Returns a
+    RegistrationResult with best_iteration (-1: none), num_validations and
+    final_iteration_bound as extra attributes."""
+    source, target = _check_pair(source, target)
+    corres = require_cuda(corres, "corres")
+    if corres.dtype != torch.int64 or corres.dim() != 2 or \
+            corres.shape[1] != 2:
+        raise ValueError("corres must be int64 {K,2}")
+    sn, tn = _ransac_normals(source, target, source_normals, target_normals)
+    code, scaling = _ransac_estimation(estimation_method)
+    opt = _ransac_options(checkers, criteria, seed, batch_size)
+    ns = source.shape[0]
+    corr = torch.full((max(ns, 1),), -1, dtype=torch.int64, device="cuda")
+    res = _lib.RegistrationResultC()
+    info = _lib.RansacInfoC()
+    _lib.check(_lib.lib().o3dmi_registration_ransac_correspondence(
+        _lib.ptr(source), ns, _lib.ptr(target), target.shape[0],
+        _lib.ptr(sn), _lib.ptr(tn), TORCH_TO_O3DMI[source.dtype],
+        _lib.ptr(corres), corres.shape[0],
+        C.c_double(max_correspondence_distance), code, scaling, int(ransac_n),
+        C.byref(opt), _lib.ptr(corr), C.byref(res), C.byref(info), stream()),
+        "registration_ransac_based_on_correspondence")
+    return _ransac_result(res, info, corr[:ns])
+
+
+def registration_ransac_based_on_feature_matching(
+        source, target, source_features, target_features, mutual_filter,
+        max_correspondence_distance, estimation_method=None, ransac_n=3,
+        checkers=(), criteria=None, seed=0, source_normals=None,
+        target_normals=None, batch_size=0):
+    """Legacy RegistrationRANSACBasedOnFeatureMatching (Registration.cpp:
+    382-406): correspondences_from_features(source_features, target_features,
+    mutual_filter) followed by the function above. Features {N,D}, row r of
+    point r."""
+    source, target = _check_pair(source, target)
+    fs = require_cuda(source_features, "source_features")
+    ft = require_cuda(target_features, "target_features")
+    if fs.dtype != ft.dtype or fs.dim() != 2 or ft.dim() != 2 or \
+            fs.shape[1] != ft.shape[1] or fs.shape[0] != source.shape[0] or \
+            ft.shape[0] != target.shape[0]:
+        raise ValueError("features must be {N,D} / {M,D} of one dtype, one "
+                         "row per point")
+    sn, tn = _ransac_normals(source, target, source_normals, target_normals)
+    code, scaling = _ransac_estimation(estimation_method)
+    opt = _ransac_options(checkers, criteria, seed, batch_size)
+    ns = source.shape[0]
+    corr = torch.full((max(ns, 1),), -1, dtype=torch.int64, device="cuda")
+    res = _lib.RegistrationResultC()
+    info = _lib.RansacInfoC()
+    _lib.check(_lib.lib().o3dmi_registration_ransac_feature_matching(
+        _lib.ptr(source), ns, _lib.ptr(target), target.shape[0],
+        _lib.ptr(sn), _lib.ptr(tn), TORCH_TO_O3DMI[source.dtype],
+        _lib.ptr(fs), _lib.ptr(ft), fs.shape[1], TORCH_TO_O3DMI[fs.dtype],
+        int(bool(mutual_filter)), C.c_double(max_correspondence_distance),
+        code, scaling, int(ransac_n), C.byref(opt), _lib.ptr(corr),
+        C.byref(res), C.byref(info), stream()),
+        "registration_ransac_based_on_feature_matching")
+    return _ransac_result(res, info, corr[:ns])

@@ -869,6 +869,56 @@ int o3dmi_odometry_information(int rows, int cols,
                                float square_dist_thr, double* information_host,
                                o3dmi_stream_t stream);
 
+/* ------------------------------------------------------------------------ */
+/* Rigid multiway alignment (t::pipelines::slac, rigid half)                 */
+/* ------------------------------------------------------------------------ */
+
+/* FillInRigidAlignmentTermCUDA (t/pipelines/kernel/FillInLinearSystemImpl.h:
+ * 27-154), the reference's seam: Ti_ps / Tj_qs / Ri_normal_ps {n,3} float32
+ * are the gathered and transformed rows of one edge (i, j). Per pair, in
+ * float32 and the reference's order: r = (p' - q') . n', skipped when
+ * |r| > threshold; J = (-q'z n'y + q'y n'z, q'z n'x - q'x n'z,
+ * -q'y n'x + q'x n'y, n'x, n'y, n'z) for node i and -J for node j. The block
+ * [[A, -A], [-A, A]], the rhs [b, -b] (A = sum J J^T, b = sum J r) and
+ * sum r r are added to the caller's float32 AtA {n_vars, n_vars}, Atb
+ * {n_vars} and residual {1} at rows / columns 6i..6i+5, 6j..6j+5.
+ * Differences from the reference: the sums are float64 in a fixed tree (the
+ * reference: float32 atomics in arrival order) and every float32 entry is
+ * updated once, entry += (float)sum, so results are run-to-run identical;
+ * i == j or a node id outside [0, n_vars / 6) is O3DMI_ERR_INVALID_ARG (the
+ * reference indexes out of range / writes duplicate indices). Stream-ordered,
+ * no host wait. */
+int o3dmi_fill_in_rigid_alignment_term(float* AtA_dev, float* Atb_dev,
+                                       float* residual_dev, int64_t n_vars,
+                                       const float* Ti_ps_dev,
+                                       const float* Tj_qs_dev,
+                                       const float* Ri_normal_ps_dev,
+                                       int64_t n, int i, int j,
+                                       float threshold, o3dmi_stream_t stream);
+
+/* The same terms for ALL edges of a pose graph in one launch, from the
+ * fragments themselves (t/pipelines/slac/FillInLinearSystemImpl.h:55-100
+ * without its per-edge IndexGet / Transform temporaries). Host arrays:
+ * positions_dev / normals_dev [n_fragments] device pointers to {sizes[k],3}
+ * float32; edges {n_edges,2} int32 (i, j); corres_dev [n_edges] device
+ * pointers to int64 {corres_counts[e],2} rows (index in i, index in j),
+ * 16-byte aligned; poses {n_fragments,16} float64 row-major, rounded to
+ * float32 as the reference does. p' = Ti p_a, q' = Tj q_b, n' = Ri n_a, each
+ * row t0 x + t1 y + t2 z (+ t3), then the per-pair terms above.
+ * sums_dev {n_edges,29} float64: per edge the 21 lower-triangle values of A
+ * (sums[u (u + 1) / 2 + v] = A[u][v]), the 6 values of b, sum r r, and the
+ * number of pairs within the threshold. An edge with count 0 gives 29 zeros.
+ * A correspondence outside [0, sizes[i]) x [0, sizes[j]) is never followed:
+ * the call returns O3DMI_ERR_INVALID_ARG and sums_dev is not written; so do
+ * i == j and node ids out of range. Synchronises. */
+int o3dmi_slac_rigid_terms(const void* const* positions_dev,
+                           const void* const* normals_dev,
+                           const int64_t* sizes, int n_fragments,
+                           const int32_t* edges, const void* const* corres_dev,
+                           const int64_t* corres_counts, int n_edges,
+                           const double* poses, float threshold,
+                           double* sums_dev, o3dmi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,8 @@
  *   o3dmi_registration_correspondences_from_features (Feature.cpp:23-333)
  *   o3dmi_registration_ransac_correspondence, <- legacy RegistrationRANSACBasedOnCorrespondence /
  *   o3dmi_registration_ransac_feature_matching   ...FeatureMatching (pipelines/registration/Registration.cpp:212-406)
+ *   o3dmi_slac_correspondence_set,     <- t::pipelines::slac::RunRigidOptimizerForFragments
+ *   o3dmi_slac_rigid_optimize             (t/pipelines/slac/SLACOptimizer.cpp:85-204,265-286,369-414)
  *   o3dmi_voxel_down_sample,           <- t::geometry::PointCloud::{VoxelDownSample, EstimateNormals,
  *   o3dmi_pointcloud_estimate_*           EstimateColorGradients} (t/geometry/PointCloud.cpp:496-567,856-1060)
  *   o3dmi_vbg_*                        <- t::geometry::VoxelBlockGrid (+ Save / Load)
@@ -371,6 +373,64 @@ int o3dmi_registration_ransac_feature_matching(
         int with_scaling, int ransac_n, const o3dmi_ransac_options_t* options,
         int64_t* correspondences_dev, o3dmi_registration_result_t* result,
         o3dmi_ransac_info_t* info, o3dmi_stream_t stream);
+
+/* GetCorrespondenceSetForPointCloudPair (t/pipelines/slac/SLACOptimizer.cpp:
+ * 85-204) for the edge (i, j) of a pose graph: fragment i moved by T_ij is
+ * hybrid-searched (radius distance_threshold, k = 1) in fragment j; the
+ * matched {a, b} pairs go to corres_dev (int64, room for {ni,2}) in ascending
+ * a, *n_corres = C. *n_inliers counts the pairs with
+ * |Ti p_a - Tj q_b|^2 <= distance_threshold^2 (float32, <=), *inlier_ratio =
+ * (float)n_inliers / (float)C (NaN when C = 0, as the reference's division).
+ * *kept = 0 -- the reference returns an empty set -- iff (j != i + 1 and
+ * inlier_ratio < fitness_threshold) or C = 0. T_i, T_j, T_ij: host 4x4
+ * float64 row-major, cast to float32 first. Float32 positions only (the
+ * reference loads every fragment as Float32). Synchronises. */
+int o3dmi_slac_correspondence_set(const void* positions_i_dev, int64_t ni,
+                                  const void* positions_j_dev, int64_t nj,
+                                  int i, int j, const double* T_i,
+                                  const double* T_j, const double* T_ij,
+                                  float distance_threshold,
+                                  float fitness_threshold,
+                                  int64_t* corres_dev, int64_t* n_corres,
+                                  int64_t* n_inliers, float* inlier_ratio,
+                                  int* kept, o3dmi_stream_t stream);
+
+/* RunRigidOptimizerForFragments (SLACOptimizer.cpp:265-286,369-414) on
+ * fragments in device memory: "extended ICP to simultaneously align multiple
+ * point clouds with dense pairwise point-to-plane distances".
+ *   positions_dev / normals_dev [n_nodes]: device pointers, {sizes[k],3} float32
+ *   poses {n_nodes,16}: float64 row-major node poses, in/out
+ *   edges {n_edges,2} int32 (source, target), T_ij {n_edges,16} float64
+ * The correspondence sets are computed once from the input graph (the call
+ * above); an edge that is not kept contributes nothing. Per iteration: one
+ * o3dmi_slac_rigid_terms launch with threshold = distance_threshold, one
+ * download of n_edges x 29 doubles, the dense 6N x 6N float64 system on the
+ * host with 1e5 on the first six diagonal entries, x = solve(AtA, -Atb) by LU
+ * with partial pivoting, T_k <- PoseToTransformation(x[6k..6k+5]) T_k.
+ * Outputs (each may be NULL): losses {max_iterations} = sum of the edges'
+ * residuals (the reference's "Loss" log line), kept / n_corres {n_edges},
+ * n_inliers {n_edges} = pairs within the threshold in the last iteration
+ * (zeros when max_iterations <= 0).
+ * Differences from the reference: fragments and correspondence sets are in
+ * memory (the reference takes file names and caches .npy / .ply files in
+ * slac_folder; its PreprocessPointClouds -- VoxelDownSample, statistical
+ * outlier removal, EstimateNormals -- is the caller's); the sums, the solve
+ * and the pose update are float64 (the reference: float32 atomics, a float32
+ * gesv on a matrix holding 1e5 beside O(1) entries, poses rounded through
+ * float32 every iteration). n_nodes > 512: O3DMI_ERR_UNSUPPORTED. i == j or a
+ * node id out of range: O3DMI_ERR_INVALID_ARG. A zero or non-finite pivot
+ * (for example a node no kept edge reaches; the reference's LAPACK check
+ * throws): O3DMI_ERR_SINGULAR, and the poses are left as they came in.
+ * Synchronises. */
+int o3dmi_slac_rigid_optimize(const void* const* positions_dev,
+                              const void* const* normals_dev,
+                              const int64_t* sizes, int n_nodes, double* poses,
+                              const int32_t* edges, const double* T_ij,
+                              int n_edges, int max_iterations,
+                              float distance_threshold,
+                              float fitness_threshold, double* losses,
+                              int32_t* kept, int64_t* n_corres,
+                              int64_t* n_inliers, o3dmi_stream_t stream);
 
 /* PointCloud::VoxelDownSample (t/geometry/PointCloud.cpp:496-567) for
  * positions (+ optional normals): mean per voxel in float32, voxel order =

@@ -250,6 +250,21 @@ PROTOTYPES.update({
         _i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _i32,
                _i32, _d, _i32, _i32, _i32, C.POINTER(RansacOptionsC), _vp,
                C.POINTER(RegistrationResultC), C.POINTER(RansacInfoC), _vp]),
+    "o3dmi_fill_in_rigid_alignment_term": (
+        _i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _f,
+               _vp]),
+    "o3dmi_slac_rigid_terms": (
+        _i32, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64), _i32,
+               C.POINTER(_i32), C.POINTER(_vp), C.POINTER(_i64), _i32, _dp,
+               _f, _vp, _vp]),
+    "o3dmi_slac_correspondence_set": (
+        _i32, [_vp, _i64, _vp, _i64, _i32, _i32, _dp, _dp, _dp, _f, _f, _vp,
+               C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_f),
+               C.POINTER(_i32), _vp]),
+    "o3dmi_slac_rigid_optimize": (
+        _i32, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64), _i32, _dp,
+               C.POINTER(_i32), _dp, _i32, _i32, _f, _f, _dp,
+               C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "o3dmi_pointcloud_estimate_normals": (_i32, [_vp, _i64, _i32, _i32, _d,
                                                  _vp, _i32, _vp]),
     "o3dmi_voxel_down_sample": (_i32, [_vp, _vp, _i64, _i32, _d, _vp, _vp,

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "common.h"
+#include "preload.h"
 
 namespace o3dmi {
 
@@ -382,11 +383,7 @@ int RecoverOverflow(o3dmi_hash* h, hipStream_t s, int64_t* wanted) {
 // o3dmi_preload: HIP loads this translation unit's code object at the first
 // launch of one of its kernels; asking for a kernel's attributes does it now.
 int PreloadBlockHash() {
-    hipFuncAttributes attr;
-    return hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(
-                                               &ClearKernel)) == hipSuccess
-                   ? 0
-                   : 1;
+    return LoadCodeObjectOf(reinterpret_cast<const void*>(&ClearKernel));
 }
 
 }  // namespace o3dmi

@@ -27,6 +27,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "feature.h"
 #include "scan.h"
 
 using namespace o3dmi;

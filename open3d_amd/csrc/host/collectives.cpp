@@ -6,7 +6,7 @@
 //     posts the sums to the host mailbox -- ncclAllReduce, no host in between;
 //   * frame-sharded integration: all-gather of per-owner block counts and an
 //     all-to-all of block IDs + voxel rows to the ranks that own them
-//     (o3dmi_vbg_merge_frame_sharded in voxel_block_grid.cpp).
+//     (o3dmi_vbg_merge_frame_sharded in vbg_exchange.cpp).
 // RCCL is resolved with dlopen at first use, so the library carries no link
 // dependency on it and single-GPU users never load it. When the process
 // already holds an RCCL (PyTorch bundles one) that instance is used: a

@@ -28,16 +28,8 @@
 
 #include "../common.h"
 #include "../mailbox.h"
+#include "../odometry.h"
 #include "o3d_mi355x_host.h"
-
-extern "C" int o3dmi_odometry_sums_post(
-        int method, int rows, int cols, const float* const* maps11,
-        const double* intrinsics, const double* init_source_to_target,
-        float depth_outlier_trunc, float depth_huber_delta,
-        float intensity_huber_delta, double* scratch_dev, double* sums29_dev,
-        double* mail_data, int* mail_flag, int mail_seq, o3dmi_stream_t stream);
-
-
 
 using namespace o3dmi;
 

@@ -41,62 +41,12 @@
 #include <vector>
 
 #include "../common.h"
+#include "../icp.h"
 #include "../mailbox.h"
+#include "../nns.h"
 #include "../collectives.h"
 #include "../vds.h"
 #include "o3d_mi355x_host.h"
-
-extern "C" int o3dmi_icp_search_accumulate_post(
-        const o3dmi_nns_t* nns, const void* src_dev,
-        const void* tgt_normals_dev, int64_t n, int estimation,
-        int robust_kernel, double scaling_parameter, double shape_parameter,
-        int64_t* corr_out_dev, double* sums32_dev, double* mail_data,
-        int* mail_flag, int mail_seq, o3dmi_stream_t stream);
-
-extern "C" int o3dmi_nns_set_normals(o3dmi_nns_t* nns, const void* normals_dev,
-                                     o3dmi_stream_t stream);
-
-extern "C" int o3dmi_icp_colored_accumulate_post(
-        const void* src_dev, const void* src_colors_dev, const void* tgt_dev,
-        const void* tgt_normals_dev, const void* tgt_colors_dev,
-        const void* tgt_color_gradients_dev, const int64_t* corr_dev, int64_t n,
-        int dtype, double lambda_geometric, int robust_kernel,
-        double scaling_parameter, double shape_parameter, double* sums29_dev,
-        double* partials_dev, double* mail_data, int* mail_flag, int mail_seq,
-        o3dmi_stream_t stream);
-
-extern "C" int o3dmi_icp_symmetric_accumulate_post(
-        const void* src_dev, const void* src_normals_dev, const void* tgt_dev,
-        const void* tgt_normals_dev, const int64_t* corr_dev, int64_t n,
-        int dtype, const double* source_mean3, const double* target_mean3,
-        int robust_kernel, double scaling_parameter, double shape_parameter,
-        double* sums29_dev, double* partials_dev, double* mail_data,
-        int* mail_flag, int mail_seq, o3dmi_stream_t stream);
-
-extern "C" int o3dmi_internal_nns_destroy_completed(o3dmi_nns_t* nns);
-extern "C" int o3dmi_internal_nns_create_with_normals(
-        const void* points_dev, const void* normals_dev, int64_t n, int dtype,
-        double radius, o3dmi_stream_t stream, o3dmi_nns_t** out);
-extern "C" int o3dmi_internal_nns_create_small_deferred(
-        const void* points_dev, const void* normals_dev, const int* n_dev,
-        int dtype, double radius, o3dmi_stream_t stream, o3dmi_nns_t** out);
-extern "C" int o3dmi_internal_nns_adopt_count(o3dmi_nns_t* nns, int64_t n);
-extern "C" int o3dmi_internal_nns_create_many(
-        int count, const void* const* points_dev,
-        const void* const* normals_dev, const int64_t* n, int dtype,
-        const double* radius, o3dmi_stream_t stream, o3dmi_nns_t** out);
-extern "C" int o3dmi_internal_icp_transform_search_accumulate(
-        const o3dmi_nns_t* nns, void* src_dev, const double* transformation,
-        const void* tgt_normals_dev, int64_t n, int estimation,
-        int robust_kernel, double scaling_parameter, double shape_parameter,
-        int64_t* corr_out_dev, double* sums32_dev, double* mail_data,
-        int* mail_flag, int mail_seq, o3dmi_stream_t stream);
-extern "C" int o3dmi_internal_sums_tail(double* sums32_dev, double t29,
-                                        double t30, double t31,
-                                        o3dmi_stream_t stream);
-extern "C" int o3dmi_internal_sums_post(const double* sums32_dev,
-                                        double* mail_data, int* mail_flag,
-                                        int seq, o3dmi_stream_t stream);
 
 using namespace o3dmi;
 
@@ -1383,13 +1333,6 @@ extern "C" int o3dmi_registration_information_matrix(
         }
     return O3DMI_OK;
 }
-
-extern "C" int o3dmi_icp_residual_squares(const void* src_dev,
-                                          const void* tgt_dev,
-                                          const void* tgt_normals_dev,
-                                          const int64_t* corr_dev, int64_t n,
-                                          int dtype, double* sums2_dev,
-                                          o3dmi_stream_t stream);
 
 extern "C" int o3dmi_registration_compute_rmse(
         int estimation, const void* source_dev, int64_t ns,

@@ -9,13 +9,7 @@
 #include <cstring>
 
 #include "../common.h"
-#include "o3d_mi355x_host.h"
-
-extern "C" int o3dmi_vbg_export_last_frame_blocks(o3dmi_vbg_t* g,
-                                                  int32_t* out_keys_dev,
-                                                  int64_t out_capacity,
-                                                  int32_t* out_count_dev,
-                                                  o3dmi_stream_t stream);
+#include "vbg_last_frame.h"
 
 using namespace o3dmi;
 

@@ -1,0 +1,60 @@
+// Private seam between the ICP driver (host/registration.cpp) and icp.hip:
+// the entry points that are not in the public header.
+#pragma once
+
+#include "common.h"
+
+extern "C" {
+
+// o3dmi_icp_search_accumulate[_p2point] (`estimation` 0 / 1) that also posts
+// the 32 sums to a host mailbox (mailbox.h) when mail_data != NULL;
+// sums32_dev may then be NULL.
+int o3dmi_icp_search_accumulate_post(
+        const o3dmi_nns_t* nns, const void* src_dev,
+        const void* tgt_normals_dev, int64_t n, int estimation,
+        int robust_kernel, double scaling_parameter, double shape_parameter,
+        int64_t* corr_out_dev, double* sums32_dev, double* mail_data,
+        int* mail_flag, int mail_seq, o3dmi_stream_t stream);
+
+// The same with the source moved by `transformation` (4x4, NULL: as it is) in
+// place before it is searched.
+int o3dmi_internal_icp_transform_search_accumulate(
+        const o3dmi_nns_t* nns, void* src_dev, const double* transformation,
+        const void* tgt_normals_dev, int64_t n, int estimation,
+        int robust_kernel, double scaling_parameter, double shape_parameter,
+        int64_t* corr_out_dev, double* sums32_dev, double* mail_data,
+        int* mail_flag, int mail_seq, o3dmi_stream_t stream);
+
+// o3dmi_icp_colored_accumulate / o3dmi_icp_symmetric_accumulate that also post
+// the 29 sums to a host mailbox when mail_data != NULL.
+int o3dmi_icp_colored_accumulate_post(
+        const void* src_dev, const void* src_colors_dev, const void* tgt_dev,
+        const void* tgt_normals_dev, const void* tgt_colors_dev,
+        const void* tgt_color_gradients_dev, const int64_t* corr_dev, int64_t n,
+        int dtype, double lambda_geometric, int robust_kernel,
+        double scaling_parameter, double shape_parameter, double* sums29_dev,
+        double* partials_dev, double* mail_data, int* mail_flag, int mail_seq,
+        o3dmi_stream_t stream);
+
+int o3dmi_icp_symmetric_accumulate_post(
+        const void* src_dev, const void* src_normals_dev, const void* tgt_dev,
+        const void* tgt_normals_dev, const int64_t* corr_dev, int64_t n,
+        int dtype, const double* source_mean3, const double* target_mean3,
+        int robust_kernel, double scaling_parameter, double shape_parameter,
+        double* sums29_dev, double* partials_dev, double* mail_data,
+        int* mail_flag, int mail_seq, o3dmi_stream_t stream);
+
+// sums32_dev[29..31] = {t29, t30, t31}; the 32 sums to a host mailbox.
+int o3dmi_internal_sums_tail(double* sums32_dev, double t29, double t30,
+                             double t31, o3dmi_stream_t stream);
+int o3dmi_internal_sums_post(const double* sums32_dev, double* mail_data,
+                             int* mail_flag, int seq, o3dmi_stream_t stream);
+
+// o3dmi_registration_compute_rmse: sums2_dev[0] = sum of squared residual
+// components, [1] = number of correspondences.
+int o3dmi_icp_residual_squares(const void* src_dev, const void* tgt_dev,
+                               const void* tgt_normals_dev,
+                               const int64_t* corr_dev, int64_t n, int dtype,
+                               double* sums2_dev, o3dmi_stream_t stream);
+
+}  // extern "C"

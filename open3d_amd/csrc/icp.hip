@@ -30,8 +30,10 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "icp.h"
 #include "nns.h"
 #include "kabsch.h"
+#include "preload.h"
 #include "mailbox.h"
 
 #ifndef O3DMI_ABLATE_TAIL
@@ -1032,19 +1034,13 @@ int ReduceGrid(int64_t n) {
 // o3dmi_preload: HIP loads this translation unit's code object at the first
 // launch of one of its kernels; asking for a kernel's attributes does it now.
 int PreloadIcp() {
-    hipFuncAttributes attr;
-    return hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(
-                                               &TransformNormalsKernel<float>)) == hipSuccess
-                   ? 0
-                   : 1;
+    return LoadCodeObjectOf(
+            reinterpret_cast<const void*>(&TransformNormalsKernel<float>));
 }
 
 }  // namespace o3dmi
 
 using namespace o3dmi;
-
-extern "C" int o3dmi_nns_set_normals(o3dmi_nns_t* nns, const void* normals_dev,
-                                     o3dmi_stream_t stream);
 
 extern "C" {
 
@@ -1312,20 +1308,6 @@ int o3dmi_icp_information_accumulate(const void* tgt_dev,
     O3DMI_HIP_CHECK(hipFreeAsync(partials, s));
     return O3DMI_OK;
 }
-
-int o3dmi_icp_search_accumulate_post(
-        const o3dmi_nns_t* nns, const void* src_dev,
-        const void* tgt_normals_dev, int64_t n, int estimation,
-        int robust_kernel, double scaling_parameter, double shape_parameter,
-        int64_t* corr_out_dev, double* sums32_dev, double* mail_data,
-        int* mail_flag, int mail_seq, o3dmi_stream_t stream);
-
-int o3dmi_internal_icp_transform_search_accumulate(
-        const o3dmi_nns_t* nns, void* src_dev, const double* transformation,
-        const void* tgt_normals_dev, int64_t n, int estimation,
-        int robust_kernel, double scaling_parameter, double shape_parameter,
-        int64_t* corr_out_dev, double* sums32_dev, double* mail_data,
-        int* mail_flag, int mail_seq, o3dmi_stream_t stream);
 
 int o3dmi_icp_search_accumulate_p2point(const o3dmi_nns_t* nns,
                                         const void* src_dev, int64_t n,

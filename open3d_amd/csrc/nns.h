@@ -36,6 +36,33 @@ struct o3dmi_nns {
                                      // between launches
 };
 
+// Entry points of nns.hip for the host drivers and the other kernels' host
+// sides, not in the public header (each is described at its definition).
+extern "C" {
+int o3dmi_nns_set_normals(o3dmi_nns_t* nns, const void* normals_dev,
+                          o3dmi_stream_t stream);
+int o3dmi_internal_nns_create_with_normals(
+        const void* points_dev, const void* normals_dev, int64_t n, int dtype,
+        double radius, o3dmi_stream_t stream, o3dmi_nns_t** out);
+int o3dmi_internal_nns_create_many(
+        int count, const void* const* points_dev,
+        const void* const* normals_dev, const int64_t* n, int dtype,
+        const double* radius, o3dmi_stream_t stream, o3dmi_nns_t** out);
+int o3dmi_internal_nns_create_small_deferred(
+        const void* points_dev, const void* normals_dev, const int* n_dev,
+        int dtype, double radius, o3dmi_stream_t stream, o3dmi_nns_t** out);
+int o3dmi_internal_nns_adopt_count(o3dmi_nns_t* nns, int64_t n);
+int o3dmi_internal_nns_destroy_completed(o3dmi_nns_t* nns);
+int o3dmi_internal_nns_hybrid_search_wide(
+        const o3dmi_nns_t* nns, const void* queries_dev, const int32_t* ids_dev,
+        int64_t nq, int max_knn, int32_t* idx_dev, void* dist2_dev,
+        int32_t* counts_dev, o3dmi_stream_t stream);
+int o3dmi_nns_knn_search_counts(const void* points_dev, int64_t n,
+                                const void* queries_dev, int64_t q, int dtype,
+                                int knn, int32_t* idx_dev, void* dist2_dev,
+                                int32_t* counts_dev, o3dmi_stream_t stream);
+}  // extern "C"
+
 namespace o3dmi {
 
 constexpr int kNumSums = 32;  // 29 + sum d2 + match count + pad

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "nns.h"
+#include "preload.h"
 
 namespace o3dmi {
 namespace {
@@ -1131,11 +1132,7 @@ __global__ void CountOccupiedKernel(const uint2* __restrict__ ranges,
 // o3dmi_preload: HIP loads this translation unit's code object at the first
 // launch of one of its kernels; asking for a kernel's attributes does it now.
 int PreloadNns() {
-    hipFuncAttributes attr;
-    return hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(
-                                               &CountKernel<float>)) == hipSuccess
-                   ? 0
-                   : 1;
+    return LoadCodeObjectOf(reinterpret_cast<const void*>(&CountKernel<float>));
 }
 
 }  // namespace o3dmi
@@ -1286,12 +1283,6 @@ extern "C" int o3dmi_nns_set_normals(o3dmi_nns_t* nns, const void* normals_dev,
 
 extern "C" {
 
-int o3dmi_internal_nns_create_with_normals(const void* points_dev,
-                                           const void* normals_dev, int64_t n,
-                                           int dtype, double radius,
-                                           o3dmi_stream_t stream,
-                                           o3dmi_nns_t** out);
-
 int o3dmi_nns_create(const void* points_dev, int64_t n, int dtype,
                      double radius, o3dmi_stream_t stream, o3dmi_nns_t** out) {
     return o3dmi_internal_nns_create_with_normals(points_dev, nullptr, n,
@@ -1382,8 +1373,6 @@ int o3dmi_internal_nns_create_many(int count, const void* const* points_dev,
 // one-workgroup build is queued now, sized for the largest cloud it can take
 // (8192 buckets); o3dmi_internal_nns_adopt_count tells the index its size once
 // the host knows it. The build does nothing when the cloud is larger.
-int o3dmi_internal_nns_destroy_completed(o3dmi_nns_t* nns);
-
 int o3dmi_internal_nns_create_small_deferred(const void* points_dev,
                                              const void* normals_dev,
                                              const int* n_dev, int dtype,

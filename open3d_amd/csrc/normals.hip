@@ -14,6 +14,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "nns.h"
 #include "scan.h"
 
 namespace o3dmi {
@@ -438,11 +439,6 @@ int o3dmi_pointcloud_normals_from_covariances(const void* covariances_dev,
     O3DMI_HIP_CHECK(hipGetLastError());
     return O3DMI_OK;
 }
-
-int o3dmi_nns_knn_search_counts(const void* points_dev, int64_t n,
-                                const void* queries_dev, int64_t q, int dtype,
-                                int knn, int32_t* idx_dev, void* dist2_dev,
-                                int32_t* counts_dev, o3dmi_stream_t stream);
 
 // PointCloud::EstimateNormals(max_knn, radius), PointCloud.cpp:856-976: index
 // over the cloud itself, hybrid search (both given), KNN search (radius <= 0,

@@ -28,6 +28,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "odometry.h"
 #include "reduce_sums.h"
 
 namespace o3dmi {
@@ -1075,18 +1076,6 @@ int o3dmi_image_clip_transform_pair(const void* src0_dev, int src0_dtype,
 int o3dmi_odometry_sums_scratch_doubles(void) {
     return kSumsMaxGrid * kOdoSums;
 }
-
-// Internal (not in the public header): the same reduction, with the result
-// also posted to a host mailbox (mailbox.h) when mail_data != NULL.
-int o3dmi_odometry_sums_post(int method, int rows, int cols,
-                             const float* const* maps11,
-                             const double* intrinsics,
-                             const double* init_source_to_target,
-                             float depth_outlier_trunc, float depth_huber_delta,
-                             float intensity_huber_delta, double* scratch_dev,
-                             double* sums29_dev, double* mail_data,
-                             int* mail_flag, int mail_seq,
-                             o3dmi_stream_t stream);
 
 int o3dmi_odometry_sums(int method, int rows, int cols,
                         const float* source_depth_dev,

@@ -50,6 +50,7 @@
 #include <vector>
 
 #include "common.h"
+#include "preload.h"
 #include "o3d_mi355x_host.h"
 #include "mailbox.h"
 #include "vds.h"
@@ -1558,11 +1559,7 @@ int VdsAsync(const void* pos, const void* attr, int64_t n_max, const int* n_dev,
 // o3dmi_preload: HIP loads this translation unit's code object at the first
 // launch of one of its kernels; asking for a kernel's attributes does it now.
 int PreloadPointcloud() {
-    hipFuncAttributes attr;
-    return hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(
-                                               &VdsInitKernel)) == hipSuccess
-                   ? 0
-                   : 1;
+    return LoadCodeObjectOf(reinterpret_cast<const void*>(&VdsInitKernel));
 }
 
 }  // namespace o3dmi

@@ -15,7 +15,7 @@ namespace o3dmi {
 // Running out of buffer indices: callers that reserved for an exact count
 // never do, and for them it is an error (kErrCapacity, reported at the next
 // sync). The frame stream issues groups on an ESTIMATE of what they add
-// (host/voxel_block_grid.cpp): it passes its group stamp as `overflow_stamp`,
+// (host/vbg_frame_stream.cpp): it passes its group stamp as `overflow_stamp`,
 // an overflow then records the first failing group in counters[3] and leaves
 // the slot with the marker index -1 (Find: absent); the group's work is
 // dropped on the device, the host reserves and replays it (RecoverOverflow).

@@ -28,6 +28,8 @@
 #include <vector>
 
 #include "common.h"
+#include "preload.h"
+#include "raycast.h"
 
 namespace o3dmi {
 namespace {
@@ -863,11 +865,7 @@ RayCastKernel(HashView hv, RayCastParams p, const float* __restrict__ tsdf_base,
 // o3dmi_preload: HIP loads this translation unit's code object at the first
 // launch of one of its kernels; asking for a kernel's attributes does it now.
 int PreloadRaycast() {
-    hipFuncAttributes attr;
-    return hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(
-                                               &RangeFillKernel)) == hipSuccess
-                   ? 0
-                   : 1;
+    return LoadCodeObjectOf(reinterpret_cast<const void*>(&RangeFillKernel));
 }
 
 }  // namespace o3dmi
@@ -889,60 +887,6 @@ int o3dmi_vbg_estimate_range(const int32_t* block_keys_dev, int64_t n_blocks,
             depth_min, depth_max, stream);
 }
 
-// Internal (o3dmi_vbg_ray_cast_dev with a grid-owned range map / block list):
-// the keys are every `key_stride`-th int triple from block_keys_dev; a map the
-// last ray cast left clean skips the clearing launch.
-int o3dmi_internal_estimate_range(const int32_t* block_keys_dev, int key_stride,
-                                  int64_t max_blocks,
-                                  const int32_t* n_blocks_dev,
-                                  float* range_minmax_map_dev, int map_is_clean,
-                                  const double* intrinsic,
-                                  const double* extrinsic, int h, int w,
-                                  int down_factor, int64_t block_resolution,
-                                  float voxel_size, float depth_min,
-                                  float depth_max, o3dmi_stream_t stream);
-
-// The NEXT ray-cast launch of this host thread writes every range cell it
-// reads back to the {lo, hi} stored in the two floats behind the map's last
-// cell (consumed by that launch; whole-image launches with a down factor of 8
-// only).
-static thread_local int g_reset_range = 0;
-int o3dmi_internal_raycast_reset_range(void) {
-    g_reset_range = 1;
-    return O3DMI_OK;
-}
-// The NEXT ray-cast launch of this host thread takes its tiles in `order`
-// (NULL: index order) and writes their durations to `cost` tagged `seq`;
-// the NEXT range-estimate launch sorts `cost` entries tagged `want_seq` into
-// `order` first (n_tiles of them). Consumed by those launches.
-static thread_local TileOrder g_sort_tiles = {};
-static thread_local const int* g_tile_order = nullptr;
-static thread_local unsigned long long* g_tile_cost = nullptr;
-static thread_local unsigned g_cost_seq = 0;
-int o3dmi_internal_raycast_tile_order(unsigned long long* cost, int* order,
-                                      int n_tiles, unsigned want_seq,
-                                      unsigned seq) {
-    g_sort_tiles.cost = cost;
-    g_sort_tiles.order = order;
-    g_sort_tiles.n_tiles = n_tiles;
-    g_sort_tiles.want_seq = want_seq;
-    g_tile_order = order;
-    g_tile_cost = cost;
-    g_cost_seq = seq;
-    return O3DMI_OK;
-}
-
-// Drops whatever the two calls above left for launches that were never made
-// (an error return between the call and its launch): the caller's scope guard.
-int o3dmi_internal_raycast_forget(void) {
-    g_reset_range = 0;
-    g_sort_tiles = TileOrder{};
-    g_tile_order = nullptr;
-    g_tile_cost = nullptr;
-    g_cost_seq = 0;
-    return O3DMI_OK;
-}
-
 int o3dmi_vbg_estimate_range_dev(const int32_t* block_keys_dev,
                                  int64_t max_blocks,
                                  const int32_t* n_blocks_dev,
@@ -955,7 +899,7 @@ int o3dmi_vbg_estimate_range_dev(const int32_t* block_keys_dev,
     return o3dmi_internal_estimate_range(
             block_keys_dev, 3, max_blocks, n_blocks_dev, range_minmax_map_dev,
             0, intrinsic, extrinsic, h, w, down_factor, block_resolution,
-            voxel_size, depth_min, depth_max, stream);
+            voxel_size, depth_min, depth_max, RayCastOptions{}, stream);
 }
 
 int o3dmi_internal_estimate_range(const int32_t* block_keys_dev, int key_stride,
@@ -966,10 +910,11 @@ int o3dmi_internal_estimate_range(const int32_t* block_keys_dev, int key_stride,
                                   const double* extrinsic, int h, int w,
                                   int down_factor, int64_t block_resolution,
                                   float voxel_size, float depth_min,
-                                  float depth_max, o3dmi_stream_t stream) {
-    // (the side channel is this call's whether or not it gets to its launch)
-    const TileOrder to = g_sort_tiles;
-    g_sort_tiles = TileOrder{};
+                                  float depth_max,
+                                  const RayCastOptions& options,
+                                  o3dmi_stream_t stream) {
+    const TileOrder to = {options.cost, options.order, options.n_tiles,
+                          options.want_seq};
     O3DMI_REQUIRE(range_minmax_map_dev && intrinsic && extrinsic,
                   "null argument");
     O3DMI_REQUIRE(down_factor > 0 && h >= down_factor && w >= down_factor,
@@ -1032,17 +977,28 @@ int o3dmi_vbg_raycast_rows(
         float voxel_size, float depth_scale, float depth_min, float depth_max,
         float weight_threshold, float trunc_voxel_multiplier,
         int range_map_down_factor, o3dmi_stream_t stream) {
-    (void)depth_min;
-    (void)depth_max;
-    // (the side channels are this call's whether or not it gets to its launch)
-    const int reset_range = g_reset_range;
-    const int* const tile_order = g_tile_order;
-    unsigned long long* const tile_cost = g_tile_cost;
-    const unsigned cost_seq = g_cost_seq;
-    g_reset_range = 0;
-    g_tile_order = nullptr;
-    g_tile_cost = nullptr;
-    g_cost_seq = 0;
+    return o3dmi_internal_raycast_rows(
+            block_hash, tsdf_dev, weight_dev, color_buf_dev, grid_dtype,
+            range_map_dev, out_depth, out_vertex, out_color, out_normal,
+            out_index, out_mask, out_ratio, out_ratio_dx, out_ratio_dy,
+            out_ratio_dz, intrinsic, extrinsic, h, w, row_begin, row_end,
+            block_resolution, voxel_size, depth_scale, depth_min, depth_max,
+            weight_threshold, trunc_voxel_multiplier, range_map_down_factor,
+            RayCastOptions{}, stream);
+}
+
+int o3dmi_internal_raycast_rows(
+        o3dmi_hash_t* block_hash, const float* tsdf_dev, const void* weight_dev,
+        const void* color_buf_dev, int grid_dtype, const float* range_map_dev,
+        float* out_depth, float* out_vertex, float* out_color,
+        float* out_normal, int64_t* out_index, uint8_t* out_mask,
+        float* out_ratio, float* out_ratio_dx, float* out_ratio_dy,
+        float* out_ratio_dz, const double* intrinsic, const double* extrinsic,
+        int h, int w, int row_begin, int row_end, int block_resolution,
+        float voxel_size, float depth_scale, float depth_min, float depth_max,
+        float weight_threshold, float trunc_voxel_multiplier,
+        int range_map_down_factor, const RayCastOptions& options,
+        o3dmi_stream_t stream) {
     O3DMI_REQUIRE(block_hash && tsdf_dev && weight_dev && range_map_dev &&
                           intrinsic && extrinsic,
                   "null argument");
@@ -1107,17 +1063,17 @@ int o3dmi_vbg_raycast_rows(
                             (whole ? (h + 7) / 8 : p.band_tys);
     p.xcd_bands = n_tiles <= kCUs * 5 ? 1 : 0;
     p.coop = 1;
-    // (o3dmi_internal_raycast_reset_range: consumed by this launch)
-    if (reset_range && whole && range_map_down_factor == 8) p.coop |= 2;
-    // (o3dmi_internal_raycast_tile_order: consumed by this launch; only for
-    // launches that run in rounds, whose grid is one workgroup per tile)
+    if (options.reset_range && whole && range_map_down_factor == 8)
+        p.coop |= 2;
+    // (the tile order: only for launches that run in rounds, whose grid is one
+    // workgroup per tile)
     p.tile_order = nullptr;
     p.tile_cost = nullptr;
     p.cost_seq = 0;
-    if (tile_cost && whole && !p.xcd_bands && n_tiles <= kCUs * 16) {
-        p.tile_order = tile_order;
-        p.tile_cost = tile_cost;
-        p.cost_seq = cost_seq;
+    if (options.cost && whole && !p.xcd_bands && n_tiles <= kCUs * 16) {
+        p.tile_order = options.order;
+        p.tile_cost = options.cost;
+        p.cost_seq = options.seq;
     }
     // a multiple of 8 workgroups: every XCD gets the same number
     dim3 grid((unsigned)((GridFor(n_tiles, 1, kCUs * 16) + 7) & ~7)),

@@ -17,6 +17,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "preload.h"
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1993,11 +1994,7 @@ int LaunchChunkIntegrate(o3dmi_hash* bh, const ChunkIntegrateArgs& a,
 // o3dmi_preload: HIP loads this translation unit's code object at the first
 // launch of one of its kernels; asking for a kernel's attributes does it now.
 int PreloadStream() {
-    hipFuncAttributes attr;
-    return hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(
-                                               &VerifyRcpKernel)) == hipSuccess
-                   ? 0
-                   : 1;
+    return LoadCodeObjectOf(reinterpret_cast<const void*>(&VerifyRcpKernel));
 }
 
 }  // namespace o3dmi

@@ -14,6 +14,7 @@
 // each key appends it to the output list. Counts stay on the device.
 
 #include "common.h"
+#include "preload.h"
 #include <map>
 #include <utility>
 
@@ -378,11 +379,8 @@ UnprojectPairKernel(UnprojectJob job_a, UnprojectJob job_b, unsigned seq) {
 // o3dmi_preload: HIP loads this translation unit's code object at the first
 // launch of one of its kernels; asking for a kernel's attributes does it now.
 int PreloadTouch() {
-    hipFuncAttributes attr;
-    return hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(
-                                               &DepthTouchKernel<uint16_t>)) == hipSuccess
-                   ? 0
-                   : 1;
+    return LoadCodeObjectOf(
+            reinterpret_cast<const void*>(&DepthTouchKernel<uint16_t>));
 }
 
 }  // namespace o3dmi

@@ -1,0 +1,502 @@
+// The pyramids of the MultiScaleICP driver (registration.cpp):
+// InitializePointCloudPyramidForMultiScaleICP, Registration.cpp:221-273, for
+// the source and the target cloud, and the coarsest scale's index.
+//
+// The source pyramid and the target pyramid are independent chains of
+// VoxelDownSample levels, each a string of small launches whose sizes stay
+// on the device (the voxel count of one level is the point count of the
+// next; level buffers are sized by the input cloud) -- latency, not
+// throughput. One host thread issues both, level by level, so the GPU works
+// on the two chains at once; the counts of both are read back once, at the
+// end. (Round 2 first ran the target chain from a helper thread: the thread
+// start and its first HIP call cost more than issuing the second chain's
+// launches from here.)
+
+#include <cstdlib>
+#include <initializer_list>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../common.h"
+#include "../mailbox.h"
+#include "../nns.h"
+#include "../vds.h"
+#include "icp_driver.h"
+#include "o3d_mi355x_host.h"
+
+namespace o3dmi {
+
+namespace {
+
+// One pyramid level without a host wait (vds.h). PointCloud::VoxelDownSample
+// averages every attribute; the kernel takes positions + one attribute, so
+// further attributes go through it again (the voxel order, first occurrence,
+// is the same every time, and so are the positions and the count).
+// next_voxel > 0: the chain's next call down-samples out_pos by that size;
+// from_previous: pos is the out_pos of the chain's previous call (vds.h: a
+// level with a single pass then carries the next level's hash insert).
+int DownSampleAttrsAsync(const void* pos, int64_t n_max, const int* n_dev,
+                         int dtype, double voxel, void* out_pos, int* m_dev,
+                         int* err_dev, std::vector<void*>& scratch,
+                         hipStream_t cs, int chain,
+                         std::initializer_list<std::pair<const void*, void*>>
+                                 attrs,
+                         double next_voxel = 0, bool from_previous = false,
+                         VdsLevelJob* defer = nullptr) {
+    if (voxel <= 0) {
+        SetLastError("voxel_size must be positive.");
+        return O3DMI_ERR_INVALID_ARG;
+    }
+    int passes = 0;
+    for (const auto& a : attrs) passes += a.first ? 1 : 0;
+    const bool single = passes <= 1;
+    if (defer && single) {
+        // one pass: the caller launches it together with the other cloud's
+        // level (VdsPairAsync)
+        defer->pos = pos;
+        defer->n_max = n_max;
+        defer->n_dev = n_dev;
+        defer->voxel_size = voxel;
+        defer->out_pos = out_pos;
+        defer->m_dev = m_dev;
+        defer->err_dev = err_dev;
+        defer->chain = chain;
+        defer->next_voxel_size = next_voxel;
+        defer->from_previous = from_previous;
+        for (const auto& a : attrs)
+            if (a.first) {
+                defer->attr = a.first;
+                defer->out_attr = a.second;
+            }
+        return O3DMI_OK;
+    }
+    bool done = false;
+    for (const auto& a : attrs) {
+        if (!a.first) continue;
+        int st = VdsAsync(pos, a.first, n_max, n_dev, dtype, voxel, out_pos,
+                          a.second, m_dev, err_dev, scratch, cs, chain,
+                          single ? next_voxel : 0.0, single && from_previous);
+        if (st) return st;
+        done = true;
+    }
+    if (!done)
+        return VdsAsync(pos, nullptr, n_max, n_dev, dtype, voxel, out_pos,
+                        nullptr, m_dev, err_dev, scratch, cs, chain,
+                        next_voxel, from_previous);
+    return O3DMI_OK;
+}
+
+// Device-side level counts of one cloud's pyramid: [level] voxel counts, then
+// one word of error flags, in a persistent buffer per host thread, device and
+// chain (zero when allocated; the posting launch re-zeroes the error word).
+// Read once, at the end of the chain, through the chain's host mailbox: no
+// clearing fill, no copy, no stream synchronisation per call.
+constexpr int kMaxDevices = 64;
+int CurrentDevice() {
+    int d = 0;
+    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDevices) return -1;
+    return d;
+}
+constexpr int kMaxScales = 30;
+static_assert(kMaxScales + 1 <= kCountsErr && kMaxScales + 1 <= 32,
+              "level counts below the error word; a post carries <= 32 values");
+struct ChainCounts {
+    int* dev = nullptr;
+    int levels = 0;
+    int chain = 0;
+    std::vector<void*> scratch;  // pooled scratch of the level launches
+    // The counts, the error word and the VoxelDownSample workspaces of a
+    // chain are cleaned by the chain's own last launches (the posting launch,
+    // the levels' reduce launches). `open`: a chain was started on this
+    // thread / device / chain slot and its counts were never waited for -- an
+    // error return somewhere between its first launch and Wait. The next
+    // chain then starts from re-zeroed counts and fresh workspaces instead of
+    // inheriting a stale error bit or stale table entries.
+    static bool& Open(int d, int chain_id) {
+        static thread_local bool open[kMaxDevices][2] = {};
+        return open[d][chain_id];
+    }
+    int device = -1;
+    int Init(int n_levels, int chain_id, hipStream_t cs) {
+        static thread_local int* bufs[kMaxDevices][2] = {};
+        O3DMI_REQUIRE(n_levels >= 1 && n_levels <= kMaxScales,
+                      "too many scales");
+        const int d = CurrentDevice();
+        O3DMI_REQUIRE(d >= 0 && (chain_id == 0 || chain_id == 1),
+                      "bad device / chain");
+        int*& b = bufs[d][chain_id];
+        const bool fresh = !b;
+        if (!b)
+            O3DMI_HIP_CHECK(hipMalloc((void**)&b,
+                                      sizeof(int) * 2 * kCountsKeep));
+        if (fresh || Open(d, chain_id)) {
+            if (!fresh) {
+                O3DMI_HIP_CHECK(hipDeviceSynchronize());
+                VdsChainInvalidate(chain_id);
+            }
+            O3DMI_HIP_CHECK(hipMemsetAsync(b, 0,
+                                           sizeof(int) * 2 * kCountsKeep, cs));
+        }
+        Open(d, chain_id) = true;
+        dev = b;
+        levels = n_levels;
+        chain = chain_id;
+        device = d;
+        return O3DMI_OK;
+    }
+    int* Count(int level) { return dev + level; }
+    // (valid behind the posting launch, PostCountsPairAsync)
+    const int* KeptCount(int level) const { return dev + kCountsKeep + level; }
+    int* Err() { return dev + kCountsErr; }  // (a post's value `levels`)
+    // Post: the counts leave for the chain's mailbox behind the chain's
+    // launches; Wait: for that, and returns them. (Both chains post before
+    // either is waited for: one host round trip, not two.)
+    int posted_seq = 0;
+    int Post(hipStream_t cs) {
+        Mailbox* mb = ThreadMailbox(1 + chain);
+        O3DMI_REQUIRE(mb != nullptr, "host mailbox allocation failed");
+        posted_seq = ++mb->seq;
+        return PostCountsAsync(dev, levels + 1, mb->data, mb->flag, posted_seq,
+                               cs);
+    }
+    // The post carried by the chain's last level launch (vds.h VdsPost): the
+    // request to hand to that level's job, then Posted() if it was taken up.
+    bool sealed = false;
+    int offered_seq = 0;
+    VdsPost OfferPost() {
+        VdsPost p;
+        Mailbox* mb = ThreadMailbox(1 + chain);
+        if (!mb) return p;
+        offered_seq = ++mb->seq;
+        p.counts = dev;
+        p.n = levels + 1;
+        p.mail_data = mb->data;
+        p.mail_flag = mb->flag;
+        p.mail_seq = offered_seq;
+        return p;
+    }
+    void Posted() {
+        posted_seq = offered_seq;
+        sealed = true;
+    }
+    // both chains were built in the same launches: one posting launch
+    static int PostPair(ChainCounts& a, ChainCounts& b, hipStream_t cs) {
+        Mailbox* ma = ThreadMailbox(1 + a.chain);
+        Mailbox* mb = ThreadMailbox(1 + b.chain);
+        O3DMI_REQUIRE(ma != nullptr && mb != nullptr && a.levels == b.levels,
+                      "host mailbox allocation failed");
+        a.posted_seq = ++ma->seq;
+        b.posted_seq = ++mb->seq;
+        return PostCountsPairAsync(a.dev, ma->data, ma->flag, a.posted_seq,
+                                   b.dev, mb->data, mb->flag, b.posted_seq,
+                                   a.levels + 1, cs);
+    }
+    int Wait(std::vector<int>& out, hipStream_t cs) {
+        out.assign((size_t)levels + 1, 0);
+        Mailbox* mb = ThreadMailbox(1 + chain);
+        O3DMI_REQUIRE(mb != nullptr && posted_seq != 0, "counts not posted");
+        const int seq = posted_seq;
+        posted_seq = 0;
+        double sealed32[32];
+        hipError_t e = sealed ? MailboxWaitSealed(mb, seq, cs, sealed32)
+                              : MailboxWait(mb, seq, cs);
+        const bool was_sealed = sealed;
+        sealed = false;
+        // the posting launch was the chain's last: its stream has drained
+        // (no hipStreamSynchronize, 16 us on an idle stream). (A sealed post
+        // comes from the last level's launch while it runs: only chains of
+        // the tiled form, which hold no pooled scratch.)
+        if (e == hipSuccess && !was_sealed) {
+            for (void* p : scratch) PoolFree(p);
+            scratch.clear();
+        }
+        Release(cs);
+        if (e != hipSuccess) {
+            SetLastError(std::string("pyramid read-back: ") +
+                         hipGetErrorString(e));
+            return O3DMI_ERR_HIP;
+        }
+        // the posting launch has run: counts and error word are zero again,
+        // every level's last launch has cleaned its workspace
+        if (device >= 0) Open(device, chain) = false;
+        for (int k = 0; k <= levels; ++k)
+            out[(size_t)k] = (int)(was_sealed ? sealed32[k] : mb->data[k]);
+        if (out[(size_t)levels] & kErrKeyRange) {
+            SetLastError("VoxelDownSample: voxel coordinate outside +-2^20");
+            return O3DMI_ERR_KEY_RANGE;
+        }
+        return O3DMI_OK;
+    }
+    void Release(hipStream_t cs) {
+        if (scratch.empty()) return;
+        (void)hipStreamSynchronize(cs);  // pooled blocks: stream drained
+        for (void* p : scratch) PoolFree(p);
+        scratch.clear();
+    }
+};
+
+// One cloud's chain of levels: what the level function needs to know about
+// the cloud, and the two things in which the clouds differ.
+struct CloudChain {
+    const void* pos = nullptr;  // the caller's cloud
+    const void* attr[kCloudAttrs] = {};
+    int64_t n = 0;
+    const int* n_dev = nullptr;
+    int id = 0;  // chain 0 (source) / 1 (target)
+    hipStream_t cs = nullptr;
+    CloudLevel Level::*which = nullptr;  // its half of a pyramid level
+    // the source is moved in place every iteration: a finest level that is
+    // the input itself is a private copy (the target's aliases the caller's)
+    bool clone_input = false;
+    // coloured ICP: the finest level needs colour gradients (target)
+    bool needs_gradients = false;
+    // the finest level's size is a host number: it is the input itself, or it
+    // was read back for the gradients
+    bool finest_on_host = false;
+    ChainCounts counts;
+    CloudChain(const IcpCall& c, const void* cloud, int64_t size,
+               const int32_t* size_dev, int chain, hipStream_t stream,
+               CloudLevel Level::*half)
+        : pos(cloud), n(size), n_dev((const int*)size_dev), id(chain),
+          cs(stream), which(half), finest_on_host(c.finest_is_input) {}
+    // releases the chain's pooled scratch on every exit path
+    ~CloudChain() { counts.Release(cs); }
+};
+
+int Clone(const IcpCall& c, DeviceBuffer& dst, const void* src, int64_t n,
+          hipStream_t cs) {
+    int e = dst.Alloc((size_t)n * 3 * c.esz);
+    if (e) return e;
+    O3DMI_HIP_CHECK(hipMemcpyAsync(dst.p, src, (size_t)n * 3 * c.esz,
+                                   hipMemcpyDeviceToDevice, cs));
+    return O3DMI_OK;
+}
+
+// Registration.cpp:243-262: EstimateColorGradients(30, radius) on the finest
+// level of the target pyramid. The operator needs the level's size on the
+// host: this (rare) path waits.
+int EstimateFinestGradients(const IcpCall& c, CloudChain& ch, CloudLevel& L) {
+    const int k = c.num_scales - 1;
+    if (!c.finest_is_input) {
+        int host_n = 0;
+        O3DMI_HIP_CHECK(hipMemcpyAsync(&host_n, ch.counts.Count(k), sizeof(int),
+                                       hipMemcpyDeviceToHost, ch.cs));
+        O3DMI_HIP_CHECK(hipStreamSynchronize(ch.cs));
+        L.n = host_n;
+        ch.finest_on_host = true;
+    }
+    const double radius = c.voxel_sizes[k] <= 0 ? c.max_dists[k] * 2.0
+                                                : c.voxel_sizes[k] * 4.0;
+    DeviceBuffer& grad = L.attr_buf[kGradients];
+    int e = grad.Alloc((size_t)ch.n * 3 * c.esz);
+    if (e) return e;
+    e = o3dmi_pointcloud_estimate_color_gradients(
+            L.pos, L.attr[kNormals], L.attr[kColors], L.n, c.dtype, 30, radius,
+            grad.p, (o3dmi_stream_t)ch.cs);
+    if (e) return e;
+    L.attr[kGradients] = grad.p;
+    return O3DMI_OK;
+}
+
+// Level k of one cloud's pyramid: the input itself (voxel size <= 0, finest
+// level only), else the down-sampled input (finest) or finer level. With
+// `job` a level of a single pass is left for the caller to launch.
+int BuildLevel(const IcpCall& c, CloudChain& ch, std::vector<Level>& pyr, int k,
+               VdsLevelJob* job) {
+    int e;
+    const int last = c.num_scales - 1;
+    CloudLevel& L = pyr[(size_t)k].*ch.which;
+    ChainCounts& cc = ch.counts;
+    if (k == last && c.finest_is_input) {
+        L.n = ch.n;
+        L.pos = ch.pos;
+        for (int a = 0; a < kCloudAttrs; ++a) L.attr[a] = ch.attr[a];
+        if (ch.clone_input) {
+            if ((e = Clone(c, L.pos_buf, ch.pos, ch.n, ch.cs))) return e;
+            L.pos = L.pos_buf.p;
+            for (int a = 0; a < kCloudAttrs; ++a) {
+                if (!ch.attr[a]) continue;
+                if ((e = Clone(c, L.attr_buf[a], ch.attr[a], ch.n, ch.cs)))
+                    return e;
+                L.attr[a] = L.attr_buf[a].p;
+            }
+        }
+    } else {
+        // (the coarser level is built from this one's output: vds.h)
+        const double next_vs = k > 0 ? c.voxel_sizes[k - 1] : 0.0;
+        const CloudLevel* F =
+                k == last ? nullptr : &(pyr[(size_t)k + 1].*ch.which);
+        const void* const* in_attr = F ? F->attr : ch.attr;
+        if ((e = L.pos_buf.Alloc((size_t)ch.n * 3 * c.esz))) return e;
+        for (int a = 0; a < kCloudAttrs; ++a)
+            if (in_attr[a] &&
+                (e = L.attr_buf[a].Alloc((size_t)ch.n * 3 * c.esz)))
+                return e;
+        // the finer level's size is a host number when it is the input
+        // itself (or was read back): then n_max = that size
+        const bool f_host = F && k + 1 == last && ch.finest_on_host;
+        e = DownSampleAttrsAsync(
+                F ? F->pos : ch.pos, f_host ? F->n : ch.n,
+                F ? (f_host ? nullptr : cc.Count(k + 1)) : ch.n_dev, c.dtype,
+                c.voxel_sizes[k], L.pos_buf.p, cc.Count(k), cc.Err(),
+                cc.scratch, ch.cs, ch.id,
+                {{in_attr[0], L.attr_buf[0].p},
+                 {in_attr[1], L.attr_buf[1].p},
+                 {in_attr[2], L.attr_buf[2].p}},
+                next_vs, F && !f_host, job);
+        if (e) return e;
+        L.pos = L.pos_buf.p;
+        // (an attribute the cloud does not have stays NULL)
+        for (int a = 0; a < kCloudAttrs; ++a) L.attr[a] = L.attr_buf[a].p;
+    }
+    if (k == last && ch.needs_gradients && !L.attr[kGradients])
+        return EstimateFinestGradients(c, ch, L);
+    return O3DMI_OK;
+}
+
+// Every level of both pyramids, coarsest last. `paired`: the two clouds'
+// levels go out in the SAME launches on the caller's stream; *counts_posted:
+// the coarsest pair's launch took the counts' post with it.
+int LaunchLevels(const IcpCall& c, CloudChain& src, CloudChain& tgt,
+                 std::vector<Level>& pyr, bool paired, bool* counts_posted) {
+    static const bool no_folded_post =
+            std::getenv("O3DMI_VDS_POST_LAUNCH") != nullptr;
+    int st;
+    for (int k = c.num_scales - 1; k >= 0; --k) {
+        VdsLevelJob jobs[2];
+        // the target level's job is prepared before the source level's
+        if ((st = BuildLevel(c, tgt, pyr, k, paired ? &jobs[1] : nullptr)))
+            return st;
+        if ((st = BuildLevel(c, src, pyr, k, paired ? &jobs[0] : nullptr)))
+            return st;
+        if (!paired) continue;
+        // (a level that is the input itself leaves its job empty)
+        VdsLevelJob both[2];
+        int n_jobs = 0;
+        if (jobs[0].pos) both[n_jobs++] = jobs[0];
+        if (jobs[1].pos) both[n_jobs++] = jobs[1];
+        // the coarsest level's launch posts both chains' counts itself
+        const bool offer = k == 0 && n_jobs == 2 && !no_folded_post;
+        if (offer) {
+            both[0].post = src.counts.OfferPost();
+            both[1].post = tgt.counts.OfferPost();
+        }
+        bool posted = false;
+        if (n_jobs && (st = VdsPairAsync(both, n_jobs, c.dtype,
+                                         src.counts.scratch, c.s, &posted)))
+            return st;
+        if (posted) {
+            src.counts.Posted();
+            tgt.counts.Posted();
+            *counts_posted = true;
+        }
+    }
+    return O3DMI_OK;
+}
+
+}  // namespace
+
+hipStream_t SideStream() {
+    static thread_local hipStream_t side[kMaxDevices] = {};
+    const int d = CurrentDevice();
+    if (d < 0) return nullptr;
+    if (!side[d] &&
+        hipStreamCreateWithFlags(&side[d], hipStreamNonBlocking) != hipSuccess)
+        side[d] = nullptr;
+    return side[d];
+}
+
+hipEvent_t SideEvent() {
+    static thread_local hipEvent_t ev[kMaxDevices] = {};
+    const int d = CurrentDevice();
+    if (d < 0) return nullptr;
+    if (!ev[d] &&
+        hipEventCreateWithFlags(&ev[d], hipEventDisableTiming) != hipSuccess)
+        ev[d] = nullptr;
+    return ev[d];
+}
+
+int BuildPyramids(const IcpCall& c, std::vector<Level>& pyr,
+                  NnsGuard& first_index) {
+    const int last = c.num_scales - 1;
+    int st;
+    if (c.side != c.s) {
+        // the caller's clouds may still be in flight on its stream
+        O3DMI_HIP_CHECK(hipEventRecord(c.ev, c.s));
+        O3DMI_HIP_CHECK(hipStreamWaitEvent(c.side, c.ev, 0));
+    }
+    // Round 6: the two pyramids advance level by level in the SAME
+    // launches on the caller's stream (VdsPairAsync: blockIdx.y = cloud)
+    // -- 7 launches + one posting launch for a three-level pair of
+    // pyramids instead of two chains of 8 on two streams (the source chain on
+    // the caller's stream, the target chain on the side stream). Coloured ICP
+    // (three attribute passes per target level) keeps the two chains.
+    static const bool unpaired = std::getenv("O3DMI_VDS_UNPAIRED") != nullptr;
+    const bool paired = !c.colored && !unpaired;
+    hipStream_t ts = paired ? c.s : c.side;
+    // (declared in this order: the target chain's scratch is released first)
+    CloudChain src(c, c.source, c.ns, c.ns_dev, 0, c.s, &Level::source);
+    src.attr[kNormals] = c.source_normals;
+    src.attr[kColors] = c.source_colors;
+    src.clone_input = true;
+    CloudChain tgt(c, c.target, c.nt, c.nt_dev, 1, ts, &Level::target);
+    tgt.attr[kNormals] = c.target_normals;
+    tgt.attr[kColors] = c.target_colors;
+    tgt.attr[kGradients] = c.target_gradients;
+    tgt.needs_gradients = c.colored;
+    ChainCounts &scc = src.counts, &tcc = tgt.counts;
+    if ((st = scc.Init(c.num_scales, 0, c.s))) return st;
+    if ((st = tcc.Init(c.num_scales, 1, ts))) return st;
+    bool counts_posted = false;
+    if ((st = LaunchLevels(c, src, tgt, pyr, paired, &counts_posted)))
+        return st;
+    // The coarsest scale's index, queued behind the posting launch BEFORE
+    // the sizes are read back (its one-workgroup build takes the target
+    // level's size from the count the posting launch keeps): it runs while
+    // the counts cross PCIe and the host gets ready to launch the first
+    // search -- that search used to wait for count -> host -> allocation ->
+    // build launch -> build (a 20 us hole in every tracked frame, r6a).
+    NnsGuard early;  // (destroyed with a device-wide wait if not adopted)
+    const CloudLevel& T0 = pyr[0].target;
+    const void* nrm0 = c.p2plane ? T0.attr[kNormals] : nullptr;
+    const bool early_build =
+            paired && !(last == 0 && c.finest_is_input) && T0.pos;
+    if (paired) {
+        if (!counts_posted && (st = ChainCounts::PostPair(scc, tcc, c.s)))
+            return st;
+        if (early_build &&
+            (st = o3dmi_internal_nns_create_small_deferred(
+                     T0.pos, nrm0, tcc.KeptCount(0), c.dtype, c.max_dists[0],
+                     c.stream(), &early.nns)))
+            return st;
+    } else {
+        if ((st = tcc.Post(ts))) return st;
+        if ((st = scc.Post(c.s))) return st;
+    }
+    std::vector<int> counts;
+    if ((st = tcc.Wait(counts, ts))) return st;
+    for (int k = 0; k < c.num_scales; ++k)
+        if (!(k == last && tgt.finest_on_host))
+            pyr[(size_t)k].target.n = counts[(size_t)k];
+    if ((st = scc.Wait(counts, c.s))) return st;
+    for (int k = 0; k < c.num_scales; ++k)
+        if (!(k == last && c.finest_is_input))
+            pyr[(size_t)k].source.n = counts[(size_t)k];
+    // Indices: the first scale's on the caller's stream (its first search
+    // follows at once). The others go to the side stream LATER, issued while
+    // the host would otherwise spin on a search launch's sums (registration.cpp
+    // IndexScheduler): issuing them here kept the host busy for ~60 us (eight
+    // launch calls) before it got to the first search -- with the GPU idle
+    // (tools/slam_timeline.py).
+    if (early.nns && o3dmi_internal_nns_adopt_count(early.nns, T0.n)) {
+        first_index.nns = early.nns;
+        early.nns = nullptr;
+        return O3DMI_OK;
+    }
+    return o3dmi_internal_nns_create_with_normals(T0.pos, nrm0, T0.n, c.dtype,
+                                                  c.max_dists[0], c.stream(),
+                                                  &first_index.nns);
+}
+
+}  // namespace o3dmi

@@ -29,22 +29,12 @@
 #include "../common.h"
 #include "../mailbox.h"
 #include "../odometry.h"
+#include "host_util.h"
 #include "o3d_mi355x_host.h"
 
 using namespace o3dmi;
 
 namespace {
-
-void Matmul4(const double* A, const double* B, double* C) {
-    double R[16];
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-            double s = 0;
-            for (int k = 0; k < 4; ++k) s += A[i * 4 + k] * B[k * 4 + j];
-            R[i * 4 + j] = s;
-        }
-    std::memcpy(C, R, sizeof(R));
-}
 
 struct Level {
     int rows = 0, cols = 0;
@@ -136,7 +126,7 @@ extern "C" int o3dmi_rgbd_odometry_multiscale(
     slab.size = total + sums_bytes + 256;
     // `drained`: the host has seen the mailbox of the call's last launch and
     // issued nothing since -- the stream is idle, and hipStreamSynchronize
-    // costs 16 us even then (registration.cpp SyncOnExit). Valid because that
+    // costs 16 us even then (host_util.h SyncOnExit). Valid because that
     // last launch is a single-workgroup tail (the final-sum / posting launch
     // of the host-driven loop).
     struct SlabFree {

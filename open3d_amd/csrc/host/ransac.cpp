@@ -14,6 +14,7 @@
 #include <limits>
 
 #include "common.h"
+#include "host/host_util.h"
 #include "nns.h"
 #include "o3d_mi355x_host.h"
 #include "ransac.h"
@@ -54,13 +55,6 @@ void* ThreadPinned(size_t bytes) {
     }
     return p;
 }
-
-struct IndexGuard {
-    o3dmi_nns_t* nns = nullptr;
-    ~IndexGuard() {
-        if (nns) o3dmi_nns_destroy(nns);
-    }
-};
 
 int Unsupported(const char* msg) {
     SetLastError(msg);
@@ -129,7 +123,7 @@ extern "C" int o3dmi_registration_ransac_correspondence(
     const int64_t bmax = adaptive ? cap : batch;
 
     PoolScratch sc(s);
-    IndexGuard index;
+    NnsGuard index;
     int* bad = nullptr;
     int64_t* samples = nullptr;
     double* T_all = nullptr;

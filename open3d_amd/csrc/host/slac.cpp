@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "common.h"
+#include "host/host_util.h"
 #include "o3d_mi355x_host.h"
 #include "scan.h"
 #include "slac.h"
@@ -20,13 +21,6 @@ using namespace o3dmi;
 namespace {
 
 constexpr int kSlacMaxNodes = 512;  // a 3072^2 float64 host matrix, 75 MB
-
-struct IndexGuard {
-    o3dmi_nns_t* nns = nullptr;
-    ~IndexGuard() {
-        if (nns) o3dmi_nns_destroy(nns);
-    }
-};
 
 void Pose12(const double* T, float* out) {
     for (int k = 0; k < 12; ++k) out[k] = (float)T[k];
@@ -101,7 +95,7 @@ extern "C" int o3dmi_slac_correspondence_set(
     O3DMI_REQUIRE(distance_threshold > 0, "distance_threshold must be > 0");
     hipStream_t s = (hipStream_t)stream;
     PoolScratch sc(s);
-    IndexGuard index;
+    NnsGuard index;
     float* moved = nullptr;
     int32_t* idx = nullptr;
     float* dist2 = nullptr;

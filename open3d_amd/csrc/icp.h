@@ -1,5 +1,6 @@
-// Private seam between the ICP driver (host/registration.cpp) and icp.hip:
-// the entry points that are not in the public header.
+// Private seam between the ICP driver (host/registration.cpp: the scale loop;
+// host/registration_eval.cpp: EvaluateRegistration, information matrix, RMSE)
+// and icp.hip: the entry points that are not in the public header.
 #pragma once
 
 #include "common.h"

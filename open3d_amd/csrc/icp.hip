@@ -1030,6 +1030,33 @@ int ReduceGrid(int64_t n) {
     return (int)g;
 }
 
+// The frame of the gather-and-accumulate entry points: `launch(T(), partials,
+// g, s)` launches the accumulate kernel of the clouds' type T with grid g, one
+// row of kNumSums partial sums per workgroup; the single-workgroup final pass
+// then sums the rows into out_dev[0..n_sums) (and / or a host mailbox,
+// mailbox.h). partials_dev: the caller's rows (>= ReduceGrid rows), NULL:
+// allocated here, stream-ordered.
+template <typename Launch>
+int AccumulateAndReduce(int64_t n, int dtype, int n_sums, double* out_dev,
+                        double* partials_dev, double* mail_data,
+                        int* mail_flag, int mail_seq, o3dmi_stream_t stream,
+                        Launch&& launch) {
+    hipStream_t s = (hipStream_t)stream;
+    const int g = ReduceGrid(n);
+    double* partials = partials_dev;
+    if (!partials)
+        O3DMI_HIP_CHECK(hipMallocAsync((void**)&partials,
+                                       sizeof(double) * (size_t)g * kNumSums,
+                                       s));
+    if (dtype == O3DMI_F64) launch(double(), partials, g, s);
+    else launch(float(), partials, g, s);
+    hipLaunchKernelGGL(FinalReduceKernel, dim3(1), dim3(256), 0, s, partials, g,
+                       out_dev, n_sums, mail_data, mail_flag, mail_seq);
+    O3DMI_HIP_CHECK(hipGetLastError());
+    if (!partials_dev) O3DMI_HIP_CHECK(hipFreeAsync(partials, s));
+    return O3DMI_OK;
+}
+
 }  // namespace
 // o3dmi_preload: HIP loads this translation unit's code object at the first
 // launch of one of its kernels; asking for a kernel's attributes does it now.
@@ -1057,29 +1084,18 @@ int o3dmi_icp_p2plane_accumulate(const void* src_dev, const void* tgt_dev,
                   "points must be Float32 or Float64");
     O3DMI_REQUIRE(robust_kernel >= 0 && robust_kernel <= 6,
                   "Unsupported method.");
-    hipStream_t s = (hipStream_t)stream;
-    int g = ReduceGrid(n);
-    double* partials = nullptr;
-    O3DMI_HIP_CHECK(hipMallocAsync((void**)&partials,
-                                   sizeof(double) * (size_t)g * kNumSums, s));
     RobustParams rp = MakeRobust(robust_kernel, scaling_parameter,
                                  shape_parameter);
-    if (dtype == O3DMI_F64)
-        hipLaunchKernelGGL(P2PlaneAccumulateKernel<double>, dim3(g),
-                           dim3(kReduceBlock), 0, s, (const double*)src_dev,
-                           (const double*)tgt_dev,
-                           (const double*)tgt_normals_dev, corr_dev, n, rp,
-                           partials);
-    else
-        hipLaunchKernelGGL(P2PlaneAccumulateKernel<float>, dim3(g),
-                           dim3(kReduceBlock), 0, s, (const float*)src_dev,
-                           (const float*)tgt_dev, (const float*)tgt_normals_dev,
-                           corr_dev, n, rp, partials);
-    hipLaunchKernelGGL(FinalReduceKernel, dim3(1), dim3(256), 0, s, partials, g,
-                       sums29_dev, 29, (double*)nullptr, (int*)nullptr, 0);
-    O3DMI_HIP_CHECK(hipGetLastError());
-    O3DMI_HIP_CHECK(hipFreeAsync(partials, s));
-    return O3DMI_OK;
+    return AccumulateAndReduce(
+            n, dtype, 29, sums29_dev, nullptr, nullptr, nullptr, 0, stream,
+            [&](auto t, double* partials, int g, hipStream_t s) {
+                using T = decltype(t);
+                hipLaunchKernelGGL(P2PlaneAccumulateKernel<T>, dim3(g),
+                                   dim3(kReduceBlock), 0, s, (const T*)src_dev,
+                                   (const T*)tgt_dev,
+                                   (const T*)tgt_normals_dev, corr_dev, n, rp,
+                                   partials);
+            });
 }
 
 // Internal (host header: o3dmi_registration_compute_rmse): sums2_dev[0] = sum
@@ -1091,29 +1107,19 @@ int o3dmi_icp_residual_squares(const void* src_dev, const void* tgt_dev,
     O3DMI_REQUIRE(src_dev && tgt_dev && corr_dev && sums2_dev, "null argument");
     O3DMI_REQUIRE(dtype == O3DMI_F32 || dtype == O3DMI_F64,
                   "points must be Float32 or Float64");
-    hipStream_t s = (hipStream_t)stream;
-    int g = ReduceGrid(n);
-    double* partials = nullptr;
-    O3DMI_HIP_CHECK(hipMallocAsync((void**)&partials,
-                                   sizeof(double) * (size_t)g * kNumSums, s));
-#define O3DMI_RESID(T, P)                                                      \
+    return AccumulateAndReduce(
+            n, dtype, 2, sums2_dev, nullptr, nullptr, nullptr, 0, stream,
+            [&](auto t, double* partials, int g, hipStream_t s) {
+                using T = decltype(t);
+#define O3DMI_RESID(P)                                                         \
     hipLaunchKernelGGL((ResidualSquaresKernel<T, P>), dim3(g),                 \
                        dim3(kReduceBlock), 0, s, (const T*)src_dev,            \
                        (const T*)tgt_dev, (const T*)tgt_normals_dev, corr_dev, \
                        n, partials)
-    if (dtype == O3DMI_F64) {
-        if (tgt_normals_dev) O3DMI_RESID(double, true);
-        else O3DMI_RESID(double, false);
-    } else {
-        if (tgt_normals_dev) O3DMI_RESID(float, true);
-        else O3DMI_RESID(float, false);
-    }
+                if (tgt_normals_dev) O3DMI_RESID(true);
+                else O3DMI_RESID(false);
 #undef O3DMI_RESID
-    hipLaunchKernelGGL(FinalReduceKernel, dim3(1), dim3(256), 0, s, partials, g,
-                       sums2_dev, 2, (double*)nullptr, (int*)nullptr, 0);
-    O3DMI_HIP_CHECK(hipGetLastError());
-    O3DMI_HIP_CHECK(hipFreeAsync(partials, s));
-    return O3DMI_OK;
+            });
 }
 
 int o3dmi_icp_p2point_accumulate(const void* src_dev, const void* tgt_dev,
@@ -1123,24 +1129,14 @@ int o3dmi_icp_p2point_accumulate(const void* src_dev, const void* tgt_dev,
                   "null argument");
     O3DMI_REQUIRE(dtype == O3DMI_F32 || dtype == O3DMI_F64,
                   "points must be Float32 or Float64");
-    hipStream_t s = (hipStream_t)stream;
-    int g = ReduceGrid(n);
-    double* partials = nullptr;
-    O3DMI_HIP_CHECK(hipMallocAsync((void**)&partials,
-                                   sizeof(double) * (size_t)g * kNumSums, s));
-    if (dtype == O3DMI_F64)
-        hipLaunchKernelGGL(P2PointAccumulateKernel<double>, dim3(g),
-                           dim3(kReduceBlock), 0, s, (const double*)src_dev,
-                           (const double*)tgt_dev, corr_dev, n, partials);
-    else
-        hipLaunchKernelGGL(P2PointAccumulateKernel<float>, dim3(g),
-                           dim3(kReduceBlock), 0, s, (const float*)src_dev,
-                           (const float*)tgt_dev, corr_dev, n, partials);
-    hipLaunchKernelGGL(FinalReduceKernel, dim3(1), dim3(256), 0, s, partials, g,
-                       sums16_dev, 16, (double*)nullptr, (int*)nullptr, 0);
-    O3DMI_HIP_CHECK(hipGetLastError());
-    O3DMI_HIP_CHECK(hipFreeAsync(partials, s));
-    return O3DMI_OK;
+    return AccumulateAndReduce(
+            n, dtype, 16, sums16_dev, nullptr, nullptr, nullptr, 0, stream,
+            [&](auto t, double* partials, int g, hipStream_t s) {
+                using T = decltype(t);
+                hipLaunchKernelGGL(P2PointAccumulateKernel<T>, dim3(g),
+                                   dim3(kReduceBlock), 0, s, (const T*)src_dev,
+                                   (const T*)tgt_dev, corr_dev, n, partials);
+            });
 }
 
 // Internal: also posts the 29 sums to a host mailbox when mail_data != NULL.
@@ -1162,40 +1158,24 @@ int o3dmi_icp_colored_accumulate_post(
                   "Unsupported method.");
     O3DMI_REQUIRE(lambda_geometric >= 0 && lambda_geometric <= 1.0,
                   "lambda_geometric must be in [0, 1]");
-    hipStream_t s = (hipStream_t)stream;
-    int g = ReduceGrid(n);
-    double* partials = partials_dev;
-    if (!partials)
-        O3DMI_HIP_CHECK(hipMallocAsync((void**)&partials,
-                                       sizeof(double) * (size_t)g * kNumSums,
-                                       s));
     RobustParams rp = MakeRobust(robust_kernel, scaling_parameter,
                                  shape_parameter);
     // ComputePoseColoredICPCPU, RegistrationCPU.cpp:310-313
     const double slg = std::sqrt(lambda_geometric);
     const double slp = std::sqrt(1.0 - lambda_geometric);
-    if (dtype == O3DMI_F64)
-        hipLaunchKernelGGL(ColoredAccumulateKernel<double>, dim3(g),
-                           dim3(kReduceBlock), 0, s, (const double*)src_dev,
-                           (const double*)src_colors_dev,
-                           (const double*)tgt_dev,
-                           (const double*)tgt_normals_dev,
-                           (const double*)tgt_colors_dev,
-                           (const double*)tgt_color_gradients_dev, corr_dev, n,
-                           slg, slp, rp, partials);
-    else
-        hipLaunchKernelGGL(ColoredAccumulateKernel<float>, dim3(g),
-                           dim3(kReduceBlock), 0, s, (const float*)src_dev,
-                           (const float*)src_colors_dev, (const float*)tgt_dev,
-                           (const float*)tgt_normals_dev,
-                           (const float*)tgt_colors_dev,
-                           (const float*)tgt_color_gradients_dev, corr_dev, n,
-                           (float)slg, (float)slp, rp, partials);
-    hipLaunchKernelGGL(FinalReduceKernel, dim3(1), dim3(256), 0, s, partials, g,
-                       sums29_dev, 29, mail_data, mail_flag, mail_seq);
-    O3DMI_HIP_CHECK(hipGetLastError());
-    if (!partials_dev) O3DMI_HIP_CHECK(hipFreeAsync(partials, s));
-    return O3DMI_OK;
+    return AccumulateAndReduce(
+            n, dtype, 29, sums29_dev, partials_dev, mail_data, mail_flag,
+            mail_seq, stream,
+            [&](auto t, double* partials, int g, hipStream_t s) {
+                using T = decltype(t);
+                hipLaunchKernelGGL(ColoredAccumulateKernel<T>, dim3(g),
+                                   dim3(kReduceBlock), 0, s, (const T*)src_dev,
+                                   (const T*)src_colors_dev, (const T*)tgt_dev,
+                                   (const T*)tgt_normals_dev,
+                                   (const T*)tgt_colors_dev,
+                                   (const T*)tgt_color_gradients_dev, corr_dev,
+                                   n, (T)slg, (T)slp, rp, partials);
+            });
 }
 
 int o3dmi_icp_colored_accumulate(
@@ -1229,44 +1209,24 @@ int o3dmi_icp_symmetric_accumulate_post(
                   "points must be Float32 or Float64");
     O3DMI_REQUIRE(robust_kernel >= 0 && robust_kernel <= 6,
                   "Unsupported method.");
-    hipStream_t s = (hipStream_t)stream;
-    int g = ReduceGrid(n);
-    double* partials = partials_dev;
-    if (!partials)
-        O3DMI_HIP_CHECK(hipMallocAsync((void**)&partials,
-                                       sizeof(double) * (size_t)g * kNumSums,
-                                       s));
     RobustParams rp = MakeRobust(robust_kernel, scaling_parameter,
                                  shape_parameter);
-    if (dtype == O3DMI_F64) {
-        Means3<double> m;
-        for (int k = 0; k < 3; ++k) {
-            m.s[k] = source_mean3[k];
-            m.t[k] = target_mean3[k];
-        }
-        hipLaunchKernelGGL(SymmetricAccumulateKernel<double>, dim3(g),
-                           dim3(kReduceBlock), 0, s, (const double*)src_dev,
-                           (const double*)src_normals_dev,
-                           (const double*)tgt_dev,
-                           (const double*)tgt_normals_dev, corr_dev, n, m, rp,
-                           partials);
-    } else {
-        Means3<float> m;
-        for (int k = 0; k < 3; ++k) {
-            m.s[k] = (float)source_mean3[k];
-            m.t[k] = (float)target_mean3[k];
-        }
-        hipLaunchKernelGGL(SymmetricAccumulateKernel<float>, dim3(g),
-                           dim3(kReduceBlock), 0, s, (const float*)src_dev,
-                           (const float*)src_normals_dev, (const float*)tgt_dev,
-                           (const float*)tgt_normals_dev, corr_dev, n, m, rp,
-                           partials);
-    }
-    hipLaunchKernelGGL(FinalReduceKernel, dim3(1), dim3(256), 0, s, partials, g,
-                       sums29_dev, 29, mail_data, mail_flag, mail_seq);
-    O3DMI_HIP_CHECK(hipGetLastError());
-    if (!partials_dev) O3DMI_HIP_CHECK(hipFreeAsync(partials, s));
-    return O3DMI_OK;
+    return AccumulateAndReduce(
+            n, dtype, 29, sums29_dev, partials_dev, mail_data, mail_flag,
+            mail_seq, stream,
+            [&](auto t, double* partials, int g, hipStream_t s) {
+                using T = decltype(t);
+                Means3<T> m;
+                for (int k = 0; k < 3; ++k) {
+                    m.s[k] = (T)source_mean3[k];
+                    m.t[k] = (T)target_mean3[k];
+                }
+                hipLaunchKernelGGL(SymmetricAccumulateKernel<T>, dim3(g),
+                                   dim3(kReduceBlock), 0, s, (const T*)src_dev,
+                                   (const T*)src_normals_dev, (const T*)tgt_dev,
+                                   (const T*)tgt_normals_dev, corr_dev, n, m,
+                                   rp, partials);
+            });
 }
 
 int o3dmi_icp_symmetric_accumulate(
@@ -1289,24 +1249,14 @@ int o3dmi_icp_information_accumulate(const void* tgt_dev,
     O3DMI_REQUIRE(tgt_dev && corr_dev && sums21_dev, "null argument");
     O3DMI_REQUIRE(dtype == O3DMI_F32 || dtype == O3DMI_F64,
                   "points must be Float32 or Float64");
-    hipStream_t s = (hipStream_t)stream;
-    int g = ReduceGrid(n);
-    double* partials = nullptr;
-    O3DMI_HIP_CHECK(hipMallocAsync((void**)&partials,
-                                   sizeof(double) * (size_t)g * kNumSums, s));
-    if (dtype == O3DMI_F64)
-        hipLaunchKernelGGL(InformationAccumulateKernel<double>, dim3(g),
-                           dim3(kReduceBlock), 0, s, (const double*)tgt_dev,
-                           corr_dev, n, partials);
-    else
-        hipLaunchKernelGGL(InformationAccumulateKernel<float>, dim3(g),
-                           dim3(kReduceBlock), 0, s, (const float*)tgt_dev,
-                           corr_dev, n, partials);
-    hipLaunchKernelGGL(FinalReduceKernel, dim3(1), dim3(256), 0, s, partials, g,
-                       sums21_dev, 21, (double*)nullptr, (int*)nullptr, 0);
-    O3DMI_HIP_CHECK(hipGetLastError());
-    O3DMI_HIP_CHECK(hipFreeAsync(partials, s));
-    return O3DMI_OK;
+    return AccumulateAndReduce(
+            n, dtype, 21, sums21_dev, nullptr, nullptr, nullptr, 0, stream,
+            [&](auto t, double* partials, int g, hipStream_t s) {
+                using T = decltype(t);
+                hipLaunchKernelGGL(InformationAccumulateKernel<T>, dim3(g),
+                                   dim3(kReduceBlock), 0, s, (const T*)tgt_dev,
+                                   corr_dev, n, partials);
+            });
 }
 
 int o3dmi_icp_search_accumulate_p2point(const o3dmi_nns_t* nns,
@@ -1349,7 +1299,7 @@ int o3dmi_icp_search_accumulate_post(
 // Internal: as above, and when `transformation` (row-major 4x4, float64) is
 // given the source points are first moved by it IN PLACE, with
 // o3dmi_transform_points' arithmetic, inside the same launch.
-static int LaunchSearchAccumulate(
+int o3dmi_internal_icp_transform_search_accumulate(
         const o3dmi_nns_t* nns, void* src_dev, const double* transformation,
         const void* tgt_normals_dev, int64_t n, int estimation,
         int robust_kernel, double scaling_parameter, double shape_parameter,
@@ -1446,19 +1396,6 @@ static int LaunchSearchAccumulate(
 #undef O3DMI_SEARCH_E
     O3DMI_HIP_CHECK(hipGetLastError());
     return O3DMI_OK;
-}
-
-int o3dmi_internal_icp_transform_search_accumulate(
-        const o3dmi_nns_t* nns, void* src_dev, const double* transformation,
-        const void* tgt_normals_dev, int64_t n, int estimation,
-        int robust_kernel, double scaling_parameter, double shape_parameter,
-        int64_t* corr_out_dev, double* sums32_dev, double* mail_data,
-        int* mail_flag, int mail_seq, o3dmi_stream_t stream) {
-    return LaunchSearchAccumulate(nns, src_dev, transformation, tgt_normals_dev,
-                                  n, estimation, robust_kernel,
-                                  scaling_parameter, shape_parameter,
-                                  corr_out_dev, sums32_dev, mail_data, mail_flag,
-                                  mail_seq, stream);
 }
 
 int o3dmi_transform_points(const double* transformation, void* points_dev,

@@ -119,12 +119,17 @@ int o3dmi_hash_clear(o3dmi_hash_t* h, o3dmi_stream_t stream);
  * otherwise masks[i] = 0, buf_indices[i] = 0 (TBBHashBackend.h:203-247).
  * `n_dev` (optional, may be NULL) is a device int32 holding the live count
  * (<= n); when given, only the first *n_dev keys are processed.
- * Caller guarantees size + n <= capacity (HashMap::Activate reserves first). */
+ * Caller guarantees size + n <= capacity (HashMap::Activate reserves first).
+ * Past the capacity, the next o3dmi_hash_size returns O3DMI_ERR_CAPACITY, the
+ * keys that got no index are absent (Find, GetActiveIndices) and the map needs
+ * o3dmi_hash_clear before further use. */
 int o3dmi_hash_activate(o3dmi_hash_t* h, const int32_t* keys_dev, int64_t n,
                         const int32_t* n_dev, int32_t* buf_indices_dev,
                         uint8_t* masks_dev, o3dmi_stream_t stream);
-/* DeviceHashBackend::Insert with values: value i of the winner of key k is
- * copied from values_soa_dev[j] + k * value_dsizes[j]. */
+/* DeviceHashBackend::Insert with values: value array j of a new key is copied
+ * from values_soa_dev[j] + k * value_dsizes[j], where k is the position in
+ * `keys_dev` of the winning occurrence of that key (the one with masks[k] = 1),
+ * not of any other duplicate. */
 int o3dmi_hash_insert(o3dmi_hash_t* h, const int32_t* keys_dev,
                       const void* const* values_soa_dev, int64_t n,
                       int32_t* buf_indices_dev, uint8_t* masks_dev,

@@ -68,6 +68,10 @@ __global__ void ActivateKernel(HashView hv, const int* __restrict__ keys,
             if (ClaimSlot(hv, PackKey(x, y, z), h) == 1) {
                 int top = atomicAdd(&hv.counters[0], 1);
                 if (top >= hv.capacity) {
+                    // the slot holds the key but no buffer index: the marker
+                    // of the frame-stream path, so that Find reports the key
+                    // absent and GetActiveIndices passes the slot over
+                    hv.slot_vals[h] = -1;
                     atomicOr(&hv.counters[1], kErrCapacity);
                 } else {
                     int idx = hv.heap[top];
@@ -147,9 +151,12 @@ __global__ void ActiveIndicesKernel(HashView hv, int64_t n_slots, int* out,
     for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
          s < ((n_slots + 63) / 64) * 64; s += (int64_t)gridDim.x * blockDim.x) {
         bool occ = false;
+        int idx = -1;
         if (s < n_slots) {
             unsigned long long k = hv.slot_keys[s];
-            occ = (k != kEmptyKey) && (k != kTombKey);
+            // -1: a key that found no buffer index (capacity overflow)
+            if ((k != kEmptyKey) && (k != kTombKey)) idx = hv.slot_vals[s];
+            occ = idx != -1;
         }
         unsigned long long ballot = __ballot(occ);
         int lane = threadIdx.x & 63;
@@ -158,7 +165,7 @@ __global__ void ActiveIndicesKernel(HashView hv, int64_t n_slots, int* out,
         base = __shfl(base, 0);
         if (occ) {
             int off = __popcll(ballot & ((1ull << lane) - 1ull));
-            out[base + off] = hv.slot_vals[s];
+            out[base + off] = idx;
         }
     }
 }

@@ -13,6 +13,8 @@
  *   o3dmi_registration_ransac_feature_matching   ...FeatureMatching (pipelines/registration/Registration.cpp:212-406)
  *   o3dmi_slac_correspondence_set,     <- t::pipelines::slac::RunRigidOptimizerForFragments
  *   o3dmi_slac_rigid_optimize             (t/pipelines/slac/SLACOptimizer.cpp:85-204,265-286,369-414)
+ *   o3dmi_control_grid_*,              <- t::pipelines::slac::ControlGrid (t/pipelines/slac/ControlGrid.cpp:24-322),
+ *   o3dmi_project_to_{depth,rgbd}_image   PointCloud::ProjectTo{Depth,RGBD}Image (t/geometry/PointCloud.cpp:1471-1530)
  *   o3dmi_voxel_down_sample,           <- t::geometry::PointCloud::{VoxelDownSample, EstimateNormals,
  *   o3dmi_pointcloud_estimate_*           EstimateColorGradients} (t/geometry/PointCloud.cpp:496-567,856-1060)
  *   o3dmi_vbg_*                        <- t::geometry::VoxelBlockGrid (+ Save / Load)
@@ -431,6 +433,121 @@ int o3dmi_slac_rigid_optimize(const void* const* positions_dev,
                               float fitness_threshold, double* losses,
                               int32_t* kept, int64_t* n_corres,
                               int64_t* n_inliers, o3dmi_stream_t stream);
+
+/* slac::ControlGrid (t/pipelines/slac/ControlGrid.{h,cpp}): a hashed lattice
+ * of control points, key = lattice coordinate (int32 x 3), value = current
+ * position (float32 x 3), with trilinear embedding of points and normals.
+ * All point data is float32; every call synchronises unless it says otherwise.
+ *
+ * Differences from the reference: a point with a non-finite coordinate, or
+ * whose cell leaves the hash's key range (|floor(p / grid_size)| < 2^20), is
+ * never touched and never valid in parameterize (the reference casts such a
+ * float to int32, which is undefined); parameterize keeps the INPUT order;
+ * deform sums the eight corners in corner order 0..7; the projection's winner
+ * on equal depth is the lowest point index (upstream's CUDA rule; its CPU path
+ * takes arrival order).
+ *
+ * create: an empty grid with room for grid_count nodes. create_from: the
+ * constructor slac_integrate uses, capacity 2 n, keys {n,3} int32 and values
+ * {n,3} float32 on the device. grid_size <= 0, null pointers or negative
+ * counts are O3DMI_ERR_INVALID_ARG everywhere. */
+typedef struct o3dmi_control_grid o3dmi_control_grid_t;
+int o3dmi_control_grid_create(float grid_size, int64_t grid_count,
+                              o3dmi_stream_t stream,
+                              o3dmi_control_grid_t** out);
+int o3dmi_control_grid_create_from(float grid_size, const int32_t* keys_dev,
+                                   const float* values_dev, int64_t n,
+                                   o3dmi_stream_t stream,
+                                   o3dmi_control_grid_t** out);
+int o3dmi_control_grid_destroy(o3dmi_control_grid_t* g);
+/* Touch (:46-80): inserts the eight corner nodes of the cell of every point,
+ * value = key * grid_size. The insert is fed from the kernel (no 8 n candidate
+ * list); a map that is too small grows (Reserve(max(wanted, 2 capacity))) and
+ * the cloud is replayed, which moves the key / value buffers. */
+int o3dmi_control_grid_touch(o3dmi_control_grid_t* g, const float* points_dev,
+                             int64_t n, o3dmi_stream_t stream);
+/* Compactify (:82-112): Reserve(2 size); the anchor is the active node at
+ * position size / 2 of the active keys sorted by (z, y, x) (-1 when empty). */
+int o3dmi_control_grid_compactify(o3dmi_control_grid_t* g,
+                                  o3dmi_stream_t stream);
+int o3dmi_control_grid_size(o3dmi_control_grid_t* g, o3dmi_stream_t stream,
+                            int64_t* size);
+int o3dmi_control_grid_anchor_idx(const o3dmi_control_grid_t* g);
+float o3dmi_control_grid_grid_size(const o3dmi_control_grid_t* g);
+/* The node map: o3dmi_hash_active_indices / _find / _key_buffer work on it. */
+o3dmi_hash_t* o3dmi_control_grid_hashmap(o3dmi_control_grid_t* g);
+/* {capacity,3}: key * grid_size of every buffer row (0 for unused rows).
+ * Asynchronous. */
+int o3dmi_control_grid_init_positions(o3dmi_control_grid_t* g, float* out_dev,
+                                      o3dmi_stream_t stream);
+/* The value buffer itself, {capacity,3} float32, writable; a touch, a
+ * compactify or a Reserve of the map moves it. */
+float* o3dmi_control_grid_curr_positions(o3dmi_control_grid_t* g);
+/* GetNeighborGridMap (:114-148): the active buffer indices in ascending order
+ * (active_dev, room for `capacity`), and for each the buffer indices {n,6}
+ * int32 and masks {n,6} uint8 of its -x +x -y +y -z +z neighbours (index 0
+ * where the mask is 0). */
+int o3dmi_control_grid_neighbor_grid_map(o3dmi_control_grid_t* g,
+                                         int32_t* active_dev,
+                                         int32_t* nb_indices_dev,
+                                         uint8_t* nb_masks_dev, int64_t* n_out,
+                                         o3dmi_stream_t stream);
+/* Parameterize (:150-239): the points whose eight corners are all nodes, in
+ * input order, with their corner buffer indices {m,8} int32, vertex ratios
+ * {m,8} and -- with normals -- normal ratios {m,8}. normals_dev / colors_dev
+ * and their outputs may be NULL. *m_out receives the count; more than
+ * out_capacity rows: O3DMI_ERR_CAPACITY, nothing written. */
+int o3dmi_control_grid_parameterize(
+        o3dmi_control_grid_t* g, const float* points_dev,
+        const float* normals_dev, const float* colors_dev, int64_t n,
+        int64_t out_capacity, float* out_points_dev, float* out_normals_dev,
+        float* out_colors_dev, int32_t* out_indices_dev,
+        float* out_vertex_ratios_dev, float* out_normal_ratios_dev,
+        int64_t* m_out, o3dmi_stream_t stream);
+/* Deform (:241-288) of a parameterized cloud: position = sum_k ratio_k curr_k,
+ * normal = the same sum with the normal ratios, normalised. An index outside
+ * [0, capacity): O3DMI_ERR_INVALID_ARG, nothing written (checked on the
+ * device). normal_ratios_dev / out_normals_dev may be NULL. */
+int o3dmi_control_grid_deform(o3dmi_control_grid_t* g,
+                              const int32_t* indices_dev,
+                              const float* vertex_ratios_dev,
+                              const float* normal_ratios_dev, int64_t n,
+                              float* out_points_dev, float* out_normals_dev,
+                              o3dmi_stream_t stream);
+/* PointCloud::ProjectToDepthImage / ProjectToRGBDImage (t/geometry/
+ * PointCloud.cpp:1471-1530, kernel/PointCloudCUDA.cu:26-160): u, v =
+ * round(project); skipped when out of bounds, zc <= 0 or zc > depth_max;
+ * d = zc * depth_scale; the smallest (d, point index) of a pixel wins; empty
+ * pixels are 0. depth_out_dev {rows,cols} float32, color_out_dev
+ * {rows,cols,3} float32. n < 2^32. Two launches; waits for them (the packed
+ * words are pooled scratch). */
+int o3dmi_project_to_depth_image(const float* points_dev, int64_t n, int rows,
+                                 int cols, const double* intrinsic,
+                                 const double* extrinsic, float depth_scale,
+                                 float depth_max, float* depth_out_dev,
+                                 o3dmi_stream_t stream);
+int o3dmi_project_to_rgbd_image(const float* points_dev,
+                                const float* colors_dev, int64_t n, int rows,
+                                int cols, const double* intrinsic,
+                                const double* extrinsic, float depth_scale,
+                                float depth_max, float* depth_out_dev,
+                                float* color_out_dev, o3dmi_stream_t stream);
+/* Deform of a depth / RGB-D image (:290-322), fused: bit for bit what
+ * o3dmi_unproject (stride 1) -> parameterize -> deform -> project give, in two
+ * launches and without the compacted cloud. depth_dtype O3DMI_U16 or
+ * O3DMI_F32; color_dtype O3DMI_U8 ({rows,cols,3}, scaled by 1/255 as
+ * Image::To does) or O3DMI_F32. Waits for its two launches. */
+int o3dmi_control_grid_deform_depth_image(
+        o3dmi_control_grid_t* g, const void* depth_dev, int depth_dtype,
+        int rows, int cols, const double* intrinsic, const double* extrinsic,
+        float depth_scale, float depth_max, float* depth_out_dev,
+        o3dmi_stream_t stream);
+int o3dmi_control_grid_deform_rgbd_image(
+        o3dmi_control_grid_t* g, const void* depth_dev, int depth_dtype,
+        const void* color_dev, int color_dtype, int rows, int cols,
+        const double* intrinsic, const double* extrinsic, float depth_scale,
+        float depth_max, float* depth_out_dev, float* color_out_dev,
+        o3dmi_stream_t stream);
 
 /* PointCloud::VoxelDownSample (t/geometry/PointCloud.cpp:496-567) for
  * positions (+ optional normals): mean per voxel in float32, voxel order =

@@ -265,6 +265,34 @@ PROTOTYPES.update({
         _i32, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64), _i32, _dp,
                C.POINTER(_i32), _dp, _i32, _i32, _f, _f, _dp,
                C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64), _vp]),
+    "o3dmi_control_grid_create": (_i32, [_f, _i64, _vp, C.POINTER(_vp)]),
+    "o3dmi_control_grid_create_from": (_i32, [_f, _vp, _vp, _i64, _vp,
+                                              C.POINTER(_vp)]),
+    "o3dmi_control_grid_destroy": (_i32, [_vp]),
+    "o3dmi_control_grid_touch": (_i32, [_vp, _vp, _i64, _vp]),
+    "o3dmi_control_grid_compactify": (_i32, [_vp, _vp]),
+    "o3dmi_control_grid_size": (_i32, [_vp, _vp, C.POINTER(_i64)]),
+    "o3dmi_control_grid_anchor_idx": (_i32, [_vp]),
+    "o3dmi_control_grid_grid_size": (_f, [_vp]),
+    "o3dmi_control_grid_hashmap": (_vp, [_vp]),
+    "o3dmi_control_grid_init_positions": (_i32, [_vp, _vp, _vp]),
+    "o3dmi_control_grid_curr_positions": (_vp, [_vp]),
+    "o3dmi_control_grid_neighbor_grid_map": (_i32, [_vp, _vp, _vp, _vp,
+                                                    C.POINTER(_i64), _vp]),
+    "o3dmi_control_grid_parameterize": (
+        _i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+               C.POINTER(_i64), _vp]),
+    "o3dmi_control_grid_deform": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                                         _vp]),
+    "o3dmi_project_to_depth_image": (_i32, [_vp, _i64, _i32, _i32, _dp, _dp,
+                                            _f, _f, _vp, _vp]),
+    "o3dmi_project_to_rgbd_image": (_i32, [_vp, _vp, _i64, _i32, _i32, _dp,
+                                           _dp, _f, _f, _vp, _vp, _vp]),
+    "o3dmi_control_grid_deform_depth_image": (
+        _i32, [_vp, _vp, _i32, _i32, _i32, _dp, _dp, _f, _f, _vp, _vp]),
+    "o3dmi_control_grid_deform_rgbd_image": (
+        _i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _dp, _dp, _f, _f, _vp,
+               _vp, _vp]),
     "o3dmi_pointcloud_estimate_normals": (_i32, [_vp, _i64, _i32, _i32, _d,
                                                  _vp, _i32, _vp]),
     "o3dmi_voxel_down_sample": (_i32, [_vp, _vp, _i64, _i32, _d, _vp, _vp,

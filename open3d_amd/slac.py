@@ -1,5 +1,5 @@
-"""Mirror of the rigid half of open3d.t.pipelines.slac on the HIP backend
-(tests and tools; a binding calls the C ABI directly).
+"""Mirror of open3d.t.pipelines.slac on the HIP backend: the rigid optimizer
+and ControlGrid (tests and tools; a binding calls the C ABI directly).
 
 Fragments are (positions, normals) float32 CUDA tensors in memory; the
 reference takes file names and caches .npy / .ply files in slac_folder.
@@ -154,3 +154,276 @@ def run_rigid_optimizer_for_fragments(fragments, pose_graph, params=None,
     out = PoseGraph([P[k].copy() for k in range(P.shape[0])],
                     list(pose_graph.edges))
     return (out, info) if return_info else out
+
+
+# ---- ControlGrid (t/pipelines/slac/ControlGrid.{h,cpp}) ---------------------
+
+def _rows(t, name, cols=3, dtype=torch.float32):
+    assert isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype \
+        and t.dim() == 2 and t.shape[1] == cols, \
+        "%s must be a {n,%d} %s device tensor" % (name, cols, dtype)
+    return t.contiguous()
+
+
+def _frame_args(depth, intrinsic, extrinsic):
+    from .core import host_mat
+    from .geometry import _image
+    depth = _image(depth, "depth", 1)
+    return (depth, host_mat(intrinsic, (3, 3), "intrinsic"),
+            host_mat(extrinsic, (4, 4), "extrinsic"))
+
+
+def create_from_rgbd_image(depth, color, intrinsic, extrinsic,
+                           depth_scale=1000.0, depth_max=3.0):
+    """PointCloud::CreateFromDepthImage / CreateFromRGBDImage at stride 1:
+    (positions, colors or None) in the row-major order of the pixels. A UInt8
+    colour image is scaled by 1/255 first (Image::To)."""
+    from .core import TORCH_TO_O3DMI
+    from .odometry import to_float
+    depth, K, T = _frame_args(depth, intrinsic, extrinsic)
+    rows, cols = depth.shape
+    pts = torch.empty((rows * cols, 3), dtype=torch.float32, device="cuda")
+    image_colors = cols_out = None
+    if color is not None:
+        image_colors = color if color.dtype == torch.float32 else \
+            to_float(color.contiguous(), 1.0 / 255)
+        cols_out = torch.empty_like(pts)
+    count = torch.zeros(1, dtype=torch.int32, device="cuda")
+    _lib.check(_lib.lib().o3dmi_unproject(
+        _lib.ptr(depth), TORCH_TO_O3DMI[depth.dtype], rows, cols,
+        _lib.ptr(image_colors), _lib.ptr(pts), _lib.ptr(cols_out),
+        _lib.ptr(count), _lib.f64p(K), _lib.f64p(T), float(depth_scale),
+        float(depth_max), 1, _stream()), "unproject")
+    n = int(count.item())
+    return pts[:n], (cols_out[:n] if cols_out is not None else None)
+
+
+def project_to_depth_image(positions, width, height, intrinsic, extrinsic,
+                           depth_scale=1000.0, depth_max=3.0):
+    """PointCloud::ProjectToDepthImage: {height,width} Float32."""
+    from .core import host_mat
+    p = _rows(positions, "positions")
+    K = host_mat(intrinsic, (3, 3), "intrinsic")
+    T = host_mat(extrinsic, (4, 4), "extrinsic")
+    depth = torch.empty((height, width), dtype=torch.float32, device="cuda")
+    _lib.check(_lib.lib().o3dmi_project_to_depth_image(
+        _lib.ptr(p), p.shape[0], int(height), int(width), _lib.f64p(K),
+        _lib.f64p(T), float(depth_scale), float(depth_max), _lib.ptr(depth),
+        _stream()), "project_to_depth_image")
+    return depth
+
+
+def project_to_rgbd_image(positions, colors, width, height, intrinsic,
+                          extrinsic, depth_scale=1000.0, depth_max=3.0):
+    """PointCloud::ProjectToRGBDImage: (depth {height,width}, color
+    {height,width,3}), Float32."""
+    from .core import host_mat
+    p, c = _rows(positions, "positions"), _rows(colors, "colors")
+    assert p.shape == c.shape, "one colour per point"
+    K = host_mat(intrinsic, (3, 3), "intrinsic")
+    T = host_mat(extrinsic, (4, 4), "extrinsic")
+    depth = torch.empty((height, width), dtype=torch.float32, device="cuda")
+    color = torch.empty((height, width, 3), dtype=torch.float32,
+                        device="cuda")
+    _lib.check(_lib.lib().o3dmi_project_to_rgbd_image(
+        _lib.ptr(p), _lib.ptr(c), p.shape[0], int(height), int(width),
+        _lib.f64p(K), _lib.f64p(T), float(depth_scale), float(depth_max),
+        _lib.ptr(depth), _lib.ptr(color), _stream()),
+        "project_to_rgbd_image")
+    return depth, color
+
+
+@dataclass
+class ParameterizedCloud:
+    """The point cloud ControlGrid.parameterize returns: the attributes
+    Grid8NbIndices, Grid8NbVertexInterpRatios and Grid8NbNormalInterpRatios
+    beside positions / normals / colors (None where the input had none)."""
+    positions: torch.Tensor
+    normals: torch.Tensor
+    colors: torch.Tensor
+    Grid8NbIndices: torch.Tensor
+    Grid8NbVertexInterpRatios: torch.Tensor
+    Grid8NbNormalInterpRatios: torch.Tensor
+
+
+class ControlGrid:
+    """Mirror of o3d.t.pipelines.slac.control_grid. Clouds are {n,3} Float32
+    device tensors; images as in VoxelBlockGrid."""
+
+    def __init__(self, grid_size, grid_count=1000, keys=None, values=None):
+        h = C.c_void_p()
+        if keys is not None:
+            k = _rows(keys, "keys", 3, torch.int32)
+            v = _rows(values, "values")
+            assert k.shape == v.shape, "one value per key"
+            _lib.check(_lib.lib().o3dmi_control_grid_create_from(
+                float(grid_size), _lib.ptr(k), _lib.ptr(v), k.shape[0],
+                _stream(), C.byref(h)), "ControlGrid")
+        else:
+            _lib.check(_lib.lib().o3dmi_control_grid_create(
+                float(grid_size), int(grid_count), _stream(), C.byref(h)),
+                "ControlGrid")
+        self._g = h
+        self.grid_size = float(grid_size)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_g", None):
+                _lib.lib().o3dmi_control_grid_destroy(self._g)
+                self._g = None
+        except Exception:
+            pass
+
+    def touch(self, positions):
+        p = _rows(positions, "positions")
+        _lib.check(_lib.lib().o3dmi_control_grid_touch(
+            self._g, _lib.ptr(p), p.shape[0], _stream()), "ControlGrid.touch")
+
+    def compactify(self):
+        _lib.check(_lib.lib().o3dmi_control_grid_compactify(
+            self._g, _stream()), "ControlGrid.compactify")
+
+    def size(self):
+        n = C.c_int64(0)
+        _lib.check(_lib.lib().o3dmi_control_grid_size(
+            self._g, _stream(), C.byref(n)), "ControlGrid.size")
+        return int(n.value)
+
+    def get_anchor_idx(self):
+        return int(_lib.lib().o3dmi_control_grid_anchor_idx(self._g))
+
+    def get_hashmap(self):
+        from .geometry import HashMapView
+        return HashMapView(
+            C.c_void_p(_lib.lib().o3dmi_control_grid_hashmap(self._g)), self)
+
+    def get_init_positions(self):
+        cap = self.get_hashmap().capacity()
+        out = torch.empty((cap, 3), dtype=torch.float32, device="cuda")
+        _lib.check(_lib.lib().o3dmi_control_grid_init_positions(
+            self._g, _lib.ptr(out), _stream()),
+            "ControlGrid.get_init_positions")
+        return out
+
+    def get_curr_positions(self):
+        """The value buffer itself (writable); a touch or a compactify moves
+        it, so take it again afterwards."""
+        from .core import tensor_from_ptr
+        p = _lib.lib().o3dmi_control_grid_curr_positions(self._g)
+        return tensor_from_ptr(p, (self.get_hashmap().capacity(), 3),
+                               _lib.F32, self)
+
+    def get_neighbor_grid_map(self):
+        """(active buffer indices {n}, neighbour indices {n,6}, masks {n,6}),
+        neighbours in the order -x +x -y +y -z +z."""
+        cap = self.get_hashmap().capacity()
+        active = torch.empty(cap, dtype=torch.int32, device="cuda")
+        nb = torch.empty((cap, 6), dtype=torch.int32, device="cuda")
+        masks = torch.empty((cap, 6), dtype=torch.bool, device="cuda")
+        n = C.c_int64(0)
+        _lib.check(_lib.lib().o3dmi_control_grid_neighbor_grid_map(
+            self._g, _lib.ptr(active), _lib.ptr(nb), _lib.ptr(masks),
+            C.byref(n), _stream()), "ControlGrid.get_neighbor_grid_map")
+        return active[:n.value], nb[:n.value], masks[:n.value]
+
+    def parameterize(self, positions, normals=None, colors=None):
+        p = _rows(positions, "positions")
+        nm = _rows(normals, "normals") if normals is not None else None
+        cl = _rows(colors, "colors") if colors is not None else None
+        n = p.shape[0]
+
+        def new(cols, dtype=torch.float32):
+            return torch.empty((n, cols), dtype=dtype, device="cuda")
+        op, idx, vr = new(3), new(8, torch.int32), new(8)
+        on = new(3) if nm is not None else None
+        nr = new(8) if nm is not None else None
+        oc = new(3) if cl is not None else None
+        m = C.c_int64(0)
+        _lib.check(_lib.lib().o3dmi_control_grid_parameterize(
+            self._g, _lib.ptr(p), _lib.ptr(nm), _lib.ptr(cl), n, n,
+            _lib.ptr(op), _lib.ptr(on), _lib.ptr(oc), _lib.ptr(idx),
+            _lib.ptr(vr), _lib.ptr(nr), C.byref(m), _stream()),
+            "ControlGrid.parameterize")
+
+        def cut(t):
+            return t[:m.value] if t is not None else None
+        return ParameterizedCloud(cut(op), cut(on), cut(oc), cut(idx), cut(vr),
+                                  cut(nr))
+
+    def deform_raw(self, cloud, out_positions, out_normals=None):
+        """o3dmi_control_grid_deform into caller-provided outputs; returns the
+        status instead of raising."""
+        idx = _rows(cloud.Grid8NbIndices, "Grid8NbIndices", 8, torch.int32)
+        vr = _rows(cloud.Grid8NbVertexInterpRatios, "vertex ratios", 8)
+        nr = cloud.Grid8NbNormalInterpRatios
+        if out_normals is None:
+            nr = None
+        return _lib.lib().o3dmi_control_grid_deform(
+            self._g, _lib.ptr(idx), _lib.ptr(vr), _lib.ptr(nr), idx.shape[0],
+            _lib.ptr(out_positions), _lib.ptr(out_normals), _stream())
+
+    def deform(self, *args, **kwargs):
+        """deform(cloud) -> (positions, normals, colors);
+        deform(depth, intrinsic, extrinsic, depth_scale, depth_max) -> depth;
+        deform((depth, color), intrinsic, extrinsic, depth_scale, depth_max)
+        -> (depth, color). Images come back as Float32."""
+        first = args[0]
+        if isinstance(first, ParameterizedCloud):
+            return self._deform_cloud(first)
+        if isinstance(first, (tuple, list)):
+            return self._deform_rgbd(first[0], first[1], *args[1:], **kwargs)
+        return self._deform_depth(*args, **kwargs)
+
+    def _deform_cloud(self, cloud):
+        n = cloud.Grid8NbIndices.shape[0]
+        pos = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+        nrm = torch.empty_like(pos) \
+            if cloud.Grid8NbNormalInterpRatios is not None else None
+        _lib.check(self.deform_raw(cloud, pos, nrm), "ControlGrid.deform")
+        return pos, nrm, cloud.colors
+
+    def _deform_depth(self, depth, intrinsic, extrinsic, depth_scale=1000.0,
+                      depth_max=3.0):
+        from .core import TORCH_TO_O3DMI
+        depth, K, T = _frame_args(depth, intrinsic, extrinsic)
+        rows, cols = depth.shape
+        out = torch.empty((rows, cols), dtype=torch.float32, device="cuda")
+        _lib.check(_lib.lib().o3dmi_control_grid_deform_depth_image(
+            self._g, _lib.ptr(depth), TORCH_TO_O3DMI[depth.dtype], rows, cols,
+            _lib.f64p(K), _lib.f64p(T), float(depth_scale), float(depth_max),
+            _lib.ptr(out), _stream()), "ControlGrid.deform")
+        return out
+
+    def _deform_rgbd(self, depth, color, intrinsic, extrinsic,
+                     depth_scale=1000.0, depth_max=3.0):
+        from .core import TORCH_TO_O3DMI
+        from .geometry import _image
+        depth, K, T = _frame_args(depth, intrinsic, extrinsic)
+        color = _image(color, "color", 3)
+        rows, cols = depth.shape
+        assert color.shape[:2] == (rows, cols), "depth / colour size mismatch"
+        out_d = torch.empty((rows, cols), dtype=torch.float32, device="cuda")
+        out_c = torch.empty((rows, cols, 3), dtype=torch.float32,
+                            device="cuda")
+        _lib.check(_lib.lib().o3dmi_control_grid_deform_rgbd_image(
+            self._g, _lib.ptr(depth), TORCH_TO_O3DMI[depth.dtype],
+            _lib.ptr(color), TORCH_TO_O3DMI[color.dtype], rows, cols,
+            _lib.f64p(K), _lib.f64p(T), float(depth_scale), float(depth_max),
+            _lib.ptr(out_d), _lib.ptr(out_c), _stream()),
+            "ControlGrid.deform")
+        return out_d, out_c
+
+    def deform_seam_by_seam(self, depth, color, intrinsic, extrinsic,
+                            depth_scale=1000.0, depth_max=3.0):
+        """The reference's chain for an image: CreateFrom{Depth,RGBD}Image ->
+        Parameterize -> Deform -> ProjectTo{Depth,RGBD}Image. Same bits as
+        deform(); kept callable for checks and measurements."""
+        rows, cols = depth.shape[:2]
+        pts, cl = create_from_rgbd_image(depth, color, intrinsic, extrinsic,
+                                         depth_scale, depth_max)
+        pos, _, cl = self._deform_cloud(self.parameterize(pts, colors=cl))
+        if color is None:
+            return project_to_depth_image(pos, cols, rows, intrinsic,
+                                          extrinsic, depth_scale, depth_max)
+        return project_to_rgbd_image(pos, cl, cols, rows, intrinsic,
+                                     extrinsic, depth_scale, depth_max)

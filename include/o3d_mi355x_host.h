@@ -13,6 +13,9 @@
  *   o3dmi_registration_ransac_feature_matching   ...FeatureMatching (pipelines/registration/Registration.cpp:212-406)
  *   o3dmi_slac_correspondence_set,     <- t::pipelines::slac::RunRigidOptimizerForFragments
  *   o3dmi_slac_rigid_optimize             (t/pipelines/slac/SLACOptimizer.cpp:85-204,265-286,369-414)
+ *   o3dmi_slac_optimize,               <- t::pipelines::slac::RunSLACOptimizerForFragments, kernel::FillInSLAC*Term
+ *   o3dmi_fill_in_slac_*_term,            (t/pipelines/slac/SLACOptimizer.cpp:253-367, kernel/FillInLinearSystemImpl.h:156-524)
+ *   o3dmi_slac_solve_spd
  *   o3dmi_control_grid_*,              <- t::pipelines::slac::ControlGrid (t/pipelines/slac/ControlGrid.cpp:24-322),
  *   o3dmi_project_to_{depth,rgbd}_image   PointCloud::ProjectTo{Depth,RGBD}Image (t/geometry/PointCloud.cpp:1471-1530)
  *   o3dmi_voxel_down_sample,           <- t::geometry::PointCloud::{VoxelDownSample, EstimateNormals,
@@ -548,6 +551,101 @@ int o3dmi_control_grid_deform_rgbd_image(
         const double* intrinsic, const double* extrinsic, float depth_scale,
         float depth_max, float* depth_out_dev, float* color_out_dev,
         o3dmi_stream_t stream);
+
+/* The non-rigid SLAC optimizer (t/pipelines/slac/SLACOptimizer.cpp:253-367,
+ * slac/FillInLinearSystemImpl.h:102-236, kernel/FillInLinearSystemImpl.h:
+ * 156-524). Unknowns: 6 per fragment, then 3 per control node, n_vars in all.
+ *
+ * o3dmi_fill_in_slac_alignment_term is kernel::FillInSLACAlignmentTerm: the
+ * 60 x 60 block J J^T, 60 values J r and r r of every pair with
+ * |r| <= threshold are added to the float32 AtA {n_vars,n_vars}, Atb {n_vars},
+ * residual {1} in place. The nine per-pair arrays ({n,3} float32, {n,8} int32
+ * indices, {n,8} float32 ratios) are the reference's, with each ratio array
+ * beside its own index array; an index is the reference's raw cgrid_idx, its
+ * unknowns are 6 n_frags + 3 idx + {0,1,2}. Differences from the reference:
+ * the products are float32 in its expressions but every sum is float64 and
+ * each entry of the output is updated once, by the float32 rounding of its
+ * sum; 6 n_frags + 3 idx + 2 >= n_vars or idx < 0 (checked on the device) is
+ * O3DMI_ERR_INVALID_ARG with nothing written, where the reference indexes out
+ * of bounds. n_vars > 32768: O3DMI_ERR_UNSUPPORTED. Cost: every call
+ * allocates and zeroes a float64 {n_vars,n_vars} scratch and passes over all
+ * n_vars^2 entries of AtA once (8.6 GB at the limit), so a one-fill-per-edge
+ * loop is O(E n_vars^2); the seam is for parity and small systems,
+ * o3dmi_slac_optimize fills one float64 system for all edges. Synchronises. */
+int o3dmi_fill_in_slac_alignment_term(
+        float* AtA_dev, float* Atb_dev, float* residual_dev, int64_t n_vars,
+        const float* Ti_Cps_dev, const float* Tj_Cqs_dev,
+        const float* Cnormal_ps_dev, const float* Ri_Cnormal_ps_dev,
+        const float* RjT_Ri_Cnormal_ps_dev, const int32_t* cgrid_idx_ps_dev,
+        const int32_t* cgrid_idx_qs_dev, const float* cgrid_ratio_ps_dev,
+        const float* cgrid_ratio_qs_dev, int64_t n, int i, int j, int n_frags,
+        float threshold, o3dmi_stream_t stream);
+
+/* kernel::FillInSLACRegularizerTerm over GetNeighborGridMap's output
+ * (grid_idx {n}, grid_nbs_idx {n,6} int32, grid_nbs_mask {n,6} bytes) and the
+ * init / curr positions ({n_positions,3} float32), same seam rules and the
+ * same range check as above. A node with fewer than three masked neighbours is
+ * skipped; the local rotation comes from a converged float64 Jacobi SVD of the
+ * float32 covariance (the reference: its approximate float32 svd3x3), with
+ * det = +1 and the identity at anchor_idx. weight = n_frags x
+ * regularizer_weight is the caller's product. */
+int o3dmi_fill_in_slac_regularizer_term(
+        float* AtA_dev, float* Atb_dev, float* residual_dev, int64_t n_vars,
+        const int32_t* grid_idx_dev, const int32_t* grid_nbs_idx_dev,
+        const uint8_t* grid_nbs_mask_dev, int64_t n,
+        const float* positions_init_dev, const float* positions_curr_dev,
+        int64_t n_positions, float weight, int n_frags, int anchor_idx,
+        o3dmi_stream_t stream);
+
+/* x = solve(A, b) for a symmetric positive definite float64 A {n,n} given by
+ * its lower triangle (row-major; the upper triangle is never read or
+ * written): blocked Cholesky in place (A becomes L), b becomes x. A pivot that
+ * is <= 0 or not finite: O3DMI_ERR_SINGULAR (A and b are then partly
+ * overwritten). n > 32768: O3DMI_ERR_UNSUPPORTED before anything is allocated.
+ * Synchronises. */
+int o3dmi_slac_solve_spd(double* A_dev, double* b_dev, int64_t n,
+                         o3dmi_stream_t stream);
+
+/* RunSLACOptimizerForFragments on fragments in device memory. Fragments,
+ * poses, edges, T_ij, thresholds, kept / n_corres / n_inliers and the limits
+ * (512 nodes, node ids, empty fragments) as o3dmi_slac_rigid_optimize.
+ * grid: an empty grid is touched with every fragment and compactified
+ * (InitializeControlGrid; the reference creates it with 3.0 / 8 and 8000); one
+ * that has nodes is used as it is, so a run can be continued. Node g of the
+ * ascending active buffer-index list owns the unknowns 6 n_nodes + 3 g + ..
+ * (the reference uses the raw buffer index and leaves the matrix when the
+ * indices are not 0..G-1). Per iteration: zero the float64 system, ones on the
+ * first six diagonal entries, one launch for the alignment terms of all edges
+ * (threshold = distance_threshold), the regularizer with weight n_nodes x
+ * regularizer_weight, the anchor node's three unknowns taken out (see below),
+ * x = solve_spd(AtA, -Atb), T_k <-
+ * PoseToTransformation(x[6k..]) T_k in float64, curr_positions[active[g]] +=
+ * (float)x[6 n_nodes + 3 g ..]. A correspondence with a point whose cell has
+ * an inactive corner contributes nothing (the reference drops the point in
+ * Parameterize and then fails on the length mismatch); *skipped is their
+ * number in the last iteration. alignment_losses / regularizer_losses
+ * {max_iterations}: the two residuals before each step. Outputs may be NULL.
+ * The anchor: the reference's system is singular -- moving every node by t
+ * and translating fragment k >= 1 by (R_0 - R_k) t changes no term, and the
+ * ones on the first six diagonals only hold fragment 0 -- and its LU returns
+ * one of the solutions, chosen by rounding noise. Here the anchor node of
+ * Compactify keeps its position (a grid that has nodes but no anchor, one
+ * that was never compactified, is O3DMI_ERR_INVALID_ARG): identity rows and columns, rhs 0. Everything that can be observed
+ * (residuals, deformed points up to a common translation, nodes relative to
+ * the anchor) is the same for every solution.
+ * 6 n_nodes + 3 G > 32768: O3DMI_ERR_UNSUPPORTED. A pivot <= 0 (a node no kept
+ * edge reaches): O3DMI_ERR_SINGULAR; poses and node positions are then as they
+ * came in; the same holds for every other error. A correspondence or node
+ * index out of range inside the driver is O3DMI_ERR_INTERNAL, not the seams'
+ * O3DMI_ERR_INVALID_ARG: the driver computes both itself. Synchronises. */
+int o3dmi_slac_optimize(
+        const void* const* positions_dev, const void* const* normals_dev,
+        const int64_t* sizes, int n_nodes, double* poses, const int32_t* edges,
+        const double* T_ij, int n_edges, o3dmi_control_grid_t* grid,
+        int max_iterations, float distance_threshold, float fitness_threshold,
+        float regularizer_weight, double* alignment_losses,
+        double* regularizer_losses, int32_t* kept, int64_t* n_corres,
+        int64_t* n_inliers, int64_t* skipped, o3dmi_stream_t stream);
 
 /* PointCloud::VoxelDownSample (t/geometry/PointCloud.cpp:496-567) for
  * positions (+ optional normals): mean per voxel in float32, voxel order =

@@ -293,6 +293,18 @@ PROTOTYPES.update({
     "o3dmi_control_grid_deform_rgbd_image": (
         _i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _dp, _dp, _f, _f, _vp,
                _vp, _vp]),
+    "o3dmi_fill_in_slac_alignment_term": (
+        _i32, [_vp, _vp, _vp, _i64] + [_vp] * 9 + [_i64, _i32, _i32, _i32, _f,
+                                                   _vp]),
+    "o3dmi_fill_in_slac_regularizer_term": (
+        _i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _f,
+               _i32, _i32, _vp]),
+    "o3dmi_slac_solve_spd": (_i32, [_vp, _vp, _i64, _vp]),
+    "o3dmi_slac_optimize": (
+        _i32, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64), _i32, _dp,
+               C.POINTER(_i32), _dp, _i32, _vp, _i32, _f, _f, _f, _dp, _dp,
+               C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64),
+               C.POINTER(_i64), _vp]),
     "o3dmi_pointcloud_estimate_normals": (_i32, [_vp, _i64, _i32, _i32, _d,
                                                  _vp, _i32, _vp]),
     "o3dmi_voxel_down_sample": (_i32, [_vp, _vp, _i64, _i32, _d, _vp, _vp,

@@ -15,16 +15,11 @@
 #include "o3d_mi355x_host.h"
 #include "scan.h"
 #include "slac.h"
+#include "host/slac_common.h"
 
 using namespace o3dmi;
 
 namespace {
-
-constexpr int kSlacMaxNodes = 512;  // a 3072^2 float64 host matrix, 75 MB
-
-void Pose12(const double* T, float* out) {
-    for (int k = 0; k < 12; ++k) out[k] = (float)T[k];
-}
 
 // x = solve(A, b) for the n x n row-major A (overwritten) by LU with partial
 // pivoting; false on a zero or non-finite pivot.
@@ -65,16 +60,6 @@ bool SolveLU(std::vector<double>& A, std::vector<double>& b, int n) {
         if (!std::isfinite(b[k])) return false;
     }
     return true;
-}
-
-int CheckEdges(const int32_t* edges, int n_edges, int n_nodes) {
-    for (int e = 0; e < n_edges; ++e) {
-        const int i = edges[2 * e], j = edges[2 * e + 1];
-        O3DMI_REQUIRE(i >= 0 && j >= 0 && i < n_nodes && j < n_nodes,
-                      "node id out of range");
-        O3DMI_REQUIRE(i != j, "an edge joins two different nodes");
-    }
-    return O3DMI_OK;
 }
 
 }  // namespace
@@ -158,45 +143,19 @@ extern "C" int o3dmi_slac_rigid_optimize(
         float distance_threshold, float fitness_threshold, double* losses,
         int32_t* kept, int64_t* n_corres, int64_t* n_inliers,
         o3dmi_stream_t stream) {
-    O3DMI_REQUIRE(n_nodes > 0 && n_edges >= 0, "empty pose graph");
-    if (n_nodes > kSlacMaxNodes) {
-        SetLastError("slac: more than 512 nodes are not supported");
-        return O3DMI_ERR_UNSUPPORTED;
-    }
-    O3DMI_REQUIRE(positions_dev && normals_dev && sizes && poses &&
-                          (n_edges == 0 || (edges && T_ij)),
-                  "null argument");
-    int st = CheckEdges(edges, n_edges, n_nodes);
+    int st = CheckPoseGraph(positions_dev, normals_dev, sizes, n_nodes, poses,
+                            edges, T_ij, n_edges);
     if (st) return st;
-    for (int k = 0; k < n_nodes; ++k)
-        O3DMI_REQUIRE(sizes[k] > 0 && positions_dev[k] && normals_dev[k],
-                      "empty fragment");
     hipStream_t s = (hipStream_t)stream;
     PoolScratch sc(s);
 
     // ---- correspondence sets, once, from the input graph -------------------
-    std::vector<SlacEdge> ed((size_t)n_edges);
-    for (int e = 0; e < n_edges; ++e) {
-        const int i = edges[2 * e], j = edges[2 * e + 1];
-        int64_t* corres = nullptr;
-        if ((st = sc.Alloc(&corres, 16 * (size_t)sizes[i]))) return st;
-        int64_t C = 0, inl = 0;
-        float ratio = 0;
-        int keep = 0;
-        if ((st = o3dmi_slac_correspondence_set(
-                     positions_dev[i], sizes[i], positions_dev[j], sizes[j], i,
-                     j, poses + 16 * i, poses + 16 * j, T_ij + 16 * e,
-                     distance_threshold, fitness_threshold, corres, &C, &inl,
-                     &ratio, &keep, stream)))
-            return st;
-        ed[e].corres = corres;
-        ed[e].count = keep ? C : 0;
-        ed[e].i = i;
-        ed[e].j = j;
-        if (kept) kept[e] = keep;
-        if (n_corres) n_corres[e] = C;
-        if (n_inliers) n_inliers[e] = 0;
-    }
+    std::vector<SlacEdge> ed;
+    if ((st = SlacCorrespondenceSets(positions_dev, sizes, poses, edges, T_ij,
+                                     n_edges, distance_threshold,
+                                     fitness_threshold, sc, ed, kept, n_corres,
+                                     n_inliers, stream)))
+        return st;
     if (max_iterations <= 0) return O3DMI_OK;
 
     const int64_t n_tiles = SlacLayoutTiles(ed.data(), n_edges);
@@ -282,19 +241,7 @@ extern "C" int o3dmi_slac_rigid_optimize(
             SetLastError("slac: singular linear system");
             return O3DMI_ERR_SINGULAR;
         }
-        // UpdatePoses, SLACOptimizer.cpp:265-286, kept in float64
-        for (int k = 0; k < n_nodes; ++k) {
-            double D[16], R[16];
-            o3dmi_pose_to_transformation(&rhs[6 * (size_t)k], D);
-            const double* Tk = &T[16 * (size_t)k];
-            for (int r = 0; r < 4; ++r)
-                for (int c = 0; c < 4; ++c) {
-                    double v = 0;
-                    for (int m = 0; m < 4; ++m) v += D[4 * r + m] * Tk[4 * m + c];
-                    R[4 * r + c] = v;
-                }
-            std::copy(R, R + 16, &T[16 * (size_t)k]);
-        }
+        SlacUpdatePoses(rhs.data(), n_nodes, T.data());
     }
     std::copy(T.begin(), T.end(), poses);
     if (losses) std::copy(loss.begin(), loss.end(), losses);

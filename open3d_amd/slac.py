@@ -1,5 +1,5 @@
-"""Mirror of open3d.t.pipelines.slac on the HIP backend: the rigid optimizer
-and ControlGrid (tests and tools; a binding calls the C ABI directly).
+"""Mirror of open3d.t.pipelines.slac on the HIP backend: the rigid and the
+non-rigid optimizer and ControlGrid (tests and tools; a binding calls the C ABI directly).
 
 Fragments are (positions, normals) float32 CUDA tensors in memory; the
 reference takes file names and caches .npy / .ply files in slac_folder.
@@ -25,6 +25,7 @@ class SLACOptimizerParams:
     voxel_size: float = 0.05
     distance_threshold: float = 0.07
     fitness_threshold: float = 0.3
+    regularizer_weight: float = 1.0
 
 
 @dataclass
@@ -427,3 +428,136 @@ class ControlGrid:
                                           extrinsic, depth_scale, depth_max)
         return project_to_rgbd_image(pos, cl, cols, rows, intrinsic,
                                      extrinsic, depth_scale, depth_max)
+
+
+# ---- the non-rigid optimizer (SLACOptimizer.cpp:253-367) --------------------
+
+def _system(AtA, Atb, residual):
+    for t in (AtA, Atb, residual):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+    assert AtA.dim() == 2 and AtA.shape[0] == AtA.shape[1] == Atb.numel()
+
+
+def fill_in_slac_alignment_term_raw(AtA, Atb, residual, Ti_Cps, Tj_Cqs,
+                                    Cnormal_ps, Ri_Cnormal_ps,
+                                    RjT_Ri_Cnormal_ps, cgrid_idx_ps,
+                                    cgrid_idx_qs, cgrid_ratio_ps,
+                                    cgrid_ratio_qs, i, j, n_frags, threshold):
+    """o3dmi_fill_in_slac_alignment_term; returns the status."""
+    _system(AtA, Atb, residual)
+    rows = [_f32(t) for t in (Ti_Cps, Tj_Cqs, Cnormal_ps, Ri_Cnormal_ps,
+                              RjT_Ri_Cnormal_ps)]
+    ip = _rows(cgrid_idx_ps, "cgrid_idx_ps", 8, torch.int32)
+    iq = _rows(cgrid_idx_qs, "cgrid_idx_qs", 8, torch.int32)
+    rp = _rows(cgrid_ratio_ps, "cgrid_ratio_ps", 8)
+    rq = _rows(cgrid_ratio_qs, "cgrid_ratio_qs", 8)
+    n = rows[0].shape[0]
+    assert all(t.shape[0] == n for t in rows + [ip, iq, rp, rq]), \
+        "input length mismatch"
+    return _lib.lib().o3dmi_fill_in_slac_alignment_term(
+        _lib.ptr(AtA), _lib.ptr(Atb), _lib.ptr(residual), AtA.shape[0],
+        *[_lib.ptr(t) for t in rows], _lib.ptr(ip), _lib.ptr(iq),
+        _lib.ptr(rp), _lib.ptr(rq), n, int(i), int(j), int(n_frags),
+        float(threshold), _stream())
+
+
+def fill_in_slac_alignment_term(*args):
+    """kernel::FillInSLACAlignmentTerm: adds an edge's terms to the float32
+    AtA {n,n}, Atb {n}, residual {1} in place. The ratio arrays follow their
+    index arrays: (.., idx_ps, idx_qs, ratio_ps, ratio_qs, i, j, n_frags,
+    threshold)."""
+    _lib.check(fill_in_slac_alignment_term_raw(*args),
+               "fill_in_slac_alignment_term")
+
+
+def fill_in_slac_regularizer_term_raw(AtA, Atb, residual, grid_idx,
+                                      grid_nbs_idx, grid_nbs_mask,
+                                      positions_init, positions_curr, weight,
+                                      n_frags, anchor_idx):
+    """o3dmi_fill_in_slac_regularizer_term; returns the status."""
+    _system(AtA, Atb, residual)
+    gi = grid_idx.contiguous()
+    assert gi.is_cuda and gi.dtype == torch.int32 and gi.dim() == 1
+    nb = _rows(grid_nbs_idx, "grid_nbs_idx", 6, torch.int32)
+    mk = _rows(grid_nbs_mask, "grid_nbs_mask", 6, torch.bool)
+    p0, p1 = _rows(positions_init, "init"), _rows(positions_curr, "curr")
+    assert nb.shape[0] == mk.shape[0] == gi.shape[0] and p0.shape == p1.shape
+    return _lib.lib().o3dmi_fill_in_slac_regularizer_term(
+        _lib.ptr(AtA), _lib.ptr(Atb), _lib.ptr(residual), AtA.shape[0],
+        _lib.ptr(gi), _lib.ptr(nb), _lib.ptr(mk), gi.shape[0], _lib.ptr(p0),
+        _lib.ptr(p1), p0.shape[0], float(weight), int(n_frags),
+        int(anchor_idx), _stream())
+
+
+def fill_in_slac_regularizer_term(*args):
+    """kernel::FillInSLACRegularizerTerm on GetNeighborGridMap's output."""
+    _lib.check(fill_in_slac_regularizer_term_raw(*args),
+               "fill_in_slac_regularizer_term")
+
+
+def solve_spd_raw(A, b):
+    """o3dmi_slac_solve_spd in place on a float64 {n,n} lower triangle and
+    {n} right-hand side; returns the status."""
+    for t in (A, b):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    return _lib.lib().o3dmi_slac_solve_spd(_lib.ptr(A), _lib.ptr(b),
+                                           b.numel(), _stream())
+
+
+def solve_spd(A, b):
+    """x = solve(A, b) for symmetric positive definite A (only the lower
+    triangle is read); neither input is modified."""
+    L, x = A.clone(), b.clone()
+    _lib.check(solve_spd_raw(L, x), "slac_solve_spd")
+    return x
+
+
+def slac_optimize_raw(fragments, nodes, edges, params, control_grid):
+    """o3dmi_slac_optimize without the status check: (status, poses {N,4,4}
+    as the call left them, info). The grid is updated in place."""
+    pos = [_f32(f[0]) for f in fragments]
+    nrm = [_f32(f[1]) for f in fragments]
+    N, E = len(nodes), len(edges)
+    assert N == len(pos), "one fragment per node"
+    sizes = (C.c_int64 * N)(*[p.shape[0] for p in pos])
+    P = np.ascontiguousarray(np.stack([_T(T) for T in nodes]))
+    ed = (C.c_int32 * max(2 * E, 1))(*[int(v) for e in edges for v in e[:2]])
+    Tij = np.ascontiguousarray(
+        np.stack([_T(e[2]) for e in edges]) if E else np.zeros((1, 4, 4)))
+    iters = max(int(params.max_iterations), 0)
+    align = np.zeros(max(iters, 1), np.float64)
+    reg = np.zeros(max(iters, 1), np.float64)
+    kept = (C.c_int32 * max(E, 1))()
+    n_corres = (C.c_int64 * max(E, 1))()
+    n_inliers = (C.c_int64 * max(E, 1))()
+    skipped = C.c_int64(0)
+    status = _lib.lib().o3dmi_slac_optimize(
+        _ptr_array(pos), _ptr_array(nrm), sizes, N, _lib.f64p(P), ed,
+        _lib.f64p(Tij), E, control_grid._g, int(params.max_iterations),
+        float(params.distance_threshold), float(params.fitness_threshold),
+        float(params.regularizer_weight), _lib.f64p(align), _lib.f64p(reg),
+        kept, n_corres, n_inliers, C.byref(skipped), _stream())
+    return status, P, dict(alignment_losses=align[:iters].copy(),
+                           regularizer_losses=reg[:iters].copy(),
+                           kept=[bool(v) for v in kept[:E]],
+                           n_corres=list(n_corres[:E]),
+                           n_inliers=list(n_inliers[:E]),
+                           skipped=int(skipped.value))
+
+
+def run_slac_optimizer_for_fragments(fragments, pose_graph, params=None,
+                                     control_grid=None, return_info=False):
+    """RunSLACOptimizerForFragments: (PoseGraph with the updated node poses,
+    ControlGrid). control_grid None: the reference's ControlGrid(3.0 / 8,
+    8000), touched with every fragment; a grid that has nodes is continued.
+    return_info adds dict(alignment_losses, regularizer_losses, kept,
+    n_corres, n_inliers, skipped)."""
+    params = params or SLACOptimizerParams()
+    grid = control_grid if control_grid is not None else \
+        ControlGrid(3.0 / 8, 8000)
+    status, P, info = slac_optimize_raw(fragments, pose_graph.nodes,
+                                        pose_graph.edges, params, grid)
+    _lib.check(status, "slac_optimize")
+    out = PoseGraph([P[k].copy() for k in range(P.shape[0])],
+                    list(pose_graph.edges))
+    return (out, grid, info) if return_info else (out, grid)

@@ -29,7 +29,7 @@
 // rank, rank r on device r % device_count, every rank the same loop on the
 // same frames with a replicated model (the ray cast needs every block); what
 // is sharded is (1) the Gauss-Newton work of MultiScaleICP -- o3dmi_set_comm +
-// o3dmi_set_icp_level_sharding(1): each rank searches / accumulates its slice
+// o3dmi_icp_options_t.level_sharding: each rank searches / accumulates its slice
 // of every pyramid level and the 32 float64 sums are all-reduced inside the
 // iteration by the library itself (ncclAllReduce on the launch stream over
 // xGMI; no Python anywhere) -- and (2) the model frame's ray cast --
@@ -230,7 +230,6 @@ int main(int argc, char** argv) {
                                                    r, world, &comm));
             }
             CHECK_O3D(o3dmi_set_comm(comm));
-            CHECK_O3D(o3dmi_set_icp_level_sharding(1));
             rc[(size_t)r] = RunRank(argc, argv, r, world, comm,
                                     &res[(size_t)r]);
             CHECK_O3D(o3dmi_set_comm(nullptr));
@@ -430,12 +429,16 @@ int RunRank(int argc, char** argv, int rank, int world, o3dmi_comm_t* comm,
         // (the host arguments are then the buffer capacities).
         // ---- track ----------------------------------------------------------
         o3dmi_registration_result_t r;
-        CHECK_O3D(o3dmi_registration_set_device_counts(counts + 1, counts));
-        CHECK_O3D(o3dmi_registration_multiscale_icp(
+        o3dmi_icp_options_t options = {};
+        options.ns_dev = counts + 1;
+        options.nt_dev = counts;
+        options.level_sharding = world > 1;
+        CHECK_O3D(o3dmi_registration_multiscale_icp_ex(
                 frame_pts, (int64_t)cloud_cap, model_pts, model_nrm,
                 (int64_t)cloud_cap, O3DMI_F32, 3, voxel_sizes, criteria,
-                max_dist, nullptr, /*L2Loss*/ 0, 1.0, 1.0, nullptr, nullptr,
-                nullptr, nullptr, nullptr, &r, stream));
+                max_dist, nullptr, O3DMI_ICP_POINT_TO_PLANE, nullptr, &options,
+                /*L2Loss*/ 0, 1.0, 1.0, nullptr, nullptr, nullptr, nullptr,
+                nullptr, &r, stream));
         iterations += r.num_iterations;
         const double p3 = now();
         // p_prev_cam = r.T p_cam, p_prev_cam = X_prev p_world

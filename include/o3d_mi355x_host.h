@@ -74,16 +74,10 @@ typedef int (*o3dmi_allreduce_sum_t)(double* host_buf, int n, void* user);
 /* The same exchange on the DEVICE: the hook enqueues an in-place sum
  * all-reduce of dev_buf[0..n) (float64) over all ranks on `stream`
  * (asynchronously -- e.g. RCCL's ncclAllReduce, or torch.distributed's
- * all_reduce under that stream) and returns 0. When set for the calling host
- * thread it takes precedence over the host hook of the driver functions: the
- * per-iteration sums then stay on the device from the final reduction kernel
- * through the collective to the kernel that posts them to the host mailbox
- * (one host wait per iteration, no staging copies). fn = NULL restores the
- * host path. Thread-local: one rank per process, or one host thread per
- * device. */
+ * all_reduce under that stream) and returns 0. Passed to a driver call in
+ * o3dmi_icp_options_t. */
 typedef int (*o3dmi_allreduce_device_t)(double* dev_buf, int n,
                                         o3dmi_stream_t stream, void* user);
-int o3dmi_set_device_allreduce(o3dmi_allreduce_device_t fn, void* user);
 
 /* ---- Collectives owned by the library (multi-GPU) -------
  * One process (or host thread) per GPU. An o3dmi_comm_t carries the three
@@ -105,8 +99,8 @@ int o3dmi_set_device_allreduce(o3dmi_allreduce_device_t fn, void* user);
  * o3dmi_set_comm(c) makes c the communicator of the calling host thread: the
  * registration drivers (every estimator) then sum their per-iteration values
  * through it ON THE DEVICE, between the final reduction kernel and the kernel that
- * posts them to the host mailbox (takes precedence over both hooks below;
- * NULL restores them). o3dmi_set_rccl_comm(ncclComm) = adopt + set in one
+ * posts them to the host mailbox (takes precedence over both hooks of the
+ * call; NULL restores them). o3dmi_set_rccl_comm(ncclComm) = adopt + set in one
  * call (NULL clears). The reference has no counterpart. */
 typedef struct o3dmi_comm o3dmi_comm_t;
 typedef struct {
@@ -136,18 +130,6 @@ int o3dmi_comm_world(const o3dmi_comm_t* c);
 int o3dmi_comm_rccl_ranks(const o3dmi_comm_t* c);
 int o3dmi_set_comm(o3dmi_comm_t* c);
 int o3dmi_set_rccl_comm(void* nccl_comm);
-/* Who shards the source cloud of an ICP call made with a communicator
- * installed (thread-local, default 0):
- *   0  the caller: each rank passes ITS shard of the source (the semantics of
- *      the two hooks). A voxel pyramid is then built per shard, i.e. the
- *      coarse levels differ from the unsharded run's.
- *   1  the driver: every rank passes the WHOLE source; the pyramid is built
- *      from it on every rank (it IS the unsharded pyramid), and each rank
- *      searches and accumulates a contiguous slice of every level. The poses
- *      equal the unsharded run's to the rounding of the float64 sums for any
- *      number of scales. correspondences_dev: a rank fills its slice of the
- *      finest level's rows, the other rows read -1. */
-int o3dmi_set_icp_level_sharding(int on);
 /* The exchanges themselves (what the drivers call). Counts / offsets of the
  * all-to-all are host arrays of `world` entries, in bytes. */
 int o3dmi_comm_allreduce_sum_f64(o3dmi_comm_t* c, double* dev_buf, int64_t n,
@@ -180,21 +162,6 @@ int o3dmi_registration_multiscale_icp(
         int64_t* correspondences_dev, o3dmi_registration_result_t* result,
         o3dmi_stream_t stream);
 
-/* Sizes that are still on the device. A tracking loop produces its clouds
- * with o3dmi_unproject, which leaves the point counts in device words; reading
- * them back costs the loop a stream drain per frame. After this call the NEXT
- * o3dmi_registration_multiscale_icp[_ex] of the calling host thread takes the
- * live source / target sizes from ns_dev / nt_dev (int32, written by work
- * queued earlier on the call's stream; NULL = the host argument as usual) and
- * reads its ns / nt arguments as the capacities of the buffers. With a
- * down-sampled finest level (voxel_sizes[last] > 0, the tracking
- * configuration) nothing waits for them: the pyramid launches bound themselves
- * by the device words. Without one the driver fetches them first. A live size
- * of zero is then reported through the usual "0 correspondence" result. The
- * reference has no counterpart (its Tensor shapes live on the host). */
-int o3dmi_registration_set_device_counts(const int32_t* ns_dev,
-                                         const int32_t* nt_dev);
-
 /* TransformationEstimation choice for o3dmi_registration_multiscale_icp_ex
  * (t/pipelines/registration/TransformationEstimation.h:28-34). */
 typedef enum {
@@ -216,6 +183,47 @@ typedef struct {
     double lambda_geometric;            /* COLORED; outside [0,1] -> 0.968    */
 } o3dmi_icp_attributes_t;
 
+/* What one o3dmi_registration_multiscale_icp_ex call is given beyond the
+ * reference's arguments; zeroed (or a NULL pointer) = none of it. The
+ * communicator is not here: o3dmi_set_comm is ambient per-thread state that
+ * integrate, ray cast and ICP all read, not an argument of one call. */
+typedef struct {
+    /* Sizes that are still on the device. A tracking loop produces its clouds
+     * with o3dmi_unproject, which leaves the point counts in device words;
+     * reading them back costs the loop a stream drain per frame. With a
+     * pointer given, the call takes the live source / target size from it
+     * (int32, written by work queued earlier on the call's stream; NULL = the
+     * host argument as usual) and reads its ns / nt argument as the capacity
+     * of the buffer. With a down-sampled finest level (voxel_sizes[last] > 0,
+     * the tracking configuration) nothing waits for them: the pyramid launches
+     * bound themselves by the device words. Without one the driver fetches
+     * them first. A live size of zero is then reported through the usual "0
+     * correspondence" result. The reference has no counterpart (its Tensor
+     * shapes live on the host). */
+    const int32_t* ns_dev;
+    const int32_t* nt_dev;
+    /* Device-side all-reduce hook (NULL = the host hook, or none). It takes
+     * precedence over the host hook `allreduce` and yields to a communicator
+     * installed with o3dmi_set_comm: the per-iteration sums then stay on the
+     * device from the final reduction kernel through the collective to the
+     * kernel that posts them to the host mailbox (one host wait per
+     * iteration, no staging copies). */
+    o3dmi_allreduce_device_t device_allreduce;
+    void* device_allreduce_user;
+    /* Who shards the source cloud when the calling thread has a communicator
+     * of more than one rank installed (ignored without one):
+     *   0  the caller: each rank passes ITS shard of the source (the semantics
+     *      of the two hooks). A voxel pyramid is then built per shard, i.e.
+     *      the coarse levels differ from the unsharded run's.
+     *   1  the driver: every rank passes the WHOLE source; the pyramid is
+     *      built from it on every rank (it IS the unsharded pyramid), and each
+     *      rank searches and accumulates a contiguous slice of every level.
+     *      The poses equal the unsharded run's to the rounding of the float64
+     *      sums for any number of scales. correspondences_dev: a rank fills
+     *      its slice of the finest level's rows, the other rows read -1. */
+    int level_sharding;
+} o3dmi_icp_options_t;
+
 /* MultiScaleICP with a selectable estimator. POINT_TO_PLANE is exactly
  * o3dmi_registration_multiscale_icp; POINT_TO_POINT
  * (TransformationEstimationPointToPoint, TransformationEstimation.cpp:101-160)
@@ -227,15 +235,15 @@ typedef struct {
  * both colour sets, every attribute is averaged through the VoxelDownSample
  * pyramid, and missing colour gradients are estimated on the finest level
  * with EstimateColorGradients(30, 4 voxel_size or 2 max_distance).
- * attrs may be NULL for the first two estimators. */
+ * attrs may be NULL for the first two estimators, options always. */
 int o3dmi_registration_multiscale_icp_ex(
         const void* source_dev, int64_t ns, const void* target_dev,
         const void* target_normals_dev, int64_t nt, int dtype, int num_scales,
         const double* voxel_sizes, const o3dmi_icp_criteria_t* criterias,
         const double* max_correspondence_distances,
         const double* init_source_to_target, int estimation,
-        const o3dmi_icp_attributes_t* attrs, int robust_kernel,
-        double scaling_parameter, double shape_parameter,
+        const o3dmi_icp_attributes_t* attrs, const o3dmi_icp_options_t* options,
+        int robust_kernel, double scaling_parameter, double shape_parameter,
         o3dmi_icp_callback_t callback, void* callback_user,
         o3dmi_allreduce_sum_t allreduce, void* allreduce_user,
         int64_t* correspondences_dev, o3dmi_registration_result_t* result,

@@ -183,8 +183,14 @@ ICP_CALLBACK = C.CFUNCTYPE(None, _i64, _i64, _i64, _d, _d, _dp, _vp)
 ALLREDUCE_SUM = C.CFUNCTYPE(_i32, _dp, _i32, _vp)
 ALLREDUCE_DEVICE = C.CFUNCTYPE(_i32, _vp, _i32, _vp, _vp)
 
+
+class IcpOptions(C.Structure):
+    _fields_ = [("ns_dev", _vp), ("nt_dev", _vp),
+                ("device_allreduce", ALLREDUCE_DEVICE),
+                ("device_allreduce_user", _vp), ("level_sharding", _i32)]
+
+
 PROTOTYPES.update({
-    "o3dmi_set_device_allreduce": (_i32, [ALLREDUCE_DEVICE, _vp]),
     "o3dmi_registration_multiscale_icp": (
         _i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _dp,
                C.POINTER(IcpCriteria), _dp, _dp, _i32, _d, _d, ICP_CALLBACK,
@@ -193,8 +199,9 @@ PROTOTYPES.update({
     "o3dmi_registration_multiscale_icp_ex": (
         _i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _dp,
                C.POINTER(IcpCriteria), _dp, _dp, _i32,
-               C.POINTER(IcpAttributes), _i32, _d, _d, ICP_CALLBACK, _vp,
-               ALLREDUCE_SUM, _vp, _vp, C.POINTER(RegistrationResultC), _vp]),
+               C.POINTER(IcpAttributes), C.POINTER(IcpOptions), _i32, _d, _d,
+               ICP_CALLBACK, _vp, ALLREDUCE_SUM, _vp, _vp,
+               C.POINTER(RegistrationResultC), _vp]),
     "o3dmi_icp_colored_accumulate": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _i64, _i32, _d, _i32, _d, _d, _vp,
                                             _vp]),
@@ -434,8 +441,6 @@ PROTOTYPES.update({
     "o3dmi_comm_rccl_ranks": (_i32, [_vp]),
     "o3dmi_set_comm": (_i32, [_vp]),
     "o3dmi_set_rccl_comm": (_i32, [_vp]),
-    "o3dmi_set_icp_level_sharding": (_i32, [_i32]),
-    "o3dmi_registration_set_device_counts": (_i32, [_vp, _vp]),
     "o3dmi_comm_allreduce_sum_f64": (_i32, [_vp, _vp, _i64, _vp]),
     "o3dmi_comm_allgather": (_i32, [_vp, _vp, _vp, _i64, _vp]),
     "o3dmi_comm_alltoallv": (_i32, [_vp, _vp, C.POINTER(_i64),

@@ -15,7 +15,7 @@ namespace o3dmi {
 
 // Everything one driver call was asked to do, resolved once by the entry point
 // (o3dmi_registration_multiscale_icp_ex) and const below it: nothing there
-// reads a per-thread option or an argument of the C ABI again.
+// reads the thread's communicator or an argument of the C ABI again.
 struct IcpCall {
     int dtype = O3DMI_F32;
     size_t esz = 4;
@@ -34,7 +34,7 @@ struct IcpCall {
     const void *target = nullptr, *target_normals = nullptr,
                *target_colors = nullptr, *target_gradients = nullptr;
     int64_t ns = 0, nt = 0;
-    // sizes that live on the device (o3dmi_registration_set_device_counts)
+    // sizes that live on the device (o3dmi_icp_options_t)
     const int32_t *ns_dev = nullptr, *nt_dev = nullptr;
 
     int num_scales = 0;
@@ -49,8 +49,10 @@ struct IcpCall {
     o3dmi_icp_callback_t callback = nullptr;
     o3dmi_allreduce_sum_t allreduce = nullptr;  // host all-reduce hook
     void *callback_user = nullptr, *allreduce_user = nullptr;
-    o3dmi_comm* comm = nullptr;  // NULL also for a world of one rank
-    // per-thread options, read once at entry
+    // the thread's communicator, read once at entry; NULL also for a world of
+    // one rank
+    o3dmi_comm* comm = nullptr;
+    // o3dmi_icp_options_t: device hook; level sharding (false without `comm`)
     o3dmi_allreduce_device_t dev_allreduce = nullptr;
     void* dev_allreduce_user = nullptr;
     bool level_sharding = false;

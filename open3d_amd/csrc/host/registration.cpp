@@ -27,7 +27,8 @@
 // symmetric / coloured -> a second launch that gathers by correspondence and
 // accumulates their 29 sums (two mailbox waits per iteration).
 //
-// This file: the entry point, which resolves a call into an IcpCall
+// This file: the entry point, which resolves its arguments (the options
+// struct among them) and the thread's communicator into an IcpCall
 // (icp_driver.h), and below it the index scheduler, the sums fetcher, the
 // per-iteration update and the scale loop. Which host call is issued in the
 // shadow of which launch is the design: the comments at each say why. The
@@ -54,61 +55,7 @@
 
 using namespace o3dmi;
 
-// Device-side all-reduce hook of the calling host thread (one rank = one
-// process, or one thread per device): see o3dmi_set_device_allreduce.
-static thread_local o3dmi_allreduce_device_t g_dev_allreduce = nullptr;
-static thread_local void* g_dev_allreduce_user = nullptr;
-
-extern "C" int o3dmi_set_device_allreduce(o3dmi_allreduce_device_t fn,
-                                          void* user) {
-    g_dev_allreduce = fn;
-    g_dev_allreduce_user = user;
-    return O3DMI_OK;
-}
-
-// Device-resident cloud sizes for the NEXT driver call of this host thread
-// (o3dmi_registration_set_device_counts).
-static thread_local const int32_t* g_ns_dev = nullptr;
-static thread_local const int32_t* g_nt_dev = nullptr;
-
-extern "C" int o3dmi_registration_set_device_counts(const int32_t* ns_dev,
-                                                    const int32_t* nt_dev) {
-    g_ns_dev = ns_dev;
-    g_nt_dev = nt_dev;
-    return O3DMI_OK;
-}
-
-// With a communicator installed (o3dmi_set_comm): who shards the source cloud.
-// 0: the caller -- it passes ITS shard (the semantics of the two hooks);
-// 1: the driver -- every rank passes the WHOLE source, the pyramid is built
-//    from it on every rank (so it is the unsharded run's pyramid, level for
-//    level), and each rank searches / accumulates its contiguous slice of
-//    every level.
-static thread_local int g_level_sharding = 0;
-
-extern "C" int o3dmi_set_icp_level_sharding(int on) {
-    g_level_sharding = on ? 1 : 0;
-    return O3DMI_OK;
-}
-
 namespace {
-
-// The per-thread options of a driver call, read once, before any validation:
-// the device counts (consumed by the call, whatever it does), the device
-// all-reduce hook, level sharding, and the thread's communicator (ThreadComm;
-// a world of one rank counts as none).
-IcpCall TakeThreadOptions() {
-    IcpCall c;
-    c.ns_dev = g_ns_dev;
-    c.nt_dev = g_nt_dev;
-    g_ns_dev = g_nt_dev = nullptr;
-    c.dev_allreduce = g_dev_allreduce;
-    c.dev_allreduce_user = g_dev_allreduce_user;
-    c.comm = ThreadComm();
-    if (c.comm && c.comm->world <= 1) c.comm = nullptr;
-    c.level_sharding = c.comm != nullptr && g_level_sharding != 0;
-    return c;
-}
 
 // The last of a call's description, which needs HIP (the caller holds the
 // exit guard). Without a down-sampled finest level the sizes size the
@@ -676,9 +623,9 @@ extern "C" int o3dmi_registration_multiscale_icp(
     return o3dmi_registration_multiscale_icp_ex(
             source_dev, ns, target_dev, target_normals_dev, nt, dtype,
             num_scales, voxel_sizes, criterias, max_dists, init,
-            O3DMI_ICP_POINT_TO_PLANE, nullptr, robust_kernel, scaling_parameter,
-            shape_parameter, callback, callback_user, allreduce, allreduce_user,
-            correspondences_dev, result, stream);
+            O3DMI_ICP_POINT_TO_PLANE, nullptr, nullptr, robust_kernel,
+            scaling_parameter, shape_parameter, callback, callback_user,
+            allreduce, allreduce_user, correspondences_dev, result, stream);
 }
 
 extern "C" int o3dmi_registration_multiscale_icp_ex(
@@ -686,15 +633,23 @@ extern "C" int o3dmi_registration_multiscale_icp_ex(
         const void* target_normals_dev, int64_t nt, int dtype, int num_scales,
         const double* voxel_sizes, const o3dmi_icp_criteria_t* criterias,
         const double* max_dists, const double* init, int estimation,
-        const o3dmi_icp_attributes_t* attrs, int robust_kernel,
-        double scaling_parameter, double shape_parameter,
+        const o3dmi_icp_attributes_t* attrs, const o3dmi_icp_options_t* options,
+        int robust_kernel, double scaling_parameter, double shape_parameter,
         o3dmi_icp_callback_t callback, void* callback_user,
         o3dmi_allreduce_sum_t allreduce, void* allreduce_user,
         int64_t* correspondences_dev, o3dmi_registration_result_t* result,
         o3dmi_stream_t stream) {
-    // first of all: the device counts are consumed whatever this call does; the
-    // other per-thread options and the communicator are read here too
-    IcpCall c = TakeThreadOptions();
+    IcpCall c;
+    // the thread's communicator; a world of one rank counts as none
+    c.comm = ThreadComm();
+    if (c.comm && c.comm->world <= 1) c.comm = nullptr;
+    if (options) {
+        c.ns_dev = options->ns_dev;
+        c.nt_dev = options->nt_dev;
+        c.dev_allreduce = options->device_allreduce;
+        c.dev_allreduce_user = options->device_allreduce_user;
+        c.level_sharding = c.comm != nullptr && options->level_sharding != 0;
+    }
     // AssertInputMultiScaleICP, Registration.cpp:119-219.
     O3DMI_REQUIRE(result != nullptr, "result is null");
     O3DMI_REQUIRE(dtype == O3DMI_F32 || dtype == O3DMI_F64,

@@ -1591,7 +1591,7 @@ void o3dmi_pose_to_transformation(const double* pose_ptr, double* T) {
 
 // ---- device-side all-reduce support (multi-GPU source-sharded ICP) ----------
 // The driver keeps the iteration's 32 sums on the device, lets the caller's
-// collective (RCCL all-reduce through the hook of o3dmi_set_device_allreduce)
+// collective (RCCL all-reduce through the hook in o3dmi_icp_options_t)
 // run on the launch stream, and only then posts them to the host mailbox:
 //   final sum -> SumsTailKernel -> [all-reduce on the stream] -> SumsPostKernel
 namespace o3dmi {

@@ -82,15 +82,18 @@ def multi_scale_icp(source, target, target_normals, voxel_sizes, criteria_list,
                     estimation_method=None, callback_after_iteration=None,
                     allreduce=None, source_normals=None, source_colors=None,
                     target_colors=None, target_color_gradients=None,
-                    device_allreduce=None, device_counts=None):
+                    device_allreduce=None, device_counts=None,
+                    level_sharding=False):
     """source/target/target_normals: device tensors {N,3}. `device_counts`
     (optional): (ns, nt) int32 device tensors of one element holding the LIVE
     sizes of source / target, whose tensors are then buffers of at least that
-    many rows (o3dmi_registration_set_device_counts: no read-back of the
-    sizes). `allreduce`
+    many rows (o3dmi_icp_options_t: no read-back of the sizes). `allreduce`
     (optional) sums a length-32 numpy float64 array over ranks in place;
     `device_allreduce(dev_ptr, n, stream_ptr)` (optional, takes precedence;
     sharding.make_device_allreduce) enqueues the same sum on the device.
+    `level_sharding`: with a communicator installed (sharding.Comm.install)
+    every rank passes the WHOLE source and the driver shards each pyramid
+    level; otherwise each rank passes its shard.
     `source_normals` is read by the symmetric estimator, the colours (and the
     optional target colour gradients) by the coloured one."""
     est = estimation_method or TransformationEstimationPointToPlane()
@@ -170,7 +173,12 @@ def multi_scale_icp(source, target, target_normals, voxel_sizes, criteria_list,
             return 0
         ar = _lib.ALLREDUCE_SUM(_ar)
 
-    dar = None
+    opts = _lib.IcpOptions()
+    opts.level_sharding = 1 if level_sharding else 0
+    if device_counts is not None:
+        ns_dev, nt_dev = device_counts
+        opts.ns_dev = ns_dev.data_ptr()
+        opts.nt_dev = nt_dev.data_ptr()
     if device_allreduce is not None:
         def _dar(buf, n, strm, user):
             try:
@@ -180,25 +188,19 @@ def multi_scale_icp(source, target, target_normals, voxel_sizes, criteria_list,
                 import traceback
                 traceback.print_exc()
                 return 1
+        # (`dar` keeps the callback object alive for the call)
         dar = _lib.ALLREDUCE_DEVICE(_dar)
-        _lib.lib().o3dmi_set_device_allreduce(dar, None)
-    try:
-        if device_counts is not None:
-            ns_dev, nt_dev = device_counts
-            _lib.check(_lib.lib().o3dmi_registration_set_device_counts(
-                _lib.ptr(ns_dev), _lib.ptr(nt_dev)), "set_device_counts")
-        st = _icp_call(source, ns, target, target_normals, nt, S, vs, crit, md,
-                       init, p2point, symmetric, colored, attrs, est, cb, ar,
-                       corr, res)
-    finally:
-        if dar is not None:
-            _lib.lib().o3dmi_set_device_allreduce(_lib.ALLREDUCE_DEVICE(0),
-                                                  None)
-        if device_counts is not None:
-            # the driver consumes the pointers on entry; if Python raised
-            # before it got there they must not wait for the NEXT call of this
-            # thread
-            _lib.lib().o3dmi_registration_set_device_counts(None, None)
+        opts.device_allreduce = dar
+    st = _lib.lib().o3dmi_registration_multiscale_icp_ex(
+        _lib.ptr(source), ns, _lib.ptr(target),
+        _lib.ptr(target_normals) if target_normals is not None else None, nt,
+        TORCH_TO_O3DMI[source.dtype], S, _lib.f64p(vs), crit, _lib.f64p(md),
+        _lib.f64p(init),
+        1 if p2point else (2 if symmetric else (3 if colored else 0)),
+        C.byref(attrs), C.byref(opts), int(est.kernel.type),
+        C.c_double(est.kernel.scaling_parameter),
+        C.c_double(est.kernel.shape_parameter), cb, None, ar, None,
+        _lib.ptr(corr), C.byref(res), stream())
     _lib.check(st, "multi_scale_icp")
     out = RegistrationResult()
     out.transformation = np.array(res.transformation[:]).reshape(4, 4)
@@ -210,26 +212,12 @@ def multi_scale_icp(source, target, target_normals, voxel_sizes, criteria_list,
     return out
 
 
-def _icp_call(source, ns, target, target_normals, nt, S, vs, crit, md, init,
-              p2point, symmetric, colored, attrs, est, cb, ar, corr, res):
-    return _lib.lib().o3dmi_registration_multiscale_icp_ex(
-        _lib.ptr(source), ns, _lib.ptr(target),
-        _lib.ptr(target_normals) if target_normals is not None else None, nt,
-        TORCH_TO_O3DMI[source.dtype], S, _lib.f64p(vs), crit, _lib.f64p(md),
-        _lib.f64p(init),
-        1 if p2point else (2 if symmetric else (3 if colored else 0)),
-        C.byref(attrs), int(est.kernel.type),
-        C.c_double(est.kernel.scaling_parameter),
-        C.c_double(est.kernel.shape_parameter), cb, None, ar, None,
-        _lib.ptr(corr), C.byref(res), stream())
-
-
 def icp(source, target, target_normals, max_correspondence_distance,
         init_source_to_target=None, estimation_method=None, criteria=None,
         voxel_size=-1.0, callback_after_iteration=None, allreduce=None,
         source_normals=None, source_colors=None, target_colors=None,
         target_color_gradients=None, device_allreduce=None,
-        device_counts=None):
+        device_counts=None, level_sharding=False):
     """t::pipelines::registration::ICP (Registration.cpp:93-106)."""
     return multi_scale_icp(source, target, target_normals, [voxel_size],
                            [criteria or ICPConvergenceCriteria()],
@@ -238,7 +226,7 @@ def icp(source, target, target_normals, max_correspondence_distance,
                            callback_after_iteration, allreduce, source_normals,
                            source_colors, target_colors,
                            target_color_gradients, device_allreduce,
-                           device_counts)
+                           device_counts, level_sharding)
 
 
 def _check_pair(source, target):

@@ -410,24 +410,20 @@ class Comm:
         print(msg + "; using the torch.distributed transport", file=sys.stderr)
         return Comm.torch(dist)
 
-    def install(self, level_sharding=False):
+    def install(self):
         """Makes this communicator the all-reduce of the ICP drivers called
-        from this host thread (o3dmi_set_comm). level_sharding: every rank
-        passes the WHOLE source cloud and the driver shards each pyramid level
-        (reference-identical pyramid); otherwise each rank passes its shard."""
+        from this host thread (o3dmi_set_comm). Each rank passes its shard of
+        the source cloud, or the whole cloud with
+        registration.multi_scale_icp(level_sharding=True)."""
         from . import _lib
         _lib.check(_lib.lib().o3dmi_set_comm(self.handle), "set_comm")
         _tls.installed = self
-        _lib.check(_lib.lib().o3dmi_set_icp_level_sharding(
-            1 if level_sharding else 0), "set_icp_level_sharding")
 
     @staticmethod
     def uninstall():
         from . import _lib
         _lib.check(_lib.lib().o3dmi_set_comm(None), "set_comm")
         _tls.installed = None
-        _lib.check(_lib.lib().o3dmi_set_icp_level_sharding(0),
-                   "set_icp_level_sharding")
 
     def allreduce_sum(self, t):
         """In-place sum of a float64 device tensor over the ranks."""

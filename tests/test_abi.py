@@ -35,6 +35,16 @@ def test_every_declared_symbol_is_exported(built, header):
     assert not unbound, "declared in header but not bound in _lib.py: %s" % unbound
 
 
+def test_icp_options_replaced_the_per_thread_setters(built):
+    """The per-call ICP options are an argument (o3dmi_icp_options_t)."""
+    so = ctypes.CDLL(built.SO_PATH)
+    for name in ("o3dmi_registration_set_device_counts",
+                 "o3dmi_set_device_allreduce",
+                 "o3dmi_set_icp_level_sharding"):
+        assert not hasattr(so, name), name
+        assert name not in built.PROTOTYPES, name
+
+
 def test_library_loads_and_reports_version(built):
     L = built.lib()
     assert L.o3dmi_abi_version() == 1

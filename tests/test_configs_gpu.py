@@ -593,9 +593,10 @@ def test_configs3_level_sharded_multiscale_icp_8_ranks_equals_unsharded():
 
     def rank_body(r):
         comm = lb.comm(r)
-        comm.install(level_sharding=True)
+        comm.install()
         try:
-            out = reg.multi_scale_icp(src.clone(), tgt, nrm, vs, crit, md)
+            out = reg.multi_scale_icp(src.clone(), tgt, nrm, vs, crit, md,
+                                      level_sharding=True)
             torch.cuda.synchronize()
         finally:
             sharding_uninstall()

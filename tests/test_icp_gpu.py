@@ -1501,23 +1501,44 @@ def test_voxel_down_sample_tiled_form_sizes_and_tile_boundaries():
     check(np.ascontiguousarray(pts[:777]), None, 0.05)   # table clean again
 
 
-@pytest.mark.parametrize("voxels", [[0.05, 0.025, 0.0125], [0.05, -1.0]])
-def test_multiscale_icp_with_device_resident_cloud_sizes(voxels):
-    """o3dmi_registration_set_device_counts: the clouds sit in buffers larger
-    than their live sizes (as o3dmi_unproject leaves them) and the sizes are
-    int32 device words; the call must equal the one given exact-size tensors,
-    bit for bit, with a down-sampled finest level (nothing waits for the
-    sizes) and without one (the driver fetches them)."""
-    _lib, reg = _gpu()
-    p = _pair(50000, seed=13)
-    ns, nt, cap = 41234, 47001, 50000
+def _icp_ex(_lib, src, tgt, nrm, voxels, crit, md, options, num_scales=None):
+    """o3dmi_registration_multiscale_icp_ex itself, point-to-plane on Float32
+    clouds; `options`: an _lib.IcpOptions, or None for a NULL pointer.
+    -> (status, RegistrationResultC)."""
+    from open3d_amd.core import stream
+    S = len(voxels)
+    vs = np.ascontiguousarray(voxels, dtype=np.float64)
+    mdv = np.ascontiguousarray(md, dtype=np.float64)
+    cr = (_lib.IcpCriteria * S)(*[
+        _lib.IcpCriteria(c.relative_fitness, c.relative_rmse, c.max_iteration)
+        for c in crit])
+    res = _lib.RegistrationResultC()
+    st = _lib.lib().o3dmi_registration_multiscale_icp_ex(
+        _lib.ptr(src), src.shape[0], _lib.ptr(tgt), _lib.ptr(nrm),
+        tgt.shape[0], 0, S if num_scales is None else num_scales,
+        _lib.f64p(vs), cr, _lib.f64p(mdv), None, 0, None,
+        C.byref(options) if options is not None else None, 0,
+        C.c_double(1.0), C.c_double(1.0), _lib.ICP_CALLBACK(0), None,
+        _lib.ALLREDUCE_SUM(0), None, None, C.byref(res), stream())
+    return st, res
+
+
+def _same_result(a, b):
+    """Pose, fitness, rmse and iteration count, bit for bit (either the Python
+    mirror's result or the C struct)."""
+    return (np.array_equal(np.asarray(a.transformation[:]).reshape(-1),
+                           np.asarray(b.transformation[:]).reshape(-1)) and
+            a.fitness == b.fitness and a.inlier_rmse == b.inlier_rmse and
+            a.num_iterations == b.num_iterations)
+
+
+def _padded(p, ns, nt):
+    """The pair in full-size buffers of which ns / nt rows are live, junk
+    behind them, and the live sizes as int32 device words."""
     src = torch.from_numpy(p["source"]).cuda()
     tgt = torch.from_numpy(p["target"]).cuda()
     nrm = torch.from_numpy(p["target_normals"]).cuda()
-    crit = [reg.ICPConvergenceCriteria(1e-6, 1e-6, 10)] * len(voxels)
-    md = [0.15, 0.07] if len(voxels) == 2 else [0.15, 0.075, 0.0375]
-    want = reg.multi_scale_icp(src[:ns].clone(), tgt[:nt].contiguous(),
-                               nrm[:nt].contiguous(), voxels, crit, md)
+    exact = (src[:ns].clone(), tgt[:nt].contiguous(), nrm[:nt].contiguous())
     # rows past the live sizes hold junk the call must never look at
     src_buf = src.clone()
     src_buf[ns:] = float("nan")
@@ -1525,23 +1546,114 @@ def test_multiscale_icp_with_device_resident_cloud_sizes(voxels):
     tgt_buf[nt:] = 1e6
     nrm_buf[nt:] = float("nan")
     counts = torch.tensor([ns, nt], dtype=torch.int32, device="cuda")
-    L = _lib.lib()
-    _lib.check(L.o3dmi_registration_set_device_counts(
-        C.c_void_p(counts.data_ptr()), C.c_void_p(counts.data_ptr() + 4)),
-        "set_device_counts")
-    got = reg.multi_scale_icp(src_buf, tgt_buf, nrm_buf, voxels, crit, md)
+    return exact, (src_buf, tgt_buf, nrm_buf), counts
+
+
+@pytest.mark.parametrize("voxels", [[0.05, 0.025, 0.0125], [0.05, -1.0]])
+def test_multiscale_icp_with_device_resident_cloud_sizes(voxels):
+    """o3dmi_icp_options_t ns_dev / nt_dev: the clouds sit in buffers larger
+    than their live sizes (as o3dmi_unproject leaves them) and the sizes are
+    int32 device words; the call must equal the one given exact-size tensors,
+    bit for bit, with a down-sampled finest level (nothing waits for the
+    sizes) and without one (the driver fetches them)."""
+    _lib, reg = _gpu()
+    exact, bufs, counts = _padded(_pair(50000, seed=13), 41234, 47001)
+    crit = [reg.ICPConvergenceCriteria(1e-6, 1e-6, 10)] * len(voxels)
+    md = [0.15, 0.07] if len(voxels) == 2 else [0.15, 0.075, 0.0375]
+    want = reg.multi_scale_icp(*exact, voxels, crit, md)
+    got = reg.multi_scale_icp(*bufs, voxels, crit, md,
+                              device_counts=(counts[0:1], counts[1:2]))
     assert np.array_equal(got.transformation, want.transformation)
     assert got.num_iterations == want.num_iterations
     assert got.fitness == want.fitness and got.inlier_rmse == want.inlier_rmse
     # the setting is consumed by one call
-    again = reg.multi_scale_icp(src[:ns].clone(), tgt[:nt].contiguous(),
-                                nrm[:nt].contiguous(), voxels, crit, md)
+    again = reg.multi_scale_icp(*exact, voxels, crit, md)
     assert np.array_equal(again.transformation, want.transformation)
-    # the keyword form of the Python mirror is the same setting
-    kw = reg.multi_scale_icp(src_buf, tgt_buf, nrm_buf, voxels, crit, md,
-                             device_counts=(counts[0:1], counts[1:2]))
-    assert np.array_equal(kw.transformation, want.transformation)
-    assert kw.num_iterations == want.num_iterations
+    # zeroed options are no options
+    st0, zeroed = _icp_ex(_lib, *exact, voxels, crit, md, _lib.IcpOptions())
+    st1, null = _icp_ex(_lib, *exact, voxels, crit, md, None)
+    assert st0 == 0 and st1 == 0
+    assert _same_result(zeroed, null)
+    assert _same_result(null, want)
+
+
+def test_rejected_call_with_device_counts_leaves_nothing_behind():
+    """A call that carries device counts and is rejected before any launch
+    (no scales) must not hand them on: the plain call after it equals the same
+    plain call made before it, bit for bit. The counts differ from the
+    tensors' sizes, so a call that took them would compute something else."""
+    _lib, reg = _gpu()
+    p = _pair(2000, seed=5)
+    _, bufs, counts = _padded(p, 1500, 1700)
+    plain = tuple(torch.from_numpy(p[k]).cuda()
+                  for k in ("source", "target", "target_normals"))
+    voxels, md = [0.05, -1.0], [0.15, 0.07]
+    crit = [reg.ICPConvergenceCriteria(1e-6, 1e-6, 10)] * 2
+    first = reg.multi_scale_icp(*plain, voxels, crit, md)
+    assert first.num_iterations > 0 and first.fitness > 0
+    opts = _lib.IcpOptions()
+    opts.ns_dev = counts[0:1].data_ptr()
+    opts.nt_dev = counts[1:2].data_ptr()
+    st, _ = _icp_ex(_lib, *bufs, voxels, crit, md, opts, num_scales=0)
+    assert st == 1                  # O3DMI_ERR_INVALID_ARG
+    after = reg.multi_scale_icp(*plain, voxels, crit, md)
+    assert _same_result(after, first)
+    # ... which the counts would have changed
+    live = reg.multi_scale_icp(*bufs, voxels, crit, md,
+                               device_counts=(counts[0:1], counts[1:2]))
+    assert not _same_result(live, first)
+
+
+def test_device_counts_belong_to_the_call_not_the_thread():
+    """Two host threads on one device, five calls each, at the same time: one
+    passes device counts over padded buffers, the other exact-size tensors of
+    another pair. Every result equals the thread's own single-threaded one,
+    bit for bit."""
+    import threading
+    _lib, reg = _gpu()
+    exact_a, bufs_a, counts = _padded(_pair(2000, seed=7), 1611, 1803)
+    pb = _pair(2000, seed=8)
+    args_b = tuple(torch.from_numpy(pb[k]).cuda()
+                   for k in ("source", "target", "target_normals"))
+    voxels, md = [0.05, 0.025], [0.15, 0.075]
+    crit = [reg.ICPConvergenceCriteria(1e-6, 1e-6, 10)] * 2
+
+    def call_a():
+        return reg.multi_scale_icp(*bufs_a, voxels, crit, md,
+                                   device_counts=(counts[0:1], counts[1:2]))
+
+    def call_b():
+        return reg.multi_scale_icp(*args_b, voxels, crit, md)
+
+    want = [call_a(), call_b()]
+    assert _same_result(want[0],
+                        reg.multi_scale_icp(*exact_a, voxels, crit, md))
+    assert all(w.num_iterations > 0 and w.fitness > 0 for w in want)
+    assert not _same_result(want[0], want[1])
+    torch.cuda.synchronize()
+    got, errs = [[], []], []
+    start = threading.Barrier(2)
+
+    def main(k, call):
+        try:
+            torch.cuda.set_device(0)
+            start.wait(timeout=30)
+            for _ in range(5):
+                got[k].append(call())
+        except BaseException as e:  # surfaced below
+            errs.append((k, e))
+    ts = [threading.Thread(target=main, args=(k, call), daemon=True)
+          for k, call in enumerate((call_a, call_b))]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join(timeout=60)
+        assert not t.is_alive(), "a thread did not return"
+    if errs:
+        raise errs[0][1]
+    for k in range(2):
+        assert len(got[k]) == 5
+        assert all(_same_result(g, want[k]) for g in got[k]), k
 
 
 _FUSED_PYRAMID_SCRIPT = r"""

@@ -238,7 +238,7 @@ def test_multiscale_icp_finest_level_is_the_input_on_a_mixed_pair(clouds):
 
 def test_multiscale_icp_device_counts_with_capacities_across_the_limit(
         clouds):
-    """o3dmi_registration_set_device_counts: the buffers' capacities (2^20,
+    """o3dmi_icp_options_t ns_dev / nt_dev: the buffers' capacities (2^20,
     2^20 + 4096) size the pyramid's launches -- a mixed pair -- while the
     live sizes (1 000 000, 1 040 000) would both fit the tiled form. The
     result is the same bits as the call given exact-size tensors, and

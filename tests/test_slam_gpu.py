@@ -277,8 +277,8 @@ def test_cpp_icp_tracking_example_runs_configs2_through_the_c_abi():
 
 def test_cpp_icp_tracking_example_sharded_ranks_through_the_library_comm():
     """examples/icp_slam.cpp with ranks = 3: one host thread per rank, the
-    library's communicator installed from C++ (o3dmi_set_comm +
-    o3dmi_set_icp_level_sharding), the per-iteration all-reduce inside the
+    library's communicator installed from C++ (o3dmi_set_comm, level sharding
+    in the call's o3dmi_icp_options_t), the per-iteration all-reduce inside the
     library, and the model frame rendered by the ranks together
     (o3dmi_vbg_ray_cast_sharded: a band of rows each, all-gathered -- the whole
     multi-GPU tracking frame of SURVEY 8(e)). On this one-GPU box the in-process loopback transport stands in

@@ -696,6 +696,100 @@ int o3dmi_pointcloud_estimate_color_gradients(
         int64_t n, int dtype, int max_nn, double radius, void* gradients_dev,
         o3dmi_stream_t stream);
 
+/* PointCloud::SelectByMask (t/geometry/PointCloud.cpp:435-459) for up to 8
+ * attributes at once: attribute a has n rows of row_bytes[a] >= 1 bytes at
+ * attrs_in[a] (12 / 24 for positions and normals, 3 for uint8 colours, ...);
+ * the rows with (mask != 0) != invert go to attrs_out[a], which must hold n
+ * rows, IN INPUT ORDER on every run. mask_dev: uint8 {n}. *m_out receives the
+ * number of rows kept (synchronises). n_attrs outside [1, 8], a NULL pointer
+ * or n < 0: O3DMI_ERR_INVALID_ARG before anything is written. */
+int o3dmi_pointcloud_select_by_mask(int64_t n, const uint8_t* mask_dev,
+                                    int invert, int n_attrs,
+                                    const void* const* attrs_in,
+                                    const int64_t* row_bytes,
+                                    void* const* attrs_out, int64_t* m_out,
+                                    o3dmi_stream_t stream);
+
+/* PointCloud::SelectByIndex (t/geometry/PointCloud.cpp:461-494). indices_dev:
+ * int64 {m}. Plain form (invert = remove_duplicates = 0): a row gather,
+ * duplicates repeat, attrs_out hold m rows. Otherwise index -> mask ->
+ * SelectByMask as upstream (rows in input order, each once), attrs_out hold n
+ * rows. An index outside [0, n) is O3DMI_ERR_INVALID_ARG with nothing written
+ * (checked on the device first; upstream reads out of bounds). Synchronises. */
+int o3dmi_pointcloud_select_by_index(int64_t n, const int64_t* indices_dev,
+                                     int64_t m, int invert,
+                                     int remove_duplicates, int n_attrs,
+                                     const void* const* attrs_in,
+                                     const int64_t* row_bytes,
+                                     void* const* attrs_out, int64_t* m_out,
+                                     o3dmi_stream_t stream);
+
+/* The Remove* filters below return a uint8 mask {n} (1 = kept) and the number
+ * of ones in *m_out; SelectByMask applies it to the attributes. All
+ * synchronise. n == 0: O3DMI_OK, *m_out = 0. */
+
+/* PointCloud::RemoveNonFinitePoints (t/geometry/PointCloud.cpp:716-738). */
+int o3dmi_pointcloud_remove_non_finite_points(const void* points_dev,
+                                              int64_t n, int dtype,
+                                              int remove_nan, int remove_inf,
+                                              uint8_t* mask_out_dev,
+                                              int64_t* m_out,
+                                              o3dmi_stream_t stream);
+
+/* PointCloud::RemoveDuplicatedPoints (t/geometry/PointCloud.cpp:740-760): the
+ * key is the bit pattern of the three coordinates (+0 and -0 differ, NaNs of
+ * equal bits are equal). Of every key the LOWEST index is kept, on every run
+ * (upstream: whichever thread inserts first). n < 2^30. */
+int o3dmi_pointcloud_remove_duplicated_points(const void* points_dev,
+                                              int64_t n, int dtype,
+                                              uint8_t* mask_out_dev,
+                                              int64_t* m_out,
+                                              o3dmi_stream_t stream);
+
+/* PointCloud::RemoveRadiusOutliers (t/geometry/PointCloud.cpp:650-676):
+ * mask_i = (points with d2 < r2 of point i, itself included) >= nb_points;
+ * r2 = search_radius squared in the point dtype, the comparison strict.
+ * nb_points < 1 or search_radius <= 0: O3DMI_ERR_INVALID_ARG; so is a NaN or
+ * Inf coordinate (upstream: undefined -- run RemoveNonFinitePoints first),
+ * with the mask untouched. */
+int o3dmi_pointcloud_remove_radius_outliers(const void* points_dev, int64_t n,
+                                            int dtype, int64_t nb_points,
+                                            double search_radius,
+                                            uint8_t* mask_out_dev,
+                                            int64_t* m_out,
+                                            o3dmi_stream_t stream);
+
+/* PointCloud::RemoveStatisticalOutliers (t/geometry/PointCloud.cpp:678-714).
+ * avg_i = (sum over the k' = min(nb_neighbors, n) nearest points, i itself
+ * first, ascending by (d2, index), of sqrt(d2)) / k', summed and divided in
+ * the point dtype; no {n, k} neighbour table is allocated. mean = sum avg / n,
+ * S = sum ((double)avg - mean)^2 as float64 sums in a fixed tree (same bits on
+ * every run), std = sqrt(S / (n - 1)), threshold = mean + std_ratio * std,
+ * mask_i = (double)avg_i <= threshold. n == 1: std is NaN, nothing is kept.
+ * avg_distances_out_dev (optional): {n} in the point dtype; stats_out
+ * (optional, host): {mean, std, threshold}. nb_neighbors < 1, std_ratio <= 0
+ * or a NaN / Inf coordinate: O3DMI_ERR_INVALID_ARG, mask untouched;
+ * nb_neighbors > 64: O3DMI_ERR_UNSUPPORTED (upstream: no limit). */
+int o3dmi_pointcloud_remove_statistical_outliers(
+        const void* points_dev, int64_t n, int dtype, int64_t nb_neighbors,
+        double std_ratio, uint8_t* mask_out_dev, void* avg_distances_out_dev,
+        double* stats_out, int64_t* m_out, o3dmi_stream_t stream);
+
+/* The per-fragment step of slac::PreprocessPointClouds (t/pipelines/slac/
+ * SLACOptimizer.cpp:47-57). voxel_size > 0: VoxelDownSample ->
+ * RemoveStatisticalOutliers(20, 2.0) -> EstimateNormals (KNN, 30); otherwise
+ * the filter, then EstimateNormals only when normals_dev is NULL.
+ * apply_outlier_mask = 0 reproduces upstream, which computes the filter and
+ * DROPS its result (the legacy method returns a tuple nobody reads);
+ * 1 applies it. Outputs {n,3} each; *m_out rows are valid. Synchronises. */
+int o3dmi_slac_preprocess_point_cloud(const void* points_dev,
+                                      const void* normals_dev, int64_t n,
+                                      int dtype, double voxel_size,
+                                      int apply_outlier_mask,
+                                      void* out_points_dev,
+                                      void* out_normals_dev, int64_t* m_out,
+                                      o3dmi_stream_t stream);
+
 /* ------------------------------------------------------------------------ */
 /* VoxelBlockGrid                                                            */
 /* ------------------------------------------------------------------------ */

@@ -316,6 +316,24 @@ PROTOTYPES.update({
                                                  _vp, _i32, _vp]),
     "o3dmi_voxel_down_sample": (_i32, [_vp, _vp, _i64, _i32, _d, _vp, _vp,
                                        C.POINTER(_i64), _vp]),
+    "o3dmi_pointcloud_select_by_mask": (
+        _i32, [_i64, _vp, _i32, _i32, C.POINTER(_vp), C.POINTER(_i64),
+               C.POINTER(_vp), C.POINTER(_i64), _vp]),
+    "o3dmi_pointcloud_select_by_index": (
+        _i32, [_i64, _vp, _i64, _i32, _i32, _i32, C.POINTER(_vp),
+               C.POINTER(_i64), C.POINTER(_vp), C.POINTER(_i64), _vp]),
+    "o3dmi_pointcloud_remove_non_finite_points": (
+        _i32, [_vp, _i64, _i32, _i32, _i32, _vp, C.POINTER(_i64), _vp]),
+    "o3dmi_pointcloud_remove_duplicated_points": (
+        _i32, [_vp, _i64, _i32, _vp, C.POINTER(_i64), _vp]),
+    "o3dmi_pointcloud_remove_radius_outliers": (
+        _i32, [_vp, _i64, _i32, _i64, _d, _vp, C.POINTER(_i64), _vp]),
+    "o3dmi_pointcloud_remove_statistical_outliers": (
+        _i32, [_vp, _i64, _i32, _i64, _d, _vp, _vp, _dp, C.POINTER(_i64),
+               _vp]),
+    "o3dmi_slac_preprocess_point_cloud": (
+        _i32, [_vp, _vp, _i64, _i32, _d, _i32, _vp, _vp, C.POINTER(_i64),
+               _vp]),
     "o3dmi_vbg_to_device": (_i32, [_vp, _i32, C.POINTER(_vp)]),
     "o3dmi_hash_to_device": (_i32, [_vp, _i32, C.POINTER(_vp)]),
     "o3dmi_vbg_create": (_i32, [_i32, C.POINTER(C.c_char_p), C.POINTER(_i32),

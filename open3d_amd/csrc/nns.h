@@ -61,6 +61,9 @@ int o3dmi_nns_knn_search_counts(const void* points_dev, int64_t n,
                                 const void* queries_dev, int64_t q, int dtype,
                                 int knn, int32_t* idx_dev, void* dist2_dev,
                                 int32_t* counts_dev, o3dmi_stream_t stream);
+int o3dmi_internal_nns_knn_avg_distance(const void* points_dev, int64_t n,
+                                        int dtype, int knn, void* avg_dev,
+                                        o3dmi_stream_t stream);
 }  // extern "C"
 
 namespace o3dmi {

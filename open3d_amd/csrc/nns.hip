@@ -633,6 +633,40 @@ __device__ __forceinline__ void WriteTopK(const WaveTopK<T>& list, int64_t i,
     if (cnt_out && lane == 0) cnt_out[i] = list.nbest;
 }
 
+// What a finished KNN list becomes (KnnSearchKernel's output policy).
+// TopKOut: the {q, knn} index / distance rows of KnnSearch.
+template <typename T>
+struct TopKOut {
+    int* idx;
+    T* d2;
+    int* cnt;
+    __device__ __forceinline__ void Write(const WaveTopK<T>& list,
+                                          int64_t i) const {
+        WriteTopK(list, i, idx, d2, cnt);
+    }
+};
+
+__device__ __forceinline__ float SqrtOf(float x) { return sqrtf(x); }
+__device__ __forceinline__ double SqrtOf(double x) { return sqrt(x); }
+
+// AvgDistanceOut: only the mean distance to the neighbours
+// (RemoveStatisticalOutliers: distance2.Sqrt().Mean({1}), t/geometry/
+// PointCloud.cpp:700) -- no {q, knn} array exists on this path. The sum runs
+// over the neighbours in list order (ascending by (d2, index)) in T and is
+// divided by the row width in T, so the value does not depend on how the
+// wave found the list.
+template <typename T>
+struct AvgDistanceOut {
+    T* avg;
+    __device__ __forceinline__ void Write(const WaveTopK<T>& list,
+                                          int64_t i) const {
+        T sum = T(0);
+        for (int j = 0; j < list.nbest; ++j)
+            sum += SqrtOf(__shfl(list.best_d, j));
+        if ((threadIdx.x & 63) == 0) avg[i] = sum / (T)list.knn;
+    }
+};
+
 // HybridSearch for general max_knn (core/nns/NanoFlannImpl.h:305-370 semantics:
 // neighbours with d2 < r2, ascending by (d2, index), the first max_knn kept;
 // idx padded with -1, dist with 0, count = min(found, max_knn)).
@@ -936,13 +970,12 @@ struct KnnPyramid {
     KnnGrid<T> level[kKnnMaxLevels];
 };
 
-template <typename T>
+template <typename T, typename Out>
 __global__ void __launch_bounds__(kCoopBlock)
 __attribute__((amdgpu_waves_per_eu(4)))
 KnnSearchKernel(KnnPyramid<T> pyr, const T* __restrict__ q, int64_t nq, int knn,
                 const int* __restrict__ query_ids, int* __restrict__ retry_ids,
-                int* __restrict__ retry_count, int* __restrict__ idx_out,
-                T* __restrict__ d2_out, int* __restrict__ cnt_out) {
+                int* __restrict__ retry_count, Out out) {
     extern __shared__ __align__(16) char coop_lds[];
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -1049,7 +1082,7 @@ KnnSearchKernel(KnnPyramid<T> pyr, const T* __restrict__ q, int64_t nq, int knn,
                 retry_ids[atomicAdd(retry_count, 1)] = (int)i;
             continue;
         }
-        WriteTopK(list, i, idx_out, d2_out, cnt_out);
+        out.Write(list, i);
     }
 }
 
@@ -1649,11 +1682,15 @@ struct KnnResources {
 
 }  // namespace
 
-// Internal form (also fills counts_dev {q} with the row width when given).
-int o3dmi_nns_knn_search_counts(const void* points_dev, int64_t n,
-                                const void* queries_dev, int64_t q, int dtype,
-                                int knn, int32_t* idx_dev, void* dist2_dev,
-                                int32_t* counts_dev, o3dmi_stream_t stream) {
+namespace {
+
+// The KNN search behind both entry points below. avg_dev == NULL: the rows go
+// to idx_dev / dist2_dev / counts_dev (TopKOut); else only the mean neighbour
+// distance of every query goes to avg_dev {q} (AvgDistanceOut).
+int KnnSearchRun(const void* points_dev, int64_t n, const void* queries_dev,
+                 int64_t q, int dtype, int knn, int32_t* idx_dev,
+                 void* dist2_dev, int32_t* counts_dev, void* avg_dev,
+                 o3dmi_stream_t stream) {
     O3DMI_REQUIRE(dtype == O3DMI_F32 || dtype == O3DMI_F64,
                   "points must be Float32 or Float64");
     O3DMI_REQUIRE(knn > 0, "knn should be larger than 0.");
@@ -1662,7 +1699,7 @@ int o3dmi_nns_knn_search_counts(const void* points_dev, int64_t n,
     const int k = (int)(n < (int64_t)knn ? n : (int64_t)knn);
     O3DMI_REQUIRE(k <= kMaxKnn, "knn > 64 is not supported");
     if (q == 0) return O3DMI_OK;
-    O3DMI_REQUIRE(queries_dev && idx_dev, "null argument");
+    O3DMI_REQUIRE(queries_dev && (idx_dev || avg_dev), "null argument");
     hipStream_t s = (hipStream_t)stream;
     KnnResources res;
     int st;
@@ -1770,11 +1807,20 @@ int o3dmi_nns_knn_search_counts(const void* points_dev, int64_t n,
                                                    lv->inv_cell) + 1;          \
             }                                                                  \
         }                                                                      \
-        hipLaunchKernelGGL(KnnSearchKernel<T>, grid, block,                    \
-                           CoopLdsBytesPerWave<T>() * (kCoopBlock / 64), s,    \
-                           pyr, (const T*)queries_dev, count, k, ids,          \
-                           retry_ids, retry_count, idx_dev, (T*)dist2_dev,     \
-                           counts_dev);                                        \
+        if (avg_dev)                                                           \
+            hipLaunchKernelGGL((KnnSearchKernel<T, AvgDistanceOut<T>>), grid,  \
+                               block,                                          \
+                               CoopLdsBytesPerWave<T>() * (kCoopBlock / 64),   \
+                               s, pyr, (const T*)queries_dev, count, k, ids,   \
+                               retry_ids, retry_count,                         \
+                               AvgDistanceOut<T>{(T*)avg_dev});                \
+        else                                                                   \
+            hipLaunchKernelGGL((KnnSearchKernel<T, TopKOut<T>>), grid, block,  \
+                               CoopLdsBytesPerWave<T>() * (kCoopBlock / 64),   \
+                               s, pyr, (const T*)queries_dev, count, k, ids,   \
+                               retry_ids, retry_count,                         \
+                               TopKOut<T>{idx_dev, (T*)dist2_dev,              \
+                                          counts_dev});                        \
     } while (0)
         if (dtype == O3DMI_F64) O3DMI_KNN(double);
         else O3DMI_KNN(float);
@@ -1822,6 +1868,30 @@ int o3dmi_nns_knn_search_counts(const void* points_dev, int64_t n,
                      (long long)n, k, h, (int)res.levels.size(), target,
                      n_retry, brute ? "sweep" : "pyramid");
     return O3DMI_OK;
+}
+
+}  // namespace
+
+// Internal form (also fills counts_dev {q} with the row width when given).
+int o3dmi_nns_knn_search_counts(const void* points_dev, int64_t n,
+                                const void* queries_dev, int64_t q, int dtype,
+                                int knn, int32_t* idx_dev, void* dist2_dev,
+                                int32_t* counts_dev, o3dmi_stream_t stream) {
+    O3DMI_REQUIRE(q <= 0 || idx_dev, "null argument");
+    return KnnSearchRun(points_dev, n, queries_dev, q, dtype, knn, idx_dev,
+                        dist2_dev, counts_dev, nullptr, stream);
+}
+
+// Internal (RemoveStatisticalOutliers): avg_dev[i] = mean over the
+// min(knn, n) nearest points of point i (itself included, at distance 0) of
+// sqrt(d2), in the point dtype; see AvgDistanceOut. Returns with the search
+// queued on the stream (its scratch is released after a wait, as above).
+int o3dmi_internal_nns_knn_avg_distance(const void* points_dev, int64_t n,
+                                        int dtype, int knn, void* avg_dev,
+                                        o3dmi_stream_t stream) {
+    O3DMI_REQUIRE(avg_dev != nullptr, "null argument");
+    return KnnSearchRun(points_dev, n, points_dev, n, dtype, knn, nullptr,
+                        nullptr, nullptr, avg_dev, stream);
 }
 
 int o3dmi_nns_knn_search(const void* points_dev, int64_t n,

@@ -1,0 +1,477 @@
+// Kernels behind PointCloud::SelectByMask / SelectByIndex and the Remove*
+// filters (t/geometry/PointCloud.cpp:435-494, 650-760). The reference builds
+// these from tensor ops (IndexGet, Sqrt, Mean, a HashSet insert); here each is
+// one or two launches over the cloud:
+//
+//   compaction     flags -> PrefixSumAsync -> one scatter of up to 8 attributes;
+//                  kept rows stay in input order (the scan decides the row, no
+//                  atomics), so the result is the same on every run
+//   non-finite     one pass
+//   duplicates     open-addressing table of point INDICES keyed by the bit
+//                  pattern of the point (the block hash holds keys within
+//                  +-2^20 only); equal keys meet in one slot and keep the
+//                  lowest index with atomicMin, so the survivor of a key does
+//                  not depend on which thread came first
+//   radius         threshold on the counts of the fixed-radius count kernel
+//   statistical    mean and centred sum of the per-point average distances
+//                  (written by the KNN search's AvgDistanceOut policy, nns.hip)
+//                  as float64 sums in the fixed tree of reduce_sums.h, then the
+//                  threshold and the mask in one launch
+//
+// All of it is HBM-bound streaming except the table inserts (one atomic per
+// probe, load factor <= 1/2).
+
+#include "pointcloud_filter.h"
+
+#include "common.h"
+#include "reduce_sums.h"
+#include "scan.h"
+
+namespace o3dmi {
+namespace {
+
+// Adds the number of lanes with `keep` to *count: one atomic per wave. Every
+// lane of the wave must call it.
+__device__ __forceinline__ void CountKept(bool keep,
+                                          unsigned long long* count) {
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(keep);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(count, (unsigned long long)__popcll(m));
+}
+
+// Rounds of a grid-stride loop in which every lane takes part.
+__device__ __forceinline__ int64_t Rounds(int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    return (n + stride - 1) / stride;
+}
+
+// ---- compaction ---------------------------------------------------------------
+__global__ void MaskFlagsKernel(const uint8_t* __restrict__ mask, int64_t n,
+                                int invert, int32_t* __restrict__ flags) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x)
+        flags[i] = ((mask[i] != 0) != (invert != 0)) ? 1 : 0;
+}
+
+// Row `src` of every attribute to row `dst`. words: bit a set = attribute a is
+// 4-byte aligned with a width that is a multiple of 4 (positions, normals,
+// float colours); the others (uint8 colours) move byte by byte.
+__device__ __forceinline__ void MoveRow(const SelectAttrs& a, unsigned words,
+                                        int64_t src, int64_t dst) {
+    for (int k = 0; k < a.n_attrs; ++k) {
+        const long long w = a.row_bytes[k];
+        if (words & (1u << k)) {
+            const uint32_t* in = (const uint32_t*)a.in[k] + src * (w >> 2);
+            uint32_t* out = (uint32_t*)a.out[k] + dst * (w >> 2);
+            if (w == 12) {
+                const uint32_t x = in[0], y = in[1], z = in[2];
+                out[0] = x;
+                out[1] = y;
+                out[2] = z;
+            } else {
+                for (long long b = 0; b < (w >> 2); ++b) out[b] = in[b];
+            }
+        } else {
+            const uint8_t* in = (const uint8_t*)a.in[k] + src * w;
+            uint8_t* out = (uint8_t*)a.out[k] + dst * w;
+            for (long long b = 0; b < w; ++b) out[b] = in[b];
+        }
+    }
+}
+
+__global__ void CompactRowsKernel(const int32_t* __restrict__ flags,
+                                  const long long* __restrict__ offsets,
+                                  int64_t n, SelectAttrs a, unsigned words) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x)
+        if (flags[i]) MoveRow(a, words, i, offsets[i]);
+}
+
+__global__ void IndexRangeKernel(const int64_t* __restrict__ idx, int64_t m,
+                                 int64_t n, int* __restrict__ bad) {
+    for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < m;
+         r += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = idx[r];
+        if (i < 0 || i >= n) atomicOr(bad, 1);
+    }
+}
+
+__global__ void GatherRowsByIndexKernel(const int64_t* __restrict__ idx,
+                                        int64_t m, SelectAttrs a,
+                                        unsigned words) {
+    for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < m;
+         r += (int64_t)gridDim.x * blockDim.x)
+        MoveRow(a, words, idx[r], r);
+}
+
+__global__ void IndexMaskKernel(const int64_t* __restrict__ idx, int64_t m,
+                                uint8_t* __restrict__ mask) {
+    for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < m;
+         r += (int64_t)gridDim.x * blockDim.x)
+        mask[idx[r]] = 1;  // every writer stores the same byte
+}
+
+unsigned WordAttrs(const SelectAttrs& a) {
+    unsigned words = 0;
+    for (int k = 0; k < a.n_attrs; ++k)
+        if (((uintptr_t)a.in[k] | (uintptr_t)a.out[k] |
+             (uintptr_t)a.row_bytes[k]) % 4 == 0)
+            words |= 1u << k;
+    return words;
+}
+
+// ---- non-finite -----------------------------------------------------------------
+template <typename T>
+__global__ void FiniteCheckKernel(const T* __restrict__ p, int64_t n3,
+                                  int* __restrict__ bad) {
+    bool any = false;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n3;
+         i += (int64_t)gridDim.x * blockDim.x)
+        any |= !isfinite(p[i]);
+    if (any) atomicOr(bad, 1);
+}
+
+template <typename T>
+__global__ void NonFiniteMaskKernel(const T* __restrict__ p, int64_t n,
+                                    int remove_nan, int remove_inf,
+                                    uint8_t* __restrict__ mask,
+                                    unsigned long long* __restrict__ count) {
+    const int64_t rounds = Rounds(n);
+    for (int64_t r = 0; r < rounds; ++r) {
+        const int64_t i = (r * gridDim.x + blockIdx.x) * (int64_t)blockDim.x +
+                          threadIdx.x;
+        bool keep = false;
+        if (i < n) {
+            const T x = p[3 * i + 0], y = p[3 * i + 1], z = p[3 * i + 2];
+            const bool has_nan = isnan(x) || isnan(y) || isnan(z);
+            const bool has_inf = isinf(x) || isinf(y) || isinf(z);
+            keep = !((remove_nan && has_nan) || (remove_inf && has_inf));
+            mask[i] = keep ? 1 : 0;
+        }
+        CountKept(keep, count);
+    }
+}
+
+// ---- duplicates -----------------------------------------------------------------
+template <typename W> struct KeyOf;
+template <> struct KeyOf<float> { using word = uint32_t; };
+template <> struct KeyOf<double> { using word = uint64_t; };
+
+__device__ __forceinline__ uint32_t Fold(uint32_t w) { return w; }
+__device__ __forceinline__ uint32_t Fold(uint64_t w) {
+    return (uint32_t)w ^ ((uint32_t)(w >> 32) * 0x9E3779B1u);
+}
+
+template <typename W>
+__device__ __forceinline__ uint32_t HashKey(W x, W y, W z) {
+    uint32_t h = Fold(x) * 0x9E3779B1u;
+    h ^= (Fold(y) * 0x85EBCA77u) + (h >> 15);
+    h ^= (Fold(z) * 0xC2B2AE3Du) + (h << 11);
+    h ^= h >> 16;
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+    h *= 0xC2B2AE35u;
+    h ^= h >> 16;
+    return h;
+}
+
+// A slot's key never changes once it is claimed (atomicMin only swaps in
+// another point of the same key), so a probe sequence means the same on every
+// thread and in both launches.
+template <typename W>
+__global__ void DuplicateInsertKernel(const W* __restrict__ p, int64_t n,
+                                      int32_t* __restrict__ table,
+                                      uint32_t slot_mask) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const W x = p[3 * i + 0], y = p[3 * i + 1], z = p[3 * i + 2];
+        uint32_t h = HashKey(x, y, z) & slot_mask;
+        for (;;) {
+            const int32_t prev = atomicCAS(&table[h], -1, (int32_t)i);
+            if (prev == -1) break;
+            const W* q = p + 3 * (int64_t)prev;
+            if (q[0] == x && q[1] == y && q[2] == z) {
+                atomicMin(&table[h], (int32_t)i);
+                break;
+            }
+            h = (h + 1) & slot_mask;
+        }
+    }
+}
+
+template <typename W>
+__global__ void DuplicateMaskKernel(const W* __restrict__ p, int64_t n,
+                                    const int32_t* __restrict__ table,
+                                    uint32_t slot_mask,
+                                    uint8_t* __restrict__ mask,
+                                    unsigned long long* __restrict__ count) {
+    const int64_t rounds = Rounds(n);
+    for (int64_t r = 0; r < rounds; ++r) {
+        const int64_t i = (r * gridDim.x + blockIdx.x) * (int64_t)blockDim.x +
+                          threadIdx.x;
+        bool keep = false;
+        if (i < n) {
+            const W x = p[3 * i + 0], y = p[3 * i + 1], z = p[3 * i + 2];
+            uint32_t h = HashKey(x, y, z) & slot_mask;
+            for (;;) {
+                const int32_t res = table[h];
+                if (res < 0) break;  // unreachable: i was inserted
+                const W* q = p + 3 * (int64_t)res;
+                if (q[0] == x && q[1] == y && q[2] == z) {
+                    keep = res == (int32_t)i;
+                    break;
+                }
+                h = (h + 1) & slot_mask;
+            }
+            mask[i] = keep ? 1 : 0;
+        }
+        CountKept(keep, count);
+    }
+}
+
+// ---- radius -----------------------------------------------------------------------
+__global__ void CountThresholdKernel(const int32_t* __restrict__ counts,
+                                     int64_t n, int nb_points,
+                                     uint8_t* __restrict__ mask,
+                                     unsigned long long* __restrict__ count) {
+    const int64_t rounds = Rounds(n);
+    for (int64_t r = 0; r < rounds; ++r) {
+        const int64_t i = (r * gridDim.x + blockIdx.x) * (int64_t)blockDim.x +
+                          threadIdx.x;
+        bool keep = false;
+        if (i < n) {
+            keep = counts[i] >= nb_points;
+            mask[i] = keep ? 1 : 0;
+        }
+        CountKept(keep, count);
+    }
+}
+
+// ---- statistical ------------------------------------------------------------------
+// kCentred: sum of (avg_i - mean)^2 with mean = sum_in[0] / n, else sum of
+// avg_i. One partial per workgroup; the geometry depends on n alone.
+template <typename T, bool kCentred>
+__global__ void __launch_bounds__(kSumsBlock)
+AvgSumKernel(const T* __restrict__ avg, int64_t n,
+             const double* __restrict__ sum_in, double* __restrict__ partials) {
+    const double mean = kCentred ? sum_in[0] / (double)n : 0.0;
+    double acc[1] = {0.0};
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const double v = (double)avg[i];
+        if (kCentred) {
+            const double c = v - mean;
+            acc[0] += c * c;
+        } else {
+            acc[0] += v;
+        }
+    }
+    BlockSumAndStore<1>(acc, partials);
+}
+
+template <typename T>
+__global__ void StatisticalMaskKernel(const T* __restrict__ avg, int64_t n,
+                                      const double* __restrict__ sums,
+                                      double std_ratio,
+                                      double* __restrict__ stats,
+                                      uint8_t* __restrict__ mask) {
+    const double mean = sums[0] / (double)n;
+    // n == 1: 0 / 0, the threshold is NaN and nothing is kept (as upstream)
+    const double sd = sqrt(sums[1] / (double)(n - 1));
+    const double threshold = mean + std_ratio * sd;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        stats[0] = mean;
+        stats[1] = sd;
+        stats[2] = threshold;
+    }
+    unsigned long long* count = (unsigned long long*)(stats + 3);
+    const int64_t rounds = Rounds(n);
+    for (int64_t r = 0; r < rounds; ++r) {
+        const int64_t i = (r * gridDim.x + blockIdx.x) * (int64_t)blockDim.x +
+                          threadIdx.x;
+        bool keep = false;
+        if (i < n) {
+            keep = (double)avg[i] <= threshold;
+            mask[i] = keep ? 1 : 0;
+        }
+        CountKept(keep, count);
+    }
+}
+
+constexpr int64_t kMaskLimit = 1ll << 40;  // rows; keeps 3 * i in int64 by far
+
+}  // namespace
+
+size_t CompactScratchBytes(int64_t n) {
+    const size_t rows = (size_t)(n > 0 ? n : 1);
+    return sizeof(int64_t) * rows + ((sizeof(int32_t) * rows + 7) & ~(size_t)7) +
+           ScanScratchBytes(n);
+}
+
+int CompactByMaskAsync(const uint8_t* mask_dev, int64_t n, bool invert,
+                       const SelectAttrs& attrs, int64_t* count_dev,
+                       void* scratch_dev, hipStream_t s) {
+    if (n <= 0) {
+        O3DMI_HIP_CHECK(hipMemsetAsync(count_dev, 0, sizeof(int64_t), s));
+        return O3DMI_OK;
+    }
+    const size_t rows = (size_t)n;
+    long long* offsets = (long long*)scratch_dev;
+    int32_t* flags = (int32_t*)(offsets + rows);
+    void* tiles = (char*)flags + ((sizeof(int32_t) * rows + 7) & ~(size_t)7);
+    const dim3 grid(GridFor(n, kBlock)), block(kBlock);
+    hipLaunchKernelGGL(MaskFlagsKernel, grid, block, 0, s, mask_dev, n,
+                       invert ? 1 : 0, flags);
+    const int st = PrefixSumAsync(flags, n, false, (int64_t*)offsets, count_dev,
+                                  tiles, s);
+    if (st) return st;
+    hipLaunchKernelGGL(CompactRowsKernel, grid, block, 0, s, flags, offsets, n,
+                       attrs, WordAttrs(attrs));
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
+int CheckIndexRangeAsync(const int64_t* indices_dev, int64_t m, int64_t n,
+                         int* bad_dev, hipStream_t s) {
+    if (m <= 0) return O3DMI_OK;
+    hipLaunchKernelGGL(IndexRangeKernel, dim3(GridFor(m, kBlock)), dim3(kBlock),
+                       0, s, indices_dev, m, n, bad_dev);
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
+int GatherByIndexAsync(const int64_t* indices_dev, int64_t m,
+                       const SelectAttrs& attrs, hipStream_t s) {
+    if (m <= 0) return O3DMI_OK;
+    hipLaunchKernelGGL(GatherRowsByIndexKernel, dim3(GridFor(m, kBlock)),
+                       dim3(kBlock), 0, s, indices_dev, m, attrs,
+                       WordAttrs(attrs));
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
+int IndexToMaskAsync(const int64_t* indices_dev, int64_t m, uint8_t* mask_dev,
+                     hipStream_t s) {
+    if (m <= 0) return O3DMI_OK;
+    hipLaunchKernelGGL(IndexMaskKernel, dim3(GridFor(m, kBlock)), dim3(kBlock),
+                       0, s, indices_dev, m, mask_dev);
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
+int CheckFiniteAsync(const void* points_dev, int64_t n, int dtype,
+                     int* bad_dev, hipStream_t s) {
+    if (n <= 0) return O3DMI_OK;
+    O3DMI_REQUIRE(n < kMaskLimit, "too many points");
+    const dim3 grid(GridFor(3 * n, kBlock)), block(kBlock);
+    if (dtype == O3DMI_F64)
+        hipLaunchKernelGGL(FiniteCheckKernel<double>, grid, block, 0, s,
+                           (const double*)points_dev, 3 * n, bad_dev);
+    else
+        hipLaunchKernelGGL(FiniteCheckKernel<float>, grid, block, 0, s,
+                           (const float*)points_dev, 3 * n, bad_dev);
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
+int NonFiniteMaskAsync(const void* points_dev, int64_t n, int dtype,
+                       bool remove_nan, bool remove_inf, uint8_t* mask_dev,
+                       unsigned long long* count_dev, hipStream_t s) {
+    if (n <= 0) return O3DMI_OK;
+    O3DMI_REQUIRE(n < kMaskLimit, "too many points");
+    const dim3 grid(GridFor(n, kBlock)), block(kBlock);
+    if (dtype == O3DMI_F64)
+        hipLaunchKernelGGL(NonFiniteMaskKernel<double>, grid, block, 0, s,
+                           (const double*)points_dev, n, remove_nan ? 1 : 0,
+                           remove_inf ? 1 : 0, mask_dev, count_dev);
+    else
+        hipLaunchKernelGGL(NonFiniteMaskKernel<float>, grid, block, 0, s,
+                           (const float*)points_dev, n, remove_nan ? 1 : 0,
+                           remove_inf ? 1 : 0, mask_dev, count_dev);
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
+int64_t DuplicateTableSlots(int64_t n) {
+    int64_t slots = 64;
+    while (slots < 2 * n) slots <<= 1;
+    return slots;
+}
+
+int DuplicateMaskAsync(const void* points_dev, int64_t n, int dtype,
+                       int32_t* table_dev, int64_t slots, uint8_t* mask_dev,
+                       unsigned long long* count_dev, hipStream_t s) {
+    if (n <= 0) return O3DMI_OK;
+    // the table holds int32 indices and is addressed by 32-bit slot numbers
+    O3DMI_REQUIRE(n < (1ll << 30), "too many points (< 2^30)");
+    O3DMI_REQUIRE(slots >= 2 * n && (slots & (slots - 1)) == 0,
+                  "duplicate table: bad capacity");
+    O3DMI_HIP_CHECK(hipMemsetAsync(table_dev, 0xFF,
+                                   sizeof(int32_t) * (size_t)slots, s));
+    const dim3 grid(GridFor(n, kBlock)), block(kBlock);
+    const uint32_t slot_mask = (uint32_t)(slots - 1);
+    if (dtype == O3DMI_F64) {
+        hipLaunchKernelGGL(DuplicateInsertKernel<uint64_t>, grid, block, 0, s,
+                           (const uint64_t*)points_dev, n, table_dev,
+                           slot_mask);
+        hipLaunchKernelGGL(DuplicateMaskKernel<uint64_t>, grid, block, 0, s,
+                           (const uint64_t*)points_dev, n, table_dev, slot_mask,
+                           mask_dev, count_dev);
+    } else {
+        hipLaunchKernelGGL(DuplicateInsertKernel<uint32_t>, grid, block, 0, s,
+                           (const uint32_t*)points_dev, n, table_dev,
+                           slot_mask);
+        hipLaunchKernelGGL(DuplicateMaskKernel<uint32_t>, grid, block, 0, s,
+                           (const uint32_t*)points_dev, n, table_dev, slot_mask,
+                           mask_dev, count_dev);
+    }
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
+int CountThresholdMaskAsync(const int32_t* counts_dev, int64_t n,
+                            int nb_points, uint8_t* mask_dev,
+                            unsigned long long* count_dev, hipStream_t s) {
+    if (n <= 0) return O3DMI_OK;
+    hipLaunchKernelGGL(CountThresholdKernel, dim3(GridFor(n, kBlock)),
+                       dim3(kBlock), 0, s, counts_dev, n, nb_points, mask_dev,
+                       count_dev);
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
+size_t StatisticalScratchDoubles() { return (size_t)kSumsMaxGrid + 8; }
+
+int StatisticalMaskAsync(const void* avg_dev, int64_t n, int dtype,
+                         double std_ratio, double* scratch_dev,
+                         double* stats_dev, uint8_t* mask_dev, hipStream_t s) {
+    if (n <= 0) return O3DMI_OK;
+    double* partials = scratch_dev;
+    double* sums = scratch_dev + kSumsMaxGrid;  // {sum avg, centred sum}
+    const int rows = SumsGrid(n);
+    const dim3 grid(GridFor(n, kBlock)), block(kBlock);
+#define O3DMI_STAT(T)                                                          \
+    do {                                                                       \
+        hipLaunchKernelGGL((AvgSumKernel<T, false>), dim3(rows),               \
+                           dim3(kSumsBlock), 0, s, (const T*)avg_dev, n,       \
+                           (const double*)nullptr, partials);                  \
+        hipLaunchKernelGGL(FinalSumKernel<1>, dim3(1), dim3(kFinalThreads), 0, \
+                           s, partials, rows, sums, (double*)nullptr,          \
+                           (int*)nullptr, 0);                                  \
+        hipLaunchKernelGGL((AvgSumKernel<T, true>), dim3(rows),                \
+                           dim3(kSumsBlock), 0, s, (const T*)avg_dev, n, sums, \
+                           partials);                                          \
+        hipLaunchKernelGGL(FinalSumKernel<1>, dim3(1), dim3(kFinalThreads), 0, \
+                           s, partials, rows, sums + 1, (double*)nullptr,      \
+                           (int*)nullptr, 0);                                  \
+        hipLaunchKernelGGL(StatisticalMaskKernel<T>, grid, block, 0, s,        \
+                           (const T*)avg_dev, n, sums, std_ratio, stats_dev,   \
+                           mask_dev);                                          \
+    } while (0)
+    if (dtype == O3DMI_F64) O3DMI_STAT(double);
+    else O3DMI_STAT(float);
+#undef O3DMI_STAT
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
+}  // namespace o3dmi

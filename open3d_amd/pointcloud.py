@@ -1,0 +1,187 @@
+"""Mirror of t::geometry::PointCloud's selection and filter methods
+(t/geometry/PointCloud.cpp:435-494, 650-760) on the HIP backend.
+
+A cloud is a dict of CUDA attribute tensors with "positions" ({N,3} Float32 or
+Float64) required; every other attribute has N rows of any width and dtype
+("normals", uint8 "colors", ...). Each function returns (attrs_out, mask) as
+the reference's (PointCloud, Tensor) tuples do; mask is a bool {N} tensor.
+"""
+import ctypes as C
+
+import torch
+
+from . import _lib
+from .core import TORCH_TO_O3DMI, require_cuda, stream
+
+MAX_ATTRS = 8  # attributes moved by one compaction launch
+
+
+def _positions(attrs):
+    if "positions" not in attrs:
+        raise ValueError('a cloud needs "positions"')
+    p = require_cuda(attrs["positions"], "positions")
+    if p.dim() != 2 or p.shape[1] != 3 or p.dtype not in (torch.float32,
+                                                          torch.float64):
+        raise ValueError("positions must be {N,3} Float32 or Float64")
+    return p.contiguous()
+
+
+def _rows(attrs):
+    p = _positions(attrs)
+    n = p.shape[0]
+    out = {}
+    for name, t in attrs.items():
+        t = p if name == "positions" else require_cuda(t, name).contiguous()
+        if t.dim() < 1 or t.shape[0] != n:
+            raise ValueError("attribute %r must have %d rows" % (name, n))
+        out[name] = t
+    return out, n
+
+
+def _row_bytes(t):
+    w = t.element_size()
+    for d in t.shape[1:]:
+        w *= d
+    return w
+
+
+def _tables(ins, outs):
+    k = len(ins)
+    return ((C.c_void_p * k)(*[t.data_ptr() for t in ins]),
+            (C.c_int64 * k)(*[_row_bytes(t) for t in ins]),
+            (C.c_void_p * k)(*[t.data_ptr() for t in outs]))
+
+
+def _select(attrs, rows_out, call, where):
+    """Runs `call(n_attrs, in, row_bytes, out, m)` over the attributes in
+    groups of MAX_ATTRS and trims the outputs to the rows kept."""
+    attrs, _ = _rows(attrs)
+    names = list(attrs)
+    out = {}
+    for g in range(0, len(names), MAX_ATTRS):
+        group = names[g:g + MAX_ATTRS]
+        ins = [attrs[k] for k in group]
+        outs = [torch.empty((rows_out,) + tuple(t.shape[1:]), dtype=t.dtype,
+                            device=t.device) for t in ins]
+        m = C.c_int64(0)
+        a_in, widths, a_out = _tables(ins, outs)
+        _lib.check(call(len(group), a_in, widths, a_out, C.byref(m)), where)
+        for k, t in zip(group, outs):
+            out[k] = t[:m.value]
+    return out
+
+
+def _mask_u8(mask, n):
+    mask = require_cuda(mask, "mask")
+    if mask.dtype not in (torch.bool, torch.uint8) or mask.shape != (n,):
+        raise ValueError("mask must be a bool {N} tensor")
+    return mask.contiguous().view(torch.uint8)
+
+
+def select_by_mask(attrs, mask, invert=False):
+    """PointCloud::SelectByMask: the rows with mask != invert, in input
+    order. -> (attrs_out, mask)."""
+    _, n = _rows(attrs)
+    m8 = _mask_u8(mask, n)
+    out = _select(
+        attrs, n,
+        lambda k, a, w, o, m: _lib.lib().o3dmi_pointcloud_select_by_mask(
+            n, _lib.ptr(m8), int(bool(invert)), k, a, w, o, m, stream()),
+        "select_by_mask")
+    return out, m8.view(torch.bool)
+
+
+def select_by_index(attrs, indices, invert=False, remove_duplicates=False):
+    """PointCloud::SelectByIndex: a row gather (duplicates repeat), or, with
+    invert / remove_duplicates, index -> mask -> select_by_mask.
+    -> (attrs_out, indices)."""
+    _, n = _rows(attrs)
+    indices = require_cuda(indices, "indices")
+    if indices.dtype != torch.int64 or indices.dim() != 1:
+        raise ValueError("indices must be an Int64 {M} tensor")
+    indices = indices.contiguous()
+    cnt = indices.shape[0]
+    by_mask = bool(invert) or bool(remove_duplicates)
+    out = _select(
+        attrs, n if by_mask else cnt,
+        lambda k, a, w, o, m: _lib.lib().o3dmi_pointcloud_select_by_index(
+            n, _lib.ptr(indices), cnt, int(bool(invert)),
+            int(bool(remove_duplicates)), k, a, w, o, m, stream()),
+        "select_by_index")
+    return out, indices
+
+
+def _filtered(attrs, mask8):
+    out, _ = select_by_mask(attrs, mask8)
+    return out, mask8.view(torch.bool)
+
+
+def remove_non_finite_points(attrs, remove_nan=True, remove_inf=True):
+    """PointCloud::RemoveNonFinitePoints -> (attrs_out, mask)."""
+    p = _positions(attrs)
+    n = p.shape[0]
+    mask = torch.empty(n, dtype=torch.uint8, device=p.device)
+    m = C.c_int64(0)
+    _lib.check(_lib.lib().o3dmi_pointcloud_remove_non_finite_points(
+        _lib.ptr(p), n, TORCH_TO_O3DMI[p.dtype], int(bool(remove_nan)),
+        int(bool(remove_inf)), _lib.ptr(mask), C.byref(m), stream()),
+        "remove_non_finite_points")
+    return _filtered(attrs, mask)
+
+
+def remove_duplicated_points(attrs):
+    """PointCloud::RemoveDuplicatedPoints: points are equal when their bits
+    are; the lowest index of each survives. -> (attrs_out, mask)."""
+    p = _positions(attrs)
+    n = p.shape[0]
+    mask = torch.empty(n, dtype=torch.uint8, device=p.device)
+    m = C.c_int64(0)
+    _lib.check(_lib.lib().o3dmi_pointcloud_remove_duplicated_points(
+        _lib.ptr(p), n, TORCH_TO_O3DMI[p.dtype], _lib.ptr(mask), C.byref(m),
+        stream()), "remove_duplicated_points")
+    return _filtered(attrs, mask)
+
+
+def remove_radius_outliers(attrs, nb_points, search_radius):
+    """PointCloud::RemoveRadiusOutliers: keeps the points with at least
+    nb_points points (themselves included) within search_radius.
+    -> (attrs_out, mask)."""
+    p = _positions(attrs)
+    n = p.shape[0]
+    mask = torch.empty(n, dtype=torch.uint8, device=p.device)
+    m = C.c_int64(0)
+    _lib.check(_lib.lib().o3dmi_pointcloud_remove_radius_outliers(
+        _lib.ptr(p), n, TORCH_TO_O3DMI[p.dtype], int(nb_points),
+        C.c_double(search_radius), _lib.ptr(mask), C.byref(m), stream()),
+        "remove_radius_outliers")
+    return _filtered(attrs, mask)
+
+
+def statistical_outlier_mask(positions, nb_neighbors, std_ratio):
+    """The filter alone: -> (mask uint8 {N}, avg_distances {N}, dict(mean,
+    std, threshold, kept))."""
+    p = _positions({"positions": positions})
+    n = p.shape[0]
+    mask = torch.empty(n, dtype=torch.uint8, device=p.device)
+    avg = torch.empty(n, dtype=p.dtype, device=p.device)
+    stats = (C.c_double * 3)(float("nan"), float("nan"), float("nan"))
+    m = C.c_int64(0)
+    _lib.check(_lib.lib().o3dmi_pointcloud_remove_statistical_outliers(
+        _lib.ptr(p), n, TORCH_TO_O3DMI[p.dtype], int(nb_neighbors),
+        C.c_double(std_ratio), _lib.ptr(mask), _lib.ptr(avg), stats,
+        C.byref(m), stream()), "remove_statistical_outliers")
+    return mask, avg, dict(mean=stats[0], std=stats[1], threshold=stats[2],
+                           kept=m.value)
+
+
+def remove_statistical_outliers(attrs, nb_neighbors, std_ratio,
+                                return_stats=False):
+    """PointCloud::RemoveStatisticalOutliers -> (attrs_out, mask), and with
+    return_stats a dict(mean, std, threshold, kept, avg_distances) as well."""
+    mask, avg, stats = statistical_outlier_mask(_positions(attrs),
+                                                nb_neighbors, std_ratio)
+    out, mask = _filtered(attrs, mask)
+    if return_stats:
+        stats["avg_distances"] = avg
+        return out, mask, stats
+    return out, mask

@@ -561,3 +561,26 @@ def run_slac_optimizer_for_fragments(fragments, pose_graph, params=None,
     out = PoseGraph([P[k].copy() for k in range(P.shape[0])],
                     list(pose_graph.edges))
     return (out, grid, info) if return_info else (out, grid)
+
+
+def preprocess_point_cloud(positions, normals=None, voxel_size=0.05,
+                           apply_outlier_mask=False):
+    """The per-fragment step of PreprocessPointClouds (SLACOptimizer.cpp:
+    47-57): voxel_size > 0: VoxelDownSample -> RemoveStatisticalOutliers(20,
+    2.0) -> EstimateNormals (KNN, 30); otherwise the filter, then
+    EstimateNormals only when `normals` is None. The reference computes the
+    filter and drops its result; apply_outlier_mask=True applies it.
+    -> (positions, normals)."""
+    p = positions.contiguous()
+    assert p.is_cuda and p.dim() == 2 and p.shape[1] == 3
+    nrm = None if normals is None else normals.contiguous()
+    out_p = torch.empty_like(p)
+    out_n = torch.empty_like(p)
+    m = C.c_int64(0)
+    dtype = _lib.F64 if p.dtype == torch.float64 else _lib.F32
+    _lib.check(_lib.lib().o3dmi_slac_preprocess_point_cloud(
+        _lib.ptr(p), _lib.ptr(nrm), p.shape[0], dtype,
+        C.c_double(voxel_size), int(bool(apply_outlier_mask)),
+        _lib.ptr(out_p), _lib.ptr(out_n), C.byref(m), _stream()),
+        "slac_preprocess_point_cloud")
+    return out_p[:m.value], out_n[:m.value]

@@ -587,6 +587,36 @@ int o3dmi_icp_colored_accumulate(
         double scaling_parameter, double shape_parameter, double* sums29_dev,
         o3dmi_stream_t stream);
 
+/* ComputePoseDopplerICPCUDA up to the reduction (TransformationEstimationFor
+ * DopplerICP; host preparation kernel/Registration.cpp:193-303, CPU body
+ * RegistrationCPU.cpp:336-493, Jacobians RegistrationImpl.h:525-643): 29 sums,
+ * [27] = sum r_G^2 + r_D^2, [28] = every pair with a correspondence, pairs
+ * rejected as dynamic outliers included (they add nothing else). dopplers
+ * {N,1} and directions {N,3} (vehicle frame) in the point dtype. The small
+ * vectors are host float64 holding what the dispatcher holds in the point
+ * dtype: R_S_to_V9 (row-major inverse of transform_vehicle_to_sensor's
+ * rotation), r_v_to_s_in_V3, w_v_in_V3, v_v_in_V3; v_s_in_S is formed from them
+ * on the host in the point dtype (PreComputeForDopplerICP). The two robust
+ * kernels and reject_dynamic_outliers are the ones in force at the caller's
+ * iteration. period <= 0 or lambda_doppler outside [0,1]:
+ * O3DMI_ERR_INVALID_ARG. reject_dynamic_outliers with L1Loss on either term:
+ * O3DMI_ERR_UNSUPPORTED (the reference multiplies the infinite weight at r = 0
+ * by the rejected pair's zeroed Jacobian and sums NaN). Every correspondence
+ * is range-checked on the device: an index outside [0, nt) other than -1 is
+ * O3DMI_ERR_INVALID_ARG and sums29_dev keeps its contents. The work is queued
+ * on the stream; the call then waits for the range check's verdict. */
+int o3dmi_icp_doppler_accumulate(
+        const void* src_dev, const void* src_dopplers_dev,
+        const void* src_directions_dev, const void* tgt_dev,
+        const void* tgt_normals_dev, const int64_t* corr_dev, int64_t n,
+        int64_t nt, int dtype, const double* R_S_to_V9,
+        const double* r_v_to_s_in_V3, const double* w_v_in_V3,
+        const double* v_v_in_V3, double period, int reject_dynamic_outliers,
+        double doppler_outlier_threshold, int geometric_kernel,
+        double geometric_scaling, double geometric_shape, int doppler_kernel,
+        double doppler_scaling, double doppler_shape, double lambda_doppler,
+        double* sums29_dev, o3dmi_stream_t stream);
+
 /* ComputeFPFHFeatureCUDA (t/pipelines/kernel/FeatureImpl.h:108-296), the
  * kernel step of ComputeFPFHFeature after the neighbour search. Lists are
  * either padded {n_rows, max_nn} (indices_dev, distance2_dev) with counts_dev
@@ -739,6 +769,10 @@ int o3dmi_transform_normals(const double* transformation, void* normals_dev,
 int o3dmi_decode_and_solve6x6(const double* sums29_host, double* pose6,
                               float* residual, int* inlier_count);
 void o3dmi_pose_to_transformation(const double* pose6, double* T16);
+/* TransformationToPose (TransformationConverterImpl.h:44-60): the Euler
+ * angles of T16's rotation (the sy < 1e-6 branch included) and the translation
+ * of its column 3; the inverse of o3dmi_pose_to_transformation. */
+void o3dmi_transformation_to_pose(const double* T16, double* pose6);
 
 /* ------------------------------------------------------------------------ */
 /* RGB-D odometry front end                        */

@@ -168,7 +168,8 @@ typedef enum {
     O3DMI_ICP_POINT_TO_PLANE = 0,
     O3DMI_ICP_POINT_TO_POINT = 1,
     O3DMI_ICP_SYMMETRIC = 2,
-    O3DMI_ICP_COLORED = 3
+    O3DMI_ICP_COLORED = 3,
+    O3DMI_ICP_DOPPLER = 4 /* o3dmi_registration_multiscale_icp_doppler only */
 } o3dmi_icp_estimation_t;
 
 /* Point attributes beyond positions / target normals that some estimators
@@ -249,12 +250,66 @@ int o3dmi_registration_multiscale_icp_ex(
         int64_t* correspondences_dev, o3dmi_registration_result_t* result,
         o3dmi_stream_t stream);
 
+/* TransformationEstimationForDopplerICP (TransformationEstimation.h:356-500;
+ * Hexsel et al., "DICP: Doppler Iterative Closest Point Algorithm", RSS 2022):
+ * the estimator's parameters and the two source attributes it reads. */
+typedef struct {
+    const void* source_dopplers;   /* device {N,1}, point dtype               */
+    const void* source_directions; /* device {N,3}, point dtype, unit vectors
+                                      of the vehicle frame; carried through
+                                      the pyramid, never rotated             */
+    double transform_vehicle_to_sensor[16]; /* row-major 4x4; all zero =
+                                               identity                      */
+    double period;                 /* default 0.1; <= 0: INVALID_ARG          */
+    double lambda_doppler;         /* default 0.01; outside [0,1] -> 0.01     */
+    int reject_dynamic_outliers;   /* default 0                               */
+    double doppler_outlier_threshold;        /* default 2.0                   */
+    int outlier_rejection_min_iteration;     /* default 2                     */
+    int geometric_robust_loss_min_iteration; /* default 0                     */
+    int doppler_robust_loss_min_iteration;   /* default 2                     */
+    int geometric_kernel;          /* o3dmi robust kernel method, default L2  */
+    double geometric_scaling_parameter, geometric_shape_parameter;
+    int doppler_kernel;
+    double doppler_scaling_parameter, doppler_shape_parameter;
+} o3dmi_icp_doppler_t;
+
+/* MultiScaleICP with TransformationEstimationForDopplerICP: the argument list
+ * of o3dmi_registration_multiscale_icp_ex with `estimation`, `attrs` and the
+ * single robust kernel replaced by `doppler` (o3dmi_registration_multiscale_
+ * icp_ex itself answers O3DMI_ICP_DOPPLER with O3DMI_ERR_INVALID_ARG: it has
+ * nowhere to take these from). Per iteration: search, then one launch that
+ * gathers by correspondence and accumulates the 29 sums
+ * (o3dmi_icp_doppler_accumulate); the host prepares what ComputePoseDopplerICP
+ * (kernel/Registration.cpp:222-265) prepares -- the kernels and the rejection
+ * in force at the iteration index, which restarts at 0 at every scale, and the
+ * vehicle's velocities from TransformationToPose(current transformation) / period
+ * -- in float64, narrowed to the point dtype where the reference narrows.
+ * dopplers and directions are averaged through the VoxelDownSample pyramid like
+ * any attribute (directions are not re-normalised). O3DMI_ERR_INVALID_ARG:
+ * missing target normals, dopplers or directions, period <= 0, a non-finite
+ * transform_vehicle_to_sensor. O3DMI_ERR_UNSUPPORTED: reject_dynamic_outliers
+ * with L1Loss on either term (the reference sums NaN there). Sharding: the two
+ * all-reduce hooks with a caller-sharded source see the 29 sums as for the other
+ * estimators; with level_sharding the driver slices dopplers and directions
+ * with the positions. */
+int o3dmi_registration_multiscale_icp_doppler(
+        const void* source_dev, int64_t ns, const void* target_dev,
+        const void* target_normals_dev, int64_t nt, int dtype, int num_scales,
+        const double* voxel_sizes, const o3dmi_icp_criteria_t* criterias,
+        const double* max_correspondence_distances,
+        const double* init_source_to_target, const o3dmi_icp_doppler_t* doppler,
+        const o3dmi_icp_options_t* options, o3dmi_icp_callback_t callback,
+        void* callback_user, o3dmi_allreduce_sum_t allreduce,
+        void* allreduce_user, int64_t* correspondences_dev,
+        o3dmi_registration_result_t* result, o3dmi_stream_t stream);
+
 /* TransformationEstimation*::ComputeRMSE (TransformationEstimation.cpp:
  * 101-130 point-to-point, 160-193 point-to-plane, 229-274 symmetric, 296-378
  * coloured) on given correspondences (int64, -1 = none). The reference's
  * definitions are kept as they are: point-to-plane squares every component
  * of (s - t) * n; the coloured estimator returns the SUM of squared geometric
- * and photometric residuals, not a root mean. *rmse_out is a host double; the
+ * and photometric residuals, not a root mean; O3DMI_ICP_DOPPLER (:434-467) has
+ * the point-to-plane definition. *rmse_out is a host double; the
  * call synchronises. No correspondence: 0 for the symmetric estimator (as the
  * reference), O3DMI_ERR_NO_INLIERS otherwise (the reference divides by 0). */
 int o3dmi_registration_compute_rmse(

@@ -426,6 +426,64 @@ static_assert(std::is_same<decltype(&ComputePosePointToPlaneHIP),
               "ComputePosePointToPlaneHIP has the dispatcher's per-device "
               "signature");
 
+
+// beside ComputePoseDopplerICPCUDA (RegistrationImpl.h:69-90,
+// RegistrationCUDA.cu): the small tensors the dispatcher prepared in the point
+// dtype go over as host float64
+void ComputePoseDopplerICPHIP(const core::Tensor& source_points,
+                              const core::Tensor& source_dopplers,
+                              const core::Tensor& source_directions,
+                              const core::Tensor& target_points,
+                              const core::Tensor& target_normals,
+                              const core::Tensor& correspondence_indices,
+                              core::Tensor& output_pose,
+                              float& residual,
+                              int& inlier_count,
+                              const core::Dtype& dtype,
+                              const core::Device& device,
+                              const core::Tensor& R_S_to_V,
+                              const core::Tensor& r_v_to_s_in_V,
+                              const core::Tensor& w_v_in_V,
+                              const core::Tensor& v_v_in_V,
+                              const double period,
+                              const bool reject_dynamic_outliers,
+                              const double doppler_outlier_threshold,
+                              const registration::RobustKernel& kernel_geometric,
+                              const registration::RobustKernel& kernel_doppler,
+                              const double lambda_doppler) {
+    const core::Device cpu("CPU:0");
+    const core::Tensor R = R_S_to_V.To(cpu, core::Float64).Contiguous();
+    const core::Tensor r = r_v_to_s_in_V.To(cpu, core::Float64).Contiguous();
+    const core::Tensor w = w_v_in_V.To(cpu, core::Float64).Contiguous();
+    const core::Tensor v = v_v_in_V.To(cpu, core::Float64).Contiguous();
+    core::Tensor sums = core::Tensor::Empty({29}, core::Float64, device);
+    O3DMI_CALL(o3dmi_icp_doppler_accumulate(
+            source_points.Contiguous().GetDataPtr(),
+            source_dopplers.Contiguous().GetDataPtr(),
+            source_directions.Contiguous().GetDataPtr(),
+            target_points.Contiguous().GetDataPtr(),
+            target_normals.Contiguous().GetDataPtr(),
+            correspondence_indices.Contiguous().GetDataPtr<int64_t>(),
+            source_points.GetLength(), target_points.GetLength(),
+            core::ToO3dmi(dtype), R.GetDataPtr<double>(),
+            r.GetDataPtr<double>(), w.GetDataPtr<double>(),
+            v.GetDataPtr<double>(), period, reject_dynamic_outliers ? 1 : 0,
+            doppler_outlier_threshold, (int)kernel_geometric.type_,
+            kernel_geometric.scaling_parameter_,
+            kernel_geometric.shape_parameter_, (int)kernel_doppler.type_,
+            kernel_doppler.scaling_parameter_, kernel_doppler.shape_parameter_,
+            lambda_doppler, sums.GetDataPtr<double>(), core::HipStream()));
+    const core::Tensor host = sums.To(cpu);
+    output_pose = core::Tensor::Empty({6}, core::Float64, cpu);
+    O3DMI_CALL(o3dmi_decode_and_solve6x6(host.GetDataPtr<double>(),
+                                         output_pose.GetDataPtr<double>(),
+                                         &residual, &inlier_count));
+}
+static_assert(std::is_same<decltype(&ComputePoseDopplerICPHIP),
+                           decltype(&ComputePoseDopplerICPCPU)>::value,
+              "ComputePoseDopplerICPHIP has the dispatcher's per-device "
+              "signature");
+
 }  // namespace kernel
 }  // namespace pipelines
 }  // namespace t

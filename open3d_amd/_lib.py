@@ -103,6 +103,7 @@ PROTOTYPES = {
     "o3dmi_decode_and_solve6x6": (_i32, [_dp, _dp, C.POINTER(_f),
                                          C.POINTER(_i32)]),
     "o3dmi_pose_to_transformation": (None, [_dp, _dp]),
+    "o3dmi_transformation_to_pose": (None, [_dp, _dp]),
     "o3dmi_vbg_extract_points": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i32,
                                         _i32, _f, _f, _vp, _vp, _vp, _i64,
                                         C.POINTER(_i64), _vp]),
@@ -190,7 +191,30 @@ class IcpOptions(C.Structure):
                 ("device_allreduce_user", _vp), ("level_sharding", _i32)]
 
 
+class IcpDoppler(C.Structure):
+    _fields_ = [("source_dopplers", _vp), ("source_directions", _vp),
+                ("transform_vehicle_to_sensor", _d * 16), ("period", _d),
+                ("lambda_doppler", _d), ("reject_dynamic_outliers", _i32),
+                ("doppler_outlier_threshold", _d),
+                ("outlier_rejection_min_iteration", _i32),
+                ("geometric_robust_loss_min_iteration", _i32),
+                ("doppler_robust_loss_min_iteration", _i32),
+                ("geometric_kernel", _i32),
+                ("geometric_scaling_parameter", _d),
+                ("geometric_shape_parameter", _d), ("doppler_kernel", _i32),
+                ("doppler_scaling_parameter", _d),
+                ("doppler_shape_parameter", _d)]
+
+
 PROTOTYPES.update({
+    "o3dmi_registration_multiscale_icp_doppler": (
+        _i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _dp,
+               C.POINTER(IcpCriteria), _dp, _dp, C.POINTER(IcpDoppler),
+               C.POINTER(IcpOptions), ICP_CALLBACK, _vp, ALLREDUCE_SUM, _vp,
+               _vp, C.POINTER(RegistrationResultC), _vp]),
+    "o3dmi_icp_doppler_accumulate": (
+        _i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _dp, _dp, _dp,
+               _dp, _d, _i32, _d, _i32, _d, _d, _i32, _d, _d, _d, _vp, _vp]),
     "o3dmi_registration_multiscale_icp": (
         _i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _dp,
                C.POINTER(IcpCriteria), _dp, _dp, _i32, _d, _d, ICP_CALLBACK,

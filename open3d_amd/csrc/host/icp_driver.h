@@ -25,14 +25,17 @@ struct IcpCall {
     o3dmi_stream_t stream() const { return (o3dmi_stream_t)s; }
     hipEvent_t ev = nullptr;
 
-    // estimator (none of the three: point-to-point)
-    bool p2plane = false, symmetric = false, colored = false;
+    // estimator (none of the four: point-to-point)
+    bool p2plane = false, symmetric = false, colored = false, doppler = false;
 
     // clouds and attributes (NULL: the estimator does not read it)
     const void *source = nullptr, *source_normals = nullptr,
                *source_colors = nullptr;
     const void *target = nullptr, *target_normals = nullptr,
                *target_colors = nullptr, *target_gradients = nullptr;
+    // Doppler ICP: directions {n,3}; dopplers as column 0 of an {n,3} buffer
+    // of the driver (the pyramid's levels take {n,3} attributes)
+    const void *source_directions = nullptr, *source_dopplers3 = nullptr;
     int64_t ns = 0, nt = 0;
     // sizes that live on the device (o3dmi_icp_options_t)
     const int32_t *ns_dev = nullptr, *nt_dev = nullptr;
@@ -43,6 +46,11 @@ struct IcpCall {
     bool finest_is_input = false;  // voxel_sizes[last] <= 0
 
     double lambda_geometric = 0.968;  // (clamped)
+    // TransformationEstimationForDopplerICP's parameters (lambda_doppler
+    // clamped), and from its transform_vehicle_to_sensor, in float64: the
+    // inverse of the rotation and the translation
+    o3dmi_icp_doppler_t dop = {};
+    double R_S_to_V[9] = {}, r_v_to_s_in_V[3] = {};
     int robust_kernel = 0;
     double scaling_parameter = 1.0, shape_parameter = 1.0;
 
@@ -58,10 +66,14 @@ struct IcpCall {
     bool level_sharding = false;
 };
 
-// One cloud at one pyramid level: positions and up to three {n,3} attributes.
-// Source: normals (symmetric), colours (coloured); target: normals, colours,
-// colour gradients.
-enum { kNormals = 0, kColors = 1, kGradients = 2, kCloudAttrs = 3 };
+// One cloud at one pyramid level: positions and its {n,3} attributes.
+// Source: normals (symmetric), colours (coloured), directions and dopplers
+// (Doppler; the dopplers in column 0); target: normals, colours, colour
+// gradients.
+enum {
+    kNormals = 0, kColors = 1, kGradients = 2, kDirections = 3, kDopplers = 4,
+    kCloudAttrs = 5
+};
 struct CloudLevel {
     DeviceBuffer pos_buf, attr_buf[kCloudAttrs];
     const void* pos = nullptr;  // may alias the caller's buffers (target)

@@ -328,6 +328,7 @@ int BuildLevel(const IcpCall& c, CloudChain& ch, std::vector<Level>& pyr, int k,
         const CloudLevel* F =
                 k == last ? nullptr : &(pyr[(size_t)k + 1].*ch.which);
         const void* const* in_attr = F ? F->attr : ch.attr;
+        static_assert(kCloudAttrs == 5, "the attribute passes listed below");
         if ((e = L.pos_buf.Alloc((size_t)ch.n * 3 * c.esz))) return e;
         for (int a = 0; a < kCloudAttrs; ++a)
             if (in_attr[a] &&
@@ -343,7 +344,9 @@ int BuildLevel(const IcpCall& c, CloudChain& ch, std::vector<Level>& pyr, int k,
                 cc.scratch, ch.cs, ch.id,
                 {{in_attr[0], L.attr_buf[0].p},
                  {in_attr[1], L.attr_buf[1].p},
-                 {in_attr[2], L.attr_buf[2].p}},
+                 {in_attr[2], L.attr_buf[2].p},
+                 {in_attr[3], L.attr_buf[3].p},
+                 {in_attr[4], L.attr_buf[4].p}},
                 next_vs, F && !f_host, job);
         if (e) return e;
         L.pos = L.pos_buf.p;
@@ -431,14 +434,17 @@ int BuildPyramids(const IcpCall& c, std::vector<Level>& pyr,
     // -- 7 launches + one posting launch for a three-level pair of
     // pyramids instead of two chains of 8 on two streams (the source chain on
     // the caller's stream, the target chain on the side stream). Coloured ICP
-    // (three attribute passes per target level) keeps the two chains.
+    // (three attribute passes per target level) and Doppler ICP (two per
+    // source level) keep the two chains.
     static const bool unpaired = std::getenv("O3DMI_VDS_UNPAIRED") != nullptr;
-    const bool paired = !c.colored && !unpaired;
+    const bool paired = !c.colored && !c.doppler && !unpaired;
     hipStream_t ts = paired ? c.s : c.side;
     // (declared in this order: the target chain's scratch is released first)
     CloudChain src(c, c.source, c.ns, c.ns_dev, 0, c.s, &Level::source);
     src.attr[kNormals] = c.source_normals;
     src.attr[kColors] = c.source_colors;
+    src.attr[kDirections] = c.source_directions;
+    src.attr[kDopplers] = c.source_dopplers3;
     src.clone_input = true;
     CloudChain tgt(c, c.target, c.nt, c.nt_dev, 1, ts, &Level::target);
     tgt.attr[kNormals] = c.target_normals;

@@ -24,8 +24,9 @@
 // Other estimators (o3dmi_registration_multiscale_icp_ex): the same fused
 // search launch in its point-to-point form (correspondences + raw moments),
 // then per estimator: point-to-point -> R, t from the moments on the host;
-// symmetric / coloured -> a second launch that gathers by correspondence and
-// accumulates their 29 sums (two mailbox waits per iteration).
+// symmetric / coloured / Doppler -> a second launch that gathers by
+// correspondence and accumulates their 29 sums (two mailbox waits per
+// iteration).
 //
 // This file: the entry point, which resolves its arguments (the options
 // struct among them) and the thread's communicator into an IcpCall
@@ -300,6 +301,10 @@ const double kKeep = std::nan("");
 // it; the scale's scratch of the estimators with a second launch.
 struct ScaleView {
     void *src = nullptr, *srcn = nullptr, *srcc = nullptr;
+    // Doppler: directions {ns,3}, the padded dopplers' slice and their
+    // {ns,1} form (the scale's scratch); the range check's device word
+    void *srcdir = nullptr, *srcdop3 = nullptr, *srcdop = nullptr;
+    int* bad = nullptr;
     int64_t ns = 0, first = 0, nt = 0;
     const void *tgt = nullptr, *nrm = nullptr, *tgtc = nullptr,
                *tgtg = nullptr;
@@ -321,6 +326,8 @@ void ViewOf(const IcpCall& c, const Level& L, ScaleView& v) {
     v.src = at(S.pos_buf.p);
     v.srcn = at(S.attr_buf[kNormals].p);
     v.srcc = at(S.attr_buf[kColors].p);
+    v.srcdir = at(S.attr_buf[kDirections].p);
+    v.srcdop3 = at(S.attr_buf[kDopplers].p);
     v.ns = e - b;
     v.first = b;
     v.tgt = L.target.pos;
@@ -380,16 +387,67 @@ int Search(const IcpCall& c, SumsFetcher& sums, o3dmi_nns_t* nns,
     return O3DMI_OK;
 }
 
+// What ComputePoseDopplerICP (kernel/Registration.cpp:222-265) prepares on the
+// host for iteration `iteration` of a scale with the cumulative transformation
+// `current`: the kernels and the rejection in force, and the vehicle's angular
+// and linear velocity from TransformationToPose(current) -- the pose in
+// float64, cast to the point dtype, negated and divided by the period there
+// (Tensor::Div(Scalar) casts the scalar to the tensor's dtype first).
+int DopplerSums(const IcpCall& c, SumsFetcher& sums, const ScaleView& L,
+                const double* current, int iteration, double* out32) {
+    const o3dmi_icp_doppler_t& d = c.dop;
+    const bool robust_g = iteration >= d.geometric_robust_loss_min_iteration;
+    const bool robust_d = iteration >= d.doppler_robust_loss_min_iteration;
+    const int reject = d.reject_dynamic_outliers &&
+                       iteration >= d.outlier_rejection_min_iteration;
+    double state[6], w_v_in_V[3], v_v_in_V[3];
+    o3dmi_transformation_to_pose(current, state);
+    for (int k = 0; k < 3; ++k) {
+        if (c.dtype == O3DMI_F32) {
+            const float period = (float)d.period;
+            w_v_in_V[k] = (double)(-(float)state[k] / period);
+            v_v_in_V[k] = (double)(-(float)state[3 + k] / period);
+        } else {
+            w_v_in_V[k] = -state[k] / d.period;
+            v_v_in_V[k] = -state[3 + k] / d.period;
+        }
+    }
+    int e = sums.Fetch(
+            [&](double* sums_dev, double* mail_data, int* mail_flag, int seq) {
+                return o3dmi_icp_doppler_accumulate_post(
+                        L.src, L.srcdop, L.srcdir, L.tgt, L.nrm, L.corr, L.ns,
+                        L.nt, c.dtype, c.R_S_to_V, c.r_v_to_s_in_V, w_v_in_V,
+                        v_v_in_V, d.period, reject, d.doppler_outlier_threshold,
+                        robust_g ? d.geometric_kernel : O3DMI_L2_LOSS,
+                        robust_g ? d.geometric_scaling_parameter : 1.0,
+                        robust_g ? d.geometric_shape_parameter : 1.0,
+                        robust_d ? d.doppler_kernel : O3DMI_L2_LOSS,
+                        robust_d ? d.doppler_scaling_parameter : 1.0,
+                        robust_d ? d.doppler_shape_parameter : 1.0,
+                        d.lambda_doppler, sums_dev, L.partials, L.bad,
+                        mail_data, mail_flag, seq, c.stream());
+            },
+            out32, 0.0, 0.0, 0.0);
+    if (e) return e;
+    // (the checked final pass posts NaN for an index outside the target)
+    O3DMI_REQUIRE(out32[28] == out32[28],
+                  "correspondence index out of range");
+    return O3DMI_OK;
+}
+
 // One iteration's update from its search: estimation.ComputeTransformation,
 // Registration.cpp:314. Point-to-point: R, t from the search pass' moments.
 // The others: 29 sums (point-to-plane: of the search pass; symmetric /
-// coloured: of a second launch that gathers by correspondence), the 6x6
+// coloured / Doppler: of a second launch that gathers by correspondence), the 6x6
 // solve, pose -> transformation. *solve_status: a failed solve (the reference
 // throws; the driver reports it after the loop); a returned error ends the
 // call at once.
+// `current`, `iteration`: the cumulative transformation before this update and
+// the iteration's index within its scale (read by the Doppler estimator only).
 int ComputeUpdate(const IcpCall& c, SumsFetcher& sums, const ScaleView& L,
-                  const SearchResult& r, double* update, int* solve_status) {
-    if (!c.p2plane && !c.symmetric && !c.colored) {
+                  const SearchResult& r, const double* current, int iteration,
+                  double* update, int* solve_status) {
+    if (!c.p2plane && !c.symmetric && !c.colored && !c.doppler) {
         // ComputeRtPointToPoint + RtToTransformation
         // (TransformationEstimation.cpp:150-159)
         double R[9], t[3];
@@ -445,6 +503,12 @@ int ComputeUpdate(const IcpCall& c, SumsFetcher& sums, const ScaleView& L,
                 gathered, 0.0, 0.0, 0.0);
         if (e) return e;
         sums29 = gathered;
+    } else if (c.doppler) {
+        // ComputePoseDopplerICP + PoseToTransformation
+        // (TransformationEstimation.cpp:469-519)
+        int e = DopplerSums(c, sums, L, current, iteration, gathered);
+        if (e) return e;
+        sums29 = gathered;
     }
     double pose[6];
     float residual;
@@ -496,7 +560,8 @@ int RunScaleIterations(const IcpCall& c, SumsFetcher& sums, NnsGuard& guard,
         if (r.sums[30] == 0) Eye4(st.T);  // Registration.cpp:56-58
         if (st.fitness <= std::numeric_limits<double>::min()) break;
         double update[16];
-        if ((e = ComputeUpdate(c, sums, L, r, update, &st.status))) return e;
+        if ((e = ComputeUpdate(c, sums, L, r, st.T, it, update, &st.status)))
+            return e;
         Matmul4(update, st.T, st.T);
         // source.Transform(update): rides in the next search launch of
         // this scale (a scale that ends here has no further use for its
@@ -549,8 +614,21 @@ int RunIcp(const IcpCall& c, IcpTimer& timer, std::vector<Level>& pyr,
         if (c.symmetric && (e = o3dmi_transform_normals(st.T, L.srcn, L.ns,
                                                         c.dtype, c.stream())))
             return e;
-        DeviceBuffer corr_buf, sym_partials;
-        if (c.symmetric || c.colored) {
+        DeviceBuffer corr_buf, sym_partials, doppler_buf;
+        if (c.doppler) {
+            // the level's dopplers as {ns,1}, and the range check's word
+            // behind them
+            const size_t bytes = (size_t)L.ns * c.esz;
+            const size_t word = (bytes + 7) / 8 * 8;
+            if ((e = doppler_buf.Alloc(word + sizeof(int)))) return e;
+            L.srcdop = doppler_buf.p;
+            L.bad = (int*)((char*)doppler_buf.p + word);
+            O3DMI_HIP_CHECK(hipMemsetAsync(L.bad, 0, sizeof(int), c.s));
+            if ((e = o3dmi_internal_take_column(L.srcdop3, L.ns, c.dtype,
+                                                L.srcdop, c.stream())))
+                return e;
+        }
+        if (c.symmetric || c.colored || c.doppler) {
             if ((e = corr_buf.Alloc(sizeof(int64_t) * (size_t)L.ns))) return e;
             if ((e = sym_partials.Alloc(sizeof(double) * 32 * 1024)))
                 return e;
@@ -628,13 +706,76 @@ extern "C" int o3dmi_registration_multiscale_icp(
             allreduce, allreduce_user, correspondences_dev, result, stream);
 }
 
-extern "C" int o3dmi_registration_multiscale_icp_ex(
+namespace {
+
+// TransformationEstimationForDopplerICP's constructor and argument checks
+// (TransformationEstimation.h:356-500, TransformationEstimation.cpp:469-499)
+// and what ComputePoseDopplerICP takes from transform_vehicle_to_sensor.
+int ResolveDoppler(IcpCall& c, const o3dmi_icp_doppler_t* doppler) {
+    O3DMI_REQUIRE(doppler != nullptr, "doppler is null");
+    c.dop = *doppler;
+    o3dmi_icp_doppler_t& d = c.dop;
+    O3DMI_REQUIRE(d.source_dopplers != nullptr,
+                  "DopplerICP requires source pointcloud to have Doppler "
+                  "velocities.");
+    O3DMI_REQUIRE(d.source_directions != nullptr,
+                  "DopplerICP requires source pointcloud to have pre-computed "
+                  "direction vectors.");
+    O3DMI_REQUIRE(d.period > 0, "period must be positive");
+    if (!(d.lambda_doppler >= 0 && d.lambda_doppler <= 1.0))
+        d.lambda_doppler = 0.01;
+    O3DMI_REQUIRE(d.geometric_kernel >= 0 && d.geometric_kernel <= 6 &&
+                          d.doppler_kernel >= 0 && d.doppler_kernel <= 6,
+                  "Unsupported method.");
+    if (d.reject_dynamic_outliers && (d.geometric_kernel == O3DMI_L1_LOSS ||
+                                      d.doppler_kernel == O3DMI_L1_LOSS)) {
+        SetLastError(
+                "Doppler ICP: dynamic outlier rejection with an L1Loss kernel "
+                "is not supported");
+        return O3DMI_ERR_UNSUPPORTED;
+    }
+    double* V = d.transform_vehicle_to_sensor;
+    bool all_zero = true;
+    for (int k = 0; k < 16; ++k) {
+        O3DMI_REQUIRE(std::isfinite(V[k]),
+                      "transform_vehicle_to_sensor is not finite");
+        all_zero = all_zero && V[k] == 0;
+    }
+    if (all_zero) Eye4(V);
+    // R_S_to_V = inverse of the rotation block, float64 (cofactors over the
+    // determinant; the reference calls LAPACK getrf + getri)
+    const double a = V[0], b = V[1], cc = V[2], dd = V[4], ee = V[5], f = V[6],
+                 g = V[8], h = V[9], i = V[10];
+    const double det = a * (ee * i - f * h) - b * (dd * i - f * g) +
+                       cc * (dd * h - ee * g);
+    O3DMI_REQUIRE(det != 0 && std::isfinite(1.0 / det),
+                  "transform_vehicle_to_sensor has a singular rotation");
+    double* R = c.R_S_to_V;
+    R[0] = (ee * i - f * h) / det;
+    R[1] = (cc * h - b * i) / det;
+    R[2] = (b * f - cc * ee) / det;
+    R[3] = (f * g - dd * i) / det;
+    R[4] = (a * i - cc * g) / det;
+    R[5] = (cc * dd - a * f) / det;
+    R[6] = (dd * h - ee * g) / det;
+    R[7] = (b * g - a * h) / det;
+    R[8] = (a * ee - b * dd) / det;
+    c.r_v_to_s_in_V[0] = V[3];
+    c.r_v_to_s_in_V[1] = V[7];
+    c.r_v_to_s_in_V[2] = V[11];
+    c.source_directions = d.source_directions;
+    return O3DMI_OK;
+}
+
+// Both entry points: `doppler` != NULL is O3DMI_ICP_DOPPLER.
+int MultiScaleIcpEntry(
         const void* source_dev, int64_t ns, const void* target_dev,
         const void* target_normals_dev, int64_t nt, int dtype, int num_scales,
         const double* voxel_sizes, const o3dmi_icp_criteria_t* criterias,
         const double* max_dists, const double* init, int estimation,
-        const o3dmi_icp_attributes_t* attrs, const o3dmi_icp_options_t* options,
-        int robust_kernel, double scaling_parameter, double shape_parameter,
+        const o3dmi_icp_attributes_t* attrs, const o3dmi_icp_doppler_t* doppler,
+        const o3dmi_icp_options_t* options, int robust_kernel,
+        double scaling_parameter, double shape_parameter,
         o3dmi_icp_callback_t callback, void* callback_user,
         o3dmi_allreduce_sum_t allreduce, void* allreduce_user,
         int64_t* correspondences_dev, o3dmi_registration_result_t* result,
@@ -656,14 +797,11 @@ extern "C" int o3dmi_registration_multiscale_icp_ex(
                   "Only Float32 and Float64 point clouds are supported.");
     O3DMI_REQUIRE(source_dev && target_dev && ns > 0 && nt > 0,
                   "Source and/or Target pointcloud is empty.");
-    O3DMI_REQUIRE(estimation >= O3DMI_ICP_POINT_TO_PLANE &&
-                          estimation <= O3DMI_ICP_COLORED,
-                  "estimation must be point-to-plane, point-to-point, "
-                  "symmetric or colored");
     c.p2plane = estimation == O3DMI_ICP_POINT_TO_PLANE;
     c.symmetric = estimation == O3DMI_ICP_SYMMETRIC;
     c.colored = estimation == O3DMI_ICP_COLORED;
-    const bool need_tn = c.p2plane || c.symmetric || c.colored;
+    c.doppler = estimation == O3DMI_ICP_DOPPLER;
+    const bool need_tn = c.p2plane || c.symmetric || c.colored || c.doppler;
     c.source = source_dev;
     c.target = target_dev;
     c.target_normals = need_tn ? target_normals_dev : nullptr;
@@ -680,6 +818,12 @@ extern "C" int o3dmi_registration_multiscale_icp_ex(
         c.lambda_geometric = 0.968;
     O3DMI_REQUIRE(!(c.p2plane || c.colored) || c.target_normals != nullptr,
                   "Target pointcloud missing normals attribute.");
+    O3DMI_REQUIRE(!c.doppler || c.target_normals != nullptr,
+                  "DopplerICP requires target pointcloud to have normals.");
+    if (c.doppler) {
+        int e = ResolveDoppler(c, doppler);
+        if (e) return e;
+    }
     O3DMI_REQUIRE(!c.symmetric || (c.source_normals && c.target_normals),
                   "SymmetricICP requires both source and target to have "
                   "normals.");
@@ -715,12 +859,66 @@ extern "C" int o3dmi_registration_multiscale_icp_ex(
     c.allreduce_user = allreduce_user;
     IcpTimer timer(c.s);  // (declared first: destroyed last)
     std::vector<Level> pyr((size_t)num_scales);
+    DeviceBuffer dopplers3;  // the caller's {ns,1} dopplers as column 0 of {ns,3}
     // Declared after the pyramid so that it runs first on every exit path.
     SyncOnExit sync_on_exit{c.s};
     std::vector<NnsGuard> guards((size_t)num_scales);
     int st = ResolveSizesAndStreams(c);
     sync_on_exit.side = c.side;
     if (st) return st;
+    if (c.doppler) {
+        if ((st = dopplers3.Alloc((size_t)c.ns * 3 * c.esz))) return st;
+        if ((st = o3dmi_internal_pad_column(c.dop.source_dopplers, c.ns,
+                                            c.dtype, dopplers3.p, c.stream())))
+            return st;
+        c.source_dopplers3 = dopplers3.p;
+    }
     return RunIcp(c, timer, pyr, sync_on_exit, guards, init,
                   correspondences_dev, result);
+}
+
+}  // namespace
+
+extern "C" int o3dmi_registration_multiscale_icp_ex(
+        const void* source_dev, int64_t ns, const void* target_dev,
+        const void* target_normals_dev, int64_t nt, int dtype, int num_scales,
+        const double* voxel_sizes, const o3dmi_icp_criteria_t* criterias,
+        const double* max_dists, const double* init, int estimation,
+        const o3dmi_icp_attributes_t* attrs, const o3dmi_icp_options_t* options,
+        int robust_kernel, double scaling_parameter, double shape_parameter,
+        o3dmi_icp_callback_t callback, void* callback_user,
+        o3dmi_allreduce_sum_t allreduce, void* allreduce_user,
+        int64_t* correspondences_dev, o3dmi_registration_result_t* result,
+        o3dmi_stream_t stream) {
+    // (Doppler ICP's parameters travel in o3dmi_icp_doppler_t:
+    // o3dmi_registration_multiscale_icp_doppler)
+    O3DMI_REQUIRE(estimation >= O3DMI_ICP_POINT_TO_PLANE &&
+                          estimation <= O3DMI_ICP_COLORED,
+                  "estimation must be point-to-plane, point-to-point, "
+                  "symmetric or colored");
+    return MultiScaleIcpEntry(
+            source_dev, ns, target_dev, target_normals_dev, nt, dtype,
+            num_scales, voxel_sizes, criterias, max_dists, init, estimation,
+            attrs, nullptr, options, robust_kernel, scaling_parameter,
+            shape_parameter, callback, callback_user, allreduce,
+            allreduce_user, correspondences_dev, result, stream);
+}
+
+extern "C" int o3dmi_registration_multiscale_icp_doppler(
+        const void* source_dev, int64_t ns, const void* target_dev,
+        const void* target_normals_dev, int64_t nt, int dtype, int num_scales,
+        const double* voxel_sizes, const o3dmi_icp_criteria_t* criterias,
+        const double* max_dists, const double* init,
+        const o3dmi_icp_doppler_t* doppler, const o3dmi_icp_options_t* options,
+        o3dmi_icp_callback_t callback, void* callback_user,
+        o3dmi_allreduce_sum_t allreduce, void* allreduce_user,
+        int64_t* correspondences_dev, o3dmi_registration_result_t* result,
+        o3dmi_stream_t stream) {
+    O3DMI_REQUIRE(doppler != nullptr, "doppler is null");
+    return MultiScaleIcpEntry(
+            source_dev, ns, target_dev, target_normals_dev, nt, dtype,
+            num_scales, voxel_sizes, criterias, max_dists, init,
+            O3DMI_ICP_DOPPLER, nullptr, doppler, options, O3DMI_L2_LOSS, 1.0,
+            1.0, callback, callback_user, allreduce, allreduce_user,
+            correspondences_dev, result, stream);
 }

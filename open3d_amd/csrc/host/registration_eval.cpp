@@ -122,7 +122,7 @@ extern "C" int o3dmi_registration_compute_rmse(
     O3DMI_REQUIRE(source_dev && target_dev && ns > 0 && correspondences_dev,
                   "Source and/or Target pointcloud is empty.");
     O3DMI_REQUIRE(estimation >= O3DMI_ICP_POINT_TO_PLANE &&
-                          estimation <= O3DMI_ICP_COLORED,
+                          estimation <= O3DMI_ICP_DOPPLER,
                   "unknown estimation");
     hipStream_t s = (hipStream_t)stream;
     DeviceBuffer sums;
@@ -133,6 +133,9 @@ extern "C" int o3dmi_registration_compute_rmse(
     const double zero3[3] = {0, 0, 0};
     switch (estimation) {
         case O3DMI_ICP_POINT_TO_PLANE:
+        // TransformationEstimationForDopplerICP::ComputeRMSE
+        // (TransformationEstimation.cpp:434-467) is the point-to-plane one
+        case O3DMI_ICP_DOPPLER:
             O3DMI_REQUIRE(target_normals_dev,
                           "Target pointcloud missing normals attribute.");
             st = o3dmi_icp_residual_squares(source_dev, target_dev,
@@ -175,7 +178,8 @@ extern "C" int o3dmi_registration_compute_rmse(
     }
     if (st) return st;
     const int n_read = (estimation == O3DMI_ICP_POINT_TO_PLANE ||
-                        estimation == O3DMI_ICP_POINT_TO_POINT)
+                        estimation == O3DMI_ICP_POINT_TO_POINT ||
+                        estimation == O3DMI_ICP_DOPPLER)
                                ? 2
                                : 29;
     O3DMI_HIP_CHECK(hipMemcpyAsync(h, sums.p, sizeof(double) * n_read,

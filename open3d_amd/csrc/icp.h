@@ -45,6 +45,29 @@ int o3dmi_icp_symmetric_accumulate_post(
         double* sums29_dev, double* partials_dev, double* mail_data,
         int* mail_flag, int mail_seq, o3dmi_stream_t stream);
 
+// o3dmi_icp_doppler_accumulate without its wait: bad_dev is the caller's
+// zeroed device word, raised by a correspondence index outside [0, nt); the
+// sums are then not written (sums29_dev) or posted as NaN (mailbox).
+int o3dmi_icp_doppler_accumulate_post(
+        const void* src_dev, const void* src_dopplers_dev,
+        const void* src_directions_dev, const void* tgt_dev,
+        const void* tgt_normals_dev, const int64_t* corr_dev, int64_t n,
+        int64_t nt, int dtype, const double* R_S_to_V9,
+        const double* r_v_to_s_in_V3, const double* w_v_in_V3,
+        const double* v_v_in_V3, double period, int reject_dynamic_outliers,
+        double doppler_outlier_threshold, int geometric_kernel,
+        double geometric_scaling, double geometric_shape, int doppler_kernel,
+        double doppler_scaling, double doppler_shape, double lambda_doppler,
+        double* sums29_dev, double* partials_dev, int* bad_dev,
+        double* mail_data, int* mail_flag, int mail_seq, o3dmi_stream_t stream);
+
+// {n,1} -> column 0 of {n,3} (columns 1, 2 zero), and column 0 back: a
+// 1-column attribute through the {n,3} VoxelDownSample levels of the pyramid.
+int o3dmi_internal_pad_column(const void* in_dev, int64_t n, int dtype,
+                              void* out3_dev, o3dmi_stream_t stream);
+int o3dmi_internal_take_column(const void* in3_dev, int64_t n, int dtype,
+                               void* out_dev, o3dmi_stream_t stream);
+
 // sums32_dev[29..31] = {t29, t30, t31}; the 32 sums to a host mailbox.
 int o3dmi_internal_sums_tail(double* sums32_dev, double t29, double t30,
                              double t31, o3dmi_stream_t stream);

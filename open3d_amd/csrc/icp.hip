@@ -2,14 +2,14 @@
 //
 //   o3dmi_icp_p2plane_accumulate  <- ComputePosePointToPlaneCUDA (t/pipelines/kernel/
 //                                    RegistrationCUDA.cu:29-117, RegistrationImpl.h:251-287)
-//   o3dmi_icp_{p2point,symmetric,colored,information}_accumulate
+//   o3dmi_icp_{p2point,symmetric,colored,doppler,information}_accumulate
 //                                 <- the other reductions of RegistrationCUDA.cu /
-//                                    RegistrationCPU.cpp:124-340,495-735
+//                                    RegistrationCPU.cpp:124-493,495-735
 //   o3dmi_icp_search_accumulate   fused search + fitness/rmse sums + accumulation
 //   o3dmi_transform_points/normals<- TransformPointsCUDA/TransformNormalsCUDA
 //                                    (t/geometry/kernel/TransformImpl.h:19-60)
 //   o3dmi_decode_and_solve6x6, o3dmi_pose_to_transformation,
-//   o3dmi_compute_rt_p2point, o3dmi_symmetric_pose_to_transformation (host)
+//   o3dmi_transformation_to_pose, o3dmi_compute_rt_p2point, o3dmi_symmetric_pose_to_transformation (host)
 //                                 <- TransformationConverter.cpp:81-133,189-226,
 //                                    RegistrationCPU.cpp:640-650
 //
@@ -299,6 +299,83 @@ __device__ __forceinline__ void AccumulateColored(
     A[28] += 1.0;
 }
 
+// GetJacobianDopplerICP + the 29 sums of ComputePoseDopplerICPKernelCPU
+// (RegistrationImpl.h:555-643, RegistrationCPU.cpp:336-414; Hexsel et al.,
+// "DICP", RSS 2022): a point-to-plane row and a Doppler row per pair, each
+// with its own robust kernel. The source's direction is a vector of the
+// VEHICLE frame (never rotated by the iteration updates); R_S_to_V, the lever
+// arm r_v_to_s_in_V and the sensor velocity v_s_in_S come by value.
+// A[27] = sum r_G^2 + r_D^2. A pair rejected as a dynamic outlier counts in
+// A[28] and adds nothing else (the reference adds its zeroed rows).
+template <typename T>
+struct DopplerParams {
+    T R_S_to_V[9], r_v_to_s_in_V[3], v_s_in_S[3];
+    T doppler_outlier_threshold;
+    T sqrt_lambda_geometric, sqrt_lambda_doppler, sqrt_lambda_doppler_by_dt;
+    int reject_dynamic_outliers;
+};
+
+template <typename T>
+__device__ __forceinline__ void AccumulateDoppler(
+        double (&A)[kNumSums], const T* ps, T doppler_in_S, const T* ds_in_V,
+        const T* pt, const T* nt, const DopplerParams<T>& dp,
+        const RobustParams& rp_geometric, const RobustParams& rp_doppler) {
+    const T* R = dp.R_S_to_V;
+    const T* r = dp.r_v_to_s_in_V;
+    // predicted Doppler velocity in the sensor frame
+    T ds_in_S[3];
+    ds_in_S[0] = R[0] * ds_in_V[0] + R[1] * ds_in_V[1] + R[2] * ds_in_V[2];
+    ds_in_S[1] = R[3] * ds_in_V[0] + R[4] * ds_in_V[1] + R[5] * ds_in_V[2];
+    ds_in_S[2] = R[6] * ds_in_V[0] + R[7] * ds_in_V[1] + R[8] * ds_in_V[2];
+    const T doppler_pred_in_S =
+            -(ds_in_S[0] * dp.v_s_in_S[0] + ds_in_S[1] * dp.v_s_in_S[1] +
+              ds_in_S[2] * dp.v_s_in_S[2]);
+    // "const double doppler_error": the difference is formed in T, then held
+    // in a double
+    const double doppler_error = doppler_in_S - doppler_pred_in_S;
+    if (dp.reject_dynamic_outliers &&
+        fabs(doppler_error) > dp.doppler_outlier_threshold) {
+        A[28] += 1.0;
+        return;
+    }
+    T J_G[6], J_D[6];
+    T J_D_w[3];
+    J_D_w[0] = ds_in_V[1] * r[2] - ds_in_V[2] * r[1];
+    J_D_w[1] = ds_in_V[2] * r[0] - ds_in_V[0] * r[2];
+    J_D_w[2] = ds_in_V[0] * r[1] - ds_in_V[1] * r[0];
+    J_D[0] = dp.sqrt_lambda_doppler_by_dt * J_D_w[0];
+    J_D[1] = dp.sqrt_lambda_doppler_by_dt * J_D_w[1];
+    J_D[2] = dp.sqrt_lambda_doppler_by_dt * J_D_w[2];
+    J_D[3] = dp.sqrt_lambda_doppler_by_dt * -ds_in_V[0];
+    J_D[4] = dp.sqrt_lambda_doppler_by_dt * -ds_in_V[1];
+    J_D[5] = dp.sqrt_lambda_doppler_by_dt * -ds_in_V[2];
+    // T * double: the product is float64, then narrowed
+    const T r_D = dp.sqrt_lambda_doppler * doppler_error;
+    const T p2p_error = (ps[0] - pt[0]) * nt[0] + (ps[1] - pt[1]) * nt[1] +
+                        (ps[2] - pt[2]) * nt[2];
+    J_G[0] = dp.sqrt_lambda_geometric * (-ps[2] * nt[1] + ps[1] * nt[2]);
+    J_G[1] = dp.sqrt_lambda_geometric * (ps[2] * nt[0] - ps[0] * nt[2]);
+    J_G[2] = dp.sqrt_lambda_geometric * (-ps[1] * nt[0] + ps[0] * nt[1]);
+    J_G[3] = dp.sqrt_lambda_geometric * nt[0];
+    J_G[4] = dp.sqrt_lambda_geometric * nt[1];
+    J_G[5] = dp.sqrt_lambda_geometric * nt[2];
+    const T r_G = dp.sqrt_lambda_geometric * p2p_error;
+    const T w_G = RobustWeight<T>(rp_geometric, r_G);
+    const T w_D = RobustWeight<T>(rp_doppler, r_D);
+    int i = 0;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+#pragma unroll
+        for (int k = 0; k <= j; ++k) {
+            A[i] += (double)(J_G[j] * w_G * J_G[k] + J_D[j] * w_D * J_D[k]);
+            ++i;
+        }
+        A[21 + j] += (double)(J_G[j] * w_G * r_G + J_D[j] * w_D * r_D);
+    }
+    A[27] += (double)(r_G * r_G + r_D * r_D);
+    A[28] += 1.0;
+}
+
 constexpr int kReduceBlock = 256;
 
 // Reduce-scatter wave reduction (reduce_sums.h), LDS across the 4 waves, one
@@ -402,6 +479,94 @@ ColoredAccumulateKernel(const T* __restrict__ src, const T* __restrict__ src_c,
                              sqrt_lambda_photometric, rp);
     }
     BlockReduceAndStore(A, partials);
+}
+
+// Every correspondence index is range-checked against the target's size: an
+// index outside [0, nt) (other than -1) raises *bad and is skipped; the
+// checked final pass below then delivers nothing.
+template <typename T>
+__global__ void __launch_bounds__(kReduceBlock)
+DopplerAccumulateKernel(const T* __restrict__ src,
+                        const T* __restrict__ src_dopplers,
+                        const T* __restrict__ src_directions,
+                        const T* __restrict__ tgt, const T* __restrict__ tgt_n,
+                        const int64_t* __restrict__ corr, int64_t n, int64_t nt,
+                        DopplerParams<T> dp, RobustParams rp_geometric,
+                        RobustParams rp_doppler, double* __restrict__ partials,
+                        int* __restrict__ bad) {
+    double A[kNumSums];
+#pragma unroll
+    for (int k = 0; k < kNumSums; ++k) A[k] = 0;
+    bool out_of_range = false;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t c = corr[i];
+        if (c == -1) continue;
+        if (c < 0 || c >= nt) {
+            out_of_range = true;
+            continue;
+        }
+        const T ps[3] = {src[3 * i], src[3 * i + 1], src[3 * i + 2]};
+        const T ds[3] = {src_directions[3 * i], src_directions[3 * i + 1],
+                         src_directions[3 * i + 2]};
+        const T pt[3] = {tgt[3 * c], tgt[3 * c + 1], tgt[3 * c + 2]};
+        const T nrm[3] = {tgt_n[3 * c], tgt_n[3 * c + 1], tgt_n[3 * c + 2]};
+        AccumulateDoppler<T>(A, ps, src_dopplers[i], ds, pt, nrm, dp,
+                             rp_geometric, rp_doppler);
+    }
+    if (out_of_range) atomicOr(bad, 1);
+    BlockReduceAndStore(A, partials);
+}
+
+// FinalReduceKernel behind a range check: with *bad set `out` keeps its
+// previous contents and a mailbox receives NaN in every value (the driver
+// turns that into O3DMI_ERR_INVALID_ARG).
+__global__ void FinalReduceCheckedKernel(const double* __restrict__ partials,
+                                         int n_rows, const int* __restrict__ bad,
+                                         double* __restrict__ out, int n_out,
+                                         double* mail_data, int* mail_flag,
+                                         int mail_seq) {
+    __shared__ double lds[8][kNumSums];
+    const bool is_bad = *bad != 0;
+    int col = threadIdx.x % kNumSums;
+    int rl = threadIdx.x / kNumSums;  // 0..7
+    double v = 0;
+    for (int r = rl; r < n_rows; r += 8) v += partials[(int64_t)r * kNumSums + col];
+    lds[rl][col] = v;
+    __syncthreads();
+    if (threadIdx.x < n_out) {
+        double s = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s += lds[k][threadIdx.x];
+        if (out && !is_bad) out[threadIdx.x] = s;
+        if (mail_data)
+            mail_data[threadIdx.x] = is_bad ? __longlong_as_double(
+                                                      0x7ff8000000000000ll)
+                                            : s;
+    }
+    if (mail_flag) MailboxPublish(mail_flag, mail_seq);
+}
+
+// {n,1} <-> column 0 of an {n,3} attribute: how a 1-column attribute rides
+// through the {n,3} VoxelDownSample levels of the ICP pyramid (columns 1, 2
+// are zero; every column is averaged on its own, so column 0 is the {n,1}
+// mean).
+template <typename T>
+__global__ void PadColumnKernel(const T* __restrict__ in, int64_t n,
+                                T* __restrict__ out3) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        out3[3 * i] = in[i];
+        out3[3 * i + 1] = T(0);
+        out3[3 * i + 2] = T(0);
+    }
+}
+template <typename T>
+__global__ void TakeColumnKernel(const T* __restrict__ in3, int64_t n,
+                                 T* __restrict__ out) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = in3[3 * i];
 }
 
 // TransformationEstimationPointTo{Plane,Point}::ComputeRMSE
@@ -1194,6 +1359,181 @@ int o3dmi_icp_colored_accumulate(
 }
 
 // Internal: also posts the 29 sums to a host mailbox when mail_data != NULL.
+// bad_dev: a zeroed device word, raised by a correspondence index outside
+// [0, nt); the sums are then not delivered (FinalReduceCheckedKernel).
+int o3dmi_icp_doppler_accumulate_post(
+        const void* src_dev, const void* src_dopplers_dev,
+        const void* src_directions_dev, const void* tgt_dev,
+        const void* tgt_normals_dev, const int64_t* corr_dev, int64_t n,
+        int64_t nt, int dtype, const double* R_S_to_V9,
+        const double* r_v_to_s_in_V3, const double* w_v_in_V3,
+        const double* v_v_in_V3, double period, int reject_dynamic_outliers,
+        double doppler_outlier_threshold, int geometric_kernel,
+        double geometric_scaling, double geometric_shape, int doppler_kernel,
+        double doppler_scaling, double doppler_shape, double lambda_doppler,
+        double* sums29_dev, double* partials_dev, int* bad_dev,
+        double* mail_data, int* mail_flag, int mail_seq,
+        o3dmi_stream_t stream) {
+    O3DMI_REQUIRE(n >= 0 && nt >= 0, "negative size");
+    O3DMI_REQUIRE(n == 0 || (src_dev && src_dopplers_dev &&
+                             src_directions_dev && tgt_dev &&
+                             tgt_normals_dev && corr_dev),
+                  "null argument");
+    O3DMI_REQUIRE(R_S_to_V9 && r_v_to_s_in_V3 && w_v_in_V3 && v_v_in_V3 &&
+                          bad_dev && (sums29_dev || mail_data),
+                  "null argument");
+    O3DMI_REQUIRE(dtype == O3DMI_F32 || dtype == O3DMI_F64,
+                  "points must be Float32 or Float64");
+    O3DMI_REQUIRE(geometric_kernel >= 0 && geometric_kernel <= 6 &&
+                          doppler_kernel >= 0 && doppler_kernel <= 6,
+                  "Unsupported method.");
+    O3DMI_REQUIRE(period > 0, "period must be positive");
+    O3DMI_REQUIRE(lambda_doppler >= 0 && lambda_doppler <= 1.0,
+                  "lambda_doppler must be in [0, 1]");
+    if (reject_dynamic_outliers && (geometric_kernel == O3DMI_L1_LOSS ||
+                                    doppler_kernel == O3DMI_L1_LOSS)) {
+        // the reference multiplies L1Loss' infinite weight at r = 0 by the
+        // rejected pair's zeroed Jacobian: NaN sums
+        SetLastError(
+                "Doppler ICP: dynamic outlier rejection with an L1Loss kernel "
+                "is not supported");
+        return O3DMI_ERR_UNSUPPORTED;
+    }
+    const RobustParams rpg = MakeRobust(geometric_kernel, geometric_scaling,
+                                        geometric_shape);
+    const RobustParams rpd = MakeRobust(doppler_kernel, doppler_scaling,
+                                        doppler_shape);
+    hipStream_t s = (hipStream_t)stream;
+    const int g = ReduceGrid(n);
+    double* partials = partials_dev;
+    if (!partials)
+        O3DMI_HIP_CHECK(hipMallocAsync((void**)&partials,
+                                       sizeof(double) * (size_t)g * kNumSums,
+                                       s));
+    auto launch = [&](auto tag) {
+        using T = decltype(tag);
+        DopplerParams<T> dp;
+        T w_v_in_V[3], v_v_in_V[3];
+        for (int k = 0; k < 9; ++k) dp.R_S_to_V[k] = (T)R_S_to_V9[k];
+        for (int k = 0; k < 3; ++k) {
+            dp.r_v_to_s_in_V[k] = (T)r_v_to_s_in_V3[k];
+            w_v_in_V[k] = (T)w_v_in_V3[k];
+            v_v_in_V[k] = (T)v_v_in_V3[k];
+        }
+        // PreComputeForDopplerICP (RegistrationImpl.h:525-541), in T:
+        // v_s_in_V = v_v_in_V + w_v_in_V x r_v_to_s_in_V, v_s_in_S = R v_s_in_V
+        const T* r = dp.r_v_to_s_in_V;
+        T v_s_in_V[3];
+        v_s_in_V[0] = w_v_in_V[1] * r[2] - w_v_in_V[2] * r[1];
+        v_s_in_V[1] = w_v_in_V[2] * r[0] - w_v_in_V[0] * r[2];
+        v_s_in_V[2] = w_v_in_V[0] * r[1] - w_v_in_V[1] * r[0];
+        v_s_in_V[0] += v_v_in_V[0];
+        v_s_in_V[1] += v_v_in_V[1];
+        v_s_in_V[2] += v_v_in_V[2];
+        const T* R = dp.R_S_to_V;
+        dp.v_s_in_S[0] = R[0] * v_s_in_V[0] + R[1] * v_s_in_V[1] +
+                         R[2] * v_s_in_V[2];
+        dp.v_s_in_S[1] = R[3] * v_s_in_V[0] + R[4] * v_s_in_V[1] +
+                         R[5] * v_s_in_V[2];
+        dp.v_s_in_S[2] = R[6] * v_s_in_V[0] + R[7] * v_s_in_V[1] +
+                         R[8] * v_s_in_V[2];
+        // ComputePoseDopplerICPCPU, RegistrationCPU.cpp:454-458: the square
+        // roots are float64, then narrowed; the division is in T
+        dp.sqrt_lambda_geometric = (T)std::sqrt(1.0 - (T)lambda_doppler);
+        dp.sqrt_lambda_doppler = (T)std::sqrt(lambda_doppler);
+        dp.sqrt_lambda_doppler_by_dt = dp.sqrt_lambda_doppler / (T)period;
+        dp.doppler_outlier_threshold = (T)doppler_outlier_threshold;
+        dp.reject_dynamic_outliers = reject_dynamic_outliers ? 1 : 0;
+        hipLaunchKernelGGL(DopplerAccumulateKernel<T>, dim3(g),
+                           dim3(kReduceBlock), 0, s, (const T*)src_dev,
+                           (const T*)src_dopplers_dev,
+                           (const T*)src_directions_dev, (const T*)tgt_dev,
+                           (const T*)tgt_normals_dev, corr_dev, n, nt, dp, rpg,
+                           rpd, partials, bad_dev);
+    };
+    if (dtype == O3DMI_F64) launch(double());
+    else launch(float());
+    hipLaunchKernelGGL(FinalReduceCheckedKernel, dim3(1), dim3(256), 0, s,
+                       partials, g, bad_dev, sums29_dev, 29, mail_data,
+                       mail_flag, mail_seq);
+    O3DMI_HIP_CHECK(hipGetLastError());
+    if (!partials_dev) O3DMI_HIP_CHECK(hipFreeAsync(partials, s));
+    return O3DMI_OK;
+}
+
+int o3dmi_icp_doppler_accumulate(
+        const void* src_dev, const void* src_dopplers_dev,
+        const void* src_directions_dev, const void* tgt_dev,
+        const void* tgt_normals_dev, const int64_t* corr_dev, int64_t n,
+        int64_t nt, int dtype, const double* R_S_to_V9,
+        const double* r_v_to_s_in_V3, const double* w_v_in_V3,
+        const double* v_v_in_V3, double period, int reject_dynamic_outliers,
+        double doppler_outlier_threshold, int geometric_kernel,
+        double geometric_scaling, double geometric_shape, int doppler_kernel,
+        double doppler_scaling, double doppler_shape, double lambda_doppler,
+        double* sums29_dev, o3dmi_stream_t stream) {
+    O3DMI_REQUIRE(sums29_dev != nullptr, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    int* bad = nullptr;
+    O3DMI_HIP_CHECK(hipMallocAsync((void**)&bad, sizeof(int), s));
+    int st = O3DMI_OK, host_bad = 0;
+    hipError_t e = hipMemsetAsync(bad, 0, sizeof(int), s);
+    if (e == hipSuccess) {
+        st = o3dmi_icp_doppler_accumulate_post(
+                src_dev, src_dopplers_dev, src_directions_dev, tgt_dev,
+                tgt_normals_dev, corr_dev, n, nt, dtype, R_S_to_V9,
+                r_v_to_s_in_V3, w_v_in_V3, v_v_in_V3, period,
+                reject_dynamic_outliers, doppler_outlier_threshold,
+                geometric_kernel, geometric_scaling, geometric_shape,
+                doppler_kernel, doppler_scaling, doppler_shape, lambda_doppler,
+                sums29_dev, nullptr, bad, nullptr, nullptr, 0, stream);
+        if (st == O3DMI_OK)
+            e = hipMemcpyAsync(&host_bad, bad, sizeof(int),
+                               hipMemcpyDeviceToHost, s);
+    }
+    // the range check's verdict is this call's status: wait for it
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFreeAsync(bad, s);
+    if (st != O3DMI_OK) return st;
+    O3DMI_HIP_CHECK(e);
+    O3DMI_REQUIRE(!host_bad, "correspondence index out of range");
+    return O3DMI_OK;
+}
+
+// {n,1} -> column 0 of {n,3} (columns 1, 2 zero) and back: the 1-column
+// `dopplers` attribute through the {n,3} levels of the ICP pyramid.
+int o3dmi_internal_pad_column(const void* in_dev, int64_t n, int dtype,
+                              void* out3_dev, o3dmi_stream_t stream) {
+    O3DMI_REQUIRE(in_dev && out3_dev && n > 0, "null argument");
+    dim3 grid(GridFor(n, kBlock)), block(kBlock);
+    if (dtype == O3DMI_F64)
+        hipLaunchKernelGGL(PadColumnKernel<double>, grid, block, 0,
+                           (hipStream_t)stream, (const double*)in_dev, n,
+                           (double*)out3_dev);
+    else
+        hipLaunchKernelGGL(PadColumnKernel<float>, grid, block, 0,
+                           (hipStream_t)stream, (const float*)in_dev, n,
+                           (float*)out3_dev);
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+int o3dmi_internal_take_column(const void* in3_dev, int64_t n, int dtype,
+                               void* out_dev, o3dmi_stream_t stream) {
+    O3DMI_REQUIRE(in3_dev && out_dev && n > 0, "null argument");
+    dim3 grid(GridFor(n, kBlock)), block(kBlock);
+    if (dtype == O3DMI_F64)
+        hipLaunchKernelGGL(TakeColumnKernel<double>, grid, block, 0,
+                           (hipStream_t)stream, (const double*)in3_dev, n,
+                           (double*)out_dev);
+    else
+        hipLaunchKernelGGL(TakeColumnKernel<float>, grid, block, 0,
+                           (hipStream_t)stream, (const float*)in3_dev, n,
+                           (float*)out_dev);
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
+// Internal: also posts the 29 sums to a host mailbox when mail_data != NULL.
 int o3dmi_icp_symmetric_accumulate_post(
         const void* src_dev, const void* src_normals_dev, const void* tgt_dev,
         const void* tgt_normals_dev, const int64_t* corr_dev, int64_t n,
@@ -1585,6 +1925,25 @@ void o3dmi_pose_to_transformation(const double* pose_ptr, double* T) {
     T[7] = pose_ptr[4];
     T[11] = pose_ptr[5];
     T[15] = 1;
+}
+
+// TransformationToPoseImpl + TransformationToPose
+// (TransformationConverterImpl.h:44-60, TransformationConverter.cpp): the
+// inverse of the above; translation from column 3.
+void o3dmi_transformation_to_pose(const double* T, double* pose) {
+    const double sy = sqrt(T[0] * T[0] + T[4] * T[4]);
+    if (!(sy < 1e-6)) {
+        pose[0] = atan2(T[9], T[10]);
+        pose[1] = atan2(-T[8], sy);
+        pose[2] = atan2(T[4], T[0]);
+    } else {
+        pose[0] = atan2(-T[6], T[5]);
+        pose[1] = atan2(-T[8], sy);
+        pose[2] = 0;
+    }
+    pose[3] = T[3];
+    pose[4] = T[7];
+    pose[5] = T[11];
 }
 
 }  // extern "C"

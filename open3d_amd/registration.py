@@ -67,6 +67,80 @@ class TransformationEstimationForColoredICP:
         self.kernel = kernel or RobustKernel()
 
 
+class TransformationEstimationForDopplerICP:
+    """TransformationEstimation.h:356-500 (Hexsel et al., DICP, RSS 2022):
+    needs target normals and, on the source, `dopplers` {N,1} and `directions`
+    {N,3} (unit vectors of the vehicle frame, compute_direction_vectors).
+    The robust kernels and the dynamic-outlier rejection switch on at the
+    given iteration indices, which restart at 0 at every scale."""
+    def __init__(self, period=0.1, lambda_doppler=0.01,
+                 reject_dynamic_outliers=False, doppler_outlier_threshold=2.0,
+                 outlier_rejection_min_iteration=2,
+                 geometric_robust_loss_min_iteration=0,
+                 doppler_robust_loss_min_iteration=2, geometric_kernel=None,
+                 doppler_kernel=None, transform_vehicle_to_sensor=None):
+        self.period = period
+        # TransformationEstimation.h:389-391
+        self.lambda_doppler = (lambda_doppler
+                               if 0.0 <= lambda_doppler <= 1.0 else 0.01)
+        self.reject_dynamic_outliers = reject_dynamic_outliers
+        self.doppler_outlier_threshold = doppler_outlier_threshold
+        self.outlier_rejection_min_iteration = outlier_rejection_min_iteration
+        self.geometric_robust_loss_min_iteration = \
+            geometric_robust_loss_min_iteration
+        self.doppler_robust_loss_min_iteration = \
+            doppler_robust_loss_min_iteration
+        self.geometric_kernel = geometric_kernel or RobustKernel()
+        self.doppler_kernel = doppler_kernel or RobustKernel()
+        self.transform_vehicle_to_sensor = np.array(
+            np.eye(4) if transform_vehicle_to_sensor is None
+            else transform_vehicle_to_sensor, dtype=np.float64)
+        if self.transform_vehicle_to_sensor.shape != (4, 4):
+            raise ValueError("transform_vehicle_to_sensor must be 4x4")
+    kernel = RobustKernel()
+
+    def _fill(self, d):
+        """-> the o3dmi_icp_doppler_t fields that are not pointers."""
+        d.transform_vehicle_to_sensor[:] = \
+            self.transform_vehicle_to_sensor.reshape(-1).tolist()
+        d.period = self.period
+        d.lambda_doppler = self.lambda_doppler
+        d.reject_dynamic_outliers = 1 if self.reject_dynamic_outliers else 0
+        d.doppler_outlier_threshold = self.doppler_outlier_threshold
+        d.outlier_rejection_min_iteration = \
+            int(self.outlier_rejection_min_iteration)
+        d.geometric_robust_loss_min_iteration = \
+            int(self.geometric_robust_loss_min_iteration)
+        d.doppler_robust_loss_min_iteration = \
+            int(self.doppler_robust_loss_min_iteration)
+        d.geometric_kernel = int(self.geometric_kernel.type)
+        d.geometric_scaling_parameter = self.geometric_kernel.scaling_parameter
+        d.geometric_shape_parameter = self.geometric_kernel.shape_parameter
+        d.doppler_kernel = int(self.doppler_kernel.type)
+        d.doppler_scaling_parameter = self.doppler_kernel.scaling_parameter
+        d.doppler_shape_parameter = self.doppler_kernel.shape_parameter
+
+
+def transformation_to_pose(transformation):
+    """t::pipelines::kernel::TransformationToPose: 4x4 -> pose {6} (Euler
+    angles, translation), float64."""
+    T = np.ascontiguousarray(transformation, dtype=np.float64)
+    if T.shape != (4, 4):
+        raise ValueError("transformation must be 4x4")
+    pose = np.zeros(6, np.float64)
+    _lib.lib().o3dmi_transformation_to_pose(_lib.f64p(T), _lib.f64p(pose))
+    return pose
+
+
+def compute_direction_vectors(positions):
+    """Unit direction of every point seen from the origin, p / |p| (the helper
+    of the reference's Doppler ICP tests and examples); torch or numpy."""
+    if isinstance(positions, torch.Tensor):
+        return positions / torch.linalg.norm(positions, dim=1, keepdim=True)
+    positions = np.asarray(positions)
+    return positions / np.linalg.norm(positions, axis=1, keepdims=True)
+
+
 class RegistrationResult:
     def __init__(self):
         self.transformation = np.eye(4)
@@ -83,7 +157,8 @@ def multi_scale_icp(source, target, target_normals, voxel_sizes, criteria_list,
                     allreduce=None, source_normals=None, source_colors=None,
                     target_colors=None, target_color_gradients=None,
                     device_allreduce=None, device_counts=None,
-                    level_sharding=False):
+                    level_sharding=False, source_dopplers=None,
+                    source_directions=None):
     """source/target/target_normals: device tensors {N,3}. `device_counts`
     (optional): (ns, nt) int32 device tensors of one element holding the LIVE
     sizes of source / target, whose tensors are then buffers of at least that
@@ -95,8 +170,27 @@ def multi_scale_icp(source, target, target_normals, voxel_sizes, criteria_list,
     every rank passes the WHOLE source and the driver shards each pyramid
     level; otherwise each rank passes its shard.
     `source_normals` is read by the symmetric estimator, the colours (and the
-    optional target colour gradients) by the coloured one."""
+    optional target colour gradients) by the coloured one, `source_dopplers`
+    {N,1} (or {N}) and `source_directions` {N,3} by the Doppler one."""
     est = estimation_method or TransformationEstimationPointToPlane()
+    doppler = isinstance(est, TransformationEstimationForDopplerICP)
+    dop = _lib.IcpDoppler()
+    if doppler:
+        if target_normals is None:
+            raise ValueError("DopplerICP requires target pointcloud to have "
+                             "normals.")
+        if source_dopplers is None:
+            raise ValueError("DopplerICP requires source pointcloud to have "
+                             "Doppler velocities.")
+        if source_directions is None:
+            raise ValueError("DopplerICP requires source pointcloud to have "
+                             "pre-computed direction vectors.")
+        source_dopplers = require_cuda(source_dopplers, "source_dopplers")
+        source_directions = require_cuda(source_directions,
+                                         "source_directions")
+        est._fill(dop)
+        dop.source_dopplers = source_dopplers.data_ptr()
+        dop.source_directions = source_directions.data_ptr()
     p2point = isinstance(est, TransformationEstimationPointToPoint)
     symmetric = isinstance(est, TransformationEstimationSymmetric)
     if symmetric:
@@ -129,6 +223,13 @@ def multi_scale_icp(source, target, target_normals, voxel_sizes, criteria_list,
         raise ValueError("Only Float32 and Float64 point clouds are supported.")
     if target.dtype != source.dtype:
         raise ValueError("source / target dtype mismatch")
+    if doppler:
+        if (source_dopplers.dtype != source.dtype or
+                source_directions.dtype != source.dtype):
+            raise ValueError("source / attribute dtype mismatch")
+        if (source_dopplers.numel() != source.shape[0] or
+                tuple(source_directions.shape) != tuple(source.shape)):
+            raise ValueError("dopplers must be {N,1} and directions {N,3}")
     if p2point:
         target_normals = None
     else:
@@ -191,16 +292,21 @@ def multi_scale_icp(source, target, target_normals, voxel_sizes, criteria_list,
         # (`dar` keeps the callback object alive for the call)
         dar = _lib.ALLREDUCE_DEVICE(_dar)
         opts.device_allreduce = dar
-    st = _lib.lib().o3dmi_registration_multiscale_icp_ex(
-        _lib.ptr(source), ns, _lib.ptr(target),
-        _lib.ptr(target_normals) if target_normals is not None else None, nt,
-        TORCH_TO_O3DMI[source.dtype], S, _lib.f64p(vs), crit, _lib.f64p(md),
-        _lib.f64p(init),
-        1 if p2point else (2 if symmetric else (3 if colored else 0)),
-        C.byref(attrs), C.byref(opts), int(est.kernel.type),
-        C.c_double(est.kernel.scaling_parameter),
-        C.c_double(est.kernel.shape_parameter), cb, None, ar, None,
-        _lib.ptr(corr), C.byref(res), stream())
+    common = (_lib.ptr(source), ns, _lib.ptr(target),
+              _lib.ptr(target_normals) if target_normals is not None else None,
+              nt, TORCH_TO_O3DMI[source.dtype], S, _lib.f64p(vs), crit,
+              _lib.f64p(md), _lib.f64p(init))
+    tail = (cb, None, ar, None, _lib.ptr(corr), C.byref(res), stream())
+    if doppler:
+        st = _lib.lib().o3dmi_registration_multiscale_icp_doppler(
+            *common, C.byref(dop), C.byref(opts), *tail)
+    else:
+        st = _lib.lib().o3dmi_registration_multiscale_icp_ex(
+            *common,
+            1 if p2point else (2 if symmetric else (3 if colored else 0)),
+            C.byref(attrs), C.byref(opts), int(est.kernel.type),
+            C.c_double(est.kernel.scaling_parameter),
+            C.c_double(est.kernel.shape_parameter), *tail)
     _lib.check(st, "multi_scale_icp")
     out = RegistrationResult()
     out.transformation = np.array(res.transformation[:]).reshape(4, 4)
@@ -217,7 +323,8 @@ def icp(source, target, target_normals, max_correspondence_distance,
         voxel_size=-1.0, callback_after_iteration=None, allreduce=None,
         source_normals=None, source_colors=None, target_colors=None,
         target_color_gradients=None, device_allreduce=None,
-        device_counts=None, level_sharding=False):
+        device_counts=None, level_sharding=False, source_dopplers=None,
+        source_directions=None):
     """t::pipelines::registration::ICP (Registration.cpp:93-106)."""
     return multi_scale_icp(source, target, target_normals, [voxel_size],
                            [criteria or ICPConvergenceCriteria()],
@@ -226,7 +333,8 @@ def icp(source, target, target_normals, max_correspondence_distance,
                            callback_after_iteration, allreduce, source_normals,
                            source_colors, target_colors,
                            target_color_gradients, device_allreduce,
-                           device_counts, level_sharding)
+                           device_counts, level_sharding, source_dopplers,
+                           source_directions)
 
 
 def _check_pair(source, target):
@@ -372,7 +480,8 @@ def compute_rmse(estimation_method, source, target, target_normals,
     est = estimation_method
     code = (1 if isinstance(est, TransformationEstimationPointToPoint) else
             2 if isinstance(est, TransformationEstimationSymmetric) else
-            3 if isinstance(est, TransformationEstimationForColoredICP) else 0)
+            3 if isinstance(est, TransformationEstimationForColoredICP) else
+            4 if isinstance(est, TransformationEstimationForDopplerICP) else 0)
     source, target = _check_pair(source, target)
     corr = require_cuda(correspondences, "correspondences")
     attrs = _lib.IcpAttributes()

@@ -9,6 +9,7 @@
 import numpy as np
 import pytest
 
+import _odometry_cases as cases
 import _oracle as orc
 import _ref as ref
 from open3d_amd import synthetic
@@ -265,3 +266,160 @@ def test_multiscale_driver_converges(method):
     f = orc.rgbd_odometry_multiscale(method, sd, td, K, src_color=sc,
                                      tgt_color=tc, accumulate_double=False)
     assert np.abs(f["transformation"] - r["transformation"]).max() < 1e-3
+
+
+# ---------------------------------------------------------------------------
+# 4. crafted one-level inputs (_odometry_cases.py): each regime provably
+#    reaches its branch in the oracle, and the oracle equals the reference
+#    bodies there
+# ---------------------------------------------------------------------------
+METHODS = (orc.ODO_P2PLANE, orc.ODO_INTENSITY, orc.ODO_HYBRID)
+
+
+def _sums(case, method):
+    return orc.odometry_sums(method, **case["L"], **case["kw"],
+                             accumulate_double=True)
+
+
+def _info(case):
+    L = case["L"]
+    return orc.odometry_information(L["source_vertex"], L["target_vertex"],
+                                    L["K"], L["T"], case["info_thr"],
+                                    accumulate_double=True)
+
+
+def _result(case, what):
+    """29 sums of method `what`, or the information matrix for "info"."""
+    return _info(case).ravel() if what == "info" else _sums(case, what)
+
+
+def _count(case, what):
+    return _info(case)[3, 3] if what == "info" else _sums(case, what)[28]
+
+
+@pytest.mark.parametrize("method", METHODS)
+@pytest.mark.parametrize("delta", [0.75, 1.25])
+def test_regime_huber_zones(delta, method):
+    """Each zone by its signature in J^T r (A[21:27]), which a residual in
+    another zone cannot have. Middle zone: derivative 0, so the pixels add
+    what no pixel adds and their value does not matter. Tail: +-delta, so the
+    value does not matter either, but its being there does. The hybrid method
+    sees the values through its 0.707f scale."""
+    kw = dict(delta=delta,
+              scale=1 / 0.707 if method == orc.ODO_HYBRID else 1.0)
+    full = cases.huber_zones(**kw)
+    A = _sums(full, method)
+    assert A[28] == cases.ROWS * cases.COLS      # nothing is truncated
+    b = A[21:27]
+
+    def moved(**change):
+        B = _sums(cases.huber_zones(**kw, **change), method)
+        assert B[28] == A[28]
+        return B[21:27]
+    no_mid = _sums(cases.huber_zones(**kw, drop=("mid",)), method)
+    assert A[28] - no_mid[28] == full["n_zone"]["mid"] > 0
+    # the depth delta rules methods 0 and 2, the intensity delta (0.5) method 1
+    mid_is_flat = delta == 0.75 or method == orc.ODO_INTENSITY
+    if method == orc.ODO_HYBRID and delta == 1.25:
+        # r_I is in its middle zone, r_D in the quadratic one: not flat
+        mid_is_flat = False
+    if mid_is_flat:
+        assert np.array_equal(b, no_mid[21:27])
+        assert np.array_equal(b, moved(mid=0.9375, imid=0.9375))
+        assert np.any(b != moved(mid=0.375, imid=0.375))    # small zone
+    else:       # delta 1.25 swallows the middle zone: derivative r
+        assert np.any(b != no_mid[21:27])
+        assert np.any(b != moved(mid=0.9375, imid=0.9375))
+    no_tail = _sums(cases.huber_zones(**kw, drop=("tail",)), method)
+    assert A[28] - no_tail[28] == full["n_zone"]["tail"] > 0
+    assert np.any(b != no_tail[21:27])
+    assert np.array_equal(b, moved(tail=1.75, itail=1.75))
+    assert np.any(b != moved(tail=0.875, itail=0.75))       # middle zone
+
+
+@pytest.mark.parametrize("method", METHODS)
+def test_regime_thresholds(method):
+    A = _sums(cases.thresholds(), method)
+    B = _sums(cases.thresholds(at_trunc=False), method)
+    # 2 of 10 column patterns sit at |r| == trunc: 8 columns x 6 rows
+    assert A[28] - B[28] == 8 * cases.ROWS, (A[28], B[28])
+    # |r| == delta is in the tail, where Sign(int(0.25)) = 0: those columns
+    # are inliers that add nothing to J^T r; 2^-10 below delta they do
+    D = _sums(cases.thresholds(
+        drop_columns=cases.THRESHOLD_DELTA_COLUMNS[method]), method)
+    assert A[28] - D[28] == 8 * cases.ROWS
+    assert np.array_equal(A[21:27], D[21:27])
+    C = _sums(cases.thresholds(at_delta=False), method)
+    assert C[28] == A[28]
+    assert np.any(A[21:27] != C[21:27])
+
+
+def test_regime_behind_camera():
+    on = cases.behind_camera()
+    for what in METHODS + ("info",):
+        n = _count(on, what)
+        assert 0 < n < _count(cases.behind_camera(neg=False), what), what
+        assert n < _count(cases.behind_camera(zero=False), what), what
+
+
+def test_regime_boundary():
+    on, all_in, all_out = (cases.boundary(m) for m in
+                           ("on", "all_in", "all_out"))
+    assert on["n_out"] >= 6 and on["n_in"] >= 13
+    for what in METHODS + ("info",):
+        n = _count(on, what)
+        assert _count(all_in, what) - n == on["n_out"], what
+        assert n - _count(all_out, what) == on["n_in"], what
+
+
+@pytest.mark.parametrize("which", cases.NAN_MAPS)
+def test_regime_nan_planted(which):
+    on, off = cases.nan_planted(which), cases.nan_planted(None)
+    for what in METHODS + ("info",):
+        a, b = _result(on, what), _result(off, what)
+        if what in cases.NAN_AFFECTS[which]:
+            assert _count(off, what) - _count(on, what) == \
+                len(cases.NAN_PIXELS), (which, what)
+            assert np.all(np.isfinite(a))
+        else:
+            assert np.array_equal(a, b), (which, what)
+
+
+def test_regime_rotated():
+    on, off = cases.rotated(True), cases.rotated(False)
+    for what in METHODS + ("info",):
+        a, b = _result(on, what), _result(off, what)
+        assert _count(on, what) > 1000 and _count(off, what) > 1000
+        assert np.all(np.isfinite(a)) and not np.array_equal(a, b)
+
+
+@needs_ref
+@pytest.mark.parametrize("method", METHODS)
+@pytest.mark.parametrize("name", cases.CRAFTED_NAMES)
+def test_crafted_sums_vs_reference_bodies(name, method):
+    case = cases.crafted_case(name)
+    L, kw = case["L"], case["kw"]
+    want_delta, want_res, want_cnt, want_sums = ref.odometry(method, **L, **kw)
+    got = orc.odometry_sums(method, **L, **kw, accumulate_double=False)
+    assert want_cnt > 0
+    assert np.array_equal(got.astype(np.float32), want_sums.astype(np.float32))
+    st, pose, res, cnt = orc.decode_and_solve6x6(got)
+    assert st == 0
+    assert cnt == want_cnt and np.float32(res) == np.float32(want_res)
+    assert np.array_equal(pose, want_delta)
+    dbl = orc.odometry_sums(method, **L, **kw, accumulate_double=True)
+    assert dbl[28] == got[28]
+    assert np.allclose(dbl, got, rtol=2e-3, atol=1e-3)
+
+
+@needs_ref
+@pytest.mark.parametrize("name", cases.CRAFTED_NAMES)
+def test_crafted_information_vs_reference_body(name):
+    case = cases.crafted_case(name)
+    L = case["L"]
+    want = ref.odometry_information(L["source_vertex"], L["target_vertex"],
+                                    L["K"], L["T"], case["info_thr"])
+    got = orc.odometry_information(L["source_vertex"], L["target_vertex"],
+                                   L["K"], L["T"], case["info_thr"])
+    assert np.array_equal(got, want)
+    assert got[3, 3] > 0

@@ -38,8 +38,7 @@ namespace {
 // level with a single pass then carries the next level's hash insert).
 int DownSampleAttrsAsync(const void* pos, int64_t n_max, const int* n_dev,
                          int dtype, double voxel, void* out_pos, int* m_dev,
-                         int* err_dev, std::vector<void*>& scratch,
-                         hipStream_t cs, int chain,
+                         int* err_dev, hipStream_t cs, int chain,
                          std::initializer_list<std::pair<const void*, void*>>
                                  attrs,
                          double next_voxel = 0, bool from_previous = false,
@@ -48,56 +47,48 @@ int DownSampleAttrsAsync(const void* pos, int64_t n_max, const int* n_dev,
         SetLastError("voxel_size must be positive.");
         return O3DMI_ERR_INVALID_ARG;
     }
+    VdsLevelJob job;
+    job.pos = pos;
+    job.n_max = n_max;
+    job.n_dev = n_dev;
+    job.voxel_size = voxel;
+    job.out_pos = out_pos;
+    job.m_dev = m_dev;
+    job.err_dev = err_dev;
+    job.chain = chain;
     int passes = 0;
     for (const auto& a : attrs) passes += a.first ? 1 : 0;
-    const bool single = passes <= 1;
-    if (defer && single) {
-        // one pass: the caller launches it together with the other cloud's
-        // level (VdsPairAsync)
-        defer->pos = pos;
-        defer->n_max = n_max;
-        defer->n_dev = n_dev;
-        defer->voxel_size = voxel;
-        defer->out_pos = out_pos;
-        defer->m_dev = m_dev;
-        defer->err_dev = err_dev;
-        defer->chain = chain;
-        defer->next_voxel_size = next_voxel;
-        defer->from_previous = from_previous;
+    if (passes <= 1) {
+        job.next_voxel_size = next_voxel;
+        job.from_previous = from_previous;
         for (const auto& a : attrs)
             if (a.first) {
-                defer->attr = a.first;
-                defer->out_attr = a.second;
+                job.attr = a.first;
+                job.out_attr = a.second;
             }
-        return O3DMI_OK;
+        // one pass: with `defer` the caller launches it together with the
+        // other cloud's level (VdsPairAsync)
+        if (defer) {
+            *defer = job;
+            return O3DMI_OK;
+        }
+        return VdsPairAsync(&job, 1, dtype, cs);
     }
-    bool done = false;
     for (const auto& a : attrs) {
         if (!a.first) continue;
-        int st = VdsAsync(pos, a.first, n_max, n_dev, dtype, voxel, out_pos,
-                          a.second, m_dev, err_dev, scratch, cs, chain,
-                          single ? next_voxel : 0.0, single && from_previous);
+        job.attr = a.first;
+        job.out_attr = a.second;
+        int st = VdsPairAsync(&job, 1, dtype, cs);
         if (st) return st;
-        done = true;
     }
-    if (!done)
-        return VdsAsync(pos, nullptr, n_max, n_dev, dtype, voxel, out_pos,
-                        nullptr, m_dev, err_dev, scratch, cs, chain,
-                        next_voxel, from_previous);
     return O3DMI_OK;
 }
 
 // Device-side level counts of one cloud's pyramid: [level] voxel counts, then
-// one word of error flags, in a persistent buffer per host thread, device and
-// chain (zero when allocated; the posting launch re-zeroes the error word).
-// Read once, at the end of the chain, through the chain's host mailbox: no
-// clearing fill, no copy, no stream synchronisation per call.
-constexpr int kMaxDevices = 64;
-int CurrentDevice() {
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDevices) return -1;
-    return d;
-}
+// one word of error flags, in the chain's persistent buffer (vds.h VdsChain:
+// zero at Init; the posting launch re-zeroes what it delivers). Read once, at
+// the end of the chain, through the chain's host mailbox: no clearing fill, no
+// copy, no stream synchronisation per call.
 constexpr int kMaxScales = 30;
 static_assert(kMaxScales + 1 <= kCountsErr && kMaxScales + 1 <= 32,
               "level counts below the error word; a post carries <= 32 values");
@@ -105,92 +96,53 @@ struct ChainCounts {
     int* dev = nullptr;
     int levels = 0;
     int chain = 0;
-    std::vector<void*> scratch;  // pooled scratch of the level launches
-    // The counts, the error word and the VoxelDownSample workspaces of a
-    // chain are cleaned by the chain's own last launches (the posting launch,
-    // the levels' reduce launches). `open`: a chain was started on this
-    // thread / device / chain slot and its counts were never waited for -- an
-    // error return somewhere between its first launch and Wait. The next
-    // chain then starts from re-zeroed counts and fresh workspaces instead of
-    // inheriting a stale error bit or stale table entries.
-    static bool& Open(int d, int chain_id) {
-        static thread_local bool open[kMaxDevices][2] = {};
-        return open[d][chain_id];
-    }
-    int device = -1;
+    VdsChain* state = nullptr;
     int Init(int n_levels, int chain_id, hipStream_t cs) {
-        static thread_local int* bufs[kMaxDevices][2] = {};
         O3DMI_REQUIRE(n_levels >= 1 && n_levels <= kMaxScales,
                       "too many scales");
-        const int d = CurrentDevice();
-        O3DMI_REQUIRE(d >= 0 && (chain_id == 0 || chain_id == 1),
-                      "bad device / chain");
-        int*& b = bufs[d][chain_id];
-        const bool fresh = !b;
-        if (!b)
-            O3DMI_HIP_CHECK(hipMalloc((void**)&b,
-                                      sizeof(int) * 2 * kCountsKeep));
-        if (fresh || Open(d, chain_id)) {
-            if (!fresh) {
-                O3DMI_HIP_CHECK(hipDeviceSynchronize());
-                VdsChainInvalidate(chain_id);
-            }
-            O3DMI_HIP_CHECK(hipMemsetAsync(b, 0,
-                                           sizeof(int) * 2 * kCountsKeep, cs));
-        }
-        Open(d, chain_id) = true;
-        dev = b;
+        int st = VdsChainBegin(chain_id, cs, &state, &dev);
+        if (st) return st;
         levels = n_levels;
         chain = chain_id;
-        device = d;
         return O3DMI_OK;
     }
     int* Count(int level) { return dev + level; }
-    // (valid behind the posting launch, PostCountsPairAsync)
+    // (valid behind the chain's post)
     const int* KeptCount(int level) const { return dev + kCountsKeep + level; }
     int* Err() { return dev + kCountsErr; }  // (a post's value `levels`)
-    // Post: the counts leave for the chain's mailbox behind the chain's
-    // launches; Wait: for that, and returns them. (Both chains post before
-    // either is waited for: one host round trip, not two.)
+    // The counts leave for the chain's mailbox behind the chain's launches,
+    // with the next sequence number of that mailbox (counts == NULL: there is
+    // no mailbox): NewPost is the request, Sent records who carried it out --
+    // the chain's last level launch itself (vds.h VdsPost: a sealed block) or
+    // the posting launch. Wait: for that, and returns them. (Both chains
+    // post before either is waited for: one host round trip, not two.)
     int posted_seq = 0;
-    int Post(hipStream_t cs) {
-        Mailbox* mb = ThreadMailbox(1 + chain);
-        O3DMI_REQUIRE(mb != nullptr, "host mailbox allocation failed");
-        posted_seq = ++mb->seq;
-        return PostCountsAsync(dev, levels + 1, mb->data, mb->flag, posted_seq,
-                               cs);
-    }
-    // The post carried by the chain's last level launch (vds.h VdsPost): the
-    // request to hand to that level's job, then Posted() if it was taken up.
     bool sealed = false;
-    int offered_seq = 0;
-    VdsPost OfferPost() {
+    VdsPost NewPost() {
         VdsPost p;
         Mailbox* mb = ThreadMailbox(1 + chain);
         if (!mb) return p;
-        offered_seq = ++mb->seq;
         p.counts = dev;
         p.n = levels + 1;
         p.mail_data = mb->data;
         p.mail_flag = mb->flag;
-        p.mail_seq = offered_seq;
+        p.mail_seq = ++mb->seq;
         return p;
     }
-    void Posted() {
-        posted_seq = offered_seq;
-        sealed = true;
+    void Sent(const VdsPost& p, bool by_level_launch) {
+        posted_seq = p.mail_seq;
+        sealed = by_level_launch;
     }
-    // both chains were built in the same launches: one posting launch
-    static int PostPair(ChainCounts& a, ChainCounts& b, hipStream_t cs) {
-        Mailbox* ma = ThreadMailbox(1 + a.chain);
-        Mailbox* mb = ThreadMailbox(1 + b.chain);
-        O3DMI_REQUIRE(ma != nullptr && mb != nullptr && a.levels == b.levels,
-                      "host mailbox allocation failed");
-        a.posted_seq = ++ma->seq;
-        b.posted_seq = ++mb->seq;
-        return PostCountsPairAsync(a.dev, ma->data, ma->flag, a.posted_seq,
-                                   b.dev, mb->data, mb->flag, b.posted_seq,
-                                   a.levels + 1, cs);
+    // one posting launch: for one chain, or for two built in the same launches
+    static int Post(std::initializer_list<ChainCounts*> chains,
+                    hipStream_t cs) {
+        VdsPost posts[2];
+        int n = 0;
+        for (ChainCounts* c : chains) {
+            posts[n] = c->NewPost();
+            c->Sent(posts[n++], false);
+        }
+        return PostCounts(posts, n, cs);
     }
     int Wait(std::vector<int>& out, hipStream_t cs) {
         out.assign((size_t)levels + 1, 0);
@@ -203,15 +155,6 @@ struct ChainCounts {
                               : MailboxWait(mb, seq, cs);
         const bool was_sealed = sealed;
         sealed = false;
-        // the posting launch was the chain's last: its stream has drained
-        // (no hipStreamSynchronize, 16 us on an idle stream). (A sealed post
-        // comes from the last level's launch while it runs: only chains of
-        // the tiled form, which hold no pooled scratch.)
-        if (e == hipSuccess && !was_sealed) {
-            for (void* p : scratch) PoolFree(p);
-            scratch.clear();
-        }
-        Release(cs);
         if (e != hipSuccess) {
             SetLastError(std::string("pyramid read-back: ") +
                          hipGetErrorString(e));
@@ -219,7 +162,7 @@ struct ChainCounts {
         }
         // the posting launch has run: counts and error word are zero again,
         // every level's last launch has cleaned its workspace
-        if (device >= 0) Open(device, chain) = false;
+        VdsChainEnd(state);
         for (int k = 0; k <= levels; ++k)
             out[(size_t)k] = (int)(was_sealed ? sealed32[k] : mb->data[k]);
         if (out[(size_t)levels] & kErrKeyRange) {
@@ -227,12 +170,6 @@ struct ChainCounts {
             return O3DMI_ERR_KEY_RANGE;
         }
         return O3DMI_OK;
-    }
-    void Release(hipStream_t cs) {
-        if (scratch.empty()) return;
-        (void)hipStreamSynchronize(cs);  // pooled blocks: stream drained
-        for (void* p : scratch) PoolFree(p);
-        scratch.clear();
     }
 };
 
@@ -260,8 +197,6 @@ struct CloudChain {
                CloudLevel Level::*half)
         : pos(cloud), n(size), n_dev((const int*)size_dev), id(chain),
           cs(stream), which(half), finest_on_host(c.finest_is_input) {}
-    // releases the chain's pooled scratch on every exit path
-    ~CloudChain() { counts.Release(cs); }
 };
 
 int Clone(const IcpCall& c, DeviceBuffer& dst, const void* src, int64_t n,
@@ -340,8 +275,8 @@ int BuildLevel(const IcpCall& c, CloudChain& ch, std::vector<Level>& pyr, int k,
         e = DownSampleAttrsAsync(
                 F ? F->pos : ch.pos, f_host ? F->n : ch.n,
                 F ? (f_host ? nullptr : cc.Count(k + 1)) : ch.n_dev, c.dtype,
-                c.voxel_sizes[k], L.pos_buf.p, cc.Count(k), cc.Err(),
-                cc.scratch, ch.cs, ch.id,
+                c.voxel_sizes[k], L.pos_buf.p, cc.Count(k), cc.Err(), ch.cs,
+                ch.id,
                 {{in_attr[0], L.attr_buf[0].p},
                  {in_attr[1], L.attr_buf[1].p},
                  {in_attr[2], L.attr_buf[2].p},
@@ -382,16 +317,16 @@ int LaunchLevels(const IcpCall& c, CloudChain& src, CloudChain& tgt,
         // the coarsest level's launch posts both chains' counts itself
         const bool offer = k == 0 && n_jobs == 2 && !no_folded_post;
         if (offer) {
-            both[0].post = src.counts.OfferPost();
-            both[1].post = tgt.counts.OfferPost();
+            both[0].post = src.counts.NewPost();
+            both[1].post = tgt.counts.NewPost();
         }
         bool posted = false;
-        if (n_jobs && (st = VdsPairAsync(both, n_jobs, c.dtype,
-                                         src.counts.scratch, c.s, &posted)))
+        if (n_jobs &&
+            (st = VdsPairAsync(both, n_jobs, c.dtype, c.s, &posted)))
             return st;
         if (posted) {
-            src.counts.Posted();
-            tgt.counts.Posted();
+            src.counts.Sent(both[0].post, true);
+            tgt.counts.Sent(both[1].post, true);
             *counts_posted = true;
         }
     }
@@ -439,7 +374,6 @@ int BuildPyramids(const IcpCall& c, std::vector<Level>& pyr,
     static const bool unpaired = std::getenv("O3DMI_VDS_UNPAIRED") != nullptr;
     const bool paired = !c.colored && !c.doppler && !unpaired;
     hipStream_t ts = paired ? c.s : c.side;
-    // (declared in this order: the target chain's scratch is released first)
     CloudChain src(c, c.source, c.ns, c.ns_dev, 0, c.s, &Level::source);
     src.attr[kNormals] = c.source_normals;
     src.attr[kColors] = c.source_colors;
@@ -469,7 +403,7 @@ int BuildPyramids(const IcpCall& c, std::vector<Level>& pyr,
     const bool early_build =
             paired && !(last == 0 && c.finest_is_input) && T0.pos;
     if (paired) {
-        if (!counts_posted && (st = ChainCounts::PostPair(scc, tcc, c.s)))
+        if (!counts_posted && (st = ChainCounts::Post({&scc, &tcc}, c.s)))
             return st;
         if (early_build &&
             (st = o3dmi_internal_nns_create_small_deferred(
@@ -477,8 +411,8 @@ int BuildPyramids(const IcpCall& c, std::vector<Level>& pyr,
                      c.stream(), &early.nns)))
             return st;
     } else {
-        if ((st = tcc.Post(ts))) return st;
-        if ((st = scc.Post(c.s))) return st;
+        if ((st = ChainCounts::Post({&tcc}, ts))) return st;
+        if ((st = ChainCounts::Post({&scc}, c.s))) return st;
     }
     std::vector<int> counts;
     if ((st = tcc.Wait(counts, ts))) return st;

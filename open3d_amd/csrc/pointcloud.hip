@@ -37,7 +37,7 @@
 // device (the output count of the previous, finer level), every kernel bounds
 // itself by it, and the voxel count is left on the device as well. A pyramid
 // of several levels is therefore ONE string of launches with a single read-
-// back at its end (VdsAsync, used by the ICP driver); the public entry point
+// back at its end (VdsPairAsync, used by the ICP driver); the public entry point
 // runs one level and reads the count back. History: a generic radix sort (16
 // launches) and two host waits per level took 1.3 ms of a 1.7 ms tracking
 // frame at VGA; dense voxel ids from a separate two-launch scan before the
@@ -47,7 +47,6 @@
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
-#include <vector>
 
 #include "common.h"
 #include "preload.h"
@@ -1115,35 +1114,58 @@ struct VdsWorkspace {
         *this = VdsWorkspace();
     }
 };
-constexpr int kVdsChains = 2;
-constexpr int kVdsDevices = 64;
+// Persistent buffers of the seven-launch sort (clouds beyond the bucketed
+// form), same keying as VdsWorkspace.
+struct VdsSortWorkspace {
+    int64_t n_cap = 0;
+    unsigned long long* keys = nullptr;
+    int* first = nullptr;
+    int *slot_of_point = nullptr, *tile_firsts = nullptr, *hist = nullptr,
+        *rank_of_first = nullptr;
+    unsigned *keys_a = nullptr, *vals_a = nullptr, *keys_b = nullptr,
+             *vals_b = nullptr;
+    void Free() {
+        void* all[] = {keys, first, slot_of_point, tile_firsts, hist,
+                       rank_of_first, keys_a, vals_a, keys_b, vals_b};
+        for (void* p : all) (void)hipFree(p);
+        *this = VdsSortWorkspace();
+    }
+};
 
-// The workspaces are self-cleaning: the LAST launch of a level returns the
-// table slots and `primed` state it used to their idle values. A chain that is
-// abandoned between its first launch and that last one (an error return in
-// the driver, a failed launch) leaves them dirty; the driver says so
-// (VdsChainInvalidate) and the next user of the workspace throws it away and
-// starts from freshly initialised buffers. [tiled form, sort form]
-static thread_local bool g_vds_dirty[kVdsDevices][kVdsChains][2];
+}  // namespace
 
-static bool TakeVdsDirty(int dev, int chain, int which) {
-    const bool d = g_vds_dirty[dev][chain][which];
-    g_vds_dirty[dev][chain][which] = false;
+// (vds.h) One per host thread, device and chain.
+struct VdsChain {
+    VdsWorkspace tiled;
+    VdsSortWorkspace sort;
+    int* counts = nullptr;  // [2 * kCountsKeep]
+    bool open = false;
+};
+
+int CurrentDevice() {
+    int d = 0;
+    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDevices) return -1;
     return d;
 }
 
-VdsWorkspace* ThreadVdsWorkspace(int chain, int64_t n_max, hipStream_t s) {
-    static thread_local VdsWorkspace ws[kVdsDevices][kVdsChains];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kVdsDevices ||
-        chain < 0 || chain >= kVdsChains)
-        return nullptr;
-    VdsWorkspace& w = ws[dev][chain];
-    if (TakeVdsDirty(dev, chain, 0) && w.n_cap) {
-        // whatever the abandoned chain queued (on whichever stream) is over
-        if (hipDeviceSynchronize() != hipSuccess) return nullptr;
-        w.Free();
-    }
+namespace {
+
+constexpr int kVdsChains = 2;
+VdsChain* ThreadVdsChain(int chain) {
+    static thread_local VdsChain chains[kMaxDevices][kVdsChains];
+    const int dev = CurrentDevice();
+    if (dev < 0 || chain < 0 || chain >= kVdsChains) return nullptr;
+    return &chains[dev][chain];
+}
+
+template <typename P>
+bool DevAlloc(P** p, size_t count) {
+    return hipMalloc((void**)p, sizeof(**p) * count) == hipSuccess;
+}
+
+// The chain's tiled workspace, grown to n_max points (its first launches on s).
+VdsWorkspace* TiledWorkspace(VdsChain& c, int64_t n_max, hipStream_t s) {
+    VdsWorkspace& w = c.tiled;
     if (w.n_cap >= n_max) return &w;
     // grow: everything queued on the old buffers must have run
     if (w.n_cap && hipStreamSynchronize(s) != hipSuccess) return nullptr;
@@ -1152,18 +1174,15 @@ VdsWorkspace* ThreadVdsWorkspace(int chain, int64_t n_max, hipStream_t s) {
     while (cap < n_max) cap <<= 1;
     const int64_t n_slots = 2 * cap;
     const int64_t n_tiles = cap / kTile;
-    auto get = [](auto** p, size_t count) {
-        return hipMalloc((void**)p, sizeof(**p) * count) == hipSuccess;
-    };
-    bool ok = get(&w.tb.keys, (size_t)n_slots) &&
-              get(&w.tb.first, (size_t)n_slots) &&
-              get(&w.slot_of_point, (size_t)cap) &&
-              get(&w.tb2.keys, (size_t)n_slots) &&
-              get(&w.tb2.first, (size_t)n_slots) &&
-              get(&w.slot_of_point2, (size_t)cap) &&
-              get(&w.ent, (size_t)(2 * cap)) &&
-              get(&w.tile_off, (size_t)(n_tiles * (kMaxBuckets + 1))) &&
-              get(&w.tile_firsts, (size_t)n_tiles);
+    bool ok = DevAlloc(&w.tb.keys, (size_t)n_slots) &&
+              DevAlloc(&w.tb.first, (size_t)n_slots) &&
+              DevAlloc(&w.slot_of_point, (size_t)cap) &&
+              DevAlloc(&w.tb2.keys, (size_t)n_slots) &&
+              DevAlloc(&w.tb2.first, (size_t)n_slots) &&
+              DevAlloc(&w.slot_of_point2, (size_t)cap) &&
+              DevAlloc(&w.ent, (size_t)(2 * cap)) &&
+              DevAlloc(&w.tile_off, (size_t)(n_tiles * (kMaxBuckets + 1))) &&
+              DevAlloc(&w.tile_firsts, (size_t)n_tiles);
     if (ok) {
         w.tb.mask = w.tb2.mask = (unsigned)(n_slots - 1);
         hipLaunchKernelGGL(VdsInitKernel, dim3(GridFor(n_slots, kBlock)),
@@ -1199,7 +1218,8 @@ int VdsTiledImpl(const VdsLevelJob* jobs, int n_jobs, hipStream_t s,
         const VdsLevelJob& J = jobs[q];
         O3DMI_REQUIRE(J.n_max > 0 && J.n_max <= kTiledMaxPoints,
                       "VoxelDownSample: bad point count");
-        VdsWorkspace* w = ThreadVdsWorkspace(J.chain, J.n_max, s);
+        VdsChain* c = ThreadVdsChain(J.chain);
+        VdsWorkspace* w = c ? TiledWorkspace(*c, J.n_max, s) : nullptr;
         if (!w) return O3DMI_ERR_HIP;
         wss[q] = w;
         // this call's share of the (clean) table: 2 slots per point; a bucket
@@ -1300,36 +1320,8 @@ int VdsTiledImpl(const VdsLevelJob* jobs, int n_jobs, hipStream_t s,
     return O3DMI_OK;
 }
 
-// Persistent buffers of the seven-launch sort (clouds beyond the bucketed
-// form), same keying as VdsWorkspace.
-struct VdsSortWorkspace {
-    int64_t n_cap = 0;
-    unsigned long long* keys = nullptr;
-    int* first = nullptr;
-    int *slot_of_point = nullptr, *tile_firsts = nullptr, *hist = nullptr,
-        *rank_of_first = nullptr;
-    unsigned *keys_a = nullptr, *vals_a = nullptr, *keys_b = nullptr,
-             *vals_b = nullptr;
-    void Free() {
-        void* all[] = {keys, first, slot_of_point, tile_firsts, hist,
-                       rank_of_first, keys_a, vals_a, keys_b, vals_b};
-        for (void* p : all) (void)hipFree(p);
-        *this = VdsSortWorkspace();
-    }
-};
-
-VdsSortWorkspace* ThreadVdsSortWorkspace(int chain, int64_t n_max,
-                                         hipStream_t s) {
-    static thread_local VdsSortWorkspace ws[kVdsDevices][kVdsChains];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kVdsDevices ||
-        chain < 0 || chain >= kVdsChains)
-        return nullptr;
-    VdsSortWorkspace& w = ws[dev][chain];
-    if (TakeVdsDirty(dev, chain, 1) && w.n_cap) {
-        if (hipDeviceSynchronize() != hipSuccess) return nullptr;
-        w.Free();
-    }
+VdsSortWorkspace* SortWorkspace(VdsChain& c, int64_t n_max, hipStream_t s) {
+    VdsSortWorkspace& w = c.sort;
     if (w.n_cap >= n_max) return &w;
     if (w.n_cap && hipStreamSynchronize(s) != hipSuccess) return nullptr;
     w.Free();
@@ -1338,16 +1330,16 @@ VdsSortWorkspace* ThreadVdsSortWorkspace(int chain, int64_t n_max,
     int64_t n_slots = 1024;
     while (n_slots < 2 * cap) n_slots <<= 1;
     const int64_t n_tiles = (cap + kSortTile - 1) / kSortTile;
-    auto get = [](auto** p, size_t count) {
-        return hipMalloc((void**)p, sizeof(**p) * count) == hipSuccess;
-    };
-    const bool ok = get(&w.keys, (size_t)n_slots) && get(&w.first, (size_t)n_slots) &&
-                    get(&w.slot_of_point, (size_t)cap) &&
-                    get(&w.tile_firsts, (size_t)n_tiles) &&
-                    get(&w.hist, (size_t)kSortBins * n_tiles) &&
-                    get(&w.rank_of_first, (size_t)cap) &&
-                    get(&w.keys_a, (size_t)cap) && get(&w.vals_a, (size_t)cap) &&
-                    get(&w.keys_b, (size_t)cap) && get(&w.vals_b, (size_t)cap);
+    const bool ok = DevAlloc(&w.keys, (size_t)n_slots) &&
+                    DevAlloc(&w.first, (size_t)n_slots) &&
+                    DevAlloc(&w.slot_of_point, (size_t)cap) &&
+                    DevAlloc(&w.tile_firsts, (size_t)n_tiles) &&
+                    DevAlloc(&w.hist, (size_t)kSortBins * n_tiles) &&
+                    DevAlloc(&w.rank_of_first, (size_t)cap) &&
+                    DevAlloc(&w.keys_a, (size_t)cap) &&
+                    DevAlloc(&w.vals_a, (size_t)cap) &&
+                    DevAlloc(&w.keys_b, (size_t)cap) &&
+                    DevAlloc(&w.vals_b, (size_t)cap);
     bool init_ok = ok;
     if (ok) {
         VdsTable tb;
@@ -1367,66 +1359,62 @@ VdsSortWorkspace* ThreadVdsSortWorkspace(int chain, int64_t n_max,
     return &w;
 }
 
+// One level on the seven-launch sort.
 template <typename T>
-int VdsAsyncImpl(const T* pos, const T* nrm, int64_t n_max, const int* n_dev,
-                 double voxel_size, T* out_pos, T* out_nrm, int* m_dev,
-                 int* err_dev, std::vector<void*>& scratch, hipStream_t s,
-                 int chain) {
-    O3DMI_REQUIRE(n_max > 0 && n_max < (1ll << 30),
-                  "VoxelDownSample: bad point count");
-    // One set of buffers per host thread, device and chain, sized by the
-    // largest cloud the chain has seen and reused by every level and every
-    // attribute pass (the calls of a chain are stream-ordered). Round 2 took
-    // a fresh pooled set per call: a coloured three-level pyramid held nine
-    // full-size sets until its read-back.
-    (void)scratch;
-    VdsSortWorkspace* ws = ThreadVdsSortWorkspace(chain, n_max, s);
-    if (!ws) return O3DMI_ERR_HIP;
+int VdsSortImpl(const VdsLevelJob& J, const VdsSortWorkspace& ws,
+                hipStream_t s) {
+    const T* pos = (const T*)J.pos;
+    const int64_t n_max = J.n_max;
     const int n_host = (int)n_max;
     int64_t n_slots = 1024;
     while (n_slots < 2 * n_max) n_slots <<= 1;
     const int n_tiles = (int)((n_max + kSortTile - 1) / kSortTile);
     VdsTable tb;
-    tb.keys = ws->keys;
-    tb.first = ws->first;
+    tb.keys = ws.keys;
+    tb.first = ws.first;
     tb.mask = (unsigned)(n_slots - 1);
-    int *slot_of_point = ws->slot_of_point, *tile_firsts = ws->tile_firsts,
-        *hist = ws->hist, *rank_of_first = ws->rank_of_first;
-    unsigned *keys_a = ws->keys_a, *vals_a = ws->vals_a, *keys_b = ws->keys_b,
-             *vals_b = ws->vals_b;
     const dim3 grid(GridFor(n_max, kBlock)), block(kBlock);
     const dim3 tiles((unsigned)n_tiles), sblock(kSortBlock);
-    hipLaunchKernelGGL(VdsInsertKernel<T>, grid, block, 0, s, pos, n_dev,
-                       n_host, (T)voxel_size, tb, slot_of_point, err_dev);
+    hipLaunchKernelGGL(VdsInsertKernel<T>, grid, block, 0, s, pos, J.n_dev,
+                       n_host, (T)J.voxel_size, tb, ws.slot_of_point,
+                       J.err_dev);
     // keys = index of the voxel's first point < n_max
     const SortPlan plan = PlanSort(n_max);
-    unsigned *ki = keys_a, *vi = vals_a, *ko = keys_b, *vo = vals_b;
+    unsigned *ki = ws.keys_a, *vi = ws.vals_a, *ko = ws.keys_b,
+             *vo = ws.vals_b;
     for (int p = 0; p < plan.passes; ++p) {
         const int shift = p * plan.bits;
         if (p == 0) {
             hipLaunchKernelGGL(SortHistKernel<true>, tiles, sblock, 0, s,
-                               slot_of_point, tb, ki, vi, n_dev, n_host, shift,
-                               plan.bits, hist, tile_firsts);
+                               ws.slot_of_point, tb, ki, vi, J.n_dev, n_host,
+                               shift, plan.bits, ws.hist, ws.tile_firsts);
             hipLaunchKernelGGL(SortScatterKernel<true>, tiles, sblock, 0, s, ki,
-                               vi, ko, vo, n_dev, n_host, shift, plan.bits,
-                               hist, tile_firsts, rank_of_first, m_dev);
+                               vi, ko, vo, J.n_dev, n_host, shift, plan.bits,
+                               ws.hist, ws.tile_firsts, ws.rank_of_first,
+                               J.m_dev);
         } else {
             hipLaunchKernelGGL(SortHistKernel<false>, tiles, sblock, 0, s,
-                               slot_of_point, tb, ki, vi, n_dev, n_host, shift,
-                               plan.bits, hist, tile_firsts);
+                               ws.slot_of_point, tb, ki, vi, J.n_dev, n_host,
+                               shift, plan.bits, ws.hist, ws.tile_firsts);
             hipLaunchKernelGGL(SortScatterKernel<false>, tiles, sblock, 0, s,
-                               ki, vi, ko, vo, n_dev, n_host, shift, plan.bits,
-                               hist, tile_firsts, rank_of_first, m_dev);
+                               ki, vi, ko, vo, J.n_dev, n_host, shift,
+                               plan.bits, ws.hist, ws.tile_firsts,
+                               ws.rank_of_first, J.m_dev);
         }
         std::swap(ki, ko);
         std::swap(vi, vo);
     }
-    hipLaunchKernelGGL(VdsReduceKernel<T>, grid, block, 0, s, pos, nrm, ki, vi,
-                       rank_of_first, slot_of_point, tb, n_dev, n_host, out_pos,
-                       out_nrm);
+    hipLaunchKernelGGL(VdsReduceKernel<T>, grid, block, 0, s, pos,
+                       (const T*)J.attr, ki, vi, ws.rank_of_first,
+                       ws.slot_of_point, tb, J.n_dev, n_host, (T*)J.out_pos,
+                       (T*)J.out_attr);
     O3DMI_HIP_CHECK(hipGetLastError());
     return O3DMI_OK;
 }
+
+struct VdsPostPair {
+    VdsPost p[2];
+};
 
 }  // namespace
 
@@ -1436,72 +1424,66 @@ int VdsAsyncImpl(const T* pos, const T* nrm, int64_t n_max, const int* n_dev,
 // stream synchronisation per chain. Every word is returned to zero for the
 // next chain (the buffer is persistent; a level whose input is empty writes
 // no count).
-__global__ void PostCountsKernel(int* __restrict__ counts, int n,
-                                 double* mail_data, int* mail_flag,
-                                 int mail_seq) {
-    if ((int)threadIdx.x < n) {
-        int* cp = counts + ((int)threadIdx.x == n - 1 ? kCountsErr
-                                                       : (int)threadIdx.x);
-        mail_data[threadIdx.x] = (double)*cp;
-        *cp = 0;
-    }
-    MailboxPublish(mail_flag, mail_seq);
-}
-
-int PostCountsAsync(int* counts_dev, int n, double* mail_data, int* mail_flag,
-                    int mail_seq, hipStream_t s) {
-    O3DMI_REQUIRE(n >= 1 && n <= 32, "too many levels");
-    hipLaunchKernelGGL(PostCountsKernel, dim3(1), dim3(64), 0, s, counts_dev, n,
-                       mail_data, mail_flag, mail_seq);
-    O3DMI_HIP_CHECK(hipGetLastError());
-    return O3DMI_OK;
-}
-
-__global__ void PostCountsPairKernel(int* __restrict__ counts_a,
-                                     double* mail_data_a, int* mail_flag_a,
-                                     int mail_seq_a, int* __restrict__ counts_b,
-                                     double* mail_data_b, int* mail_flag_b,
-                                     int mail_seq_b, int n) {
+__global__ void PostCountsKernel(VdsPostPair posts) {
     // one wave per chain
-    int* counts = blockIdx.x ? counts_b : counts_a;
-    double* mail_data = blockIdx.x ? mail_data_b : mail_data_a;
-    if ((int)threadIdx.x < n) {
-        int* cp = counts + ((int)threadIdx.x == n - 1 ? kCountsErr
-                                                       : (int)threadIdx.x);
+    const VdsPost p = blockIdx.x ? posts.p[1] : posts.p[0];
+    if ((int)threadIdx.x < p.n) {
+        int* cp = p.counts + ((int)threadIdx.x == p.n - 1 ? kCountsErr
+                                                          : (int)threadIdx.x);
         const int c = *cp;
-        mail_data[threadIdx.x] = (double)c;
+        p.mail_data[threadIdx.x] = (double)c;
         // a copy that survives the re-zeroing, for launches queued behind
         // this one that size themselves by a level count (the deferred small
         // index build of the ICP driver)
-        counts[kCountsKeep + threadIdx.x] = c;
+        p.counts[kCountsKeep + threadIdx.x] = c;
         *cp = 0;
     }
-    MailboxPublish(blockIdx.x ? mail_flag_b : mail_flag_a,
-                   blockIdx.x ? mail_seq_b : mail_seq_a);
+    MailboxPublish(p.mail_flag, p.mail_seq);
 }
 
-int PostCountsPairAsync(int* counts_a, double* mail_data_a, int* mail_flag_a,
-                        int mail_seq_a, int* counts_b, double* mail_data_b,
-                        int* mail_flag_b, int mail_seq_b, int n,
-                        hipStream_t s) {
-    O3DMI_REQUIRE(n >= 1 && n <= 32, "too many levels");
-    hipLaunchKernelGGL(PostCountsPairKernel, dim3(2), dim3(64), 0, s, counts_a,
-                       mail_data_a, mail_flag_a, mail_seq_a, counts_b,
-                       mail_data_b, mail_flag_b, mail_seq_b, n);
+int PostCounts(const VdsPost* posts, int n_chains, hipStream_t s) {
+    O3DMI_REQUIRE(posts && (n_chains == 1 || n_chains == 2),
+                  "bad chain count");
+    VdsPostPair pp;
+    for (int q = 0; q < n_chains; ++q) {
+        O3DMI_REQUIRE(posts[q].counts && posts[q].mail_data &&
+                              posts[q].mail_flag,
+                      "host mailbox allocation failed");
+        O3DMI_REQUIRE(posts[q].n >= 1 && posts[q].n <= 32, "too many levels");
+        pp.p[q] = posts[q];
+    }
+    hipLaunchKernelGGL(PostCountsKernel, dim3((unsigned)n_chains), dim3(64), 0,
+                       s, pp);
     O3DMI_HIP_CHECK(hipGetLastError());
     return O3DMI_OK;
 }
 
-void VdsChainInvalidate(int chain) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kVdsDevices ||
-        chain < 0 || chain >= kVdsChains)
-        return;
-    g_vds_dirty[dev][chain][0] = g_vds_dirty[dev][chain][1] = true;
+int VdsChainBegin(int chain, hipStream_t s, VdsChain** c_out, int** counts) {
+    VdsChain* c = ThreadVdsChain(chain);
+    O3DMI_REQUIRE(c != nullptr, "bad device / chain");
+    constexpr size_t kBytes = sizeof(int) * 2 * kCountsKeep;
+    const bool fresh = !c->counts;
+    if (fresh) O3DMI_HIP_CHECK(hipMalloc((void**)&c->counts, kBytes));
+    if (c->open) {
+        // The previous chain on this slot was abandoned. Whatever it queued
+        // (on whichever stream) is over after the wait; what it left in the
+        // workspaces and the counts is thrown away.
+        O3DMI_HIP_CHECK(hipDeviceSynchronize());
+        c->tiled.Free();
+        c->sort.Free();
+    }
+    if (fresh || c->open)
+        O3DMI_HIP_CHECK(hipMemsetAsync(c->counts, 0, kBytes, s));
+    c->open = true;
+    *c_out = c;
+    *counts = c->counts;
+    return O3DMI_OK;
 }
 
-int VdsPairAsync(const VdsLevelJob* jobs, int n_jobs, int dtype,
-                 std::vector<void*>& scratch, hipStream_t s, bool* posted) {
+void VdsChainEnd(VdsChain* c) { c->open = false; }
+
+int VdsPairAsync(const VdsLevelJob* jobs, int n_jobs, int dtype, hipStream_t s,
+                 bool* posted) {
     O3DMI_REQUIRE(jobs && (n_jobs == 1 || n_jobs == 2), "bad job count");
     if (posted) *posted = false;
     bool tiled = true;
@@ -1516,44 +1498,25 @@ int VdsPairAsync(const VdsLevelJob* jobs, int n_jobs, int dtype,
         VdsLevelJob J = jobs[q];
         J.post = VdsPost{};
         int st;
-        if (J.n_max > 0 && J.n_max <= kTiledMaxPoints)
+        if (J.n_max > 0 && J.n_max <= kTiledMaxPoints) {
             st = dtype == O3DMI_F64 ? VdsTiledImpl<double>(&J, 1, s)
                                     : VdsTiledImpl<float>(&J, 1, s);
-        else if (dtype == O3DMI_F64)
-            st = VdsAsyncImpl<double>((const double*)J.pos,
-                                      (const double*)J.attr, J.n_max, J.n_dev,
-                                      J.voxel_size, (double*)J.out_pos,
-                                      (double*)J.out_attr, J.m_dev, J.err_dev,
-                                      scratch, s, J.chain);
-        else
-            st = VdsAsyncImpl<float>((const float*)J.pos, (const float*)J.attr,
-                                     J.n_max, J.n_dev, J.voxel_size,
-                                     (float*)J.out_pos, (float*)J.out_attr,
-                                     J.m_dev, J.err_dev, scratch, s, J.chain);
+        } else {
+            O3DMI_REQUIRE(J.n_max > 0 && J.n_max < (1ll << 30),
+                          "VoxelDownSample: bad point count");
+            // (one set of buffers per chain, reused by every level and every
+            // attribute pass: round 2 took a fresh pooled set per call, and a
+            // coloured three-level pyramid held nine full-size sets until its
+            // read-back)
+            VdsChain* c = ThreadVdsChain(J.chain);
+            VdsSortWorkspace* ws = c ? SortWorkspace(*c, J.n_max, s) : nullptr;
+            if (!ws) return O3DMI_ERR_HIP;
+            st = dtype == O3DMI_F64 ? VdsSortImpl<double>(J, *ws, s)
+                                    : VdsSortImpl<float>(J, *ws, s);
+        }
         if (st) return st;
     }
     return O3DMI_OK;
-}
-
-int VdsAsync(const void* pos, const void* attr, int64_t n_max, const int* n_dev,
-             int dtype, double voxel_size, void* out_pos, void* out_attr,
-             int* m_dev, int* err_dev, std::vector<void*>& scratch,
-             hipStream_t s, int chain, double next_voxel_size,
-             bool from_previous) {
-    VdsLevelJob J;
-    J.pos = pos;
-    J.attr = attr;
-    J.n_max = n_max;
-    J.n_dev = n_dev;
-    J.voxel_size = voxel_size;
-    J.out_pos = out_pos;
-    J.out_attr = out_attr;
-    J.m_dev = m_dev;
-    J.err_dev = err_dev;
-    J.chain = chain;
-    J.next_voxel_size = next_voxel_size;
-    J.from_previous = from_previous;
-    return VdsPairAsync(&J, 1, dtype, scratch, s);
 }
 
 // o3dmi_preload: HIP loads this translation unit's code object at the first
@@ -1585,26 +1548,21 @@ extern "C" int o3dmi_voxel_down_sample(const void* positions_dev,
     *m_out = 0;
     if (n == 0) return O3DMI_OK;
     hipStream_t s = (hipStream_t)stream;
-    std::vector<void*> scratch;
-    struct Release {
-        std::vector<void*>& v;
-        hipStream_t s;
-        ~Release() {
-            (void)hipStreamSynchronize(s);  // pooled blocks: stream drained
-            for (void* p : v) PoolFree(p);
-        }
-    } release{scratch, s};
-    int* counts = nullptr;  // {voxel count, error flags}
-    void* q = nullptr;
-    int st = PoolAlloc(&q, sizeof(int) * 4);
+    PoolScratch scratch(s);  // (waits for the stream, then frees, on every exit)
+    int* counts = nullptr;   // {voxel count, error flags}
+    int st = scratch.Alloc(&counts, sizeof(int) * 4);
     if (st) return st;
-    scratch.push_back(q);
-    counts = (int*)q;
     O3DMI_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(int) * 4, s));
-    st = VdsAsync(positions_dev, normals_dev, n, nullptr, dtype, voxel_size,
-                  out_positions_dev, out_normals_dev, counts, counts + 1,
-                  scratch, s);
-    if (st) return st;
+    VdsLevelJob job;  // (chain 0: shares the source chain's workspaces)
+    job.pos = positions_dev;
+    job.attr = normals_dev;
+    job.n_max = n;
+    job.voxel_size = voxel_size;
+    job.out_pos = out_positions_dev;
+    job.out_attr = out_normals_dev;
+    job.m_dev = counts;
+    job.err_dev = counts + 1;
+    if ((st = VdsPairAsync(&job, 1, dtype, s))) return st;
     int host[2] = {0, 0};
     O3DMI_HIP_CHECK(hipMemcpyAsync(host, counts, sizeof(host),
                                    hipMemcpyDeviceToHost, s));

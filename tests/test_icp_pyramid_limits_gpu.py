@@ -14,6 +14,7 @@ import json
 import os
 import subprocess
 import sys
+import threading
 
 import numpy as np
 import pytest
@@ -392,3 +393,59 @@ def test_voxel_down_sample_sort_form_with_normals(clouds, dtype):
             assert np.array_equal(gp.cpu().numpy(), wp)
             assert np.array_equal(gn.cpu().numpy(), wn)
             pts, nrm = wp, wn
+
+
+def test_workspaces_across_a_grow_and_between_the_two_entry_points(clouds):
+    """The VoxelDownSample workspaces live per host thread, device and chain,
+    grow with the largest cloud seen, and chain 0's are shared by
+    MultiScaleICP and the public voxel_down_sample. On a fresh host thread
+    (fresh workspaces, whatever ran before): 3 000-point clouds allocate the
+    first capacity (16 384 points, 2^15 table slots in use), 40 000-point
+    clouds grow and re-initialise the used workspace (2^17 slots), the public
+    entry then runs on it, and the small pair reuses the grown tables under
+    its smaller mask. The second round of the same calls finds every table
+    as clean as the first round did: the same bits. The down-sampled cloud
+    is the oracle's, bit for bit."""
+    _lib, reg = _gpu()
+    p = clouds(np.float32)
+    small, large = _problem(p, 3_000, 3_000), _problem(p, 40_000, 40_000)
+    device = torch.cuda.current_device()
+
+    def icp(q):
+        r, log = _hip(reg, q, VS3, CRIT3, MD3, "plane")
+        assert r.num_iterations > 0 and r.fitness > 0
+        return (r.transformation.tobytes(), r.num_iterations, r.fitness,
+                r.inlier_rmse, [(e["scale_index"], e["fitness"],
+                                 e["inlier_rmse"]) for e in log])
+
+    def down():
+        gp, gn = reg.voxel_down_sample(_dev(large["target"]),
+                                       _dev(large["target_normals"]), VS3[0])
+        return gp.cpu().numpy(), gn.cpu().numpy()
+
+    rounds, failure = [], []
+
+    def sequence():
+        try:
+            torch.cuda.set_device(device)
+            for _ in range(2):
+                rounds.append((icp(small), icp(large), down()))
+        except BaseException as e:  # reported by the test's own thread
+            failure.append(e)
+    t = threading.Thread(target=sequence)
+    t.start()
+    t.join()
+    if failure:
+        raise failure[0]
+    (small_1, large_1, down_1), (small_2, large_2, down_2) = rounds
+    assert small_2 == small_1
+    assert large_2 == large_1
+    assert down_2[0].shape == down_1[0].shape
+    assert np.array_equal(down_2[0], down_1[0])
+    assert np.array_equal(down_2[1], down_1[1])
+    wp, wn = orc.voxel_down_sample(large["target"], large["target_normals"],
+                                   VS3[0])
+    assert 100 < wp.shape[0] < 40_000
+    assert down_1[0].shape[0] == wp.shape[0]
+    assert np.array_equal(down_1[0], wp)
+    assert np.array_equal(down_1[1], wn)

@@ -641,6 +641,31 @@ int o3dmi_fpfh_from_neighbors(const void* points_dev, const void* normals_dev,
                               void* fpfhs_dev, int64_t* n_fpfh_out,
                               o3dmi_stream_t stream);
 
+/* ComputeBoundaryPointsCUDA (t/geometry/kernel/PointCloudImpl.h:443-506), the
+ * kernel step of ComputeBoundaryPoints after the hybrid search. indices_dev:
+ * int32 {n, nn_size}, counts_dev {n}; entry 0 of every row (the point itself)
+ * is skipped. For the other count - 1 entries: angle = atan2(v . delta,
+ * u . delta) in the tangent frame of the point's normal; the angles are sorted
+ * across a wave's lanes; mask = (largest consecutive gap, the wrap-around gap
+ * 2 pi - last + first included) > angle_threshold * pi / 180. count - 1 <= 0:
+ * mask 0. mask_out_dev: uint8 {n}, every row written. No {n, nn_size} angle
+ * tensor is allocated. nn_size > 64: O3DMI_ERR_UNSUPPORTED. An index outside
+ * [0, n) is skipped (upstream reads out of bounds).
+ * Tangent frame: upstream's GetCoordinateSystemOnPlane tests |nx - nz| and
+ * |ny - nz| where its comment means |nx| and |ny|, so a normal of (0, 0, +-1)
+ * divides by zero there and its NaN angles leave the point "not boundary".
+ * This library builds the rule the comment states: the (0, -nz, ny) branch
+ * when |nx| and |ny| are both below 1e-6. Gaps between sorted angles do not
+ * depend on the orthonormal frame chosen, so wherever upstream's frame is
+ * finite the masks agree up to rounding at the threshold. Normals are not
+ * re-normalised, as upstream; a point with a NaN angle is not a boundary
+ * point. Queued on the stream; waits for nothing. */
+int o3dmi_pointcloud_boundary_from_neighbors(
+        const void* points_dev, const void* normals_dev,
+        const int32_t* indices_dev, const int32_t* counts_dev, int64_t n,
+        int nn_size, int dtype, double angle_threshold, uint8_t* mask_out_dev,
+        o3dmi_stream_t stream);
+
 /* ---- RANSAC on correspondences: the two kernel steps --------------------
  * The legacy (Eigen, float64) RegistrationRANSACBasedOnCorrespondence
  * (pipelines/registration/Registration.cpp:212-380) has no tensor version and

@@ -845,6 +845,114 @@ int o3dmi_slac_preprocess_point_cloud(const void* points_dev,
                                       void* out_normals_dev, int64_t* m_out,
                                       o3dmi_stream_t stream);
 
+/* ---- PointCloud smoothing, boundary detection, normal orientation --------
+ * (t/geometry/PointCloud.cpp:762-854, 986-1050, 1074-1203; kernels
+ * t/geometry/kernel/PointCloudImpl.h:229-506, 1339-1753.) Float32 / Float64.
+ * One wave serves a point and reduces the point's neighbour list while the
+ * search still holds it in the wave's lanes; no {n, k} neighbour, distance or
+ * angle table is allocated unless a call says so. A neighbourhood is therefore
+ * at most one wave wide (upstream: no limit): a larger max_nn is
+ * O3DMI_ERR_UNSUPPORTED. Common rules: n == 0 is O3DMI_OK with nothing
+ * written; an output that overlaps an input, or a NaN / Inf coordinate
+ * (upstream: undefined -- run RemoveNonFinitePoints first) is
+ * O3DMI_ERR_INVALID_ARG. On an argument, limit or finiteness error, and when
+ * the search index or a scratch buffer cannot be built, the outputs (*m_out
+ * included) keep their contents: they are first written after all of that has
+ * succeeded. Only a failed launch or copy after that point (O3DMI_ERR_HIP)
+ * can leave them partly written.
+ * Neighbour lists are ascending by (d2, index); sums run in list order in the
+ * point dtype. All of the Smooth* / Compute* calls synchronise. */
+
+/* PointCloud::SmoothLaplacian. Every pass: self-query KNN with
+ * k = min(n, max_nn + 1); mean = sum of the neighbours whose index is not the
+ * point's own (with duplicated points the point may sit anywhere in its list
+ * or be absent); out = p + (T)lambda * (mean * (T)(1.0 / count) - p); count ==
+ * 0 copies the point -- upstream's CPU arithmetic bit for bit.
+ * use_fixed_neighborhoods != 0: one search into an int32 {n, k} table read by
+ * every pass; else the index is rebuilt on the moved points before every pass
+ * and no table exists. iterations == 0 or max_nn <= 0: out_points = points.
+ * max_nn > 63: O3DMI_ERR_UNSUPPORTED. */
+int o3dmi_pointcloud_smooth_laplacian(const void* points_dev, int64_t n,
+                                      int dtype, int64_t iterations,
+                                      double lambda, int max_nn,
+                                      int use_fixed_neighborhoods,
+                                      void* out_points_dev,
+                                      o3dmi_stream_t stream);
+
+/* PointCloud::SmoothTaubin: every iteration is a lambda pass, then a mu pass
+ * (each with a fresh search unless the neighbourhoods are fixed). Otherwise
+ * as o3dmi_pointcloud_smooth_laplacian. */
+int o3dmi_pointcloud_smooth_taubin(const void* points_dev, int64_t n, int dtype,
+                                   int64_t iterations, double lambda, double mu,
+                                   int max_nn, int use_fixed_neighborhoods,
+                                   void* out_points_dev,
+                                   o3dmi_stream_t stream);
+
+/* PointCloud::SmoothMLS: every point is projected onto the plane through the
+ * weighted centroid of its neighbours, weights exp(-d2 / radius^2).
+ * radius > 0 and max_nn > 0: hybrid search; radius <= 0: KNN with
+ * k = min(n, max_nn) and every weight exp(-0); max_nn <= 0: every neighbour
+ * within radius (this mode builds CSR lists); both <= 0: out = in. Fewer than
+ * 3 neighbours, or a weight sum <= 0: the point stays. normals_dev (optional)
+ * with out_normals_dev: the plane normal is returned, and a point with fewer
+ * than 3 neighbours gets its incoming normal normalised; out_normals_dev
+ * without normals_dev is O3DMI_ERR_INVALID_ARG. max_nn > 64 (hybrid, KNN):
+ * O3DMI_ERR_UNSUPPORTED.
+ * Parity: centroid and covariance are upstream's expressions in the point
+ * dtype; the normal is this library's converged float64 Jacobi eigenvector
+ * (see o3dmi_pointcloud_normals_from_covariances) with its sign rule (last
+ * non-zero component positive), not upstream's closed form: a TOLERANCE. The
+ * projected position does not depend on the sign; the normal's line agrees
+ * with upstream wherever the two smallest eigenvalues are separated. */
+int o3dmi_pointcloud_smooth_mls(const void* points_dev, const void* normals_dev,
+                                int64_t n, int dtype, double radius, int max_nn,
+                                void* out_points_dev, void* out_normals_dev,
+                                o3dmi_stream_t stream);
+
+/* PointCloud::SmoothBilateral (hybrid search): the normal is normalised in
+ * the point dtype, weight = exp(-d2 / (2 sigma_s^2) - rd^2 / (2 sigma_r^2))
+ * with rd = (p - q) . normal; out = weighted mean of the neighbours. A point
+ * with count <= 1, a normal of norm <= 0 or a weight sum <= 0 stays.
+ * sigma_s <= 0, sigma_r <= 0, radius <= 0, max_nn < 1 or normals_dev == NULL:
+ * O3DMI_ERR_INVALID_ARG (the Python mirror estimates missing normals first,
+ * as upstream does); max_nn > 64: O3DMI_ERR_UNSUPPORTED. */
+int o3dmi_pointcloud_smooth_bilateral(const void* points_dev,
+                                      const void* normals_dev, int64_t n,
+                                      int dtype, double radius, int max_nn,
+                                      double sigma_s, double sigma_r,
+                                      void* out_points_dev,
+                                      o3dmi_stream_t stream);
+
+/* PointCloud::ComputeBoundaryPoints: hybrid search, then
+ * o3dmi_pointcloud_boundary_from_neighbors' test (o3d_mi355x.h) on the list
+ * in the wave. mask_out_dev: uint8 {n}, 1 = boundary; *m_out = number of
+ * ones. radius <= 0, max_nn < 1 or normals_dev == NULL: O3DMI_ERR_INVALID_ARG;
+ * max_nn > 64: O3DMI_ERR_UNSUPPORTED. */
+int o3dmi_pointcloud_compute_boundary_points(const void* points_dev,
+                                             const void* normals_dev,
+                                             int64_t n, int dtype,
+                                             double radius, int max_nn,
+                                             double angle_threshold,
+                                             uint8_t* mask_out_dev,
+                                             int64_t* m_out,
+                                             o3dmi_stream_t stream);
+
+/* PointCloud::NormalizeNormals / OrientNormalsToAlignWithDirection /
+ * OrientNormalsTowardsCameraLocation, in place on normals_dev {n,3},
+ * statement by statement (zero normals take the direction, or the normalised
+ * vector to the camera, or (0, 0, 1) for a point at the camera). direction3 /
+ * camera3: host float64 {3}, converted to the point dtype as upstream's
+ * reference.To(dtype), and handed to the kernel by value. All three are
+ * queued on the stream and wait for nothing. */
+int o3dmi_pointcloud_normalize_normals(void* normals_dev, int64_t n, int dtype,
+                                       o3dmi_stream_t stream);
+int o3dmi_pointcloud_orient_normals_to_align_with_direction(
+        void* normals_dev, int64_t n, int dtype, const double* direction3,
+        o3dmi_stream_t stream);
+int o3dmi_pointcloud_orient_normals_towards_camera_location(
+        const void* points_dev, void* normals_dev, int64_t n, int dtype,
+        const double* camera3, o3dmi_stream_t stream);
+
 /* ------------------------------------------------------------------------ */
 /* VoxelBlockGrid                                                            */
 /* ------------------------------------------------------------------------ */

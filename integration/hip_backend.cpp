@@ -26,10 +26,13 @@
 #include "open3d/core/hashmap/HashMap.h"
 #include "open3d/core/nns/FixedRadiusIndex.h"
 #include "open3d/core/nns/NeighborSearchCommon.h"
+#include "open3d/t/geometry/kernel/PointCloud.h"
 #include "open3d/t/geometry/kernel/Transform.h"
 #include "open3d/t/geometry/kernel/VoxelBlockGrid.h"
 #include "open3d/t/pipelines/kernel/RegistrationImpl.h"
 #include "open3d/t/pipelines/registration/RobustKernel.h"
+// the PointCloud smoothing drivers are whole-operator calls
+#include "o3d_mi355x_host.h"
 
 namespace open3d {
 
@@ -382,6 +385,142 @@ static_assert(std::is_same<decltype(&TransformPointsHIP),
                                    decltype(&TransformNormalsCPU)>::value,
               "Transform*HIP have the dispatcher's per-device signature");
 }  // namespace transform
+
+// 5e''. beside SmoothLaplacianCUDA ... OrientNormalsTowardsCameraLocationCUDA
+//    (t/geometry/kernel/PointCloud.h:96-110, 329-357; the dispatchers in
+//    t/geometry/PointCloud.cpp:762-854, 986-1050, 1074-1203 gain
+//    `else if (IsHIP()) { kernel::pointcloud::...HIP(...); }`)
+namespace pointcloud {
+namespace {
+// {3} reference vector on the host in float64 (the library converts it to
+// the point dtype, as upstream's reference.To(dtype) does)
+core::Tensor HostVec3(const core::Tensor& v) {
+    return v.To(core::Device("CPU:0")).To(core::Float64).Contiguous();
+}
+}  // namespace
+
+void SmoothLaplacianHIP(const core::Tensor& points,
+                        core::Tensor& smoothed_points,
+                        size_t iterations,
+                        double lambda,
+                        int max_nn,
+                        bool use_fixed_neighborhoods) {
+    smoothed_points = core::Tensor::Empty(points.GetShape(), points.GetDtype(),
+                                          points.GetDevice());
+    O3DMI_CALL(o3dmi_pointcloud_smooth_laplacian(
+            points.GetDataPtr(), points.GetLength(),
+            core::ToO3dmi(points.GetDtype()), (int64_t)iterations, lambda,
+            max_nn, use_fixed_neighborhoods ? 1 : 0,
+            smoothed_points.GetDataPtr(), core::HipStream()));
+}
+void SmoothTaubinHIP(const core::Tensor& points,
+                     core::Tensor& smoothed_points,
+                     size_t iterations,
+                     double lambda,
+                     double mu,
+                     int max_nn,
+                     bool use_fixed_neighborhoods) {
+    smoothed_points = core::Tensor::Empty(points.GetShape(), points.GetDtype(),
+                                          points.GetDevice());
+    O3DMI_CALL(o3dmi_pointcloud_smooth_taubin(
+            points.GetDataPtr(), points.GetLength(),
+            core::ToO3dmi(points.GetDtype()), (int64_t)iterations, lambda, mu,
+            max_nn, use_fixed_neighborhoods ? 1 : 0,
+            smoothed_points.GetDataPtr(), core::HipStream()));
+}
+void SmoothMLSHIP(const core::Tensor& points,
+                  core::Tensor& smoothed_points,
+                  core::Tensor& normals,
+                  bool update_normals,
+                  double radius,
+                  int max_nn) {
+    smoothed_points = core::Tensor::Empty(points.GetShape(), points.GetDtype(),
+                                          points.GetDevice());
+    // upstream updates `normals` in place; the library reads one buffer and
+    // writes another
+    core::Tensor incoming;
+    if (update_normals) incoming = normals.Clone();
+    O3DMI_CALL(o3dmi_pointcloud_smooth_mls(
+            points.GetDataPtr(),
+            update_normals ? incoming.GetDataPtr() : nullptr,
+            points.GetLength(), core::ToO3dmi(points.GetDtype()), radius,
+            max_nn, smoothed_points.GetDataPtr(),
+            update_normals ? normals.GetDataPtr() : nullptr,
+            core::HipStream()));
+}
+void SmoothBilateralHIP(const core::Tensor& points,
+                        const core::Tensor& normals,
+                        core::Tensor& smoothed_points,
+                        double radius,
+                        int max_nn,
+                        double sigma_s,
+                        double sigma_r) {
+    smoothed_points = core::Tensor::Empty(points.GetShape(), points.GetDtype(),
+                                          points.GetDevice());
+    O3DMI_CALL(o3dmi_pointcloud_smooth_bilateral(
+            points.GetDataPtr(), normals.GetDataPtr(), points.GetLength(),
+            core::ToO3dmi(points.GetDtype()), radius, max_nn, sigma_s, sigma_r,
+            smoothed_points.GetDataPtr(), core::HipStream()));
+}
+void ComputeBoundaryPointsHIP(const core::Tensor& points,
+                              const core::Tensor& normals,
+                              const core::Tensor& indices,
+                              const core::Tensor& counts,
+                              core::Tensor& mask,
+                              double angle_threshold) {
+    O3DMI_CALL(o3dmi_pointcloud_boundary_from_neighbors(
+            points.GetDataPtr(), normals.GetDataPtr(),
+            (const int32_t*)indices.GetDataPtr(),
+            (const int32_t*)counts.GetDataPtr(), points.GetLength(),
+            (int)indices.GetShape(1), core::ToO3dmi(points.GetDtype()),
+            angle_threshold, (uint8_t*)mask.GetDataPtr(), core::HipStream()));
+}
+void NormalizeNormalsHIP(core::Tensor& normals) {
+    O3DMI_CALL(o3dmi_pointcloud_normalize_normals(
+            normals.GetDataPtr(), normals.GetLength(),
+            core::ToO3dmi(normals.GetDtype()), core::HipStream()));
+}
+void OrientNormalsToAlignWithDirectionHIP(core::Tensor& normals,
+                                          const core::Tensor& direction) {
+    const core::Tensor d = HostVec3(direction);
+    O3DMI_CALL(o3dmi_pointcloud_orient_normals_to_align_with_direction(
+            normals.GetDataPtr(), normals.GetLength(),
+            core::ToO3dmi(normals.GetDtype()), d.GetDataPtr<double>(),
+            core::HipStream()));
+}
+void OrientNormalsTowardsCameraLocationHIP(const core::Tensor& points,
+                                           core::Tensor& normals,
+                                           const core::Tensor& camera) {
+    const core::Tensor c = HostVec3(camera);
+    O3DMI_CALL(o3dmi_pointcloud_orient_normals_towards_camera_location(
+            points.GetDataPtr(), normals.GetDataPtr(), normals.GetLength(),
+            core::ToO3dmi(points.GetDtype()), c.GetDataPtr<double>(),
+            core::HipStream()));
+}
+static_assert(
+        std::is_same<decltype(&SmoothLaplacianHIP),
+                     decltype(&SmoothLaplacianCPU)>::value &&
+                std::is_same<decltype(&SmoothTaubinHIP),
+                             decltype(&SmoothTaubinCPU)>::value &&
+                std::is_same<decltype(&SmoothMLSHIP),
+                             decltype(&SmoothMLSCPU)>::value &&
+                std::is_same<decltype(&SmoothBilateralHIP),
+                             decltype(&SmoothBilateralCPU)>::value &&
+                std::is_same<decltype(&ComputeBoundaryPointsHIP),
+                             decltype(&ComputeBoundaryPointsCPU)>::value &&
+                std::is_same<decltype(&NormalizeNormalsHIP),
+                             decltype(&NormalizeNormalsCPU)>::value &&
+                std::is_same<
+                        decltype(&OrientNormalsToAlignWithDirectionHIP),
+                        decltype(&OrientNormalsToAlignWithDirectionCPU)>::
+                        value &&
+                std::is_same<
+                        decltype(&OrientNormalsTowardsCameraLocationHIP),
+                        decltype(&OrientNormalsTowardsCameraLocationCPU)>::
+                        value,
+        "the PointCloud smoothing / boundary / normal ...HIP functions have "
+        "the dispatchers' per-device signatures");
+}  // namespace pointcloud
 }  // namespace kernel
 }  // namespace geometry
 

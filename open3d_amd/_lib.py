@@ -355,6 +355,24 @@ PROTOTYPES.update({
     "o3dmi_pointcloud_remove_statistical_outliers": (
         _i32, [_vp, _i64, _i32, _i64, _d, _vp, _vp, _dp, C.POINTER(_i64),
                _vp]),
+    "o3dmi_pointcloud_smooth_laplacian": (
+        _i32, [_vp, _i64, _i32, _i64, _d, _i32, _i32, _vp, _vp]),
+    "o3dmi_pointcloud_smooth_taubin": (
+        _i32, [_vp, _i64, _i32, _i64, _d, _d, _i32, _i32, _vp, _vp]),
+    "o3dmi_pointcloud_smooth_mls": (
+        _i32, [_vp, _vp, _i64, _i32, _d, _i32, _vp, _vp, _vp]),
+    "o3dmi_pointcloud_smooth_bilateral": (
+        _i32, [_vp, _vp, _i64, _i32, _d, _i32, _d, _d, _vp, _vp]),
+    "o3dmi_pointcloud_compute_boundary_points": (
+        _i32, [_vp, _vp, _i64, _i32, _d, _i32, _d, _vp, C.POINTER(_i64),
+               _vp]),
+    "o3dmi_pointcloud_boundary_from_neighbors": (
+        _i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _d, _vp, _vp]),
+    "o3dmi_pointcloud_normalize_normals": (_i32, [_vp, _i64, _i32, _vp]),
+    "o3dmi_pointcloud_orient_normals_to_align_with_direction": (
+        _i32, [_vp, _i64, _i32, _dp, _vp]),
+    "o3dmi_pointcloud_orient_normals_towards_camera_location": (
+        _i32, [_vp, _vp, _i64, _i32, _dp, _vp]),
     "o3dmi_slac_preprocess_point_cloud": (
         _i32, [_vp, _vp, _i64, _i32, _d, _i32, _vp, _vp, C.POINTER(_i64),
                _vp]),
@@ -505,6 +523,16 @@ class TransportC(C.Structure):
                 ("allgather", TRANSPORT_ALLGATHER),
                 ("alltoallv", TRANSPORT_ALLTOALLV)]
 
+# Exported entry points that are in no public header (declared in csrc/*.h):
+# bound here, once, for the tests and tools that drive them.
+INTERNAL_PROTOTYPES = {
+    # csrc/pointcloud_smooth.h: (kind, points, normals, indices, dist2, counts,
+    # n, width, dtype, p0, p1, out_points, out_normals, mask, stream)
+    "o3dmi_internal_pointcloud_smooth_from_neighbors": (
+        _i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _d, _d, _vp,
+               _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -530,7 +558,8 @@ def lib():
         # the order reversed the second runtime sees no device.
         import torch  # noqa: F401
         L = C.CDLL(SO_PATH)
-        for name, (res, args) in PROTOTYPES.items():
+        for name, (res, args) in list(PROTOTYPES.items()) + \
+                list(INTERNAL_PROTOTYPES.items()):
             fn = getattr(L, name)  # AttributeError if a symbol is missing
             fn.restype = res
             fn.argtypes = args

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "nns.h"
+#include "pointcloud_smooth_device.h"
 #include "preload.h"
 
 namespace o3dmi {
@@ -667,14 +668,70 @@ struct AvgDistanceOut {
     }
 };
 
+// The finished list as a neighbour source of the PointCloud smoothing and
+// boundary bodies (pointcloud_smooth_device.h): lane j holds entry j.
+template <typename T>
+struct ListNb {
+    int count;
+    int idx;
+    T d2;
+    __device__ __forceinline__ void Load(int, int& i, T& d) const {
+        i = idx;
+        d = d2;
+    }
+};
+
+template <typename T>
+__device__ __forceinline__ ListNb<T> ListOf(const WaveTopK<T>& list) {
+    const bool ok = (int)(threadIdx.x & 63) < list.nbest;
+    return {list.nbest, ok ? list.best_i : -1, ok ? list.best_d : T(0)};
+}
+
+// LaplacianOut / MlsOut / BilateralOut / BoundaryOut: the smoothed point (or
+// the boundary flag) of query i straight from its list -- SmoothLaplacian /
+// SmoothTaubin with re-searched neighbourhoods, SmoothMLS, SmoothBilateral,
+// ComputeBoundaryPoints. Query i is point i of the cloud the index holds.
+template <typename T>
+struct LaplacianOut {
+    LaplacianArgs<T> a;
+    __device__ __forceinline__ void Write(const WaveTopK<T>& list,
+                                          int64_t i) const {
+        LaplacianPoint(a, i, ListOf(list));
+    }
+};
+template <typename T>
+struct MlsOut {
+    MlsArgs<T> a;
+    __device__ __forceinline__ void Write(const WaveTopK<T>& list,
+                                          int64_t i) const {
+        MlsPoint(a, i, ListOf(list));
+    }
+};
+template <typename T>
+struct BilateralOut {
+    BilateralArgs<T> a;
+    __device__ __forceinline__ void Write(const WaveTopK<T>& list,
+                                          int64_t i) const {
+        BilateralPoint(a, i, ListOf(list));
+    }
+};
+template <typename T>
+struct BoundaryOut {
+    BoundaryArgs<T> a;
+    __device__ __forceinline__ void Write(const WaveTopK<T>& list,
+                                          int64_t i) const {
+        BoundaryPoint(a, i, ListOf(list));
+    }
+};
+
 // HybridSearch for general max_knn (core/nns/NanoFlannImpl.h:305-370 semantics:
 // neighbours with d2 < r2, ascending by (d2, index), the first max_knn kept;
-// idx padded with -1, dist with 0, count = min(found, max_knn)).
-template <typename T>
+// idx padded with -1, dist with 0, count = min(found, max_knn)). `out` is the
+// output policy, as in KnnSearchKernel.
+template <typename T, typename Out>
 __global__ void __launch_bounds__(kCoopBlock)
 HybridSearchKernel(NnsView<T> nv, const T* __restrict__ q, int64_t nq,
-                   int max_knn, int* __restrict__ idx_out,
-                   T* __restrict__ d2_out, int* __restrict__ cnt_out) {
+                   int max_knn, Out out) {
     extern __shared__ __align__(16) char coop_lds[];
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -688,7 +745,7 @@ HybridSearchKernel(NnsView<T> nv, const T* __restrict__ q, int64_t nq,
         GatherCells<T, true>(nv, qq, cx, cy, cz, cx - 1, cx + 1, cy - 1, cy + 1,
                              cz - 1, cz + 1, 0, list);
         list.Flush();
-        WriteTopK(list, i, idx_out, d2_out, cnt_out);
+        out.Write(list, i);
     }
 }
 
@@ -970,9 +1027,19 @@ struct KnnPyramid {
     KnnGrid<T> level[kKnnMaxLevels];
 };
 
+// Waves per SIMD the register budget of KnnSearchKernel is sized for. The
+// float64 smoothing policies keep three coordinates and a weight per lane on
+// top of the search's state: they get the budget of three waves, so that
+// nothing of theirs goes to scratch memory.
+template <typename Out> struct KnnWaves { static constexpr int value = 4; };
+template <> struct KnnWaves<LaplacianOut<double>> {
+    static constexpr int value = 3;
+};
+template <> struct KnnWaves<MlsOut<double>> { static constexpr int value = 3; };
+
 template <typename T, typename Out>
 __global__ void __launch_bounds__(kCoopBlock)
-__attribute__((amdgpu_waves_per_eu(4)))
+__attribute__((amdgpu_waves_per_eu(KnnWaves<Out>::value)))
 KnnSearchKernel(KnnPyramid<T> pyr, const T* __restrict__ q, int64_t nq, int knn,
                 const int* __restrict__ query_ids, int* __restrict__ retry_ids,
                 int* __restrict__ retry_count, Out out) {
@@ -1531,15 +1598,21 @@ int o3dmi_nns_hybrid_search(const o3dmi_nns_t* nns, const void* queries_dev,
     // one wave per query
     dim3 grid(GridFor(q, kCoopBlock / 64, kCUs * 16)), block(kCoopBlock);
     if (nns->dtype == O3DMI_F64)
-        hipLaunchKernelGGL(HybridSearchKernel<double>, grid, block,
+        hipLaunchKernelGGL((HybridSearchKernel<double, TopKOut<double>>), grid,
+                           block,
                            CoopLdsBytesPerWave<double>() * (kCoopBlock / 64), s,
                            MakeView<double>(nns), (const double*)queries_dev, q,
-                           max_knn, idx_dev, (double*)dist2_dev, counts_dev);
+                           max_knn,
+                           TopKOut<double>{idx_dev, (double*)dist2_dev,
+                                           counts_dev});
     else
-        hipLaunchKernelGGL(HybridSearchKernel<float>, grid, block,
+        hipLaunchKernelGGL((HybridSearchKernel<float, TopKOut<float>>), grid,
+                           block,
                            CoopLdsBytesPerWave<float>() * (kCoopBlock / 64), s,
                            MakeView<float>(nns), (const float*)queries_dev, q,
-                           max_knn, idx_dev, (float*)dist2_dev, counts_dev);
+                           max_knn,
+                           TopKOut<float>{idx_dev, (float*)dist2_dev,
+                                          counts_dev});
     O3DMI_HIP_CHECK(hipGetLastError());
     return O3DMI_OK;
 }
@@ -1684,13 +1757,15 @@ struct KnnResources {
 
 namespace {
 
-// The KNN search behind both entry points below. avg_dev == NULL: the rows go
-// to idx_dev / dist2_dev / counts_dev (TopKOut); else only the mean neighbour
-// distance of every query goes to avg_dev {q} (AvgDistanceOut).
+// The KNN search behind the entry points below. With `op` the finished lists
+// go through its smoothing policy (queries are the cloud itself); else, with
+// avg_dev == NULL, the rows go to idx_dev / dist2_dev / counts_dev (TopKOut);
+// else only the mean neighbour distance of every query goes to avg_dev {q}
+// (AvgDistanceOut).
 int KnnSearchRun(const void* points_dev, int64_t n, const void* queries_dev,
                  int64_t q, int dtype, int knn, int32_t* idx_dev,
                  void* dist2_dev, int32_t* counts_dev, void* avg_dev,
-                 o3dmi_stream_t stream) {
+                 const SmoothOp* op, o3dmi_stream_t stream) {
     O3DMI_REQUIRE(dtype == O3DMI_F32 || dtype == O3DMI_F64,
                   "points must be Float32 or Float64");
     O3DMI_REQUIRE(knn > 0, "knn should be larger than 0.");
@@ -1699,7 +1774,7 @@ int KnnSearchRun(const void* points_dev, int64_t n, const void* queries_dev,
     const int k = (int)(n < (int64_t)knn ? n : (int64_t)knn);
     O3DMI_REQUIRE(k <= kMaxKnn, "knn > 64 is not supported");
     if (q == 0) return O3DMI_OK;
-    O3DMI_REQUIRE(queries_dev && (idx_dev || avg_dev), "null argument");
+    O3DMI_REQUIRE(queries_dev && (idx_dev || avg_dev || op), "null argument");
     hipStream_t s = (hipStream_t)stream;
     KnnResources res;
     int st;
@@ -1807,7 +1882,20 @@ int KnnSearchRun(const void* points_dev, int64_t n, const void* queries_dev,
                                                    lv->inv_cell) + 1;          \
             }                                                                  \
         }                                                                      \
-        if (avg_dev)                                                           \
+        if (op && op->kind == kSmoothLaplacian)                                \
+            hipLaunchKernelGGL((KnnSearchKernel<T, LaplacianOut<T>>), grid,    \
+                               block,                                          \
+                               CoopLdsBytesPerWave<T>() * (kCoopBlock / 64),   \
+                               s, pyr, (const T*)queries_dev, count, k, ids,   \
+                               retry_ids, retry_count,                         \
+                               LaplacianOut<T>{MakeLaplacianArgs<T>(*op)});    \
+        else if (op)                                                           \
+            hipLaunchKernelGGL((KnnSearchKernel<T, MlsOut<T>>), grid, block,   \
+                               CoopLdsBytesPerWave<T>() * (kCoopBlock / 64),   \
+                               s, pyr, (const T*)queries_dev, count, k, ids,   \
+                               retry_ids, retry_count,                         \
+                               MlsOut<T>{MakeMlsArgs<T>(*op)});                \
+        else if (avg_dev)                                                      \
             hipLaunchKernelGGL((KnnSearchKernel<T, AvgDistanceOut<T>>), grid,  \
                                block,                                          \
                                CoopLdsBytesPerWave<T>() * (kCoopBlock / 64),   \
@@ -1879,7 +1967,7 @@ int o3dmi_nns_knn_search_counts(const void* points_dev, int64_t n,
                                 int32_t* counts_dev, o3dmi_stream_t stream) {
     O3DMI_REQUIRE(q <= 0 || idx_dev, "null argument");
     return KnnSearchRun(points_dev, n, queries_dev, q, dtype, knn, idx_dev,
-                        dist2_dev, counts_dev, nullptr, stream);
+                        dist2_dev, counts_dev, nullptr, nullptr, stream);
 }
 
 // Internal (RemoveStatisticalOutliers): avg_dev[i] = mean over the
@@ -1891,7 +1979,7 @@ int o3dmi_internal_nns_knn_avg_distance(const void* points_dev, int64_t n,
                                         o3dmi_stream_t stream) {
     O3DMI_REQUIRE(avg_dev != nullptr, "null argument");
     return KnnSearchRun(points_dev, n, points_dev, n, dtype, knn, nullptr,
-                        nullptr, nullptr, avg_dev, stream);
+                        nullptr, nullptr, avg_dev, nullptr, stream);
 }
 
 int o3dmi_nns_knn_search(const void* points_dev, int64_t n,
@@ -1904,3 +1992,61 @@ int o3dmi_nns_knn_search(const void* points_dev, int64_t n,
 }
 
 }  // extern "C"
+
+namespace {
+
+template <typename T>
+int LaunchHybridSmoothOp(const o3dmi_nns* nns, const void* points_dev,
+                         int64_t n, int max_knn, const SmoothOp& op,
+                         hipStream_t s) {
+    const dim3 grid(GridFor(n, kCoopBlock / 64, kCUs * 16)), block(kCoopBlock);
+    const size_t lds = CoopLdsBytesPerWave<T>() * (kCoopBlock / 64);
+    const NnsView<T> nv = MakeView<T>(nns);
+    const T* q = (const T*)points_dev;
+    switch (op.kind) {
+        case kSmoothMls:
+            hipLaunchKernelGGL((HybridSearchKernel<T, MlsOut<T>>), grid, block,
+                               lds, s, nv, q, n, max_knn,
+                               MlsOut<T>{MakeMlsArgs<T>(op)});
+            break;
+        case kSmoothBilateral:
+            hipLaunchKernelGGL((HybridSearchKernel<T, BilateralOut<T>>), grid,
+                               block, lds, s, nv, q, n, max_knn,
+                               BilateralOut<T>{MakeBilateralArgs<T>(op)});
+            break;
+        case kSmoothBoundary:
+            hipLaunchKernelGGL((HybridSearchKernel<T, BoundaryOut<T>>), grid,
+                               block, lds, s, nv, q, n, max_knn,
+                               BoundaryOut<T>{MakeBoundaryArgs<T>(op)});
+            break;
+        default:
+            SetLastError("hybrid search: unknown output policy");
+            return O3DMI_ERR_INTERNAL;
+    }
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
+}  // namespace
+
+int o3dmi::HybridSearchSmoothOp(const o3dmi_nns* nns, const void* points_dev,
+                                int64_t n, int max_knn, const SmoothOp& op,
+                                hipStream_t s) {
+    O3DMI_REQUIRE(nns != nullptr && points_dev != nullptr, "null argument");
+    O3DMI_REQUIRE(max_knn >= 1 && max_knn <= kMaxKnn,
+                  "max_knn must be in [1, 64]");
+    if (n <= 0) return O3DMI_OK;
+    return nns->dtype == O3DMI_F64
+                   ? LaunchHybridSmoothOp<double>(nns, points_dev, n, max_knn,
+                                                  op, s)
+                   : LaunchHybridSmoothOp<float>(nns, points_dev, n, max_knn,
+                                                 op, s);
+}
+
+int o3dmi::KnnSearchSmoothOp(const void* points_dev, int64_t n, int dtype,
+                             int knn, const SmoothOp& op, hipStream_t s) {
+    O3DMI_REQUIRE(op.kind == kSmoothLaplacian || op.kind == kSmoothMls,
+                  "knn search: unknown output policy");
+    return KnnSearchRun(points_dev, n, points_dev, n, dtype, knn, nullptr,
+                        nullptr, nullptr, nullptr, &op, (o3dmi_stream_t)s);
+}

@@ -1,5 +1,6 @@
-"""Mirror of t::geometry::PointCloud's selection and filter methods
-(t/geometry/PointCloud.cpp:435-494, 650-760) on the HIP backend.
+"""Mirror of t::geometry::PointCloud's selection, filter, smoothing, boundary
+and normal-orientation methods (t/geometry/PointCloud.cpp:435-494, 650-854,
+986-1050, 1074-1203) on the HIP backend.
 
 A cloud is a dict of CUDA attribute tensors with "positions" ({N,3} Float32 or
 Float64) required; every other attribute has N rows of any width and dtype
@@ -185,3 +186,157 @@ def remove_statistical_outliers(attrs, nb_neighbors, std_ratio,
         stats["avg_distances"] = avg
         return out, mask, stats
     return out, mask
+
+
+# ---- smoothing, boundary detection, normal orientation ------------------------
+# Each returns a new cloud dict: "positions" (and "normals" where the operator
+# moves them) replaced, every other attribute carried through unchanged.
+
+def _normals(attrs, p, required):
+    if "normals" not in attrs:
+        if required:
+            raise ValueError(required)
+        return None
+    nrm = require_cuda(attrs["normals"], "normals")
+    if nrm.shape != p.shape or nrm.dtype != p.dtype:
+        raise ValueError("normals must match positions in shape and dtype")
+    return nrm.contiguous()
+
+
+def _carried(attrs, **replaced):
+    out = dict(attrs)
+    out.update(replaced)
+    return out
+
+
+def smooth_laplacian(attrs, iterations=10, lambda_=0.5, max_nn=20,
+                     use_fixed_neighborhoods=False):
+    """PointCloud::SmoothLaplacian. max_nn defaults to 20, as in upstream's
+    header (t/geometry/PointCloud.h:590), not to the 30 of the other
+    operators."""
+    p = _positions(attrs)
+    out = torch.empty_like(p)
+    _lib.check(_lib.lib().o3dmi_pointcloud_smooth_laplacian(
+        _lib.ptr(p), p.shape[0], TORCH_TO_O3DMI[p.dtype], int(iterations),
+        C.c_double(lambda_), int(max_nn), int(bool(use_fixed_neighborhoods)),
+        _lib.ptr(out), stream()), "smooth_laplacian")
+    return _carried(attrs, positions=out)
+
+
+def smooth_taubin(attrs, iterations=10, lambda_=0.5, mu=-0.53, max_nn=20,
+                  use_fixed_neighborhoods=False):
+    """PointCloud::SmoothTaubin. max_nn defaults to 20, as in upstream's
+    header (t/geometry/PointCloud.h:610)."""
+    p = _positions(attrs)
+    out = torch.empty_like(p)
+    _lib.check(_lib.lib().o3dmi_pointcloud_smooth_taubin(
+        _lib.ptr(p), p.shape[0], TORCH_TO_O3DMI[p.dtype], int(iterations),
+        C.c_double(lambda_), C.c_double(mu), int(max_nn),
+        int(bool(use_fixed_neighborhoods)), _lib.ptr(out), stream()),
+        "smooth_taubin")
+    return _carried(attrs, positions=out)
+
+
+def smooth_mls(attrs, radius=0.05, max_nn=30):
+    """PointCloud::SmoothMLS; a cloud with normals gets the plane normals."""
+    p = _positions(attrs)
+    nrm = _normals(attrs, p, None)
+    out = torch.empty_like(p)
+    out_n = torch.empty_like(nrm) if nrm is not None else None
+    _lib.check(_lib.lib().o3dmi_pointcloud_smooth_mls(
+        _lib.ptr(p), _lib.ptr(nrm) if nrm is not None else None, p.shape[0],
+        TORCH_TO_O3DMI[p.dtype], C.c_double(radius), int(max_nn),
+        _lib.ptr(out), _lib.ptr(out_n) if out_n is not None else None,
+        stream()), "smooth_mls")
+    if out_n is None:
+        return _carried(attrs, positions=out)
+    return _carried(attrs, positions=out, normals=out_n)
+
+
+def smooth_bilateral(attrs, radius=0.05, max_nn=30, sigma_s=0.05,
+                     sigma_r=0.05):
+    """PointCloud::SmoothBilateral; a cloud without normals gets them from
+    EstimateNormals with upstream's defaults (KNN, 30) first."""
+    p = _positions(attrs)
+    n = p.shape[0]
+    if n == 0:
+        return _carried(attrs, positions=p.clone())
+    if sigma_s <= 0 or sigma_r <= 0:
+        raise ValueError("Sigma values must be positive.")
+    nrm = _normals(attrs, p, None)
+    if nrm is None:
+        nrm = torch.empty_like(p)
+        _lib.check(_lib.lib().o3dmi_pointcloud_estimate_normals(
+            _lib.ptr(p), n, TORCH_TO_O3DMI[p.dtype], 30, C.c_double(-1.0),
+            _lib.ptr(nrm), 0, stream()), "estimate_normals")
+    out = torch.empty_like(p)
+    _lib.check(_lib.lib().o3dmi_pointcloud_smooth_bilateral(
+        _lib.ptr(p), _lib.ptr(nrm), n, TORCH_TO_O3DMI[p.dtype],
+        C.c_double(radius), int(max_nn), C.c_double(sigma_s),
+        C.c_double(sigma_r), _lib.ptr(out), stream()), "smooth_bilateral")
+    return _carried(attrs, positions=out, normals=nrm)
+
+
+def compute_boundary_points(attrs, radius, max_nn=30, angle_threshold=90.0):
+    """PointCloud::ComputeBoundaryPoints -> (boundary cloud, mask)."""
+    p = _positions(attrs)
+    nrm = _normals(attrs, p, "PointCloud must have normals attribute to "
+                   "compute boundary points.")
+    n = p.shape[0]
+    mask = torch.zeros(n, dtype=torch.uint8, device=p.device)
+    m = C.c_int64(0)
+    _lib.check(_lib.lib().o3dmi_pointcloud_compute_boundary_points(
+        _lib.ptr(p), _lib.ptr(nrm), n, TORCH_TO_O3DMI[p.dtype],
+        C.c_double(radius), int(max_nn), C.c_double(angle_threshold),
+        _lib.ptr(mask), C.byref(m), stream()), "compute_boundary_points")
+    return _filtered(attrs, mask)
+
+
+def normalize_normals(attrs):
+    """PointCloud::NormalizeNormals; a cloud without normals is returned as
+    it is (upstream warns)."""
+    p = _positions(attrs)
+    nrm = _normals(attrs, p, None)
+    if nrm is None:
+        return dict(attrs)
+    nrm = nrm.clone()
+    _lib.check(_lib.lib().o3dmi_pointcloud_normalize_normals(
+        _lib.ptr(nrm), p.shape[0], TORCH_TO_O3DMI[p.dtype], stream()),
+        "normalize_normals")
+    return _carried(attrs, normals=nrm)
+
+
+def _vec3(v, name):
+    v = [float(x) for x in (v.tolist() if hasattr(v, "tolist") else v)]
+    if len(v) != 3:
+        raise ValueError("%s must have shape {3}" % name)
+    return (C.c_double * 3)(*v)
+
+
+def orient_normals_to_align_with_direction(attrs,
+                                           orientation_reference=(0.0, 0.0,
+                                                                  1.0)):
+    """PointCloud::OrientNormalsToAlignWithDirection."""
+    p = _positions(attrs)
+    nrm = _normals(attrs, p, "No normals in the PointCloud. Call "
+                   "EstimateNormals() first.").clone()
+    _lib.check(
+        _lib.lib().o3dmi_pointcloud_orient_normals_to_align_with_direction(
+            _lib.ptr(nrm), p.shape[0], TORCH_TO_O3DMI[p.dtype],
+            _vec3(orientation_reference, "orientation_reference"), stream()),
+        "orient_normals_to_align_with_direction")
+    return _carried(attrs, normals=nrm)
+
+
+def orient_normals_towards_camera_location(attrs,
+                                           camera_location=(0.0, 0.0, 0.0)):
+    """PointCloud::OrientNormalsTowardsCameraLocation."""
+    p = _positions(attrs)
+    nrm = _normals(attrs, p, "No normals in the PointCloud. Call "
+                   "EstimateNormals() first.").clone()
+    _lib.check(
+        _lib.lib().o3dmi_pointcloud_orient_normals_towards_camera_location(
+            _lib.ptr(p), _lib.ptr(nrm), p.shape[0], TORCH_TO_O3DMI[p.dtype],
+            _vec3(camera_location, "camera_location"), stream()),
+        "orient_normals_towards_camera_location")
+    return _carried(attrs, normals=nrm)

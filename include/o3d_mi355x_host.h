@@ -1176,6 +1176,13 @@ int64_t o3dmi_vbg_profile_distinct_blocks(const o3dmi_vbg_t* g);
  * results are the same either way. wait != 0 blocks until it has. */
 int o3dmi_vbg_division_forms(float voxel_size, float trunc_voxel_multiplier,
                              int wait);
+/* Diagnostics: how many frame-stream launches of this process ran their
+ * integrate role in a given form -- 0 = IEEE divisions, 1 = the short
+ * divisions, 2 = the short divisions without the per-frame range test of the
+ * projection's 1 / z (every pose of the group has |e[2][3]| >= 2^-36 and a
+ * third row bounded by 2^59). Results are the same in every form. Returns -1
+ * for any other `form`. */
+int64_t o3dmi_vbg_step_form_launches(int form);
 /* The same measurement per bracketed launch (any output may be null): HIP-event
  * duration (ms), block-frames, distinct blocks, and the map size (blocks
  * active) the launch's integrate role saw when it started. Returns the number

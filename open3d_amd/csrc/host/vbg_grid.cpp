@@ -335,6 +335,10 @@ int o3dmi_vbg_division_forms(float voxel_size, float trunc_voxel_multiplier,
     return PrefetchFastDivision(voxel_size * trunc_voxel_multiplier, wait != 0);
 }
 
+int64_t o3dmi_vbg_step_form_launches(int form) {
+    return (int64_t)StepFormLaunches(form);
+}
+
 // VoxelBlockGrid::To(device, copy) (VoxelBlockGrid.cpp, via
 // HashMap::To, core/hashmap/HashMap.cpp:230-255): the same grid on another
 // (or the same) device -- attribute layout and voxel size carried over, the

@@ -1,7 +1,9 @@
 // Host-side proofs behind the frame-step kernel's short per-voxel update
 // (IntegrateRoleWide's apply in vbg_stream.hip). Each holds for a whole launch;
 // a launch that fails one takes the IEEE-division form of the kernel, which
-// keeps every per-voxel test (same results, see vbg_stream.hip). Plain C++ with
+// keeps every per-voxel test (same results, see vbg_stream.hip); a launch that
+// passes those but fails RcpRangePoseOk keeps the short update with the range
+// test of the projection's reciprocal. Plain C++ with
 // no HIP dependency, so that tests/test_integrate_host_checks.py can compile
 // it on its own.
 #pragma once
@@ -61,6 +63,45 @@ inline bool SdfDivGuardRedundant(float depth_scale, float sdf_trunc) {
     const float min_depth = 1.0f / depth_scale;  // RN(1 / depth_scale)
     return min_depth >= 0x1p-75f && sdf_trunc >= kDivTiny &&
            std::isfinite(sdf_trunc);
+}
+
+// Bound kept on the third row of the rigid transform by RcpRangePoseOk: with
+// the float roundings on the way (three adds and four products, each
+// <= 1 + 2^-24) z stays below 2^60, the upper end of the verified range of
+// the projection's short reciprocal.
+constexpr double kRcpRowBound = 0x1p59;
+// Smallest |e[2][3]| RcpRangePoseOk accepts.
+constexpr float kRcpMinTranslation = 0x1p-36f;
+
+// The range test of the projection's 1 / z (RcpOutOfRange in vbg_stream.hip:
+// the short reciprocal is verified for [2^-60, 2^60], every other z takes the
+// IEEE division) is redundant for a launch whose poses pass this check. A
+// voxel with z <= 0 (or a NaN, which DepthFoldPoseOk excludes) is rejected by
+// the update whatever its projection was, and its gather address is made safe
+// by the in-image select, so only 0 < z outside the range matters.
+//   Upper end: |z| <= (|e20| + |e21| + |e22|) c + |e23| <= 2^59 in exact
+// arithmetic, c as in DepthFoldPoseOk; the roundings keep it below 2^60.
+//   Lower end: z leaves the transform as RN(a + t), t = e[2][3] and a the
+// float32 sum of the three products (((x e20) + y e21) + z e22: the kernel
+// adds the translation last). Suppose |t| >= 2^-36, z != 0 and |z| < 2^-60.
+// 2^-60 is a float and rounding is monotone, so |a + t| < 2^-60 and
+// |a| > |t| - 2^-60 >= 2^-37. A float of magnitude >= 2^-37 is a multiple of
+// 2^-60 (its ulp is at least 2^-37-23), so a + t is a multiple of 2^-60 of
+// magnitude below 2^-60: a + t = 0 and z = 0, a contradiction. Hence z is
+// zero, negative or at least 2^-60.
+// A pose with a smaller |e[2][3]| (the identity: the first frame of most runs)
+// fails the check and its launch keeps the range test.
+inline bool RcpRangePoseOk(const float e[3][4], float voxel_size,
+                           int resolution) {
+    if (!std::isfinite(voxel_size) || resolution <= 0) return false;
+    const double c = kFoldCoordPerRes * (double)resolution *
+                     std::fabs((double)voxel_size);
+    double s = 0.0;
+    for (int j = 0; j < 4; ++j) {
+        if (!std::isfinite(e[2][j])) return false;
+        s += std::fabs((double)e[2][j]) * (j < 3 ? c : 1.0);
+    }
+    return s <= kRcpRowBound && std::fabs(e[2][3]) >= kRcpMinTranslation;
 }
 
 }  // namespace o3dmi

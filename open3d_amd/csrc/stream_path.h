@@ -155,6 +155,12 @@ int LaunchFrameStep(o3dmi_hash* block_hash, const FrameFrontArgs* fronts,
                     int n_fronts, const IntegrateStreamArgs* integ,
                     hipStream_t s);
 
+// Diagnostics: launches of this process that carried an integrate role, by the
+// form it ran in -- 0 = IEEE divisions, 1 = the short divisions, 2 = the short
+// divisions with the reciprocal's range proven per launch (kProven). -1 for
+// any other `form`.
+long long StepFormLaunches(int form);
+
 // Starts (without waiting for it) the on-device proof that the integrate
 // role's short division forms are exact for this truncation distance; launches
 // use them once it has finished (vbg_stream.hip VerifyFastDivision).

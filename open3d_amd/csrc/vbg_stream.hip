@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "preload.h"
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -754,8 +755,16 @@ __device__ __forceinline__ f2 PkFma(f2 a, f2 b, f2 c) {
 // kLong (with kRaw): the chunk launch of the sliced path -- a work item applies
 // up to kChunkFrames frames (ChunkEntry::bits) to its register-resident voxels,
 // kChunk at a time; per-frame constants come from IntegParams::frame_tab.
+// kProven (the frame stream's records form with kDiv = 2 only): the range
+// test of the projection's 1 / z is redundant for the whole launch, proven by
+// the host from the group's poses (integrate_checks.h RcpRangePoseOk).
+// (The records' "has a colour" test is redundant too when the group was
+// prepared with identity tables; dropping it made the compiler copy the colour
+// state between the frames of a round, 44 more v_mov than the 16 v_cmp saved,
+// and measured -1.2 %: profiles/r9_README.md. It stays.)
 template <typename weight_t, typename color_t, bool kColor, int kDiv,
-          int kChunk, int kP, bool kRaw = false, bool kLong = false>
+          int kChunk, int kP, bool kRaw = false, bool kLong = false,
+          bool kProven = false>
 __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
                                                   const IntegParams& ip,
                                                   int wg, int n_wg,
@@ -783,6 +792,7 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
     // sdf / sdf_trunc (the host launches the IEEE-division form instead when
     // a proof of integrate_checks.h fails for the launch)
     constexpr bool kFold = kDiv >= 2 && !kRaw && !kLong;
+    static_assert(!kProven || kFold, "kProven is a form of the kFold update");
     float* __restrict__ tsdf_base = ip.tsdf;
     weight_t* __restrict__ weight_base = (weight_t*)ip.weight;
     color_t* __restrict__ color_base = (color_t*)ip.color;
@@ -1126,10 +1136,15 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
             // Camera::Project's 1 / z: the verified short reciprocal unless a
             // lane of the wave is outside its range. z is monotone along the
             // lane's 4 voxels, so the two end voxels decide.
+            // (kProven: no lane with z > 0 is outside it, RcpRangePoseOk)
             f2 inv_z[kP];
-            const bool out = RcpOutOfRange(R.zc[fk][0].x) ||
-                             RcpOutOfRange(R.zc[fk][kP - 1].y);
-            if (kDiv < 2 || __builtin_amdgcn_ballot_w64(out) != 0ull) {
+            bool ieee_rcp = kDiv < 2;
+            if constexpr (kDiv >= 2 && !kProven) {
+                const bool out = RcpOutOfRange(R.zc[fk][0].x) ||
+                                 RcpOutOfRange(R.zc[fk][kP - 1].y);
+                ieee_rcp = __builtin_amdgcn_ballot_w64(out) != 0ull;
+            }
+            if (ieee_rcp) {
 #pragma unroll
                 for (int p = 0; p < kP; ++p)
                     inv_z[p] = f2{1.0f / R.zc[fk][p].x, 1.0f / R.zc[fk][p].y};
@@ -1470,9 +1485,9 @@ static_assert(sizeof(StepParams) <= 4096, "kernel arguments are limited to 4 KB"
 #define O3DMI_RAW_WAVES 5
 #endif
 constexpr int kRawChunk = O3DMI_RAW_CHUNK;
-template <typename weight_t, typename color_t, bool kColor, int kDiv>
-__global__ void __launch_bounds__(256, 7)
-FrameStepKernel(StepParams sp) {
+template <typename weight_t, typename color_t, bool kColor, int kDiv,
+          bool kProven>
+__device__ __forceinline__ void FrameStep(const StepParams& sp) {
     const int b = (int)blockIdx.x;
     const int n_front_wg = sp.n_fronts * sp.front_wg;
     if (b < n_front_wg) {
@@ -1480,10 +1495,23 @@ FrameStepKernel(StepParams sp) {
         const FrontParams fp(sp.fshared, sp.front[f]);
         FrontRole(sp.hv, fp, b - f * sp.front_wg);
     } else {
-        IntegrateRoleWide<weight_t, color_t, kColor, kDiv, kGroupChunk, 1>(
+        IntegrateRoleWide<weight_t, color_t, kColor, kDiv, kGroupChunk, 1,
+                          false, false, kProven>(
                 sp.hv, sp.integ, b - n_front_wg, (int)gridDim.x - n_front_wg,
                 n_front_wg);
     }
+}
+template <typename weight_t, typename color_t, bool kColor, int kDiv>
+__global__ void __launch_bounds__(256, 7)
+FrameStepKernel(StepParams sp) {
+    FrameStep<weight_t, color_t, kColor, kDiv, false>(sp);
+}
+// The same launch with the integrate role in its kProven form (kDiv = 2):
+// LaunchFrameStep takes it when every pose of the group passes RcpRangePoseOk.
+template <typename weight_t, typename color_t, bool kColor, int kDiv>
+__global__ void __launch_bounds__(256, 7)
+FrameStepKernelProven(StepParams sp) {
+    FrameStep<weight_t, color_t, kColor, kDiv, true>(sp);
 }
 
 // The chunk launch of the sliced block-ownership path (sliced_path.h): the
@@ -1704,6 +1732,16 @@ static void CanonicalPrincipalPoint(Camera& c) {
     if (c.cy == 0.0f) c.cy = 0.0f;
 }
 
+// Launches that carried an integrate role, by the form it ran in (diagnostics,
+// StepFormLaunches): 0 = IEEE divisions, 1 = kDiv = 2, 2 = kProven.
+static std::atomic<long long> g_step_form_launches[3];
+
+long long StepFormLaunches(int form) {
+    return form >= 0 && form < 3
+                   ? g_step_form_launches[form].load(std::memory_order_relaxed)
+                   : -1;
+}
+
 int LaunchFrameStep(o3dmi_hash* bh, const FrameFrontArgs* fronts, int n_fronts,
                     const IntegrateStreamArgs* a, hipStream_t s) {
     O3DMI_REQUIRE((n_fronts > 0 && fronts) || a, "nothing to launch");
@@ -1715,6 +1753,7 @@ int LaunchFrameStep(o3dmi_hash* bh, const FrameFrontArgs* fronts, int n_fronts,
     int grid_dtype = O3DMI_U16;
     bool col = false;
     int fast_div = 0;
+    bool proven = false;
     static const double eye4[16] = {1, 0, 0, 0, 0, 1, 0, 0,
                                     0, 0, 1, 0, 0, 0, 0, 1};
     for (int i = 0; i < n_fronts; ++i) {
@@ -1788,12 +1827,18 @@ int LaunchFrameStep(o3dmi_hash* bh, const FrameFrontArgs* fronts, int n_fronts,
         // needs both proofs of integrate_checks.h for the whole launch: the
         // poses are checked frame by frame, but one rejected pose sends the
         // WHOLE group to the IEEE-division form (same bits, ~4 % slower)
+        // (the kProven form needs RcpRangePoseOk of every pose on top: a
+        // group with one pose that fails it -- the identity, say -- keeps the
+        // kDiv = 2 form as a whole)
         bool fold = SdfDivGuardRedundant(a->depth_scale, a->sdf_trunc);
+        bool rcp_ok = true;
         for (int f = 0; f < a->n_frames; ++f) {
             const Camera cf = Camera::Make(a->depth_intrinsic, a->extrinsic[f],
                                            a->voxel_size);
             fold = fold && DepthFoldPoseOk(cf.e, a->voxel_size, a->resolution,
                                            a->sdf_trunc);
+            rcp_ok = rcp_ok &&
+                     RcpRangePoseOk(cf.e, a->voxel_size, a->resolution);
             if (f == 0) {
                 ip.cam0 = cf;
                 CanonicalPrincipalPoint(ip.cam0);
@@ -1840,11 +1885,17 @@ int LaunchFrameStep(o3dmi_hash* bh, const FrameFrontArgs* fronts, int n_fronts,
         n_int_wg = (int)g;
         grid_dtype = a->grid_dtype;
         col = a->with_color && a->color != nullptr;
+        proven = fast_div == 2 && rcp_ok;
+        g_step_form_launches[proven ? 2 : (fast_div == 2 ? 1 : 0)].fetch_add(
+                1, std::memory_order_relaxed);
     }
     dim3 grid((unsigned)(n_fronts * sp.front_wg + n_int_wg)), block(256);
 #define O3DMI_LAUNCH_STEP(WT, VT, COLOR)                                      \
     do {                                                                      \
-        if (fast_div == 2)                                                    \
+        if (proven)                                                           \
+            hipLaunchKernelGGL((FrameStepKernelProven<WT, VT, COLOR, 2>),     \
+                               grid, block, 0, s, sp);                        \
+        else if (fast_div == 2)                                               \
             hipLaunchKernelGGL((FrameStepKernel<WT, VT, COLOR, 2>), grid,     \
                                block, 0, s, sp);                              \
         else                                                                  \

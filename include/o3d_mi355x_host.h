@@ -1183,6 +1183,13 @@ int o3dmi_vbg_division_forms(float voxel_size, float trunc_voxel_multiplier,
  * third row bounded by 2^59). Results are the same in every form. Returns -1
  * for any other `form`. */
 int64_t o3dmi_vbg_step_form_launches(int form);
+/* Diagnostics: the frame stream's block touch collects the block keys of one
+ * 16 x 16 tile of rays over all the frames of a launch and sends each distinct
+ * key through the hash once. This is the number of distinct keys it holds at
+ * most: before a frame that could take it further (a frame adds up to 1024)
+ * the keys collected so far are sent and the set starts empty. Results do not
+ * depend on it. */
+int32_t o3dmi_vbg_front_tile_key_limit(void);
 /* The same measurement per bracketed launch (any output may be null): HIP-event
  * duration (ms), block-frames, distinct blocks, and the map size (blocks
  * active) the launch's integrate role saw when it started. Returns the number

@@ -488,6 +488,7 @@ PROTOTYPES.update({
     "o3dmi_vbg_profile_distinct_blocks": (_i64, [_vp]),
     "o3dmi_vbg_division_forms": (_i32, [_f, _f, _i32]),
     "o3dmi_vbg_step_form_launches": (_i64, [_i32]),
+    "o3dmi_vbg_front_tile_key_limit": (_i32, []),
     "o3dmi_vbg_profile_launches": (_i64, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "o3dmi_rccl_available": (_i32, []),
     "o3dmi_rccl_unique_id": (_i32, [_vp]),

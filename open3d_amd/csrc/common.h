@@ -365,10 +365,11 @@ __device__ __forceinline__ bool LastArrival(int* tickets, int index,
     return s_last_arrival != 0;
 }
 
-// Marks `slot` as touched by frame `bit` of the frame group `stamp`. The word
-// holds (stamp << kTouchBits) | one bit per frame of the group; a word carrying
-// an older stamp is stale and is replaced. Returns true for exactly one caller per
-// (slot, stamp): the one that moved the word to this stamp.
+// Marks `slot` as touched by the frames in `bits` (one bit per frame of the
+// group) of the frame group `stamp`. The word holds (stamp << kTouchBits) | the
+// frame bits; a word carrying an older stamp is stale and is replaced. Returns
+// true for exactly one caller per (slot, stamp): the one that moved the word
+// to this stamp.
 constexpr int kTouchBits = 16;  // frames per group (stream_path.h kMaxGroup)
 __device__ __forceinline__ unsigned long long* TouchWord(const HashView& hv,
                                                          unsigned slot,
@@ -376,15 +377,15 @@ __device__ __forceinline__ unsigned long long* TouchWord(const HashView& hv,
     return hv.slot_touch + ((size_t)plane * ((size_t)hv.mask + 1) + slot);
 }
 __device__ __forceinline__ bool TouchSlot(const HashView& hv, unsigned slot,
-                                          unsigned long long stamp, int bit,
+                                          unsigned long long stamp,
+                                          unsigned long long bits,
                                           int plane = 0) {
     unsigned long long* w = TouchWord(hv, slot, plane);
     unsigned long long cur = *w;  // possibly stale; the CAS corrects it
     while (true) {
         const bool fresh = (cur >> kTouchBits) != stamp;
         const unsigned long long want =
-                fresh ? ((stamp << kTouchBits) | (1ull << bit))
-                      : (cur | (1ull << bit));
+                fresh ? ((stamp << kTouchBits) | bits) : (cur | bits);
         if (want == cur) return false;
         const unsigned long long old = atomicCAS(w, cur, want);
         if (old == cur) return fresh;

@@ -339,6 +339,8 @@ int64_t o3dmi_vbg_step_form_launches(int form) {
     return (int64_t)StepFormLaunches(form);
 }
 
+int32_t o3dmi_vbg_front_tile_key_limit(void) { return FrontTileKeyLimit(); }
+
 // VoxelBlockGrid::To(device, copy) (VoxelBlockGrid.cpp, via
 // HashMap::To, core/hashmap/HashMap.cpp:230-255): the same grid on another
 // (or the same) device -- attribute layout and voxel size carried over, the

@@ -160,6 +160,9 @@ int LaunchFrameStep(o3dmi_hash* block_hash, const FrameFrontArgs* fronts,
 // divisions with the reciprocal's range proven per launch (kProven). -1 for
 // any other `form`.
 long long StepFormLaunches(int form);
+// Distinct block keys a touch workgroup collects over the frames of a launch
+// before it flushes its set (vbg_stream.hip, kTileKeyLimit).
+int FrontTileKeyLimit();
 
 // Starts (without waiting for it) the on-device proof that the integrate
 // role's short division forms are exact for this truncation distance; launches

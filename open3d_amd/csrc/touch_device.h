@@ -95,16 +95,14 @@ struct TouchParams {
     float block_size, sdf_trunc, depth_scale, depth_max;
 };
 
-// Computes the 4 candidate block keys of strided pixel `workload_idx`
-// (VoxelBlockGridCPU.cpp:144-180). Returns false when the pixel is invalid.
-template <typename depth_t>
-__device__ __forceinline__ bool RayCandidates(const TouchParams& p,
-                                              const depth_t* __restrict__ depth,
-                                              int workload_idx, int (&xb)[4],
-                                              int (&yb)[4], int (&zb)[4]) {
-    int y = (workload_idx / p.cols_strided) * p.stride;
-    int x = (workload_idx % p.cols_strided) * p.stride;
-    float d = (float)depth[(int64_t)y * p.cols + x] / p.depth_scale;
+// The 4 candidate block keys of the ray through pixel (x, y) whose raw depth
+// value is `raw` (VoxelBlockGridCPU.cpp:144-180). Returns false when the depth
+// is invalid.
+__device__ __forceinline__ bool RayCandidatesOfDepth(const TouchParams& p,
+                                                     int x, int y, float raw,
+                                                     int (&xb)[4], int (&yb)[4],
+                                                     int (&zb)[4]) {
+    float d = raw / p.depth_scale;
     if (!(d > 0 && d < p.depth_max)) return false;
 
     float x_c, y_c, z_c, x_g, y_g, z_g;
@@ -125,6 +123,18 @@ __device__ __forceinline__ bool RayCandidates(const TouchParams& p,
         t += t_step;
     }
     return true;
+}
+
+// The same for strided pixel `workload_idx` of a depth image.
+template <typename depth_t>
+__device__ __forceinline__ bool RayCandidates(const TouchParams& p,
+                                              const depth_t* __restrict__ depth,
+                                              int workload_idx, int (&xb)[4],
+                                              int (&yb)[4], int (&zb)[4]) {
+    int y = (workload_idx / p.cols_strided) * p.stride;
+    int x = (workload_idx % p.cols_strided) * p.stride;
+    return RayCandidatesOfDepth(p, x, y, (float)depth[(int64_t)y * p.cols + x],
+                                xb, yb, zb);
 }
 
 

@@ -11,8 +11,9 @@
 //
 // FrameStepKernel runs the front roles of group g+1 and the integrate role of
 // group g in ONE launch: the front role is a latency chain of hash atomics on
-// ~75 workgroups per frame, the integrate role a bandwidth-bound sweep over
-// ~4x10^3 work items; side by side they cost max() instead of sum().
+// one workgroup per 16 x 16 tile of rays (for all frames of the group) plus
+// ~75 prepare workgroups per frame, the integrate role a sweep over ~4x10^3
+// work items; side by side they cost max() instead of sum().
 
 #include <cmath>
 
@@ -69,8 +70,20 @@ struct PrepParams {
     bool with_color;
 };
 
-// LDS key set of one 16 x 16 ray tile (<= 1024 candidates).
+// LDS key set of one 16 x 16 ray tile: key -> one bit per frame of the launch.
+// A frame adds at most 4 candidates per ray of the tile; the set is flushed
+// before a frame that could take it past kTileKeyLimit distinct keys
+// (TouchRole), so its probe loops always find an empty slot (1/32 of the
+// slots at least). A flush hands its keys out through a dense list of
+// kTileDense slot indices, half the table at a time where the set holds more
+// than that.
 constexpr int kTileKeys = 2048;
+constexpr int kTileKeyLimit = kTileKeys - kTileKeys / 32;
+constexpr int kTileDense = 1024;
+static_assert(kTileKeyLimit < kTileKeys && kTileKeys / 2 <= kTileDense &&
+                      4 * 256 <= kTileKeyLimit,
+              "the tile set must keep an empty slot, hold one frame's keys, "
+              "and half of it must fit the dense list");
 
 // Front roles of one launch: what the frames of the group share, and what
 // differs per frame (kernel arguments are limited to 4 KB; a group has up to
@@ -89,7 +102,6 @@ struct FrontShared {
     ReadyEntry* ready;
     int* tickets;
     int* touch_status;
-    int n_touch_total;  // touch workgroups of the whole group (all frames)
     unsigned long long group_stamp;
     int touch_plane;
     int n_touch_wg, n_prep_wg;
@@ -120,7 +132,6 @@ inline bool SameGroup(const FrontShared& a, const FrontShared& b) {
            a.list_capacity == b.list_capacity && a.out_count == b.out_count &&
            a.ready == b.ready && a.tickets == b.tickets &&
            a.touch_status == b.touch_status &&
-           a.n_touch_total == b.n_touch_total &&
            a.group_stamp == b.group_stamp && a.touch_plane == b.touch_plane &&
            a.n_touch_wg == b.n_touch_wg && a.n_prep_wg == b.n_prep_wg;
 }
@@ -132,9 +143,9 @@ struct FrontFrame {
     int group_bit;
 };
 
-// A frame's front parameters assembled from the two (uniform: scalar loads).
-struct FrontParams {
-    TouchParams p;
+// A frame's prepare parameters assembled from the two (uniform: scalar loads).
+struct PrepFrameParams {
+    TouchParams p;  // sizes, intrinsics, scales (the pose is not used)
     PrepParams pp;
     const uint16_t* depth;
     const uint8_t* color;
@@ -144,126 +155,237 @@ struct FrontParams {
     bool prep_identity;
     float inv_depth_scale;
     PixelRec* recs;
-    FrameBlock* list;
-    int64_t list_capacity;
-    int* out_count;
-    ReadyEntry* ready;
-    int* tickets;
-    int* touch_status;
-    int n_touch_total;
-    unsigned long long group_stamp;
-    int group_bit;
-    int touch_plane;
-    int n_touch_wg, n_prep_wg;
-    __device__ __forceinline__ FrontParams(const FrontShared& s,
-                                           const FrontFrame& f)
+    int n_prep_wg;
+    __device__ __forceinline__ PrepFrameParams(const FrontShared& s,
+                                               const FrontFrame& f)
         : p(s.p), pp(s.pp), depth(f.depth), color(f.color),
           col_lut(s.col_lut), row_lut(s.row_lut),
           depth_div_short(s.depth_div_short), prep_identity(s.prep_identity),
-          inv_depth_scale(s.inv_depth_scale), recs(f.recs), list(s.list),
-          list_capacity(s.list_capacity), out_count(s.out_count),
-          ready(s.ready), tickets(s.tickets), touch_status(s.touch_status),
-          n_touch_total(s.n_touch_total),
-          group_stamp(s.group_stamp), group_bit(f.group_bit),
-          touch_plane(s.touch_plane), n_touch_wg(s.n_touch_wg),
-          n_prep_wg(s.n_prep_wg) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) p.cam.e[i][j] = f.pose[i][j];
-    }
+          inv_depth_scale(s.inv_depth_scale), recs(f.recs),
+          n_prep_wg(s.n_prep_wg) {}
 };
 
-// `wg` = index of this workgroup within one frame's front role,
-// [0, n_touch_wg + n_prep_wg). Workgroups [0, n_touch_wg) run the fused
-// touch + activate, emitting {slot, key} entries for blocks not yet listed in
-// this group; the rest run the per-pixel prepare pass.
-__device__ __forceinline__ void FrontRole(const HashView& hv,
-                                          const FrontParams& fp, int wg) {
-    const TouchParams& p = fp.p;
-    const PrepParams& pp = fp.pp;
-    const uint16_t* __restrict__ depth = fp.depth;
-    const uint8_t* __restrict__ color = fp.color;
-    PixelRec* __restrict__ recs = fp.recs;
-    FrameBlock* __restrict__ list = fp.list;
-    const int n_touch_wg = fp.n_touch_wg;
-    if (wg < n_touch_wg) {
-        // Block touch of a 16 x 16 tile of rays (DepthTouchCPU,
-        // VoxelBlockGridCPU.cpp:144-180). The ~1000 candidate keys of a tile
-        // are a few dozen distinct blocks: they are de-duplicated in an LDS
-        // set first (LDS atomics, ~100 ns), and only the distinct keys go
-        // through the chain of global atomics -- insert into the block hash,
-        // frame bit in the touch word, list append -- one lane per key, all
-        // keys of the tile in flight together. (One lane per ray walked that
-        // chain four times in sequence, behind a wave-wide leader election
-        // per candidate: ~20 us per wave, as long as the whole integrate
-        // sweep it is supposed to hide behind.)
-        __shared__ unsigned long long tile_keys[kTileKeys];
-        for (int e = threadIdx.x; e < kTileKeys; e += blockDim.x)
-            tile_keys[e] = kEmptyKey;
-        __syncthreads();
-        const int tiles_x = (p.cols_strided + 15) >> 4;
-        const int ty = wg / tiles_x, tx = wg - ty * tiles_x;
-        const int rx = tx * 16 + (threadIdx.x & 15);
-        const int ry = ty * 16 + (threadIdx.x >> 4);
-        if (rx < p.cols_strided && ry < p.rows_strided) {
-            int xb[4], yb[4], zb[4];
-            if (RayCandidates(p, depth, ry * p.cols_strided + rx, xb, yb, zb)) {
+// Touch role: workgroup `wg` of [0, n_touch_wg) owns one 16 x 16 tile of rays
+// in ALL the frames of the launch and runs the fused touch + activate for it,
+// emitting {slot, key} entries for blocks not yet listed in this group.
+//
+// The frames of a group are consecutive views: tile t of every frame hits
+// nearly the same few dozen blocks. The candidate keys of all frames (<= 1024
+// per frame, DepthTouchCPU, VoxelBlockGridCPU.cpp:144-180) are collected in
+// one LDS set that maps a key to the OR of the bits of the frames that hit it
+// (LDS atomics, ~100 ns), and only the distinct keys go through the chain of
+// global atomics -- insert into the block hash, frame bits in the touch word,
+// list append -- ONCE for the group: the set's occupied slots are compacted
+// into a dense list and one lane takes one key, all keys in flight together,
+// a few dozen keys being a single pass of one wave. (One workgroup per tile
+// AND frame walked that chain up to 8 times per frame, once per 256-slot
+// stripe of its set, and the 12 frames of a group CASed the same touch words
+// 12 times over: ~30 us per workgroup in a wave slot the integrate role of
+// the same launch was waiting for.)
+//
+// A stream whose frames do not overlap can collect more keys than the set
+// holds: before a frame that could take the set past kTileKeyLimit it is
+// flushed (chain, then cleared) -- at worst once per frame, as before.
+struct TileSet {
+    unsigned long long keys[kTileKeys];
+    unsigned masks[kTileKeys / 2];  // 16 frame bits per slot, two slots a word
+    unsigned short dense[kTileDense];
+    // Keys a frame added to the set, frame f in word f % 3: a word is read
+    // (by every thread, into its running total: the flush decision must be
+    // the same in all of them) behind the barrier that ends its frame, while
+    // the next frame already counts into the next word, and is zeroed one
+    // barrier later.
+    int frame_keys[3];
+    int pos[2];  // dense-list length of a flush pass (alternating)
+};
+
+// Runs the global chain for every key of the set, one key per lane. All
+// threads of the workgroup call it, after a barrier behind the last insert,
+// with the number of keys in the set. `pass` counts the flush passes of the
+// workgroup (selects pos[]); unless `last` the set is empty and usable again
+// on return.
+__device__ __forceinline__ void FlushTileSet(const HashView& hv,
+                                             const FrontShared& fs,
+                                             TileSet& ts, int count, int& pass,
+                                             bool last) {
+    if (count == 0) return;  // uniform: nothing was inserted since the flush
+    const int tid = (int)threadIdx.x;
+    const int lane = tid & 63;
+    const int span = count <= kTileDense ? kTileKeys : kTileKeys / 2;
+    for (int base = 0; base < kTileKeys; base += span) {
+        int* pos = &ts.pos[pass & 1];
+        // occupied slots of [base, base + span) -> dense list: a ballot per
+        // 256-slot stripe, ONE LDS atomic per wave for its total
+        unsigned occ = 0;
+        int total = 0;
 #pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    if (s > 0 && xb[s] == xb[s - 1] && yb[s] == yb[s - 1] &&
-                        zb[s] == zb[s - 1])
-                        continue;
-                    if (!KeyInRange(xb[s], yb[s], zb[s])) {
-                        atomicOr(&hv.counters[1], kErrKeyRange);
-                        continue;
-                    }
-                    const unsigned long long k = PackKey(xb[s], yb[s], zb[s]);
-                    if (!hv.Owns(k)) continue;  // another rank's block
-                    unsigned h = HashKey(k) & (kTileKeys - 1);
-                    while (true) {  // <= 1024 keys in 2048 slots: terminates
-                        unsigned long long cur = tile_keys[h];
-                        if (cur == k) break;
-                        if (cur == kEmptyKey) {
-                            cur = atomicCAS(&tile_keys[h], kEmptyKey, k);
-                            if (cur == kEmptyKey || cur == k) break;
-                        }
-                        h = (h + 1) & (kTileKeys - 1);
-                    }
-                }
+        for (int j = 0; j < kTileKeys / 256; ++j) {
+            if (j * 256 < span) {
+                const bool o = ts.keys[base + j * 256 + tid] != kEmptyKey;
+                occ |= (unsigned)o << j;
+                total += __popcll(__ballot(o));
+            }
+        }
+        int at = 0;
+        if (lane == 0 && total) at = atomicAdd(pos, total);
+        at = __builtin_amdgcn_readfirstlane(at);
+#pragma unroll
+        for (int j = 0; j < kTileKeys / 256; ++j) {
+            if (j * 256 < span) {
+                const bool o = (occ >> j) & 1u;
+                const unsigned long long b = __ballot(o);
+                if (o)
+                    ts.dense[at + __popcll(b & ((1ull << lane) - 1ull))] =
+                            (unsigned short)(base + j * 256 + tid);
+                at += __popcll(b);
             }
         }
         __syncthreads();
-        for (int e = threadIdx.x; e < kTileKeys; e += blockDim.x) {
-            const unsigned long long k = tile_keys[e];
-            if (k == kEmptyKey) continue;
+        const int n = *pos;
+        const bool final_pass = last && base + span >= kTileKeys;
+        // (last used before the barrier above, next behind the one below)
+        if (tid == 0) ts.pos[(pass + 1) & 1] = 0;
+        for (int i = tid; i < n; i += (int)blockDim.x) {
+            const unsigned e = ts.dense[i];
+            const unsigned long long k = ts.keys[e];
+            const unsigned sh = (e & 1u) * 16u;
+            const unsigned long long bits = (ts.masks[e >> 1] >> sh) & 0xffffu;
+            if (!final_pass) {
+                ts.keys[e] = kEmptyKey;
+                atomicAnd(&ts.masks[e >> 1], ~(0xffffu << sh));
+            }
             const int x = (int)((k >> 42) & 0x1FFFFFull) - kKeyBias;
             const int y = (int)((k >> 21) & 0x1FFFFFull) - kKeyBias;
             const int z = (int)(k & 0x1FFFFFull) - kKeyBias;
             unsigned slot;
-            InsertKey<true>(hv, x, y, z, slot, (int)fp.group_stamp);
-            if (TouchSlot(hv, slot, fp.group_stamp, fp.group_bit,
-                          fp.touch_plane)) {
-                int o = atomicAdd(fp.out_count, 1);
-                if (o < fp.list_capacity) {
+            InsertKey<true>(hv, x, y, z, slot, (int)fs.group_stamp);
+            if (TouchSlot(hv, slot, fs.group_stamp, bits, fs.touch_plane)) {
+                int o = atomicAdd(fs.out_count, 1);
+                if (o < fs.list_capacity) {
                     // write-through (two 8-byte stores): the ready-list
-                    // compaction below reads the entry from another
-                    // workgroup of this launch
-                    unsigned long long* e =
-                            reinterpret_cast<unsigned long long*>(&list[o]);
-                    __hip_atomic_store(
-                            e, (unsigned long long)(unsigned)slot |
-                                       ((unsigned long long)(unsigned)x << 32),
-                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(
-                            e + 1, (unsigned long long)(unsigned)y |
-                                           ((unsigned long long)(unsigned)z << 32),
-                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    // compaction of the last touch workgroup reads the entry
+                    // from another workgroup of this launch
+                    using u64 = unsigned long long;
+                    u64* le = reinterpret_cast<u64*>(&fs.list[o]);
+                    __hip_atomic_store(le,
+                                       (u64)slot | ((u64)(unsigned)x << 32),
+                                       __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(le + 1,
+                                       (u64)(unsigned)y |
+                                               ((u64)(unsigned)z << 32),
+                                       __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
                 } else {
                     atomicOr(&hv.counters[1], kErrCapacity);
                 }
             }
         }
+        ++pass;
+        // Waves without a key of this pass (all but one, usually) wait here
+        // -- or, behind the last pass, at the ticket's barrier -- without
+        // issuing anything.
+        if (!final_pass) __syncthreads();
+    }
+}
+
+__device__ __forceinline__ void TouchRole(const HashView& hv,
+                                          const FrontShared& fp,
+                                          const FrontFrame* fronts,
+                                          int n_fronts, int wg) {
+    FrameBlock* __restrict__ list = fp.list;
+    {
+        TouchParams p = fp.p;
+        __shared__ TileSet ts;
+        for (int e = threadIdx.x; e < kTileKeys; e += blockDim.x)
+            ts.keys[e] = kEmptyKey;
+        for (int e = threadIdx.x; e < kTileKeys / 2; e += blockDim.x)
+            ts.masks[e] = 0u;
+        if (threadIdx.x < 3) ts.frame_keys[threadIdx.x] = 0;
+        if (threadIdx.x < 2) ts.pos[threadIdx.x] = 0;
+        __syncthreads();
+        // The touch role is the launch's longest dependent chain -- the
+        // frames' candidate arithmetic in sequence, the hash chain, the
+        // ticket, the ready list -- in a few hundred waves beside integrate
+        // waves that raise their own priority (up to 3): at priority 0 it
+        // was what the fused launch waited for (profiles/r10_ab_runs.txt).
+        __builtin_amdgcn_s_setprio(3);
+        const int tiles_x = (p.cols_strided + 15) >> 4;
+        const int ty = wg / tiles_x, tx = wg - ty * tiles_x;
+        const int rx = tx * 16 + (threadIdx.x & 15);
+        const int ry = ty * 16 + (threadIdx.x >> 4);
+        const bool in_tile = rx < p.cols_strided && ry < p.rows_strided;
+        // what one frame can add: 4 candidates per ray of the tile
+        const int frame_max = 4 * min(16, p.cols_strided - tx * 16) *
+                              min(16, p.rows_strided - ty * 16);
+        const int px = rx * p.stride, py = ry * p.stride;
+        const int64_t pix = in_tile ? (int64_t)py * p.cols + px : 0;
+        // this ray's depth in the next three frames, loads in flight (a raw
+        // depth of 0 is invalid: what a lane outside the image carries)
+        const auto raw_depth = [&](int f) -> unsigned {
+            const uint16_t* __restrict__ d =
+                    fronts[f < n_fronts ? f : n_fronts - 1].depth;
+            return in_tile ? (unsigned)d[pix] : 0u;
+        };
+        unsigned d0 = raw_depth(0), d1 = raw_depth(1), d2 = raw_depth(2);
+        int pass = 0;
+        int held = 0;         // keys in the set behind the last finished frame
+        int w = 0;            // word of the frame being inserted: f % 3
+        // (not unrolled: the role shares its registers with the integrate
+        // role's 72)
+#pragma unroll 1
+        for (int f = 0; f < n_fronts; ++f) {
+            const unsigned raw = d0;
+            d0 = d1;
+            d1 = d2;
+            d2 = raw_depth(f + 3);
+            if (f > 0) {
+                __syncthreads();  // the inserts of frame f - 1
+                held += ts.frame_keys[w];
+                w = w == 2 ? 0 : w + 1;
+                if (threadIdx.x == 0) ts.frame_keys[w == 2 ? 0 : w + 1] = 0;
+                if (held + frame_max > kTileKeyLimit) {
+                    FlushTileSet(hv, fp, ts, held, pass, false);
+                    held = 0;
+                }
+            }
+            const FrontFrame& ff = fronts[f];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) p.cam.e[i][j] = ff.pose[i][j];
+            const unsigned fbit = 1u << ff.group_bit;
+            int xb[4], yb[4], zb[4];
+            if (!RayCandidatesOfDepth(p, px, py, (float)raw, xb, yb, zb))
+                continue;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                if (s > 0 && xb[s] == xb[s - 1] && yb[s] == yb[s - 1] &&
+                    zb[s] == zb[s - 1])
+                    continue;
+                if (!KeyInRange(xb[s], yb[s], zb[s])) {
+                    atomicOr(&hv.counters[1], kErrKeyRange);
+                    continue;
+                }
+                const unsigned long long k = PackKey(xb[s], yb[s], zb[s]);
+                if (!hv.Owns(k)) continue;  // another rank's block
+                unsigned h = HashKey(k) & (kTileKeys - 1);
+                while (true) {  // <= kTileKeyLimit keys: terminates
+                    unsigned long long cur = ts.keys[h];
+                    if (cur == k) break;
+                    if (cur == kEmptyKey) {
+                        cur = atomicCAS(&ts.keys[h], kEmptyKey, k);
+                        if (cur == kEmptyKey) atomicAdd(&ts.frame_keys[w], 1);
+                        if (cur == kEmptyKey || cur == k) break;
+                    }
+                    h = (h + 1) & (kTileKeys - 1);
+                }
+                atomicOr(&ts.masks[h >> 1], fbit << ((h & 1u) * 16u));
+            }
+        }
+        __syncthreads();
+        held += ts.frame_keys[w];
+        FlushTileSet(hv, fp, ts, held, pass, true);
         // The ready list (stream_path.h ReadyEntry). The frame bits of a block
         // are final when EVERY touch workgroup of the group -- all its frames
         // -- has finished, so the workgroups take a ticket (their entries,
@@ -272,11 +394,9 @@ __device__ __forceinline__ void FrontRole(const HashView& hv,
         // entries: one lane per block, list entry -> buffer index + touch
         // word (the two dependent round trips an integrate work item would
         // otherwise spend on its header) -> one 16-byte entry. This happens
-        // at the tail of the front roles, which finish early in a fused
-        // launch; the entries are read in the NEXT launch.
-        if (fp.ready &&
-            LastArrival(fp.tickets, fp.group_bit * n_touch_wg + wg,
-                        fp.n_touch_total)) {
+        // at the tail of the touch role; the entries are read in the NEXT
+        // launch, so the tail is off this launch's integrate role's path.
+        if (fp.ready && LastArrival(fp.tickets, wg, fp.n_touch_wg)) {
             int n = __hip_atomic_load(fp.out_count, __ATOMIC_RELAXED,
                                       __HIP_MEMORY_SCOPE_AGENT);
             if (n > fp.list_capacity) n = (int)fp.list_capacity;
@@ -378,14 +498,22 @@ __device__ __forceinline__ void FrontRole(const HashView& hv,
                     fp.ready[i] = make_entry(i);
             }
         }
-        return;
     }
-    // Prepare pass: the voxel-independent sub-expressions of the integrate
-    // lambda (VoxelBlockGridImpl.h:258-262 depth, :277-289 colour pixel).
+}
+
+// Prepare role: workgroup `wg` of the [0, n_prep_wg) of one frame. The
+// voxel-independent sub-expressions of the integrate lambda
+// (VoxelBlockGridImpl.h:258-262 depth, :277-289 colour pixel).
+__device__ __forceinline__ void PrepareRole(const PrepFrameParams& fp, int wg) {
+    const TouchParams& p = fp.p;
+    const PrepParams& pp = fp.pp;
+    const uint16_t* __restrict__ depth = fp.depth;
+    const uint8_t* __restrict__ color = fp.color;
+    PixelRec* __restrict__ recs = fp.recs;
     const int n_px = p.rows * p.cols;
     const int n_wg = fp.n_prep_wg;
     // sentinel behind the image: what a voxel outside the image reads
-    if (wg == n_touch_wg && threadIdx.x == 0) {
+    if (wg == 0 && threadIdx.x == 0) {
         PixelRec r;
         r.d = -__builtin_inff();
         r.rgba = 0u;
@@ -403,7 +531,7 @@ __device__ __forceinline__ void FrontRole(const HashView& hv,
         const int n_groups = n_px >> 2;  // cols % 4 == 0 (checked on the host)
         const int gstep = n_wg * blockDim.x;
         constexpr int kG = 4;
-        for (int g0 = (wg - n_touch_wg) * blockDim.x + threadIdx.x;
+        for (int g0 = wg * blockDim.x + threadIdx.x;
              g0 < n_groups; g0 += kG * gstep) {
             uint2 dq[kG];
             unsigned cw[kG][3];
@@ -469,7 +597,7 @@ __device__ __forceinline__ void FrontRole(const HashView& hv,
         const int* __restrict__ row_lut = fp.row_lut;
         const int step = n_wg * blockDim.x;
         const int step_v = step / p.cols, step_u = step - step_v * p.cols;
-        for (int first = (wg - n_touch_wg) * blockDim.x + threadIdx.x;
+        for (int first = wg * blockDim.x + threadIdx.x;
              first < n_px; first += 4 * step) {
             int idx[4], uc[4], vc[4];
             float df[4];
@@ -531,7 +659,7 @@ __device__ __forceinline__ void FrontRole(const HashView& hv,
         }
         return;
     }
-    for (int i = (wg - n_touch_wg) * blockDim.x + threadIdx.x; i < n_px;
+    for (int i = wg * blockDim.x + threadIdx.x; i < n_px;
          i += n_wg * blockDim.x) {
         const int vi = i / p.cols;
         const int ui = i - vi * p.cols;
@@ -1462,7 +1590,7 @@ struct StepParams {
     FrontFrame front[kMaxGroup];
     IntegParams integ;
     int n_fronts;
-    int front_wg;  // workgroups per front role
+    int n_front_wg;  // n_touch_wg + n_fronts * n_prep_wg
 };
 static_assert(sizeof(StepParams) <= 4096, "kernel arguments are limited to 4 KB");
 
@@ -1488,17 +1616,50 @@ constexpr int kRawChunk = O3DMI_RAW_CHUNK;
 template <typename weight_t, typename color_t, bool kColor, int kDiv,
           bool kProven>
 __device__ __forceinline__ void FrameStep(const StepParams& sp) {
+    const int n_front_wg = sp.n_front_wg;
+    const int n_touch_wg = sp.fshared.n_touch_wg;
+    const int n_prep_wg = sp.fshared.n_prep_wg;
+    // b -> role: touch tile t, prepare workgroup r (of all frames' n_prep_wg
+    // each) or integrate workgroup i of n_int. The tile workgroups of the
+    // touch role come first (its chain is the launch's longest and must start
+    // at once: DESIGN 8), then groups of 8 workgroups: every fifth is a prepare
+    // group while there are any, the others integrate (the host pads both
+    // roles to whole groups; a group of 8 keeps the integrate role's XCD deal,
+    // whose first workgroup is workgroup n_touch_wg of the grid).
+    int t = -1, r = -1, i = -1, n_int = 0;
     const int b = (int)blockIdx.x;
-    const int n_front_wg = sp.n_fronts * sp.front_wg;
-    if (b < n_front_wg) {
-        const int f = b / sp.front_wg;
-        const FrontParams fp(sp.fshared, sp.front[f]);
-        FrontRole(sp.hv, fp, b - f * sp.front_wg);
+    if (b < n_touch_wg) {
+        t = b;
+    } else {
+        const int g = (b - n_touch_wg) >> 3, l = (b - n_touch_wg) & 7;
+        const int n_groups = ((int)gridDim.x - n_touch_wg) >> 3;
+        const int npg = (n_front_wg - n_touch_wg + 7) >> 3;
+        n_int = (n_groups - npg) * 8;
+        int pg = -1, before;
+        if (5 * npg <= n_groups) {
+            before = g / 5 < npg ? g / 5 : npg;
+            if (g % 5 == 4 && g / 5 < npg) pg = g / 5;
+        } else {
+            before = g < npg ? g : npg;
+            if (g < npg) pg = g;
+        }
+        if (pg >= 0) {
+            r = pg * 8 + l;
+            if (r >= n_front_wg - n_touch_wg) return;  // padding
+        } else {
+            i = (g - before) * 8 + l;
+        }
+    }
+    if (t >= 0) {
+        TouchRole(sp.hv, sp.fshared, sp.front, sp.n_fronts, t);
+    } else if (r >= 0) {
+        const int f = r / n_prep_wg;
+        const PrepFrameParams fp(sp.fshared, sp.front[f]);
+        PrepareRole(fp, r - f * n_prep_wg);
     } else {
         IntegrateRoleWide<weight_t, color_t, kColor, kDiv, kGroupChunk, 1,
-                          false, false, kProven>(
-                sp.hv, sp.integ, b - n_front_wg, (int)gridDim.x - n_front_wg,
-                n_front_wg);
+                          false, false, kProven>(sp.hv, sp.integ, i, n_int,
+                                                 n_touch_wg);
     }
 }
 template <typename weight_t, typename color_t, bool kColor, int kDiv>
@@ -1736,6 +1897,8 @@ static void CanonicalPrincipalPoint(Camera& c) {
 // StepFormLaunches): 0 = IEEE divisions, 1 = kDiv = 2, 2 = kProven.
 static std::atomic<long long> g_step_form_launches[3];
 
+int FrontTileKeyLimit() { return kTileKeyLimit; }
+
 long long StepFormLaunches(int form) {
     return form >= 0 && form < 3
                    ? g_step_form_launches[form].load(std::memory_order_relaxed)
@@ -1802,10 +1965,9 @@ int LaunchFrameStep(o3dmi_hash* bh, const FrameFrontArgs* fronts, int n_fronts,
         // 16 pixels per prepare lane
         fs.n_prep_wg = (f->rows * f->cols + kBlock * 16 - 1) / (kBlock * 16);
         if (fs.n_prep_wg < 1) fs.n_prep_wg = 1;
-        fs.n_touch_total = fs.n_touch_wg * n_fronts;
         if (i == 0) {
             sp.fshared = fs;
-            sp.front_wg = fs.n_touch_wg + fs.n_prep_wg;
+            sp.n_front_wg = fs.n_touch_wg + n_fronts * fs.n_prep_wg;
         } else {
             // the frames of a launch are one group: everything but the pose
             // and the image / record pointers is shared
@@ -1889,7 +2051,11 @@ int LaunchFrameStep(o3dmi_hash* bh, const FrameFrontArgs* fronts, int n_fronts,
         g_step_form_launches[proven ? 2 : (fast_div == 2 ? 1 : 0)].fetch_add(
                 1, std::memory_order_relaxed);
     }
-    dim3 grid((unsigned)(n_fronts * sp.front_wg + n_int_wg)), block(256);
+    // whole groups of 8 for the prepare and the integrate role
+    const int n_touch = n_fronts > 0 ? sp.fshared.n_touch_wg : 0;
+    dim3 grid((unsigned)(n_touch + ((sp.n_front_wg - n_touch + 7) & ~7) +
+                         ((n_int_wg + 7) & ~7))),
+            block(256);
 #define O3DMI_LAUNCH_STEP(WT, VT, COLOR)                                      \
     do {                                                                      \
         if (proven)                                                           \

@@ -95,7 +95,8 @@ __global__ void TouchActivateKernel(HashView hv, TouchParams p,
             if (WaveLeaderForKey(k, ok)) {
                 unsigned slot;
                 InsertKey<true>(hv, xb[s], yb[s], zb[s], slot);
-                if (TouchSlot(hv, slot, (unsigned long long)frame_stamp, 0)) {
+                if (TouchSlot(hv, slot, (unsigned long long)frame_stamp,
+                              1ull)) {
                     int o = atomicAdd(out_count, 1);
                     if (o < out_capacity) out_slots[o] = (int)slot;
                     else atomicOr(&hv.counters[1], kErrCapacity);

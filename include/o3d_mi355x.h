@@ -758,6 +758,36 @@ int o3dmi_ransac_score(const o3dmi_nns_t* nns, const void* source_dev,
                        int64_t* corres_inliers_dev, void* scratch_dev,
                        o3dmi_stream_t stream);
 
+/* ---- SegmentPlane: the sample function and the scoring step ---------------
+ * (legacy geometry/PointCloudSegmentation.cpp:157-279, run by ONE thread over
+ * a stateless sample stream; the whole operator is
+ * o3dmi_pointcloud_segment_plane in o3d_mi355x_host.h.)
+ *
+ * o3dmi_plane_sample: the ransac_n (<= 8) point indices of iteration i >= 0
+ * over n >= ransac_n points, a pure function on the host and on the device.
+ * Draw k is uniform over the n - k points not drawn yet: the counter hash of
+ * rule 1 above with counter (i, k), mapped to [0, n - k) by the high half of
+ * the 128-bit product with n - k, then shifted past the earlier picks taken in
+ * ascending order. Exact sampling without replacement, no rejection loop
+ * (upstream draws from its global Mersenne engine until distinct). Arguments
+ * outside these ranges write nothing. */
+void o3dmi_plane_sample(uint64_t seed, int64_t iteration, int ransac_n,
+                        int64_t n, int64_t* indices_out);
+
+/* For b planes {b,4} (float64, a x + b y + c z + d) against the whole cloud:
+ * distance = |((a x + b y) + c z) + d| in float64 on the coordinates widened
+ * to float64, no FMA; counts_out_dev int64 {b} = points with distance <
+ * distance_threshold (strict), d2_sums_out_dev float64 {b} = the sum of
+ * distance^2 over them, added in index order within tiles of 512 points and
+ * the tile sums in tile order (the same bits on every run). Lane = plane, the
+ * point loads are wave-uniform. distance_threshold <= 0, b < 0, n < 0 or a
+ * NULL pointer: O3DMI_ERR_INVALID_ARG. Waits for the stream before it returns
+ * (it owns the per-tile partials). */
+int o3dmi_plane_score(const void* points_dev, int64_t n, int dtype,
+                      const double* planes_dev, int64_t b,
+                      double distance_threshold, int64_t* counts_out_dev,
+                      double* d2_sums_out_dev, o3dmi_stream_t stream);
+
 /* EstimateColorGradientsUsing{Hybrid,KNN}SearchCUDA after the search
  * (t/geometry/kernel/PointCloudImpl.h:1067-1290): per point, least squares of
  * the intensity over its neighbours projected on the tangent plane plus the

@@ -830,6 +830,77 @@ int o3dmi_pointcloud_remove_statistical_outliers(
         double std_ratio, uint8_t* mask_out_dev, void* avg_distances_out_dev,
         double* stats_out, int64_t* m_out, o3dmi_stream_t stream);
 
+/* PointCloud::ClusterDBSCAN (t/geometry/PointCloud.cpp:1634-1648 -> legacy
+ * geometry/PointCloudCluster.cpp:21-97; upstream has no device path). The
+ * labels are those of upstream's sequential loop, the same on every run:
+ * neighbourhood of i = the points with d2 < eps^2 (strict, i included, d2 and
+ * eps^2 in the point dtype: the radius rule of o3dmi_nns_*); a core point has
+ * >= min_points of them (0 and 1 make every point core). A cluster is a
+ * connected component of core points under "within eps"; clusters are
+ * numbered 0, 1, ... in ascending order of their LOWEST CORE INDEX (the order
+ * in which upstream's outer loop meets their seeds). A non-core point with a
+ * core neighbour takes the smallest label among its core neighbours
+ * (upstream expands clusters one after another, never relabels a label >= 0
+ * and overwrites an earlier -1); every other point is -1. Upstream widens
+ * Float32 clouds to float64 before the search, so a pair within rounding of
+ * eps may differ.
+ * labels_out_dev int32 {n}; num_clusters_out / num_noise_out (optional, host)
+ * = number of clusters / of -1 labels. n == 0: O3DMI_OK, both 0. eps <= 0,
+ * min_points < 0, a NULL pointer or a NaN / Inf coordinate:
+ * O3DMI_ERR_INVALID_ARG with the labels untouched. n < 2^27. Synchronises. */
+int o3dmi_pointcloud_cluster_dbscan(const void* points_dev, int64_t n,
+                                    int dtype, double eps, int64_t min_points,
+                                    int32_t* labels_out_dev,
+                                    int64_t* num_clusters_out,
+                                    int64_t* num_noise_out,
+                                    o3dmi_stream_t stream);
+
+/* What upstream's SegmentPlane only logs. */
+typedef struct {
+    int64_t best_iteration;        /* -1: none                               */
+    int64_t iterations_counted;    /* iterations that formed a plane and took
+                                      part                                   */
+    int64_t final_break_iteration; /* the bound when the loop ended          */
+    double fitness;                /* of the best iteration: inliers / n     */
+    double inlier_rmse;            /* sqrt(sum d^2 / inliers)                */
+} o3dmi_segment_plane_info_t;
+
+/* PointCloud::SegmentPlane (t/geometry/PointCloud.cpp:1650-1666 -> legacy
+ * geometry/PointCloudSegmentation.cpp:157-279). The result is that of
+ * upstream's loop run by ONE thread in iteration order, whatever the batch
+ * size, over the samples of o3dmi_plane_sample(seed, i, ...):
+ *  - hypothesis, float64 on the widened coordinates: ransac_n == 3
+ *    ComputeTrianglePlane, else GetPlaneFromPoints on the sample; norms are
+ *    sqrt((x x + y y) + z z). A zero plane is skipped and NOT counted.
+ *  - score: o3dmi_plane_score; fitness = count / n, rmse = sqrt(sum / count).
+ *    Upstream adds d^2 in index order and leaves the dot product's order to
+ *    Eigen: a rounding difference at the threshold and in the rmse.
+ *  - iteration i takes part iff iterations_counted <= break_iteration as the
+ *    iterations before it left them; a new best needs a strictly better
+ *    (fitness, then rmse), so the lower iteration keeps a tie; then
+ *    break_iteration = trunc(min(log(1 - p) / log(1 - fitness^ransac_n),
+ *    num_iterations)), 0 when fitness == 1, and num_iterations when the
+ *    denominator is 0 or the quotient is not a finite number >= 0 (upstream's
+ *    cast is undefined there). Work a batch did past the bound is dropped.
+ *  - final: the inliers of the best plane, ascending, in inliers_out_dev
+ *    (int64, room for n), *m_out of them; plane_out = GetPlaneFromPoints over
+ *    them (centroid and centred sums as float64 partials in a fixed tree, the
+ *    closed form on the host). No iteration formed a plane with an inlier:
+ *    plane (0,0,0,0), m = 0, O3DMI_OK (upstream returns NaNs).
+ * probability <= 0 or > 1, ransac_n < 3, n < ransac_n, num_iterations < 1,
+ * distance_threshold <= 0 or a NaN / Inf coordinate: O3DMI_ERR_INVALID_ARG
+ * with nothing written (upstream checks none of the last three);
+ * ransac_n > 8: O3DMI_ERR_UNSUPPORTED. info_out may be NULL. Synchronises; per
+ * batch the host reads back {count, sum, valid} of every hypothesis. */
+int o3dmi_pointcloud_segment_plane(const void* points_dev, int64_t n,
+                                   int dtype, double distance_threshold,
+                                   int ransac_n, int64_t num_iterations,
+                                   double probability, uint64_t seed,
+                                   double plane_out[4],
+                                   int64_t* inliers_out_dev, int64_t* m_out,
+                                   o3dmi_segment_plane_info_t* info_out,
+                                   o3dmi_stream_t stream);
+
 /* The per-fragment step of slac::PreprocessPointClouds (t/pipelines/slac/
  * SLACOptimizer.cpp:47-57). voxel_size > 0: VoxelDownSample ->
  * RemoveStatisticalOutliers(20, 2.0) -> EstimateNormals (KNN, 30); otherwise

@@ -174,6 +174,12 @@ class RansacInfoC(C.Structure):
                 ("num_batches", _i64)]
 
 
+class SegmentPlaneInfoC(C.Structure):
+    _fields_ = [("best_iteration", _i64), ("iterations_counted", _i64),
+                ("final_break_iteration", _i64), ("fitness", _d),
+                ("inlier_rmse", _d)]
+
+
 class IcpAttributes(C.Structure):
     _fields_ = [("source_normals", _vp), ("source_colors", _vp),
                 ("target_colors", _vp), ("target_color_gradients", _vp),
@@ -355,6 +361,16 @@ PROTOTYPES.update({
     "o3dmi_pointcloud_remove_statistical_outliers": (
         _i32, [_vp, _i64, _i32, _i64, _d, _vp, _vp, _dp, C.POINTER(_i64),
                _vp]),
+    "o3dmi_pointcloud_cluster_dbscan": (
+        _i32, [_vp, _i64, _i32, _d, _i64, _vp, C.POINTER(_i64),
+               C.POINTER(_i64), _vp]),
+    "o3dmi_plane_sample": (None, [C.c_uint64, _i64, _i32, _i64,
+                                  C.POINTER(_i64)]),
+    "o3dmi_plane_score": (_i32, [_vp, _i64, _i32, _vp, _i64, _d, _vp, _vp,
+                                 _vp]),
+    "o3dmi_pointcloud_segment_plane": (
+        _i32, [_vp, _i64, _i32, _d, _i32, _i64, _d, C.c_uint64, _dp, _vp,
+               C.POINTER(_i64), C.POINTER(SegmentPlaneInfoC), _vp]),
     "o3dmi_pointcloud_smooth_laplacian": (
         _i32, [_vp, _i64, _i32, _i64, _d, _i32, _i32, _vp, _vp]),
     "o3dmi_pointcloud_smooth_taubin": (

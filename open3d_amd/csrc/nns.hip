@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "nns.h"
+#include "pointcloud_segment.h"
 #include "pointcloud_smooth_device.h"
 #include "preload.h"
 
@@ -785,6 +786,125 @@ RadiusCountKernel(NnsView<T> nv, const T* __restrict__ q, int64_t nq,
         for (int m = 32; m > 0; m >>= 1) c += __shfl_xor(c, m);
         if ((threadIdx.x & 63) == 0) counts[i] = c;
     }
+}
+
+// ---- ClusterDBSCAN's two sweeps (pointcloud_segment.h) -------------------------
+// Point j is a core point when counts[j] >= need. parent[] is a forest over
+// the core points in which a non-root's parent is always a SMALLER index:
+// a root is only ever hooked under a smaller root, with one CAS, so the root
+// of a finished tree is the lowest core index of its component whatever order
+// the waves ran in.
+
+// Follows parent[] to a root. The reads are relaxed agent-scope atomic loads:
+// other waves hook roots while this one walks, and a plain load may be served
+// from a line another XCD has since changed. What is read may still be out of
+// date (a root that has been hooked meanwhile); the CAS in DbscanUnite decides.
+__device__ __forceinline__ int DbscanFind(int* parent, int x) {
+    while (true) {
+        const int p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED,
+                                        __HIP_MEMORY_SCOPE_AGENT);
+        if (p == x) return x;
+        x = p;  // p < x: the walk ends
+    }
+}
+
+// Unites the trees of a and b. Nothing here waits for another wave: the loop
+// repeats only after a failed CAS, which means some other hook of that root
+// succeeded (at most n - 1 hooks exist), and it continues from the value the
+// CAS returned.
+__device__ __forceinline__ void DbscanUnite(int* parent, int a, int b) {
+    while (true) {
+        a = DbscanFind(parent, a);
+        b = DbscanFind(parent, b);
+        if (a == b) return;
+        const int hi = a > b ? a : b, lo = a > b ? b : a;
+        const int old = atomicCAS(&parent[hi], hi, lo);
+        if (old == hi) return;
+        a = old;  // hi was hooked under `old` < hi by somebody else
+        b = lo;
+    }
+}
+
+struct UnionSink {
+    const int* counts;
+    int* parent;
+    int need;
+    int self;
+    template <typename T>
+    __device__ __forceinline__ void Push(T, int j, T, T, T) {
+        if (j != kNoIndex && j < self && counts[j] >= need)
+            DbscanUnite(parent, self, j);
+    }
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kCoopBlock)
+DbscanUnionKernel(NnsView<T> nv, const T* __restrict__ q, int64_t nq,
+                  const int* __restrict__ counts, int need,
+                  int* __restrict__ parent) {
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t i = wave; i < nq; i += n_waves) {
+        if (counts[i] < need) continue;  // wave-uniform
+        const T qq[3] = {q[3 * i + 0], q[3 * i + 1], q[3 * i + 2]};
+        long long cx, cy, cz;
+        CellOf(qq, nv.inv_cell, cx, cy, cz);
+        UnionSink sink = {counts, parent, need, (int)i};
+        GatherCells<T, true>(nv, qq, cx, cy, cz, cx - 1, cx + 1, cy - 1, cy + 1,
+                             cz - 1, cz + 1, 0, sink);
+    }
+}
+
+// The smallest cluster label among a lane's core candidates.
+struct MinLabelSink {
+    const int* counts;
+    const int* root;
+    const int64_t* cluster;
+    int need;
+    int best;
+    template <typename T>
+    __device__ __forceinline__ void Push(T, int j, T, T, T) {
+        if (j != kNoIndex && counts[j] >= need) {
+            const int l = (int)cluster[root[j]];
+            best = l < best ? l : best;
+        }
+    }
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kCoopBlock)
+DbscanLabelKernel(NnsView<T> nv, const T* __restrict__ q, int64_t nq,
+                  const int* __restrict__ counts, int need,
+                  const int* __restrict__ root,
+                  const int64_t* __restrict__ cluster, int* __restrict__ labels,
+                  unsigned long long* __restrict__ noise) {
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    unsigned long long n_noise = 0;  // wave-uniform
+    for (int64_t i = wave; i < nq; i += n_waves) {
+        const int c = counts[i];
+        int label = -1;
+        if (c >= need) {
+            label = (int)cluster[root[i]];
+        } else if (c > 1) {  // somebody besides the point itself is in range
+            const T qq[3] = {q[3 * i + 0], q[3 * i + 1], q[3 * i + 2]};
+            long long cx, cy, cz;
+            CellOf(qq, nv.inv_cell, cx, cy, cz);
+            MinLabelSink sink = {counts, root, cluster, need, kNoIndex};
+            GatherCells<T, true>(nv, qq, cx, cy, cz, cx - 1, cx + 1, cy - 1,
+                                 cy + 1, cz - 1, cz + 1, 0, sink);
+            int m = sink.best;
+#pragma unroll
+            for (int w = 32; w > 0; w >>= 1) {
+                const int o = __shfl_xor(m, w);
+                m = o < m ? o : m;
+            }
+            label = m == kNoIndex ? -1 : m;
+        }
+        if ((threadIdx.x & 63) == 0) labels[i] = label;
+        n_noise += label < 0 ? 1 : 0;
+    }
+    if ((threadIdx.x & 63) == 0 && n_noise) atomicAdd(noise, n_noise);
 }
 
 // Candidates at or below the floor pair were emitted in an earlier round.
@@ -2049,4 +2169,47 @@ int o3dmi::KnnSearchSmoothOp(const void* points_dev, int64_t n, int dtype,
                   "knn search: unknown output policy");
     return KnnSearchRun(points_dev, n, points_dev, n, dtype, knn, nullptr,
                         nullptr, nullptr, nullptr, &op, (o3dmi_stream_t)s);
+}
+
+int o3dmi::DbscanUnionSweep(const o3dmi_nns* nns, const void* points_dev,
+                            int64_t n, const int32_t* counts_dev, int need,
+                            int32_t* parent_dev, hipStream_t s) {
+    O3DMI_REQUIRE(nns && points_dev && counts_dev && parent_dev,
+                  "null argument");
+    if (n <= 0) return O3DMI_OK;
+    const dim3 grid(GridFor(n, kCoopBlock / 64, kCUs * 16)), block(kCoopBlock);
+    if (nns->dtype == O3DMI_F64)
+        hipLaunchKernelGGL(DbscanUnionKernel<double>, grid, block, 0, s,
+                           MakeView<double>(nns), (const double*)points_dev, n,
+                           counts_dev, need, parent_dev);
+    else
+        hipLaunchKernelGGL(DbscanUnionKernel<float>, grid, block, 0, s,
+                           MakeView<float>(nns), (const float*)points_dev, n,
+                           counts_dev, need, parent_dev);
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
+int o3dmi::DbscanLabelSweep(const o3dmi_nns* nns, const void* points_dev,
+                            int64_t n, const int32_t* counts_dev, int need,
+                            const int32_t* root_dev,
+                            const int64_t* cluster_dev, int32_t* labels_dev,
+                            unsigned long long* noise_dev, hipStream_t s) {
+    O3DMI_REQUIRE(nns && points_dev && counts_dev && root_dev && cluster_dev &&
+                          labels_dev && noise_dev,
+                  "null argument");
+    if (n <= 0) return O3DMI_OK;
+    const dim3 grid(GridFor(n, kCoopBlock / 64, kCUs * 16)), block(kCoopBlock);
+    if (nns->dtype == O3DMI_F64)
+        hipLaunchKernelGGL(DbscanLabelKernel<double>, grid, block, 0, s,
+                           MakeView<double>(nns), (const double*)points_dev, n,
+                           counts_dev, need, root_dev, cluster_dev, labels_dev,
+                           noise_dev);
+    else
+        hipLaunchKernelGGL(DbscanLabelKernel<float>, grid, block, 0, s,
+                           MakeView<float>(nns), (const float*)points_dev, n,
+                           counts_dev, need, root_dev, cluster_dev, labels_dev,
+                           noise_dev);
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
 }

@@ -1,6 +1,6 @@
-"""Mirror of t::geometry::PointCloud's selection, filter, smoothing, boundary
-and normal-orientation methods (t/geometry/PointCloud.cpp:435-494, 650-854,
-986-1050, 1074-1203) on the HIP backend.
+"""Mirror of t::geometry::PointCloud's selection, filter, smoothing, boundary,
+normal-orientation and segmentation methods (t/geometry/PointCloud.cpp:435-494,
+650-854, 986-1050, 1074-1203, 1634-1666) on the HIP backend.
 
 A cloud is a dict of CUDA attribute tensors with "positions" ({N,3} Float32 or
 Float64) required; every other attribute has N rows of any width and dtype
@@ -340,3 +340,49 @@ def orient_normals_towards_camera_location(attrs,
             _vec3(camera_location, "camera_location"), stream()),
         "orient_normals_towards_camera_location")
     return _carried(attrs, normals=nrm)
+
+
+# ---- segmentation ------------------------------------------------------------------
+
+def cluster_dbscan(attrs, eps, min_points, return_counts=False):
+    """PointCloud::ClusterDBSCAN -> Int32 {N} labels (-1 = noise), the labels
+    of upstream's sequential loop; with return_counts also (clusters, noise)."""
+    p = _positions(attrs)
+    n = p.shape[0]
+    labels = torch.empty(n, dtype=torch.int32, device=p.device)
+    clusters, noise = C.c_int64(0), C.c_int64(0)
+    _lib.check(_lib.lib().o3dmi_pointcloud_cluster_dbscan(
+        _lib.ptr(p), n, TORCH_TO_O3DMI[p.dtype], C.c_double(eps),
+        int(min_points), _lib.ptr(labels), C.byref(clusters), C.byref(noise),
+        stream()), "cluster_dbscan")
+    if return_counts:
+        return labels, clusters.value, noise.value
+    return labels
+
+
+def segment_plane(attrs, distance_threshold=0.01, ransac_n=3,
+                  num_iterations=100, probability=0.99999999, seed=0,
+                  return_info=False):
+    """PointCloud::SegmentPlane -> (plane Float64 {4} on the cloud's device,
+    inliers Int64 {M} ascending); with return_info also a dict(best_iteration,
+    iterations_counted, final_break_iteration, fitness, inlier_rmse)."""
+    p = _positions(attrs)
+    n = p.shape[0]
+    inliers = torch.empty(n, dtype=torch.int64, device=p.device)
+    plane = (C.c_double * 4)(0.0, 0.0, 0.0, 0.0)
+    m = C.c_int64(0)
+    info = _lib.SegmentPlaneInfoC()
+    _lib.check(_lib.lib().o3dmi_pointcloud_segment_plane(
+        _lib.ptr(p), n, TORCH_TO_O3DMI[p.dtype], C.c_double(distance_threshold),
+        int(ransac_n), int(num_iterations), C.c_double(probability),
+        C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), plane, _lib.ptr(inliers),
+        C.byref(m), C.byref(info), stream()), "segment_plane")
+    model = torch.tensor(list(plane), dtype=torch.float64, device=p.device)
+    out = inliers[:m.value]
+    if return_info:
+        return model, out, dict(
+            best_iteration=info.best_iteration,
+            iterations_counted=info.iterations_counted,
+            final_break_iteration=info.final_break_iteration,
+            fitness=info.fitness, inlier_rmse=info.inlier_rmse)
+    return model, out

@@ -869,6 +869,19 @@ __device__ __forceinline__ f2 PkFma(f2 a, f2 b, f2 c) {
     return __builtin_elementwise_fma(a, b, c);
 }
 
+// Two floats in [0, 65536) -> their uint16 values (truncated toward zero, the
+// float -> uint16 store conversion) in one word: the second conversion writes
+// the upper half of the first one's register (sub-dword destination select)
+// instead of a register of its own and a v_perm / v_and_or to merge the two.
+__device__ __forceinline__ unsigned PackU16(float lo, float hi) {
+    unsigned r = (unsigned)lo;
+    asm("v_cvt_u32_f32_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE "
+        "src0_sel:DWORD"
+        : "+v"(r)
+        : "v"(hi));
+    return r;
+}
+
 // kP = voxel pairs per lane: 1 (2 x-consecutive voxels per lane, 72 registers,
 // 7 waves per SIMD; 4 voxels per lane -- kP = 2, ~127 registers -- measured 9 %
 // slower, profiles/r2q, and is no longer instantiated).
@@ -941,12 +954,10 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
         }
     }
 
-    const int res = ip.resolution;
-    const int res3 = res * res * res;
-    const int quads_per_row = res >> kVShift;
-    const int n_quads = res3 >> kVShift;
-    const int parts = (n_quads + 255) >> 8;
-    const int res_shift = ip.res_shift;  // log2(res) or -1
+    // (the block geometry itself -- res, res3, ... -- is a work item's: below)
+    const int parts =
+            (((ip.resolution * ip.resolution * ip.resolution) >> kVShift) +
+             255) >> 8;
     int frame_blocks = 0;  // lane 0 of part 0 counts block-frames
 
     // XCD-aware deal: this workgroup's XCD, its rank among the role's
@@ -966,7 +977,6 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
     const unsigned sentinel_off =
             (unsigned)(ip.rows * ip.cols) * (unsigned)sizeof(PixelRec);
     const unsigned row_bytes = (unsigned)ip.cols * (unsigned)sizeof(PixelRec);
-    const float vscale = ip.cam0.scale;
     const float fx = ip.cam0.fx, fyk = ip.cam0.fy;
     const float cx = ip.cam0.cx, cy = ip.cam0.cy;
     const unsigned u_max_bits = __float_as_uint(ip.cols - 1.0f);
@@ -980,6 +990,23 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
     // uneven item times better than a static stride, and the prefetched
     // header costs registers the colour form does not have.)
     for (int64_t m = rank; m < n_items; m += n_on_xcd) {
+        int opaque = 0;  // a zero the optimiser cannot see through
+        asm volatile("" : "+s"(opaque));
+        // What a work item needs ONCE -- the block geometry, the frame
+        // count, the header's source -- it reads from the argument block
+        // itself (ipi: scalar loads behind the opaque zero) and derives in
+        // scalar arithmetic. A workgroup has about one item: taken as
+        // constants of the item loop, these values were two dozen scalar
+        // registers spilled to lanes of a vector register at the start of
+        // every workgroup and read back one v_readlane at a time inside the
+        // item. What the frames use (ip) stays in scalar registers.
+        const IntegParams& ipi = *(&ip + opaque);
+        const int res = ipi.resolution;
+        const int res3 = res * res * res;
+        const int quads_per_row = res >> kVShift;
+        const int n_quads = res3 >> kVShift;
+        const int res_shift = ipi.res_shift;  // log2(res) or -1
+        const float vscale = ipi.cam0.scale;
         int64_t kb;
         int part;
         if (res_shift >= 0) {  // parts is a power of two as well
@@ -988,8 +1015,14 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
             kb = m >> ps;
             part = (int)(m & ((1 << ps) - 1));
         } else {
-            kb = m / parts;
-            part = (int)(m - kb * parts);
+            // (+ opaque here and in the lane map below: the divisors of a
+            // resolution that is no power of two are worked out where they are
+            // used -- taken as loop constants, their reciprocals are some 30
+            // vector instructions and a dozen held registers at the start of
+            // EVERY workgroup, for a path that power-of-two grids never take)
+            const int n_parts = parts + opaque;
+            kb = m / n_parts;
+            part = (int)(m - kb * n_parts);
         }
         const int64_t b = first_b + (kb << 3);
         unsigned long long item_t0 = 0ull;
@@ -1038,9 +1071,9 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
                 else if (n_set >= ip.n_frames / 4) __builtin_amdgcn_s_setprio(1);
                 else __builtin_amdgcn_s_setprio(0);
             }
-        } else if (ip.ready) {
+        } else if (ipi.ready) {
             // ONE round trip: the ready entry the group's front roles left
-            const ReadyEntry re = ip.ready[b];
+            const ReadyEntry re = ipi.ready[b];
             const unsigned klo = __builtin_amdgcn_readfirstlane((unsigned)re.key);
             const unsigned khi =
                     __builtin_amdgcn_readfirstlane((unsigned)(re.key >> 32));
@@ -1068,7 +1101,7 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
                         : 0u);
         }
         const int64_t block_base = (int64_t)block_idx * res3;
-        if (!kLong && part == 0 && threadIdx.x == 0 && ip.prof_frame_blocks)
+        if (!kLong && part == 0 && threadIdx.x == 0 && ipi.prof_frame_blocks)
             frame_blocks += __popc(bits);
         if constexpr (!kLong) {
             // The group's items get the kLong form's issue priority by frame
@@ -1076,52 +1109,103 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
             // the rounds' gathers overlapped, the many-frame items' VALU work
             // is what the launch's tail waits for.
             const int n_set = __popc(bits);
-            if (n_set >= 3 * ip.n_frames / 4) __builtin_amdgcn_s_setprio(3);
-            else if (n_set >= ip.n_frames / 2) __builtin_amdgcn_s_setprio(2);
-            else if (n_set >= ip.n_frames / 4) __builtin_amdgcn_s_setprio(1);
+            if (n_set >= 3 * ipi.n_frames / 4) __builtin_amdgcn_s_setprio(3);
+            else if (n_set >= ipi.n_frames / 2) __builtin_amdgcn_s_setprio(2);
+            else if (n_set >= ipi.n_frames / 4) __builtin_amdgcn_s_setprio(1);
             else __builtin_amdgcn_s_setprio(0);
         }
-        int opaque = 0;  // a zero the optimiser cannot see through
-        asm volatile("" : "+s"(opaque));
-
-        const int q = (part << 8) + threadIdx.x;
-        if (q >= n_quads || bits == 0u) continue;
-        int qx, yv, zv;
-        int lin_q = q;  // index of the lane's first voxel / kV in the block
-        if (res_shift - kVShift >= 2 && ip.cube) {
-            // Lane -> voxel by a permutation of q's bits: the 64 lanes of a
-            // wave take a compact (4 << kVShift) x 4 x 4 cube of the block
-            // instead of a (res x 8 x 1) slab, so that one gather instruction
-            // touches the image rows of a 4-voxel-high patch, not those of a
-            // slab res voxels long (the vector memory pipeline takes a cycle
-            // per distinct cache line of an instruction). Any bijection gives
+        if (bits == 0u) continue;
+        // The lane's first voxel: block coordinates (x0, yi, zi) and index in
+        // the block, the index split into a wave-uniform part (lin_s, folded
+        // into the scalar base addresses below) and a lane part (lin_v).
+        int x0, yi, zi;
+        int lin_s = 0;   // / kV
+        unsigned lin_v;  // / kV
+        if (res_shift - kVShift >= 2 && ipi.cube) {
+            // Lane -> voxel by a permutation of q's bits (q = part << 8 |
+            // threadIdx.x): the 64 lanes of a wave take a compact
+            // (4 << kVShift) x 4 x 4 cube of the block instead of a
+            // (res x 8 x 1) slab, so that one gather instruction touches the
+            // image rows of a 4-voxel-high patch, not those of a slab res
+            // voxels long (the vector memory pipeline takes a cycle per
+            // distinct cache line of an instruction). Any bijection gives
             // the same grid: voxels are independent.
-            const int nx = res_shift - kVShift;  // bits of qx (>= 2: res >= 8)
-            const unsigned uq = (unsigned)q;
-            unsigned rest = uq >> 6;
+            // Only q's low 6 bits differ between the lanes of a wave, and they
+            // are the low 2 bits of qx, y and z whatever the resolution: which
+            // cube of the block the wave takes is scalar arithmetic, and a
+            // lane adds three 2-bit fields to it. (n_quads is a multiple of
+            // 256 here: no lane of the last part is past the block.)
+            // (+ opaque: the masks and shifts below are scalar arithmetic per
+            // item; computed once per workgroup they are kept in spilled
+            // scalar registers, a v_readlane each to get back)
+            const int rs = res_shift + opaque;
+            const int nx = rs - kVShift;  // bits of qx (>= 2: res >= 8)
+            unsigned rest = ((unsigned)part << 2) |
+                            (unsigned)__builtin_amdgcn_readfirstlane(
+                                    (int)(threadIdx.x >> 6));
             const unsigned qx_hi = rest & ((1u << (nx - 2)) - 1u);
             rest >>= (nx - 2);
-            const unsigned y_hi = rest & ((1u << (res_shift - 2)) - 1u);
-            rest >>= (res_shift - 2);
-            qx = (int)((uq & 3u) | (qx_hi << 2));
-            yv = (int)(((uq >> 2) & 3u) | (y_hi << 2));
-            zv = (int)(((uq >> 4) & 3u) | (rest << 2));
-            lin_q = (((zv << res_shift) | yv) << nx) | qx;
-        } else if (res_shift >= 0) {
-            qx = q & (quads_per_row - 1);
-            const int row = q >> (res_shift - kVShift);
-            yv = row & (res - 1);
-            zv = row >> res_shift;
+            const unsigned y_hi = rest & ((1u << (rs - 2)) - 1u);
+            rest >>= (rs - 2);
+            // (| opaque: computed here, per item -- hoisted out of the item
+            // loop the lane's fields hold registers the rounds need)
+            const unsigned tid = threadIdx.x | (unsigned)opaque;
+            const unsigned qx_lo = tid & 3u;
+            const unsigned y_lo = (tid >> 2) & 3u;
+            const unsigned z_lo = (tid >> 4) & 3u;
+            x0 = (xb * res + (int)(qx_hi << (2 + kVShift))) +
+                 (int)(qx_lo << kVShift);
+            yi = (yb * res + (int)(y_hi << 2)) + (int)y_lo;
+            zi = (zb * res + (int)(rest << 2)) + (int)z_lo;
+            lin_s = (int)(((((rest << 2) << rs) | (y_hi << 2)) << nx) |
+                          (qx_hi << 2));
+            lin_v = (((z_lo << rs) | y_lo) << nx) | qx_lo;
         } else {
-            qx = q % quads_per_row;
-            const int row = q / quads_per_row;
-            yv = row % res;
-            zv = row / res;
+            const int q = (part << 8) + threadIdx.x;
+            if (q >= n_quads) continue;
+            int qx, yv, zv;
+            if (res_shift >= 0) {
+                qx = q & (quads_per_row - 1);
+                const int row = q >> (res_shift - kVShift);
+                yv = row & (res - 1);
+                zv = row >> res_shift;
+            } else {
+                const int qpr = quads_per_row + opaque, r = res + opaque;
+                qx = q % qpr;
+                const int row = q / qpr;
+                yv = row % r;
+                zv = row / r;
+            }
+            x0 = xb * res + (qx << kVShift);
+            yi = yb * res + yv;
+            zi = zb * res + zv;
+            lin_v = (unsigned)q;
         }
-        const int x0 = xb * res + (qx << kVShift);
-        const float fy = (float)(yb * res + yv);
-        const float fz = (float)(zb * res + zv);
-        const int64_t lin0 = block_base + ((int64_t)lin_q << kVShift);
+        const float fy = (float)yi;
+        const float fz = (float)zi;
+        // The state's addresses as a wave-uniform 64-bit base (scalar
+        // arithmetic) plus the lane's 32-bit byte offset inside the block: one
+        // vector instruction per attribute where 64-bit lane addresses took
+        // thirteen for the three. The stores work theirs out again (zero =
+        // the opaque zero) from lin_v: the one register kept across the
+        // rounds, where three 64-bit lane addresses were six.
+        const int64_t item0 = block_base + ((int64_t)lin_s << kVShift);
+        const auto tsdf_at = [&](int zero) {
+            return reinterpret_cast<char*>(tsdf_base + item0 + zero) +
+                   ((lin_v + (unsigned)zero) << kVShift) * 4u;
+        };
+        const auto weight_at = [&](int zero) {
+            return reinterpret_cast<char*>(weight_base + item0 + zero) +
+                   ((lin_v + (unsigned)zero) << kVShift) *
+                           (unsigned)sizeof(weight_t);
+        };
+        const auto color_at = [&](int zero) {
+            // (24-bit multiply: lin_v < res^3 / 2 <= 2^23, the host refuses
+            // resolutions above kMaxIntegrateResolution)
+            return reinterpret_cast<char*>(color_base + 3 * (item0 + zero)) +
+                   __umul24(lin_v + (unsigned)zero,
+                            (3u << kVShift) * (unsigned)sizeof(color_t));
+        };
 
         // 1. voxel state, widened to float once per work item. A uint16
         // weight / colour is an exact float; between the frames of the group
@@ -1129,25 +1213,22 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
         // zero = the float -> uint16 store conversion of a non-negative value
         // below 65536; the weight's wrap at 65536 = what the uint16 store
         // keeps of it). Voxel pair p = voxels 2p, 2p + 1 of the lane.
-        const TVec t4 = *reinterpret_cast<const TVec*>(tsdf_base + lin0);
+        const TVec t4 = *reinterpret_cast<const TVec*>(tsdf_at(0));
         float ts[kV];
         float wf[kV];
         float cf[kV][3];
 #pragma unroll
         for (int v = 0; v < kV; ++v) ts[v] = t4.v[v];
-        {
-            const WVec w4 = *reinterpret_cast<const WVec*>(weight_base + lin0);
+        const WVec w4 = *reinterpret_cast<const WVec*>(weight_at(0));
 #pragma unroll
-            for (int v = 0; v < kV; ++v) wf[v] = (float)w4.v[v];
-            if constexpr (kColor) {
-                const CVec c12 =
-                        *reinterpret_cast<const CVec*>(color_base + 3 * lin0);
+        for (int v = 0; v < kV; ++v) wf[v] = (float)w4.v[v];
+        CVec c12 = {};
+        if constexpr (kColor) {
+            c12 = *reinterpret_cast<const CVec*>(color_at(0));
 #pragma unroll
-                for (int v = 0; v < kV; ++v)
+            for (int v = 0; v < kV; ++v)
 #pragma unroll
-                    for (int i = 0; i < 3; ++i)
-                        cf[v][i] = (float)c12.v[3 * v + i];
-            }
+                for (int i = 0; i < 3; ++i) cf[v][i] = (float)c12.v[3 * v + i];
         }
         // Facts of the whole work item, wave-uniform (one ballot each, kept
         // in scalar registers; apply takes ONE scalar branch on them per
@@ -1162,20 +1243,32 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
         //     keeps the multiply + add.
         //   may_wrap -- some weight of the wave plus the group's frame count
         //     reaches 65536: only then can the uint16 wrap below happen.
+        // Both are taken on the loaded words, two uint16 values each, not on
+        // the widened floats: a halfword above 255 has a bit under
+        // 0xFF00FF00, and either halfword of a weight word reaching
+        // 65536 - n_frames is two unsigned compares -- five vector
+        // instructions where the float maxima and compares took seven.
         bool c_small = !(kColor && sizeof(color_t) == 2), may_wrap = true;
         if constexpr (kU16 && kFold) {
-            float w_max = wf[0];
+            constexpr int kWWords = (int)sizeof(WVec) / 4;
+            unsigned ww[kWWords];
+            __builtin_memcpy(ww, &w4, sizeof(WVec));
+            const unsigned w_lim = 65536u - (unsigned)ipi.n_frames;
+            unsigned long long near = 0ull;  // (a ballot per compare: scalar ORs)
 #pragma unroll
-            for (int v = 1; v < kV; ++v) w_max = fmaxf(w_max, wf[v]);
-            may_wrap = __builtin_amdgcn_ballot_w64(
-                               w_max + (float)ip.n_frames >= 65536.0f) != 0ull;
+            for (int k = 0; k < kWWords; ++k)
+                near |= __builtin_amdgcn_ballot_w64((ww[k] & 0xFFFFu) >= w_lim) |
+                        __builtin_amdgcn_ballot_w64((ww[k] >> 16) >= w_lim);
+            may_wrap = near != 0ull;
             if constexpr (kColor && sizeof(color_t) == 2) {
-                float c_max = cf[0][0];
+                constexpr int kCWords = (int)sizeof(CVec) / 4;
+                unsigned cw[kCWords];
+                __builtin_memcpy(cw, &c12, sizeof(CVec));
+                unsigned c_any = cw[0];
 #pragma unroll
-                for (int v = 0; v < kV; ++v)
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) c_max = fmaxf(c_max, cf[v][i]);
-                c_small = __builtin_amdgcn_ballot_w64(c_max > 255.0f) == 0ull;
+                for (int k = 1; k < kCWords; ++k) c_any |= cw[k];
+                c_small = __builtin_amdgcn_ballot_w64(
+                                  (c_any & 0xFF00FF00u) != 0u) == 0ull;
             }
         }
         const bool short_item = kU16 && kFold && c_small && !may_wrap;
@@ -1529,11 +1622,17 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
             // the chunk loop is a real loop, so that the second chunk's
             // gathers are not hoisted above the first chunk's arithmetic --
             // they would double the live registers)
+            // The loop visits the rounds that have a frame, lowest first, and
+            // has ONE way round: with a `continue` for the empty rounds of a
+            // counted loop the compiler kept the voxel state in a second set
+            // of registers at the loop's end and copied it there and back,
+            // 12 v_mov per round (profiles/r11_valu_mix.txt).
 #pragma nounroll
-            for (int c0 = 0; c0 < kMaxGroup; c0 += kChunk) {
+            for (unsigned rem = bits & ((1u << kMaxGroup) - 1u); rem != 0u;) {
+                const int c0 = __builtin_ctz(rem) & ~(kChunk - 1);
                 Round r;
                 r.cbits = round_bits(c0);
-                if (r.cbits == 0u) continue;  // wave-uniform
+                rem &= ~(((1u << kChunk) - 1u) << c0);
                 issue(c0, r);
                 apply(c0, r);
                 round_drained();
@@ -1541,26 +1640,43 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
         }
         if (touched) {
             TVec t_out;
-            WVec w4;
+            WVec w_out;
 #pragma unroll
             for (int p = 0; p < kP; ++p) {
                 t_out.v[2 * p] = ts[2 * p];
                 t_out.v[2 * p + 1] = ts[2 * p + 1];
-                w4.v[2 * p] = (weight_t)wf[2 * p];
-                w4.v[2 * p + 1] = (weight_t)wf[2 * p + 1];
+                if constexpr (kU16) {
+                    const unsigned w2 = PackU16(wf[2 * p], wf[2 * p + 1]);
+                    __builtin_memcpy(&w_out.v[2 * p], &w2, 4);
+                } else {
+                    w_out.v[2 * p] = (weight_t)wf[2 * p];
+                    w_out.v[2 * p + 1] = (weight_t)wf[2 * p + 1];
+                }
             }
-            *reinterpret_cast<TVec*>(tsdf_base + lin0) = t_out;
-            *reinterpret_cast<WVec*>(weight_base + lin0) = w4;
+            *reinterpret_cast<TVec*>(tsdf_at(opaque)) = t_out;
+            *reinterpret_cast<WVec*>(weight_at(opaque)) = w_out;
             if constexpr (kColor) {
-                CVec c12;
+                CVec c_out;
+                if constexpr (sizeof(color_t) == 2) {
+                    // the pair's six values in storage order, two per word
 #pragma unroll
-                for (int p = 0; p < kP; ++p)
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) {
-                        c12.v[6 * p + i] = (color_t)cf[2 * p][i];
-                        c12.v[6 * p + 3 + i] = (color_t)cf[2 * p + 1][i];
+                    for (int k = 0; k < 3 * kP; ++k) {
+                        const int j0 = 2 * k, j1 = 2 * k + 1;
+                        const unsigned c2 = PackU16(
+                                cf[2 * (j0 / 6) + (j0 % 6) / 3][j0 % 3],
+                                cf[2 * (j1 / 6) + (j1 % 6) / 3][j1 % 3]);
+                        __builtin_memcpy(&c_out.v[j0], &c2, 4);
                     }
-                *reinterpret_cast<CVec*>(color_base + 3 * lin0) = c12;
+                } else {
+#pragma unroll
+                    for (int p = 0; p < kP; ++p)
+#pragma unroll
+                        for (int i = 0; i < 3; ++i) {
+                            c_out.v[6 * p + i] = (color_t)cf[2 * p][i];
+                            c_out.v[6 * p + 3 + i] = (color_t)cf[2 * p + 1][i];
+                        }
+                }
+                *reinterpret_cast<CVec*>(color_at(opaque)) = c_out;
             }
         }
         if constexpr (kLong) {
@@ -1704,6 +1820,13 @@ ChunkIntegrateKernel(ChunkParams cp) {
 // profiles/r4zf -- chunk launch at 8 ranks 486 k -> 525 k frames/s, single-GPU
 // stream 127.6 k -> 128.6 k).
 static int LaneCube(int res_shift) { return res_shift >= 3 ? 1 : 0; }
+
+// The wide integrate role's largest block resolution: a lane's index in the
+// block (lin_v < res^3 / 2) goes through __umul24 and 32-bit byte offsets.
+constexpr int kMaxIntegrateResolution = 256;
+static_assert((int64_t)kMaxIntegrateResolution * kMaxIntegrateResolution *
+                              kMaxIntegrateResolution / 2 <= (1 << 24),
+              "lin_v must fit the 24-bit multiply of the colour offset");
 
 bool PrepTables(const double* depth_intrinsic, const double* color_intrinsic,
                 int rows, int cols, int color_rows, int color_cols,
@@ -1979,6 +2102,10 @@ int LaunchFrameStep(o3dmi_hash* bh, const FrameFrontArgs* fronts, int n_fronts,
     if (a) {
         O3DMI_REQUIRE(a->resolution % 4 == 0,
                       "frame-stream path needs block_resolution % 4 == 0");
+        // (the role addresses a block's voxels by 32-bit lane offsets, the
+        // colour one through a 24-bit multiply: res^3 / 2 < 2^24)
+        O3DMI_REQUIRE(a->resolution <= kMaxIntegrateResolution,
+                      "frame-stream path needs block_resolution <= 256");
         O3DMI_REQUIRE(a->n_frames >= 1 && a->n_frames <= kMaxGroup,
                       "bad group size");
         IntegParams& ip = sp.integ;
@@ -2082,7 +2209,9 @@ int LaunchFrameStep(o3dmi_hash* bh, const FrameFrontArgs* fronts, int n_fronts,
 
 int LaunchChunkIntegrate(o3dmi_hash* bh, const ChunkIntegrateArgs& a,
                          hipStream_t s) {
-    O3DMI_REQUIRE(a.resolution % 4 == 0 && a.n_frames >= 1 &&
+    O3DMI_REQUIRE(a.resolution % 4 == 0 &&
+                          a.resolution <= kMaxIntegrateResolution &&
+                          a.n_frames >= 1 &&
                           a.n_frames <= kChunkFrames && a.frames &&
                           a.entries && a.count && a.depth_scale > 0,
                   "chunk integrate: bad arguments");

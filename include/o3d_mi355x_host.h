@@ -901,6 +901,115 @@ int o3dmi_pointcloud_segment_plane(const void* points_dev, int64_t n,
                                    o3dmi_segment_plane_info_t* info_out,
                                    o3dmi_stream_t stream);
 
+/* ---- PointCloud sampling, cropping and bounds ----------------------------
+ * (t/geometry/PointCloud.cpp:569-648, 1668-1720; kernels t/geometry/kernel/
+ * PointCloudImpl.h:147-226.) Float32 / Float64. All synchronise. */
+
+/* The order in which PointCloud::FarthestPointDownSample (t/geometry/
+ * PointCloud.cpp:612-648) picks its samples, with the two points upstream
+ * leaves open pinned:
+ *   dist_j = +inf, sel = start_index;
+ *   for i = 0 .. num_samples - 1:
+ *       order[i] = sel;
+ *       dist_j = min(dist_j, ((dx dx) + dy dy) + dz dz), d = p_j - p_sel, in
+ *                the point dtype, no FMA;
+ *       sel = the LOWEST INDEX among the maxima of dist.
+ * Squares that overflow to +inf are legal and tie at +inf like any other
+ * value. Once every remaining point coincides with a chosen one the maximum is
+ * 0 and sel is 0 from then on, so order may repeat indices.
+ * form 0 picks the kernel form by n, 1 asks for the resident form (one launch,
+ * the cloud in one workgroup's registers; n above
+ * o3dmi_pointcloud_farthest_point_capacity: O3DMI_ERR_UNSUPPORTED), 2 for the
+ * streamed form (one launch per sample, no host wait in between). (max value,
+ * min index) is associative and commutative: all forms give the same bits.
+ * order_out_dev: int64 {num_samples}. num_samples > n, start_index outside
+ * [0, n) (n == 0 with num_samples == 0 is O3DMI_OK), n < 0, n >= 2^27, a NULL
+ * pointer, a dtype other than Float32 / Float64, form outside 0..2 or a NaN /
+ * Inf coordinate: O3DMI_ERR_INVALID_ARG with the outputs untouched. */
+int o3dmi_pointcloud_farthest_point_order(const void* points_dev, int64_t n,
+                                          int dtype, int64_t num_samples,
+                                          int64_t start_index, int form,
+                                          int64_t* order_out_dev,
+                                          o3dmi_stream_t stream);
+
+/* Points the resident form holds (0 for an unknown dtype): the largest cloud
+ * form 0 gives to it. */
+int64_t o3dmi_pointcloud_farthest_point_capacity(int dtype);
+
+/* PointCloud::FarthestPointDownSample as a mask, in the style of the Remove*
+ * filters: mask_out_dev uint8 {n} has a one at every index of the order above
+ * (form 0), *m_out their number; SelectByMask then gives the rows in input
+ * order, as upstream. On a cloud with fewer than num_samples distinct points
+ * the mask has FEWER THAN num_samples ONES (upstream's tensor path: the same
+ * wherever its ArgMax returns the first maximum; the legacy path re-selects
+ * the previous index instead). num_samples == 0 clears the mask; num_samples
+ * == n sets all of it (upstream's Clone()) and runs the loop only when
+ * order_out_dev (optional, int64 {num_samples}) is given. Errors as above. */
+int o3dmi_pointcloud_farthest_point_down_sample(
+        const void* points_dev, int64_t n, int dtype, int64_t num_samples,
+        int64_t start_index, uint8_t* mask_out_dev, int64_t* order_out_dev,
+        int64_t* m_out, o3dmi_stream_t stream);
+
+/* PointCloud::UniformDownSample (t/geometry/PointCloud.cpp:569-585): output
+ * row i of every attribute is input row i * every_k_points; *m_out =
+ * ceil(n / every_k_points) rows, which attrs_out must hold. Attributes as in
+ * o3dmi_pointcloud_select_by_mask. every_k_points < 1: O3DMI_ERR_INVALID_ARG. */
+int o3dmi_pointcloud_uniform_down_sample(int64_t n, int64_t every_k_points,
+                                         int n_attrs,
+                                         const void* const* attrs_in,
+                                         const int64_t* row_bytes,
+                                         void* const* attrs_out,
+                                         int64_t* m_out,
+                                         o3dmi_stream_t stream);
+
+/* Entry j of the permutation of [0, n) that seed selects (pure host function;
+ * -1 unless 0 <= j < n < 2^62): four Feistel rounds over the lowest even
+ * power of two >= n, cycle-walked back into [0, n). */
+int64_t o3dmi_sample_index(uint64_t seed, int64_t n, int64_t j);
+
+/* The indices PointCloud::RandomDownSample (t/geometry/PointCloud.cpp:587-610)
+ * gathers: *m_out = (int64)(sampling_ratio * n), upstream's truncation;
+ * indices_out_dev[j] = o3dmi_sample_index(seed, n, j) for j < m, all distinct.
+ * The plain o3dmi_pointcloud_select_by_index then gathers the rows in that
+ * order, as upstream gathers in shuffled order. Upstream shuffles with its
+ * global Mersenne engine under a mutex; here the sample is a pure function of
+ * (seed, n), the same on every run. indices_out_dev: int64, room for n.
+ * A ratio outside [0, 1] or NaN: O3DMI_ERR_INVALID_ARG. */
+int o3dmi_pointcloud_random_sample_indices(int64_t n, double sampling_ratio,
+                                           uint64_t seed,
+                                           int64_t* indices_out_dev,
+                                           int64_t* m_out,
+                                           o3dmi_stream_t stream);
+
+/* AxisAlignedBoundingBox::GetPointIndicesWithinBoundingBox's mask
+ * (GetPointMaskWithinAABB, PointCloudImpl.h:147-180): the bounds are rounded
+ * to the point dtype, both ends are inclusive. A NaN coordinate fails every
+ * comparison: outside (non-finite clouds are not refused here). A box of zero
+ * volume is no error. max < min on an axis, a NaN bound or a NULL pointer:
+ * O3DMI_ERR_INVALID_ARG. mask_out_dev uint8 {n}, *m_out its ones. */
+int o3dmi_pointcloud_aabb_mask(const void* points_dev, int64_t n, int dtype,
+                               const double min_bound[3],
+                               const double max_bound[3],
+                               uint8_t* mask_out_dev, int64_t* m_out,
+                               o3dmi_stream_t stream);
+
+/* OrientedBoundingBox's mask (GetPointMaskWithinOBB, PointCloudImpl.h:
+ * 183-226), all in the point dtype: pd = p - center, half = extent / 2, axis k
+ * = column k of rotation (row-major {3,3}); inside when
+ * |((pd0 r0k) + pd1 r1k) + pd2 r2k| <= half_k on all three axes. NaN rows and
+ * empty boxes as above. A negative or NaN extent: O3DMI_ERR_INVALID_ARG. */
+int o3dmi_pointcloud_obb_mask(const void* points_dev, int64_t n, int dtype,
+                              const double center[3], const double rotation[9],
+                              const double extent[3], uint8_t* mask_out_dev,
+                              int64_t* m_out, o3dmi_stream_t stream);
+
+/* PointCloud::GetMinBound / GetMaxBound (and so GetAxisAlignedBoundingBox):
+ * the per-axis minimum and maximum as host doubles, exact. n == 0 gives
+ * zeros, as upstream. A NaN coordinate is skipped. */
+int o3dmi_pointcloud_min_max_bound(const void* points_dev, int64_t n,
+                                   int dtype, double min_out[3],
+                                   double max_out[3], o3dmi_stream_t stream);
+
 /* The per-fragment step of slac::PreprocessPointClouds (t/pipelines/slac/
  * SLACOptimizer.cpp:47-57). voxel_size > 0: VoxelDownSample ->
  * RemoveStatisticalOutliers(20, 2.0) -> EstimateNormals (KNN, 30); otherwise

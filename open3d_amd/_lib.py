@@ -371,6 +371,23 @@ PROTOTYPES.update({
     "o3dmi_pointcloud_segment_plane": (
         _i32, [_vp, _i64, _i32, _d, _i32, _i64, _d, C.c_uint64, _dp, _vp,
                C.POINTER(_i64), C.POINTER(SegmentPlaneInfoC), _vp]),
+    "o3dmi_pointcloud_farthest_point_order": (
+        _i32, [_vp, _i64, _i32, _i64, _i64, _i32, _vp, _vp]),
+    "o3dmi_pointcloud_farthest_point_capacity": (_i64, [_i32]),
+    "o3dmi_pointcloud_farthest_point_down_sample": (
+        _i32, [_vp, _i64, _i32, _i64, _i64, _vp, _vp, C.POINTER(_i64), _vp]),
+    "o3dmi_pointcloud_uniform_down_sample": (
+        _i32, [_i64, _i64, _i32, C.POINTER(_vp), C.POINTER(_i64),
+               C.POINTER(_vp), C.POINTER(_i64), _vp]),
+    "o3dmi_sample_index": (_i64, [C.c_uint64, _i64, _i64]),
+    "o3dmi_pointcloud_random_sample_indices": (
+        _i32, [_i64, _d, C.c_uint64, _vp, C.POINTER(_i64), _vp]),
+    "o3dmi_pointcloud_aabb_mask": (
+        _i32, [_vp, _i64, _i32, _dp, _dp, _vp, C.POINTER(_i64), _vp]),
+    "o3dmi_pointcloud_obb_mask": (
+        _i32, [_vp, _i64, _i32, _dp, _dp, _dp, _vp, C.POINTER(_i64), _vp]),
+    "o3dmi_pointcloud_min_max_bound": (_i32, [_vp, _i64, _i32, _dp, _dp,
+                                              _vp]),
     "o3dmi_pointcloud_smooth_laplacian": (
         _i32, [_vp, _i64, _i32, _i64, _d, _i32, _i32, _vp, _vp]),
     "o3dmi_pointcloud_smooth_taubin": (

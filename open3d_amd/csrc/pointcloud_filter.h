@@ -22,6 +22,42 @@ struct SelectAttrs {
     int n_attrs;
 };
 
+// Row `src` of every attribute to row `dst`. words: bit a set = attribute a is
+// 4-byte aligned with a width that is a multiple of 4 (positions, normals,
+// float colours); the others (uint8 colours) move byte by byte.
+__device__ __forceinline__ void MoveRow(const SelectAttrs& a, unsigned words,
+                                        int64_t src, int64_t dst) {
+    for (int k = 0; k < a.n_attrs; ++k) {
+        const long long w = a.row_bytes[k];
+        if (words & (1u << k)) {
+            const uint32_t* in = (const uint32_t*)a.in[k] + src * (w >> 2);
+            uint32_t* out = (uint32_t*)a.out[k] + dst * (w >> 2);
+            if (w == 12) {
+                const uint32_t x = in[0], y = in[1], z = in[2];
+                out[0] = x;
+                out[1] = y;
+                out[2] = z;
+            } else {
+                for (long long b = 0; b < (w >> 2); ++b) out[b] = in[b];
+            }
+        } else {
+            const uint8_t* in = (const uint8_t*)a.in[k] + src * w;
+            uint8_t* out = (uint8_t*)a.out[k] + dst * w;
+            for (long long b = 0; b < w; ++b) out[b] = in[b];
+        }
+    }
+}
+
+// The `words` mask of MoveRow for these attributes.
+inline unsigned WordAttrs(const SelectAttrs& a) {
+    unsigned words = 0;
+    for (int k = 0; k < a.n_attrs; ++k)
+        if (((uintptr_t)a.in[k] | (uintptr_t)a.out[k] |
+             (uintptr_t)a.row_bytes[k]) % 4 == 0)
+            words |= 1u << k;
+    return words;
+}
+
 // Scratch of CompactByMaskAsync: int32 flags {n}, int64 offsets {n}, the
 // scan's tile totals.
 size_t CompactScratchBytes(int64_t n);

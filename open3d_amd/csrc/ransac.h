@@ -26,6 +26,42 @@ __host__ __device__ inline uint64_t RansacDraw(uint64_t seed, int64_t i, int j,
 #endif
 }
 
+// The finaliser RansacDraw applies to its counter.
+__host__ __device__ inline uint64_t SplitMix64(uint64_t z) {
+    z ^= z >> 30;
+    z *= 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 27;
+    z *= 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return z;
+}
+
+// Entry j of a permutation of [0, n) chosen by seed (0 <= j < n < 2^62): a
+// stateless bijection. Four rounds of a balanced Feistel network over 2 h
+// bits, 4^h the lowest even power of two >= n, with SplitMix64 of (seed, round,
+// right half) as round function; a value >= n is fed through again (cycle
+// walking). The network permutes [0, 4^h), so the walk follows the cycle of j,
+// which returns to j < n: it ends, after fewer than 4 steps on average.
+__host__ __device__ inline int64_t SampleIndex(uint64_t seed, int64_t n,
+                                               int64_t j) {
+    int h = 1;
+    while ((1ull << (2 * h)) < (uint64_t)n) ++h;
+    const uint64_t half = (1ull << h) - 1;
+    uint64_t v = (uint64_t)j;
+    do {
+        uint64_t l = v >> h, r = v & half;
+        for (uint64_t k = 0; k < 4; ++k) {
+            const uint64_t f =
+                    SplitMix64(seed + 0x9E3779B97F4A7C15ull * (r * 4 + k + 1));
+            const uint64_t t = l ^ (f & half);
+            l = r;
+            r = t;
+        }
+        v = (l << h) | r;
+    } while (v >= (uint64_t)n);
+    return (int64_t)v;
+}
+
 inline int64_t RansacTiles(int64_t ns) {
     return (ns + kRansacTile - 1) / kRansacTile;
 }

@@ -1,6 +1,7 @@
-"""Mirror of t::geometry::PointCloud's selection, filter, smoothing, boundary,
-normal-orientation and segmentation methods (t/geometry/PointCloud.cpp:435-494,
-650-854, 986-1050, 1074-1203, 1634-1666) on the HIP backend.
+"""Mirror of t::geometry::PointCloud's selection, filter, sampling, cropping,
+smoothing, boundary, normal-orientation and segmentation methods
+(t/geometry/PointCloud.cpp:435-494, 569-854, 986-1050, 1074-1203, 1634-1720) on
+the HIP backend.
 
 A cloud is a dict of CUDA attribute tensors with "positions" ({N,3} Float32 or
 Float64) required; every other attribute has N rows of any width and dtype
@@ -186,6 +187,167 @@ def remove_statistical_outliers(attrs, nb_neighbors, std_ratio,
         stats["avg_distances"] = avg
         return out, mask, stats
     return out, mask
+
+
+# ---- sampling, cropping, bounds -----------------------------------------------
+
+def uniform_down_sample(attrs, every_k_points):
+    """PointCloud::UniformDownSample: rows 0, k, 2 k, ... of every attribute."""
+    _, n = _rows(attrs)
+    k = int(every_k_points)
+    if k < 1:
+        raise ValueError(
+            "Illegal sample rate, every_k_points must be larger than 0.")
+    return _select(
+        attrs, (n + k - 1) // k,
+        lambda c, a, w, o, m: _lib.lib().o3dmi_pointcloud_uniform_down_sample(
+            n, k, c, a, w, o, m, stream()),
+        "uniform_down_sample")
+
+
+def random_sample_indices(n, sampling_ratio, seed=0, device="cuda"):
+    """The Int64 {int(ratio * n)} indices random_down_sample gathers: entries
+    0 .. m-1 of the permutation of [0, n) that seed selects."""
+    indices = torch.empty(n, dtype=torch.int64, device=device)
+    m = C.c_int64(0)
+    _lib.check(_lib.lib().o3dmi_pointcloud_random_sample_indices(
+        n, C.c_double(sampling_ratio),
+        C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _lib.ptr(indices),
+        C.byref(m), stream()), "random_down_sample")
+    return indices[:m.value]
+
+
+def random_down_sample(attrs, sampling_ratio, seed=0):
+    """PointCloud::RandomDownSample: int(ratio * N) distinct rows in shuffled
+    order. The sample is a pure function of (seed, N), the same on every run
+    (upstream draws from its global engine)."""
+    p = _positions(attrs)
+    indices = random_sample_indices(p.shape[0], sampling_ratio, seed, p.device)
+    out, _ = select_by_index(attrs, indices)
+    return out
+
+
+def farthest_point_order(positions, num_samples, start_index=0, form=0):
+    """The Int64 {num_samples} order in which FarthestPointDownSample picks
+    its samples. form: 0 by size, 1 resident, 2 streamed (same bits)."""
+    p = _positions({"positions": positions})
+    order = torch.empty(int(num_samples), dtype=torch.int64, device=p.device)
+    _lib.check(_lib.lib().o3dmi_pointcloud_farthest_point_order(
+        _lib.ptr(p), p.shape[0], TORCH_TO_O3DMI[p.dtype], int(num_samples),
+        int(start_index), int(form), _lib.ptr(order), stream()),
+        "farthest_point_order")
+    return order
+
+
+def farthest_point_mask(positions, num_samples, start_index=0,
+                        return_order=False):
+    """The filter alone: -> (mask uint8 {N}, kept) and, with return_order,
+    the Int64 {num_samples} order as well."""
+    p = _positions({"positions": positions})
+    n = p.shape[0]
+    mask = torch.empty(n, dtype=torch.uint8, device=p.device)
+    order = torch.empty(int(num_samples), dtype=torch.int64,
+                        device=p.device) if return_order else None
+    m = C.c_int64(0)
+    _lib.check(_lib.lib().o3dmi_pointcloud_farthest_point_down_sample(
+        _lib.ptr(p), n, TORCH_TO_O3DMI[p.dtype], int(num_samples),
+        int(start_index), _lib.ptr(mask),
+        _lib.ptr(order) if order is not None else None, C.byref(m), stream()),
+        "farthest_point_down_sample")
+    if return_order:
+        return mask, m.value, order
+    return mask, m.value
+
+
+def farthest_point_down_sample(attrs, num_samples, start_index=0,
+                               return_order=False):
+    """PointCloud::FarthestPointDownSample: the chosen rows in input order.
+    Ties go to the lowest index; a cloud with fewer than num_samples distinct
+    points gives fewer rows. With return_order -> (attrs_out, order)."""
+    res = farthest_point_mask(_positions(attrs), num_samples, start_index,
+                              return_order)
+    out, _ = _filtered(attrs, res[0])
+    if return_order:
+        return out, res[2]
+    return out
+
+
+def _mask_call(attrs, call, where):
+    p = _positions(attrs)
+    n = p.shape[0]
+    mask = torch.empty(n, dtype=torch.uint8, device=p.device)
+    m = C.c_int64(0)
+    _lib.check(call(_lib.ptr(p), n, TORCH_TO_O3DMI[p.dtype], _lib.ptr(mask),
+                    C.byref(m), stream()), where)
+    return mask
+
+
+def _cropped(attrs, mask, invert):
+    out, _ = select_by_mask(attrs, mask, invert)
+    return out
+
+
+def crop(attrs, min_bound=None, max_bound=None, center=None, rotation=None,
+         extent=None, invert=False):
+    """PointCloud::Crop with an axis-aligned box (min_bound, max_bound) or an
+    oriented one (center, rotation {3,3}, extent): the rows inside, both ends
+    inclusive, or with invert the rows outside. An empty box (zero volume)
+    gives an empty cloud, or a copy under invert, as upstream."""
+    aabb = min_bound is not None and max_bound is not None
+    obb = center is not None and rotation is not None and extent is not None
+    if aabb == obb or (aabb or obb) != any(
+            v is not None
+            for v in (min_bound, max_bound, center, rotation, extent)):
+        raise ValueError("crop needs (min_bound, max_bound) or "
+                         "(center, rotation, extent)")
+    if aabb:
+        lo, hi = _vec3(min_bound, "min_bound"), _vec3(max_bound, "max_bound")
+        size = [hi[k] - lo[k] for k in range(3)]
+
+        def call(p, n, dtype, mask, m, st):
+            return _lib.lib().o3dmi_pointcloud_aabb_mask(p, n, dtype, lo, hi,
+                                                         mask, m, st)
+    else:
+        c, size = _vec3(center, "center"), _vec3(extent, "extent")
+        r = [float(x) for row in (rotation.tolist() if hasattr(
+            rotation, "tolist") else rotation) for x in row]
+        if len(r) != 9:
+            raise ValueError("rotation must have shape {3,3}")
+        rot = (C.c_double * 9)(*r)
+
+        def call(p, n, dtype, mask, m, st):
+            return _lib.lib().o3dmi_pointcloud_obb_mask(p, n, dtype, c, rot,
+                                                        size, mask, m, st)
+    if min(size) < 0:
+        raise ValueError("the box has a negative extent")
+    if size[0] * size[1] * size[2] == 0:  # upstream's IsEmpty()
+        _, n = _rows(attrs)
+        p = _positions(attrs)
+        mask = torch.zeros(n, dtype=torch.uint8, device=p.device)
+        return _cropped(attrs, mask, invert)
+    return _cropped(attrs, _mask_call(attrs, call, "crop"), invert)
+
+
+def get_min_max_bound(attrs):
+    """(GetMinBound, GetMaxBound) as Float64 {3} host tensors; zeros for an
+    empty cloud, as upstream."""
+    p = _positions(attrs)
+    lo, hi = (C.c_double * 3)(), (C.c_double * 3)()
+    _lib.check(_lib.lib().o3dmi_pointcloud_min_max_bound(
+        _lib.ptr(p), p.shape[0], TORCH_TO_O3DMI[p.dtype], lo, hi, stream()),
+        "get_min_max_bound")
+    return (torch.tensor(list(lo), dtype=torch.float64),
+            torch.tensor(list(hi), dtype=torch.float64))
+
+
+def get_min_bound(attrs):
+    """PointCloud::GetMinBound."""
+    return get_min_max_bound(attrs)[0]
+
+
+def get_max_bound(attrs):
+    """PointCloud::GetMaxBound."""
+    return get_min_max_bound(attrs)[1]
 
 
 # ---- smoothing, boundary detection, normal orientation ------------------------

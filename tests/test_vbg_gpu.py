@@ -12,6 +12,8 @@ import torch
 
 import _oracle as orc
 import _scene as sc
+import _raycast_poison as poison
+from _raycast_cases import OracleGrid  # noqa: F401  (others import it here)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,32 +33,6 @@ def _mk_grid(geometry, grid_f32, block_count=4096, with_color=True, res=sc.RES):
     return geometry.VoxelBlockGrid(names, dts, ch, voxel_size=sc.VOXEL,
                                    block_resolution=res,
                                    block_count=block_count)
-
-
-class OracleGrid:
-    """Oracle-side VoxelBlockGrid: hash + numpy value buffers."""
-
-    def __init__(self, grid_f32, capacity, with_color=True, res=sc.RES):
-        self.h = orc.HashMap(capacity)
-        wd = np.float32 if grid_f32 else np.uint16
-        self.res = res
-        self.tsdf = np.zeros((capacity, res, res, res), np.float32)
-        self.weight = np.zeros((capacity, res, res, res), wd)
-        self.color = np.zeros((capacity, res, res, res, 3), wd) \
-            if with_color else None
-
-    def integrate(self, depth, color, K, T, keys=None):
-        if keys is None:
-            keys = orc.depth_touch(depth, K, T, self.res, sc.VOXEL,
-                                   sc.VOXEL * sc.TRUNC_MULT, sc.DEPTH_SCALE,
-                                   sc.DEPTH_MAX, 4)
-        self.h.activate(keys)
-        buf, m = self.h.find(keys)
-        assert m.all()
-        orc.integrate(depth, color, buf, self.h.key_buffer(), self.tsdf,
-                      self.weight, self.color, K, K, T, self.res, sc.VOXEL,
-                      sc.VOXEL * sc.TRUNC_MULT, sc.DEPTH_SCALE, sc.DEPTH_MAX)
-        return keys
 
 
 def _compare_grids(og, g, tsdf_tol=1e-4):
@@ -1572,12 +1548,15 @@ def test_last_frame_block_coordinates_equal_a_second_block_touch():
         # a caller's map must not disturb it
         for lim in ((0.1, sc.DEPTH_MAX), (0.1, sc.DEPTH_MAX), (0.3, 2.0),
                     (0.1, sc.DEPTH_MAX)):
-            own = g.ray_cast_last_frame(K, T[0], w, h, ("depth", "normal"),
-                                        sc.DEPTH_SCALE, lim[0], lim[1], 1.0,
-                                        sc.TRUNC_MULT)
-            ref = g.ray_cast(want, K, T[0], w, h, ("depth", "normal"),
-                             sc.DEPTH_SCALE, lim[0], lim[1], 1.0,
-                             sc.TRUNC_MULT)
+            # (poisoned casts: outputs from torch.empty would be the memory
+            # the previous, identical, result was just freed from)
+            own = poison.ray_cast_last_frame(g, K, T[0], w, h,
+                                             ("depth", "normal"),
+                                             sc.DEPTH_SCALE, lim[0], lim[1],
+                                             1.0, sc.TRUNC_MULT)
+            ref = poison.ray_cast(g, want, K, T[0], w, h, ("depth", "normal"),
+                                  sc.DEPTH_SCALE, lim[0], lim[1], 1.0,
+                                  sc.TRUNC_MULT)
             for name in ("depth", "normal"):
                 assert torch.equal(own[name], ref[name]), (name, lim)
     # a size whose range map cannot be self-cleaning (down factor 4), and an

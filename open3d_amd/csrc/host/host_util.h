@@ -27,6 +27,12 @@ inline void Matmul4(const double* A, const double* B, double* C) {
     std::memcpy(C, R, sizeof(R));
 }
 
+// Records `msg` and returns the status of a mode this backend does not have.
+static inline int Unsupported(const char* msg) {
+    SetLastError(msg);
+    return O3DMI_ERR_UNSUPPORTED;
+}
+
 struct DeviceBuffer {
     void* p = nullptr;
     // The driver drains the stream before its buffers go out of scope

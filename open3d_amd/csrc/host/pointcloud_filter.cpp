@@ -7,8 +7,8 @@
 #include <cmath>
 
 #include "../pointcloud_filter.h"
-#include "host_util.h"
 #include "o3d_mi355x_host.h"
+#include "pointcloud_call.h"
 
 using namespace o3dmi;
 
@@ -16,72 +16,18 @@ namespace {
 
 constexpr int kMaxFilterKnn = 64;  // one wave's list (nns.hip kMaxKnn)
 
-size_t ElemSize(int dtype) { return dtype == O3DMI_F64 ? 8 : 4; }
-
-int CheckAttrs(int n_attrs, const void* const* attrs_in,
-               const int64_t* row_bytes, void* const* attrs_out,
-               bool need_rows, SelectAttrs* out) {
-    O3DMI_REQUIRE(n_attrs >= 1 && n_attrs <= kMaxSelectAttrs,
-                  "n_attrs must be in [1, 8]");
-    O3DMI_REQUIRE(attrs_in && row_bytes && attrs_out, "null argument");
-    out->n_attrs = n_attrs;
-    for (int k = 0; k < n_attrs; ++k) {
-        O3DMI_REQUIRE(row_bytes[k] >= 1, "row_bytes must be >= 1");
-        O3DMI_REQUIRE(!need_rows || (attrs_in[k] && attrs_out[k]),
-                      "null attribute");
-        out->in[k] = attrs_in[k];
-        out->out[k] = attrs_out[k];
-        out->row_bytes[k] = row_bytes[k];
-    }
-    return O3DMI_OK;
-}
-
-// The device word block of a filter call: {error flag, pad, 64-bit count}.
-struct Words {
-    int bad;
-    int pad;
-    unsigned long long count;
-};
-
-// Refuses a cloud with a NaN or Inf coordinate (one launch, one download).
-int RequireFinite(const void* points_dev, int64_t n, int dtype, Words* w_dev,
-                  hipStream_t s) {
-    int st = CheckFiniteAsync(points_dev, n, dtype, &w_dev->bad, s);
-    if (st) return st;
-    int bad = 0;
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&bad, &w_dev->bad, sizeof(int),
-                                   hipMemcpyDeviceToHost, s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
-    O3DMI_REQUIRE(!bad,
-                  "non-finite coordinate: run RemoveNonFinitePoints first");
-    return O3DMI_OK;
-}
-
-int DownloadCount(const Words* w_dev, int64_t* m_out, hipStream_t s) {
-    unsigned long long c = 0;
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&c, &w_dev->count, sizeof(c),
-                                   hipMemcpyDeviceToHost, s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
-    *m_out = (int64_t)c;
-    return O3DMI_OK;
-}
-
 int SelectByMaskImpl(int64_t n, const uint8_t* mask_dev, bool invert,
                      const SelectAttrs& attrs, int64_t* m_out, hipStream_t s) {
     PoolScratch pool(s);
     char* scratch = nullptr;
-    int64_t* count = nullptr;
+    Words* w = nullptr;  // not zeroed: the compaction stores the count
     int st = pool.Alloc(&scratch, CompactScratchBytes(n));
-    if (!st) st = pool.Alloc(&count, 256);
+    if (!st) st = pool.Alloc(&w, 256);
     if (st) return st;
-    st = CompactByMaskAsync(mask_dev, n, invert, attrs, count, scratch, s);
+    st = CompactByMaskAsync(mask_dev, n, invert, attrs, (int64_t*)&w->count,
+                            scratch, s);
     if (st) return st;
-    int64_t m = 0;
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&m, count, sizeof(m), hipMemcpyDeviceToHost,
-                                   s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
-    *m_out = m;
-    return O3DMI_OK;
+    return DownloadCount(w, m_out, s);
 }
 
 }  // namespace
@@ -126,8 +72,7 @@ int o3dmi_pointcloud_select_by_index(int64_t n, const int64_t* indices_dev,
     hipStream_t s = (hipStream_t)stream;
     PoolScratch pool(s);
     Words* w = nullptr;
-    if ((st = pool.Alloc(&w, 256))) return st;
-    O3DMI_HIP_CHECK(hipMemsetAsync(w, 0, sizeof(Words), s));
+    if ((st = AllocWords(pool, &w))) return st;
     if ((st = CheckIndexRangeAsync(indices_dev, m, n, &w->bad, s))) return st;
     int bad = 0;
     O3DMI_HIP_CHECK(hipMemcpyAsync(&bad, &w->bad, sizeof(int),
@@ -164,9 +109,8 @@ int o3dmi_pointcloud_remove_non_finite_points(const void* points_dev,
     hipStream_t s = (hipStream_t)stream;
     PoolScratch pool(s);
     Words* w = nullptr;
-    int st = pool.Alloc(&w, 256);
+    int st = AllocWords(pool, &w);
     if (st) return st;
-    O3DMI_HIP_CHECK(hipMemsetAsync(w, 0, sizeof(Words), s));
     st = NonFiniteMaskAsync(points_dev, n, dtype, remove_nan != 0,
                             remove_inf != 0, mask_out_dev, &w->count, s);
     if (st) return st;
@@ -191,10 +135,9 @@ int o3dmi_pointcloud_remove_duplicated_points(const void* points_dev,
     Words* w = nullptr;
     int32_t* table = nullptr;
     const int64_t slots = DuplicateTableSlots(n);
-    int st = pool.Alloc(&w, 256);
+    int st = AllocWords(pool, &w);
     if (!st) st = pool.Alloc(&table, sizeof(int32_t) * (size_t)slots);
     if (st) return st;
-    O3DMI_HIP_CHECK(hipMemsetAsync(w, 0, sizeof(Words), s));
     st = DuplicateMaskAsync(points_dev, n, dtype, table, slots, mask_out_dev,
                             &w->count, s);
     if (st) return st;
@@ -222,10 +165,9 @@ int o3dmi_pointcloud_remove_radius_outliers(const void* points_dev, int64_t n,
     PoolScratch pool(s);
     Words* w = nullptr;
     int32_t* counts = nullptr;
-    int st = pool.Alloc(&w, 256);
+    int st = AllocWords(pool, &w);
     if (!st) st = pool.Alloc(&counts, sizeof(int32_t) * (size_t)n);
     if (st) return st;
-    O3DMI_HIP_CHECK(hipMemsetAsync(w, 0, sizeof(Words), s));
     if ((st = RequireFinite(points_dev, n, dtype, w, s))) return st;
     NnsGuard index;
     st = o3dmi_nns_create(points_dev, n, dtype, search_radius, stream,
@@ -254,10 +196,8 @@ int o3dmi_pointcloud_remove_statistical_outliers(
     O3DMI_REQUIRE(dtype == O3DMI_F32 || dtype == O3DMI_F64,
                   "points must be Float32 or Float64");
     O3DMI_REQUIRE(n == 0 || (points_dev && mask_out_dev), "null argument");
-    if (nb_neighbors > kMaxFilterKnn) {
-        SetLastError("nb_neighbors > 64 is not supported");
-        return O3DMI_ERR_UNSUPPORTED;
-    }
+    if (nb_neighbors > kMaxFilterKnn)
+        return Unsupported("nb_neighbors > 64 is not supported");
     O3DMI_REQUIRE(n < (1ll << 31) - 1, "too many points");
     *m_out = 0;
     if (n == 0) return O3DMI_OK;
@@ -267,12 +207,11 @@ int o3dmi_pointcloud_remove_statistical_outliers(
     double* sums = nullptr;
     double* stats = nullptr;  // {mean, std, threshold, count}
     void* avg = avg_distances_out_dev;
-    int st = pool.Alloc(&w, 256);
+    int st = AllocWords(pool, &w);
     if (!st) st = pool.Alloc(&sums, sizeof(double) * StatisticalScratchDoubles());
     if (!st) st = pool.Alloc(&stats, 256);
     if (!st && !avg) st = pool.Alloc(&avg, ElemSize(dtype) * (size_t)n);
     if (st) return st;
-    O3DMI_HIP_CHECK(hipMemsetAsync(w, 0, sizeof(Words), s));
     O3DMI_HIP_CHECK(hipMemsetAsync(stats, 0, 32, s));
     if ((st = RequireFinite(points_dev, n, dtype, w, s))) return st;
     st = o3dmi_internal_nns_knn_avg_distance(points_dev, n, dtype,

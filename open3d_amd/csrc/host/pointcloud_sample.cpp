@@ -5,44 +5,13 @@
 #include <cmath>
 
 #include "../pointcloud_sample.h"
-#include "../pointcloud_smooth.h"  // CountMaskAsync
 #include "../ransac.h"
-#include "host_util.h"
 #include "o3d_mi355x_host.h"
+#include "pointcloud_call.h"
 
 using namespace o3dmi;
 
 namespace {
-
-// The device word block of a call: {error flag, pad, 64-bit count}.
-struct Words {
-    int bad;
-    int pad;
-    unsigned long long count;
-};
-
-// Refuses a cloud with a NaN or Inf coordinate (one launch, one download).
-int RequireFinite(const void* points_dev, int64_t n, int dtype, Words* w_dev,
-                  hipStream_t s) {
-    int st = CheckFiniteAsync(points_dev, n, dtype, &w_dev->bad, s);
-    if (st) return st;
-    int bad = 0;
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&bad, &w_dev->bad, sizeof(int),
-                                   hipMemcpyDeviceToHost, s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
-    O3DMI_REQUIRE(!bad,
-                  "non-finite coordinate: run RemoveNonFinitePoints first");
-    return O3DMI_OK;
-}
-
-int DownloadCount(const Words* w_dev, int64_t* m_out, hipStream_t s) {
-    unsigned long long c = 0;
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&c, &w_dev->count, sizeof(c),
-                                   hipMemcpyDeviceToHost, s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
-    *m_out = (int64_t)c;
-    return O3DMI_OK;
-}
 
 // What both farthest-point calls refuse before anything is launched.
 int CheckFarthestArgs(const void* points_dev, int64_t n, int dtype,
@@ -103,16 +72,13 @@ int o3dmi_pointcloud_farthest_point_order(const void* points_dev, int64_t n,
     if (st) return st;
     O3DMI_REQUIRE(form >= 0 && form <= 2, "form must be 0, 1 or 2");
     O3DMI_REQUIRE(num_samples == 0 || order_out_dev, "null argument");
-    if (form == 1 && n > FarthestResidentCapacity(dtype)) {
-        SetLastError("farthest point: cloud above the resident capacity");
-        return O3DMI_ERR_UNSUPPORTED;
-    }
+    if (form == 1 && n > FarthestResidentCapacity(dtype))
+        return Unsupported("farthest point: cloud above the resident capacity");
     if (num_samples == 0) return O3DMI_OK;
     hipStream_t s = (hipStream_t)stream;
     PoolScratch pool(s);
     Words* w = nullptr;
-    if ((st = pool.Alloc(&w, 256))) return st;
-    O3DMI_HIP_CHECK(hipMemsetAsync(w, 0, sizeof(Words), s));
+    if ((st = AllocWords(pool, &w))) return st;
     if ((st = RequireFinite(points_dev, n, dtype, w, s))) return st;
     st = FarthestOrder(points_dev, n, dtype, num_samples, start_index, form,
                        order_out_dev, pool, s);
@@ -139,11 +105,10 @@ int o3dmi_pointcloud_farthest_point_down_sample(
     int64_t* order = order_out_dev;
     const bool whole = num_samples == n;  // upstream's Clone()
     const bool loop = num_samples > 0 && (!whole || order_out_dev);
-    st = pool.Alloc(&w, 256);
+    st = AllocWords(pool, &w);
     if (!st && loop && !order)
         st = pool.Alloc(&order, sizeof(int64_t) * (size_t)num_samples);
     if (st) return st;
-    O3DMI_HIP_CHECK(hipMemsetAsync(w, 0, sizeof(Words), s));
     if ((st = RequireFinite(points_dev, n, dtype, w, s))) return st;
     if (loop) {
         st = FarthestOrder(points_dev, n, dtype, num_samples, start_index, 0,
@@ -175,26 +140,16 @@ int o3dmi_pointcloud_uniform_down_sample(int64_t n, int64_t every_k_points,
     O3DMI_REQUIRE(n >= 0, "n < 0");
     O3DMI_REQUIRE(every_k_points >= 1,
                   "Illegal sample rate, every_k_points must be larger than 0.");
-    O3DMI_REQUIRE(n_attrs >= 1 && n_attrs <= kMaxSelectAttrs,
-                  "n_attrs must be in [1, 8]");
-    O3DMI_REQUIRE(attrs_in && row_bytes && attrs_out, "null argument");
     SelectAttrs attrs;
-    attrs.n_attrs = n_attrs;
-    for (int k = 0; k < n_attrs; ++k) {
-        O3DMI_REQUIRE(row_bytes[k] >= 1, "row_bytes must be >= 1");
-        O3DMI_REQUIRE(n == 0 || (attrs_in[k] && attrs_out[k]),
-                      "null attribute");
-        attrs.in[k] = attrs_in[k];
-        attrs.out[k] = attrs_out[k];
-        attrs.row_bytes[k] = row_bytes[k];
-    }
+    int st = CheckAttrs(n_attrs, attrs_in, row_bytes, attrs_out, n > 0,
+                        &attrs);
+    if (st) return st;
     // ceil(n / k) without n + k overflowing
     const int64_t m = n == 0 ? 0 : (n - 1) / every_k_points + 1;
     *m_out = m;
     if (m == 0) return O3DMI_OK;
     hipStream_t s = (hipStream_t)stream;
-    int st = StridedRowsAsync(m, every_k_points, attrs, s);
-    if (st) return st;
+    if ((st = StridedRowsAsync(m, every_k_points, attrs, s))) return st;
     O3DMI_HIP_CHECK(hipStreamSynchronize(s));
     return O3DMI_OK;
 }
@@ -241,8 +196,7 @@ int o3dmi_pointcloud_aabb_mask(const void* points_dev, int64_t n, int dtype,
     hipStream_t s = (hipStream_t)stream;
     PoolScratch pool(s);
     Words* w = nullptr;
-    if ((st = pool.Alloc(&w, 256))) return st;
-    O3DMI_HIP_CHECK(hipMemsetAsync(w, 0, sizeof(Words), s));
+    if ((st = AllocWords(pool, &w))) return st;
     st = AabbMaskAsync(points_dev, n, dtype, min_bound, max_bound,
                        mask_out_dev, &w->count, s);
     if (st) return st;
@@ -263,8 +217,7 @@ int o3dmi_pointcloud_obb_mask(const void* points_dev, int64_t n, int dtype,
     hipStream_t s = (hipStream_t)stream;
     PoolScratch pool(s);
     Words* w = nullptr;
-    if ((st = pool.Alloc(&w, 256))) return st;
-    O3DMI_HIP_CHECK(hipMemsetAsync(w, 0, sizeof(Words), s));
+    if ((st = AllocWords(pool, &w))) return st;
     st = ObbMaskAsync(points_dev, n, dtype, center, rotation, extent,
                       mask_out_dev, &w->count, s);
     if (st) return st;

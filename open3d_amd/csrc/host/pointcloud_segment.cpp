@@ -7,38 +7,14 @@
 #include <cmath>
 #include <vector>
 
-#include "../pointcloud_filter.h"
 #include "../pointcloud_segment.h"
 #include "../scan.h"
-#include "host_util.h"
 #include "o3d_mi355x_host.h"
+#include "pointcloud_call.h"
 
 using namespace o3dmi;
 
 namespace {
-
-// The device word block of a call: {error flag, pad, 64-bit count, 64-bit
-// count}.
-struct Words {
-    int bad;
-    int pad;
-    unsigned long long noise;
-    long long total;
-};
-
-// Refuses a cloud with a NaN or Inf coordinate (one launch, one download).
-int RequireFinite(const void* points_dev, int64_t n, int dtype, Words* w_dev,
-                  hipStream_t s) {
-    int st = CheckFiniteAsync(points_dev, n, dtype, &w_dev->bad, s);
-    if (st) return st;
-    int bad = 0;
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&bad, &w_dev->bad, sizeof(int),
-                                   hipMemcpyDeviceToHost, s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
-    O3DMI_REQUIRE(!bad,
-                  "non-finite coordinate: run RemoveNonFinitePoints first");
-    return O3DMI_OK;
-}
 
 // GetPlaneFromPoints' closed form (PointCloudSegmentation.cpp:134-154).
 void PlaneFromSums(const double sums[6], const double centroid[3],
@@ -114,7 +90,7 @@ int o3dmi_pointcloud_cluster_dbscan(const void* points_dev, int64_t n,
     int64_t* cluster = nullptr;
     char* scan = nullptr;
     const size_t ints = sizeof(int32_t) * (size_t)n;
-    int st = pool.Alloc(&w, 256);
+    int st = AllocWords(pool, &w);
     if (!st) st = pool.Alloc(&counts, ints);
     if (!st) st = pool.Alloc(&parent, ints);
     if (!st) st = pool.Alloc(&root, ints);
@@ -122,7 +98,6 @@ int o3dmi_pointcloud_cluster_dbscan(const void* points_dev, int64_t n,
     if (!st) st = pool.Alloc(&cluster, sizeof(int64_t) * (size_t)n);
     if (!st) st = pool.Alloc(&scan, ScanScratchBytes(n));
     if (st) return st;
-    O3DMI_HIP_CHECK(hipMemsetAsync(w, 0, sizeof(Words), s));
     if ((st = RequireFinite(points_dev, n, dtype, w, s))) return st;
     NnsGuard index;
     st = o3dmi_nns_create(points_dev, n, dtype, eps, stream, &index.nns);
@@ -140,7 +115,7 @@ int o3dmi_pointcloud_cluster_dbscan(const void* points_dev, int64_t n,
                         s);
     if (st) return st;
     st = DbscanLabelSweep(index.nns, points_dev, n, counts, need, root, cluster,
-                          labels_out_dev, &w->noise, s);
+                          labels_out_dev, &w->count, s);
     if (st) return st;
     Words host;
     O3DMI_HIP_CHECK(hipMemcpyAsync(&host, w, sizeof(Words),
@@ -148,7 +123,7 @@ int o3dmi_pointcloud_cluster_dbscan(const void* points_dev, int64_t n,
     O3DMI_HIP_CHECK(hipStreamSynchronize(s));
     index.completed = true;  // the stream has drained
     if (num_clusters_out) *num_clusters_out = (int64_t)host.total;
-    if (num_noise_out) *num_noise_out = (int64_t)host.noise;
+    if (num_noise_out) *num_noise_out = (int64_t)host.count;
     return O3DMI_OK;
 }
 
@@ -206,10 +181,8 @@ int o3dmi_pointcloud_segment_plane(const void* points_dev, int64_t n,
                   "Probability must be > 0 and <= 1.0");
     O3DMI_REQUIRE(ransac_n >= 3,
                   "ransac_n should be set to higher than or equal to 3.");
-    if (ransac_n > kPlaneMaxN) {
-        SetLastError("ransac_n > 8 is not supported");
-        return O3DMI_ERR_UNSUPPORTED;
-    }
+    if (ransac_n > kPlaneMaxN)
+        return Unsupported("ransac_n > 8 is not supported");
     O3DMI_REQUIRE(n >= ransac_n, "There must be at least 'ransac_n' points.");
     O3DMI_REQUIRE(num_iterations >= 1, "num_iterations must be >= 1");
     O3DMI_REQUIRE(distance_threshold > 0, "distance_threshold must be > 0");
@@ -230,7 +203,7 @@ int o3dmi_pointcloud_segment_plane(const void* points_dev, int64_t n,
     int32_t *part_counts = nullptr, *flags = nullptr;
     int64_t* position = nullptr;
     char *results = nullptr, *scan = nullptr;
-    int st = pool.Alloc(&w, 256);
+    int st = AllocWords(pool, &w);
     if (!st) st = pool.Alloc(&planes, sizeof(double) * 4 * (size_t)max_batch);
     if (!st) st = pool.Alloc(&results, result_bytes);
     if (!st)
@@ -245,7 +218,6 @@ int o3dmi_pointcloud_segment_plane(const void* points_dev, int64_t n,
     if (!st)
         st = pool.Alloc(&refit, sizeof(double) * 8 * (size_t)RefitBlocks(n));
     if (st) return st;
-    O3DMI_HIP_CHECK(hipMemsetAsync(w, 0, sizeof(Words), s));
     if ((st = RequireFinite(points_dev, n, dtype, w, s))) return st;
 
     int64_t* counts_dev = (int64_t*)results;

@@ -7,18 +7,15 @@
 // output policies in nns.hip.
 #include <cmath>
 
-#include "../pointcloud_filter.h"
 #include "../pointcloud_smooth.h"
 #include "../scan.h"
-#include "host_util.h"
 #include "o3d_mi355x.h"
 #include "o3d_mi355x_host.h"
+#include "pointcloud_call.h"
 
 using namespace o3dmi;
 
 namespace {
-
-size_t RowBytes(int dtype) { return dtype == O3DMI_F64 ? 24 : 12; }
 
 bool Overlap(const void* a, const void* b, size_t bytes) {
     if (!a || !b) return false;
@@ -27,28 +24,8 @@ bool Overlap(const void* a, const void* b, size_t bytes) {
     return x < y + bytes && y < x + bytes;
 }
 
-int Unsupported(const char* msg) {
-    SetLastError(msg);
-    return O3DMI_ERR_UNSUPPORTED;
-}
-
-// Refuses a cloud with a NaN or Inf coordinate (one launch, one download).
-int RequireFinite(const void* points_dev, int64_t n, int dtype, int* flag_dev,
-                  hipStream_t s) {
-    O3DMI_HIP_CHECK(hipMemsetAsync(flag_dev, 0, sizeof(int), s));
-    int st = CheckFiniteAsync(points_dev, n, dtype, flag_dev, s);
-    if (st) return st;
-    int bad = 0;
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&bad, flag_dev, sizeof(int),
-                                   hipMemcpyDeviceToHost, s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
-    O3DMI_REQUIRE(!bad,
-                  "non-finite coordinate: run RemoveNonFinitePoints first");
-    return O3DMI_OK;
-}
-
 int CopyRows(void* dst, const void* src, int64_t n, int dtype, hipStream_t s) {
-    O3DMI_HIP_CHECK(hipMemcpyAsync(dst, src, RowBytes(dtype) * (size_t)n,
+    O3DMI_HIP_CHECK(hipMemcpyAsync(dst, src, 3 * ElemSize(dtype) * (size_t)n,
                                    hipMemcpyDeviceToDevice, s));
     return O3DMI_OK;
 }
@@ -63,7 +40,8 @@ int LaplacianPasses(const void* points_dev, int64_t n, int dtype,
                   "points must be Float32 or Float64");
     if (n == 0) return O3DMI_OK;
     O3DMI_REQUIRE(points_dev && out_dev, "null argument");
-    O3DMI_REQUIRE(!Overlap(points_dev, out_dev, RowBytes(dtype) * (size_t)n),
+    const size_t bytes = 3 * ElemSize(dtype) * (size_t)n;
+    O3DMI_REQUIRE(!Overlap(points_dev, out_dev, bytes),
                   "out_points aliases points");
     if (iterations == 0 || max_nn <= 0) {
         int st = CopyRows(out_dev, points_dev, n, dtype, s);
@@ -78,14 +56,14 @@ int LaplacianPasses(const void* points_dev, int64_t n, int dtype,
     const int k = (int)(n < (int64_t)max_nn + 1 ? n : (int64_t)max_nn + 1);
     const int64_t passes = iterations * per_iteration;
     PoolScratch pool(s);
-    int* flag = nullptr;
+    Words* w = nullptr;
     char* tmp = nullptr;
     int32_t* table = nullptr;
-    int st = pool.Alloc(&flag, 256);
-    if (!st && passes > 1) st = pool.Alloc(&tmp, RowBytes(dtype) * (size_t)n);
+    int st = AllocWords(pool, &w);
+    if (!st && passes > 1) st = pool.Alloc(&tmp, bytes);
     if (!st && fixed) st = pool.Alloc(&table, sizeof(int32_t) * (size_t)n * k);
     if (st) return st;
-    if ((st = RequireFinite(points_dev, n, dtype, flag, s))) return st;
+    if ((st = RequireFinite(points_dev, n, dtype, w, s))) return st;
     if (fixed) {
         st = o3dmi_nns_knn_search_counts(points_dev, n, points_dev, n, dtype, k,
                                          table, nullptr, nullptr,
@@ -161,7 +139,7 @@ int o3dmi_pointcloud_smooth_mls(const void* points_dev, const void* normals_dev,
     O3DMI_REQUIRE(points_dev && out_points_dev, "null argument");
     O3DMI_REQUIRE(!out_normals_dev || normals_dev,
                   "out_normals without normals");
-    const size_t bytes = RowBytes(dtype) * (size_t)n;
+    const size_t bytes = 3 * ElemSize(dtype) * (size_t)n;
     O3DMI_REQUIRE(!Overlap(out_points_dev, points_dev, bytes) &&
                           !Overlap(out_points_dev, normals_dev, bytes) &&
                           !Overlap(out_normals_dev, points_dev, bytes) &&
@@ -175,10 +153,10 @@ int o3dmi_pointcloud_smooth_mls(const void* points_dev, const void* normals_dev,
     O3DMI_REQUIRE(n < (1ll << 31) - 1, "too many points");
     hipStream_t s = (hipStream_t)stream;
     PoolScratch pool(s);
-    int* flag = nullptr;
-    int st = pool.Alloc(&flag, 256);
+    Words* w = nullptr;
+    int st = AllocWords(pool, &w);
     if (st) return st;
-    if ((st = RequireFinite(points_dev, n, dtype, flag, s))) return st;
+    if ((st = RequireFinite(points_dev, n, dtype, w, s))) return st;
     // the index and the lists come first: the outputs are written only once
     // nothing but a launch can fail any more
     NnsGuard index;
@@ -210,7 +188,7 @@ int o3dmi_pointcloud_smooth_mls(const void* points_dev, const void* normals_dev,
         O3DMI_HIP_CHECK(hipStreamSynchronize(s));
         const size_t rows = (size_t)(total > 0 ? total : 1);
         st = pool.Alloc(&indices, sizeof(int32_t) * rows);
-        if (!st) st = pool.Alloc(&dist2, (RowBytes(dtype) / 3) * rows);
+        if (!st) st = pool.Alloc(&dist2, ElemSize(dtype) * rows);
         if (st) return st;
         if ((st = o3dmi_nns_radius_search(index.nns, points_dev, n, splits,
                                           indices, dist2, stream)))
@@ -256,7 +234,7 @@ int o3dmi_pointcloud_smooth_bilateral(const void* points_dev,
     int st = CheckHybridArgs(points_dev, normals_dev, n, dtype, radius, max_nn);
     if (st) return st;
     O3DMI_REQUIRE(out_points_dev != nullptr, "null argument");
-    const size_t bytes = RowBytes(dtype) * (size_t)n;
+    const size_t bytes = 3 * ElemSize(dtype) * (size_t)n;
     O3DMI_REQUIRE(!Overlap(out_points_dev, points_dev, bytes) &&
                           !Overlap(out_points_dev, normals_dev, bytes),
                   "out_points aliases an input");
@@ -264,9 +242,9 @@ int o3dmi_pointcloud_smooth_bilateral(const void* points_dev,
         return Unsupported("max_nn > 64 is not supported");
     hipStream_t s = (hipStream_t)stream;
     PoolScratch pool(s);
-    int* flag = nullptr;
-    if ((st = pool.Alloc(&flag, 256))) return st;
-    if ((st = RequireFinite(points_dev, n, dtype, flag, s))) return st;
+    Words* w = nullptr;
+    if ((st = AllocWords(pool, &w))) return st;
+    if ((st = RequireFinite(points_dev, n, dtype, w, s))) return st;
     NnsGuard index;
     st = o3dmi_nns_create(points_dev, n, dtype, radius, stream, &index.nns);
     if (st) return st;
@@ -302,7 +280,7 @@ int o3dmi_pointcloud_compute_boundary_points(const void* points_dev,
     int st = CheckHybridArgs(points_dev, normals_dev, n, dtype, radius, max_nn);
     if (st) return st;
     O3DMI_REQUIRE(mask_out_dev != nullptr, "null argument");
-    const size_t bytes = RowBytes(dtype) * (size_t)n;
+    const size_t bytes = 3 * ElemSize(dtype) * (size_t)n;
     O3DMI_REQUIRE(!Overlap(mask_out_dev, points_dev, bytes) &&
                           !Overlap(mask_out_dev, normals_dev, bytes),
                   "mask_out aliases an input");
@@ -310,16 +288,13 @@ int o3dmi_pointcloud_compute_boundary_points(const void* points_dev,
         return Unsupported("max_nn > 64 is not supported");
     hipStream_t s = (hipStream_t)stream;
     PoolScratch pool(s);
-    int* flag = nullptr;
-    unsigned long long* count = nullptr;
-    if ((st = pool.Alloc(&flag, 256))) return st;
-    if ((st = pool.Alloc(&count, 256))) return st;
-    if ((st = RequireFinite(points_dev, n, dtype, flag, s))) return st;
+    Words* w = nullptr;
+    if ((st = AllocWords(pool, &w))) return st;
+    if ((st = RequireFinite(points_dev, n, dtype, w, s))) return st;
     NnsGuard index;
     st = o3dmi_nns_create(points_dev, n, dtype, radius, stream, &index.nns);
     if (st) return st;
     O3DMI_HIP_CHECK(hipMemsetAsync(mask_out_dev, 0, (size_t)n, s));
-    O3DMI_HIP_CHECK(hipMemsetAsync(count, 0, sizeof(*count), s));
     SmoothOp op{};
     op.kind = kSmoothBoundary;
     op.points = points_dev;
@@ -327,15 +302,10 @@ int o3dmi_pointcloud_compute_boundary_points(const void* points_dev,
     op.mask = mask_out_dev;
     op.p0 = angle_threshold;
     st = HybridSearchSmoothOp(index.nns, points_dev, n, max_nn, op, s);
-    if (!st) st = CountMaskAsync(mask_out_dev, n, count, s);
-    if (st) return st;
-    unsigned long long c = 0;
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&c, count, sizeof(c), hipMemcpyDeviceToHost,
-                                   s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
-    index.completed = true;
-    *m_out = (int64_t)c;
-    return O3DMI_OK;
+    if (!st) st = CountMaskAsync(mask_out_dev, n, &w->count, s);
+    if (!st) st = DownloadCount(w, m_out, s);
+    index.completed = st == O3DMI_OK;  // the stream has drained
+    return st;
 }
 
 int o3dmi_pointcloud_boundary_from_neighbors(

@@ -56,11 +56,6 @@ void* ThreadPinned(size_t bytes) {
     return p;
 }
 
-int Unsupported(const char* msg) {
-    SetLastError(msg);
-    return O3DMI_ERR_UNSUPPORTED;
-}
-
 int CheckEstimator(int estimation, int with_scaling, int ransac_n) {
     if (estimation != O3DMI_ICP_POINT_TO_POINT)
         return Unsupported(

@@ -10,53 +10,9 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "pointcloud_rows.h"
+
 namespace o3dmi {
-
-constexpr int kMaxSelectAttrs = 8;
-
-// Up to eight attributes of one cloud, moved row by row in the same launch.
-struct SelectAttrs {
-    const void* in[kMaxSelectAttrs];
-    void* out[kMaxSelectAttrs];
-    long long row_bytes[kMaxSelectAttrs];
-    int n_attrs;
-};
-
-// Row `src` of every attribute to row `dst`. words: bit a set = attribute a is
-// 4-byte aligned with a width that is a multiple of 4 (positions, normals,
-// float colours); the others (uint8 colours) move byte by byte.
-__device__ __forceinline__ void MoveRow(const SelectAttrs& a, unsigned words,
-                                        int64_t src, int64_t dst) {
-    for (int k = 0; k < a.n_attrs; ++k) {
-        const long long w = a.row_bytes[k];
-        if (words & (1u << k)) {
-            const uint32_t* in = (const uint32_t*)a.in[k] + src * (w >> 2);
-            uint32_t* out = (uint32_t*)a.out[k] + dst * (w >> 2);
-            if (w == 12) {
-                const uint32_t x = in[0], y = in[1], z = in[2];
-                out[0] = x;
-                out[1] = y;
-                out[2] = z;
-            } else {
-                for (long long b = 0; b < (w >> 2); ++b) out[b] = in[b];
-            }
-        } else {
-            const uint8_t* in = (const uint8_t*)a.in[k] + src * w;
-            uint8_t* out = (uint8_t*)a.out[k] + dst * w;
-            for (long long b = 0; b < w; ++b) out[b] = in[b];
-        }
-    }
-}
-
-// The `words` mask of MoveRow for these attributes.
-inline unsigned WordAttrs(const SelectAttrs& a) {
-    unsigned words = 0;
-    for (int k = 0; k < a.n_attrs; ++k)
-        if (((uintptr_t)a.in[k] | (uintptr_t)a.out[k] |
-             (uintptr_t)a.row_bytes[k]) % 4 == 0)
-            words |= 1u << k;
-    return words;
-}
 
 // Scratch of CompactByMaskAsync: int32 flags {n}, int64 offsets {n}, the
 // scan's tile totals.
@@ -75,13 +31,7 @@ int CheckIndexRangeAsync(const int64_t* indices_dev, int64_t m, int64_t n,
 // out row r = in row indices[r] (indices already checked).
 int GatherByIndexAsync(const int64_t* indices_dev, int64_t m,
                        const SelectAttrs& attrs, hipStream_t s);
-// mask[indices[r]] = 1 over a mask the caller has zeroed.
-int IndexToMaskAsync(const int64_t* indices_dev, int64_t m, uint8_t* mask_dev,
-                     hipStream_t s);
 
-// *bad_dev |= 1 when a coordinate is NaN or +-Inf.
-int CheckFiniteAsync(const void* points_dev, int64_t n, int dtype,
-                     int* bad_dev, hipStream_t s);
 // The three remove_nan / remove_inf forms; *count_dev (zeroed by the caller)
 // receives the number of ones.
 int NonFiniteMaskAsync(const void* points_dev, int64_t n, int dtype,

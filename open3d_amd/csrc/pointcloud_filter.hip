@@ -30,20 +30,6 @@
 namespace o3dmi {
 namespace {
 
-// Adds the number of lanes with `keep` to *count: one atomic per wave. Every
-// lane of the wave must call it.
-__device__ __forceinline__ void CountKept(bool keep,
-                                          unsigned long long* count) {
-    const unsigned long long m = __builtin_amdgcn_ballot_w64(keep);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(count, (unsigned long long)__popcll(m));
-}
-
-// Rounds of a grid-stride loop in which every lane takes part.
-__device__ __forceinline__ int64_t Rounds(int64_t n) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    return (n + stride - 1) / stride;
-}
-
 // ---- compaction ---------------------------------------------------------------
 __global__ void MaskFlagsKernel(const uint8_t* __restrict__ mask, int64_t n,
                                 int invert, int32_t* __restrict__ flags) {
@@ -96,25 +82,16 @@ __global__ void FiniteCheckKernel(const T* __restrict__ p, int64_t n3,
 }
 
 template <typename T>
-__global__ void NonFiniteMaskKernel(const T* __restrict__ p, int64_t n,
-                                    int remove_nan, int remove_inf,
-                                    uint8_t* __restrict__ mask,
-                                    unsigned long long* __restrict__ count) {
-    const int64_t rounds = Rounds(n);
-    for (int64_t r = 0; r < rounds; ++r) {
-        const int64_t i = (r * gridDim.x + blockIdx.x) * (int64_t)blockDim.x +
-                          threadIdx.x;
-        bool keep = false;
-        if (i < n) {
-            const T x = p[3 * i + 0], y = p[3 * i + 1], z = p[3 * i + 2];
-            const bool has_nan = isnan(x) || isnan(y) || isnan(z);
-            const bool has_inf = isinf(x) || isinf(y) || isinf(z);
-            keep = !((remove_nan && has_nan) || (remove_inf && has_inf));
-            mask[i] = keep ? 1 : 0;
-        }
-        CountKept(keep, count);
+struct NonFinitePred {
+    const T* p;
+    int remove_nan, remove_inf;
+    __device__ __forceinline__ bool operator()(int64_t i) const {
+        const T x = p[3 * i + 0], y = p[3 * i + 1], z = p[3 * i + 2];
+        const bool has_nan = isnan(x) || isnan(y) || isnan(z);
+        const bool has_inf = isinf(x) || isinf(y) || isinf(z);
+        return !((remove_nan && has_nan) || (remove_inf && has_inf));
     }
-}
+};
 
 // ---- duplicates -----------------------------------------------------------------
 template <typename W> struct KeyOf;
@@ -164,52 +141,36 @@ __global__ void DuplicateInsertKernel(const W* __restrict__ p, int64_t n,
 }
 
 template <typename W>
-__global__ void DuplicateMaskKernel(const W* __restrict__ p, int64_t n,
-                                    const int32_t* __restrict__ table,
-                                    uint32_t slot_mask,
-                                    uint8_t* __restrict__ mask,
-                                    unsigned long long* __restrict__ count) {
-    const int64_t rounds = Rounds(n);
-    for (int64_t r = 0; r < rounds; ++r) {
-        const int64_t i = (r * gridDim.x + blockIdx.x) * (int64_t)blockDim.x +
-                          threadIdx.x;
+struct DuplicatePred {
+    const W* p;
+    const int32_t* table;
+    uint32_t slot_mask;
+    __device__ __forceinline__ bool operator()(int64_t i) const {
+        const W x = p[3 * i + 0], y = p[3 * i + 1], z = p[3 * i + 2];
+        uint32_t h = HashKey(x, y, z) & slot_mask;
         bool keep = false;
-        if (i < n) {
-            const W x = p[3 * i + 0], y = p[3 * i + 1], z = p[3 * i + 2];
-            uint32_t h = HashKey(x, y, z) & slot_mask;
-            for (;;) {
-                const int32_t res = table[h];
-                if (res < 0) break;  // unreachable: i was inserted
-                const W* q = p + 3 * (int64_t)res;
-                if (q[0] == x && q[1] == y && q[2] == z) {
-                    keep = res == (int32_t)i;
-                    break;
-                }
-                h = (h + 1) & slot_mask;
+        for (;;) {
+            const int32_t res = table[h];
+            if (res < 0) break;  // unreachable: i was inserted
+            const W* q = p + 3 * (int64_t)res;
+            if (q[0] == x && q[1] == y && q[2] == z) {
+                keep = res == (int32_t)i;
+                break;
             }
-            mask[i] = keep ? 1 : 0;
+            h = (h + 1) & slot_mask;
         }
-        CountKept(keep, count);
+        return keep;
     }
-}
+};
 
 // ---- radius -----------------------------------------------------------------------
-__global__ void CountThresholdKernel(const int32_t* __restrict__ counts,
-                                     int64_t n, int nb_points,
-                                     uint8_t* __restrict__ mask,
-                                     unsigned long long* __restrict__ count) {
-    const int64_t rounds = Rounds(n);
-    for (int64_t r = 0; r < rounds; ++r) {
-        const int64_t i = (r * gridDim.x + blockIdx.x) * (int64_t)blockDim.x +
-                          threadIdx.x;
-        bool keep = false;
-        if (i < n) {
-            keep = counts[i] >= nb_points;
-            mask[i] = keep ? 1 : 0;
-        }
-        CountKept(keep, count);
+struct CountThresholdPred {
+    const int32_t* counts;
+    int nb_points;
+    __device__ __forceinline__ bool operator()(int64_t i) const {
+        return counts[i] >= nb_points;
     }
-}
+};
 
 // ---- statistical ------------------------------------------------------------------
 // kCentred: sum of (avg_i - mean)^2 with mean = sum_in[0] / n, else sum of
@@ -248,18 +209,9 @@ __global__ void StatisticalMaskKernel(const T* __restrict__ avg, int64_t n,
         stats[1] = sd;
         stats[2] = threshold;
     }
-    unsigned long long* count = (unsigned long long*)(stats + 3);
-    const int64_t rounds = Rounds(n);
-    for (int64_t r = 0; r < rounds; ++r) {
-        const int64_t i = (r * gridDim.x + blockIdx.x) * (int64_t)blockDim.x +
-                          threadIdx.x;
-        bool keep = false;
-        if (i < n) {
-            keep = (double)avg[i] <= threshold;
-            mask[i] = keep ? 1 : 0;
-        }
-        CountKept(keep, count);
-    }
+    MaskAndCount(
+            n, [=](int64_t i) { return (double)avg[i] <= threshold; }, mask,
+            (unsigned long long*)(stats + 3));
 }
 
 constexpr int64_t kMaskLimit = 1ll << 40;  // rows; keeps 3 * i in int64 by far
@@ -343,17 +295,16 @@ int NonFiniteMaskAsync(const void* points_dev, int64_t n, int dtype,
                        unsigned long long* count_dev, hipStream_t s) {
     if (n <= 0) return O3DMI_OK;
     O3DMI_REQUIRE(n < kMaskLimit, "too many points");
-    const dim3 grid(GridFor(n, kBlock)), block(kBlock);
-    if (dtype == O3DMI_F64)
-        hipLaunchKernelGGL(NonFiniteMaskKernel<double>, grid, block, 0, s,
-                           (const double*)points_dev, n, remove_nan ? 1 : 0,
-                           remove_inf ? 1 : 0, mask_dev, count_dev);
-    else
-        hipLaunchKernelGGL(NonFiniteMaskKernel<float>, grid, block, 0, s,
-                           (const float*)points_dev, n, remove_nan ? 1 : 0,
-                           remove_inf ? 1 : 0, mask_dev, count_dev);
-    O3DMI_HIP_CHECK(hipGetLastError());
-    return O3DMI_OK;
+    const int no_nan = remove_nan ? 1 : 0, no_inf = remove_inf ? 1 : 0;
+    return dtype == O3DMI_F64
+                   ? LaunchMask(n,
+                                NonFinitePred<double>{(const double*)points_dev,
+                                                      no_nan, no_inf},
+                                mask_dev, count_dev, s)
+                   : LaunchMask(n,
+                                NonFinitePred<float>{(const float*)points_dev,
+                                                     no_nan, no_inf},
+                                mask_dev, count_dev, s);
 }
 
 int64_t DuplicateTableSlots(int64_t n) {
@@ -378,30 +329,25 @@ int DuplicateMaskAsync(const void* points_dev, int64_t n, int dtype,
         hipLaunchKernelGGL(DuplicateInsertKernel<uint64_t>, grid, block, 0, s,
                            (const uint64_t*)points_dev, n, table_dev,
                            slot_mask);
-        hipLaunchKernelGGL(DuplicateMaskKernel<uint64_t>, grid, block, 0, s,
-                           (const uint64_t*)points_dev, n, table_dev, slot_mask,
-                           mask_dev, count_dev);
-    } else {
-        hipLaunchKernelGGL(DuplicateInsertKernel<uint32_t>, grid, block, 0, s,
-                           (const uint32_t*)points_dev, n, table_dev,
-                           slot_mask);
-        hipLaunchKernelGGL(DuplicateMaskKernel<uint32_t>, grid, block, 0, s,
-                           (const uint32_t*)points_dev, n, table_dev, slot_mask,
-                           mask_dev, count_dev);
+        return LaunchMask(n,
+                          DuplicatePred<uint64_t>{(const uint64_t*)points_dev,
+                                                  table_dev, slot_mask},
+                          mask_dev, count_dev, s);
     }
-    O3DMI_HIP_CHECK(hipGetLastError());
-    return O3DMI_OK;
+    hipLaunchKernelGGL(DuplicateInsertKernel<uint32_t>, grid, block, 0, s,
+                       (const uint32_t*)points_dev, n, table_dev, slot_mask);
+    return LaunchMask(n,
+                      DuplicatePred<uint32_t>{(const uint32_t*)points_dev,
+                                              table_dev, slot_mask},
+                      mask_dev, count_dev, s);
 }
 
 int CountThresholdMaskAsync(const int32_t* counts_dev, int64_t n,
                             int nb_points, uint8_t* mask_dev,
                             unsigned long long* count_dev, hipStream_t s) {
     if (n <= 0) return O3DMI_OK;
-    hipLaunchKernelGGL(CountThresholdKernel, dim3(GridFor(n, kBlock)),
-                       dim3(kBlock), 0, s, counts_dev, n, nb_points, mask_dev,
-                       count_dev);
-    O3DMI_HIP_CHECK(hipGetLastError());
-    return O3DMI_OK;
+    return LaunchMask(n, CountThresholdPred{counts_dev, nb_points}, mask_dev,
+                      count_dev, s);
 }
 
 size_t StatisticalScratchDoubles() { return (size_t)kSumsMaxGrid + 8; }

@@ -10,7 +10,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "pointcloud_filter.h"
+#include "pointcloud_rows.h"
 
 namespace o3dmi {
 

@@ -299,50 +299,16 @@ FarthestStreamKernel(const T* __restrict__ p, int n, int slice, int first,
 }
 
 // ---- masks ------------------------------------------------------------------
-// Adds the number of lanes with `keep` to *count: one atomic per wave. Every
-// lane of the wave must call it.
-__device__ __forceinline__ void CountKept(bool keep,
-                                          unsigned long long* count) {
-    const unsigned long long m = __builtin_amdgcn_ballot_w64(keep);
-    if ((threadIdx.x & 63) == 0 && m)
-        atomicAdd(count, (unsigned long long)__popcll(m));
-}
-
-__device__ __forceinline__ int64_t Rounds(int64_t n) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    return (n + stride - 1) / stride;
-}
-
-template <typename T>
-struct Aabb {
-    T lo[3], hi[3];
-};
-
 // GetPointMaskWithinAABB (PointCloudImpl.h:167-177).
 template <typename T>
-__global__ void AabbMaskKernel(const T* __restrict__ p, int64_t n, Aabb<T> box,
-                               uint8_t* __restrict__ mask,
-                               unsigned long long* __restrict__ count) {
-    const int64_t rounds = Rounds(n);
-    for (int64_t r = 0; r < rounds; ++r) {
-        const int64_t i = (r * gridDim.x + blockIdx.x) * (int64_t)blockDim.x +
-                          threadIdx.x;
-        bool keep = false;
-        if (i < n) {
-            const T x = p[3 * i + 0], y = p[3 * i + 1], z = p[3 * i + 2];
-            keep = x >= box.lo[0] && x <= box.hi[0] && y >= box.lo[1] &&
-                   y <= box.hi[1] && z >= box.lo[2] && z <= box.hi[2];
-            mask[i] = keep ? 1 : 0;
-        }
-        CountKept(keep, count);
+struct AabbPred {
+    const T* p;
+    T lo[3], hi[3];
+    __device__ __forceinline__ bool operator()(int64_t i) const {
+        const T x = p[3 * i + 0], y = p[3 * i + 1], z = p[3 * i + 2];
+        return x >= lo[0] && x <= hi[0] && y >= lo[1] && y <= hi[1] &&
+               z >= lo[2] && z <= hi[2];
     }
-}
-
-template <typename T>
-struct Obb {
-    T center[3];
-    T axis[3][3];  // axis[k] = column k of the rotation
-    T half[3];
 };
 
 template <typename T>
@@ -352,30 +318,25 @@ __device__ __forceinline__ T AbsOf(T v) {
 
 // GetPointMaskWithinOBB (PointCloudImpl.h:194-223); dot_3x1 adds left to right.
 template <typename T>
-__global__ void ObbMaskKernel(const T* __restrict__ p, int64_t n, Obb<T> box,
-                              uint8_t* __restrict__ mask,
-                              unsigned long long* __restrict__ count) {
-    const int64_t rounds = Rounds(n);
-    for (int64_t r = 0; r < rounds; ++r) {
-        const int64_t i = (r * gridDim.x + blockIdx.x) * (int64_t)blockDim.x +
-                          threadIdx.x;
-        bool keep = false;
-        if (i < n) {
-            const T pd0 = p[3 * i + 0] - box.center[0];
-            const T pd1 = p[3 * i + 1] - box.center[1];
-            const T pd2 = p[3 * i + 2] - box.center[2];
-            keep = true;
+struct ObbPred {
+    const T* p;
+    T center[3];
+    T axis[3][3];  // axis[k] = column k of the rotation
+    T half[3];
+    __device__ __forceinline__ bool operator()(int64_t i) const {
+        const T pd0 = p[3 * i + 0] - center[0];
+        const T pd1 = p[3 * i + 1] - center[1];
+        const T pd2 = p[3 * i + 2] - center[2];
+        bool keep = true;
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const T dot = ((pd0 * box.axis[k][0]) + pd1 * box.axis[k][1]) +
-                              pd2 * box.axis[k][2];
-                keep = keep && AbsOf(dot) <= box.half[k];
-            }
-            mask[i] = keep ? 1 : 0;
+        for (int k = 0; k < 3; ++k) {
+            const T dot = ((pd0 * axis[k][0]) + pd1 * axis[k][1]) +
+                          pd2 * axis[k][2];
+            keep = keep && AbsOf(dot) <= half[k];
         }
-        CountKept(keep, count);
+        return keep;
     }
-}
+};
 
 // ---- uniform / random ---------------------------------------------------------
 __global__ void StridedRowsKernel(int64_t m, int64_t every_k, SelectAttrs a,
@@ -565,29 +526,29 @@ int SampleIndicesAsync(uint64_t seed, int64_t n, int64_t m,
 namespace {
 
 template <typename T>
-void LaunchAabb(const void* p, int64_t n, const double* lo, const double* hi,
-                uint8_t* mask, unsigned long long* count, hipStream_t s) {
-    Aabb<T> box;
+int LaunchAabb(const void* p, int64_t n, const double* lo, const double* hi,
+               uint8_t* mask, unsigned long long* count, hipStream_t s) {
+    AabbPred<T> box;
+    box.p = (const T*)p;
     for (int k = 0; k < 3; ++k) {
         box.lo[k] = (T)lo[k];
         box.hi[k] = (T)hi[k];
     }
-    hipLaunchKernelGGL(AabbMaskKernel<T>, dim3(GridFor(n, kBlock)),
-                       dim3(kBlock), 0, s, (const T*)p, n, box, mask, count);
+    return LaunchMask(n, box, mask, count, s);
 }
 
 template <typename T>
-void LaunchObb(const void* p, int64_t n, const double* center,
-               const double* rotation, const double* extent, uint8_t* mask,
-               unsigned long long* count, hipStream_t s) {
-    Obb<T> box;
+int LaunchObb(const void* p, int64_t n, const double* center,
+              const double* rotation, const double* extent, uint8_t* mask,
+              unsigned long long* count, hipStream_t s) {
+    ObbPred<T> box;
+    box.p = (const T*)p;
     for (int k = 0; k < 3; ++k) {
         box.center[k] = (T)center[k];
         box.half[k] = (T)extent[k] / (T)2;
         for (int r = 0; r < 3; ++r) box.axis[k][r] = (T)rotation[3 * r + k];
     }
-    hipLaunchKernelGGL(ObbMaskKernel<T>, dim3(GridFor(n, kBlock)), dim3(kBlock),
-                       0, s, (const T*)p, n, box, mask, count);
+    return LaunchMask(n, box, mask, count, s);
 }
 
 }  // namespace
@@ -597,14 +558,11 @@ int AabbMaskAsync(const void* points_dev, int64_t n, int dtype,
                   uint8_t* mask_dev, unsigned long long* count_dev,
                   hipStream_t s) {
     if (n <= 0) return O3DMI_OK;
-    if (dtype == O3DMI_F64)
-        LaunchAabb<double>(points_dev, n, min_bound, max_bound, mask_dev,
-                           count_dev, s);
-    else
-        LaunchAabb<float>(points_dev, n, min_bound, max_bound, mask_dev,
-                          count_dev, s);
-    O3DMI_HIP_CHECK(hipGetLastError());
-    return O3DMI_OK;
+    return dtype == O3DMI_F64
+                   ? LaunchAabb<double>(points_dev, n, min_bound, max_bound,
+                                        mask_dev, count_dev, s)
+                   : LaunchAabb<float>(points_dev, n, min_bound, max_bound,
+                                       mask_dev, count_dev, s);
 }
 
 int ObbMaskAsync(const void* points_dev, int64_t n, int dtype,
@@ -612,14 +570,11 @@ int ObbMaskAsync(const void* points_dev, int64_t n, int dtype,
                  const double extent[3], uint8_t* mask_dev,
                  unsigned long long* count_dev, hipStream_t s) {
     if (n <= 0) return O3DMI_OK;
-    if (dtype == O3DMI_F64)
-        LaunchObb<double>(points_dev, n, center, rotation, extent, mask_dev,
-                          count_dev, s);
-    else
-        LaunchObb<float>(points_dev, n, center, rotation, extent, mask_dev,
-                         count_dev, s);
-    O3DMI_HIP_CHECK(hipGetLastError());
-    return O3DMI_OK;
+    return dtype == O3DMI_F64
+                   ? LaunchObb<double>(points_dev, n, center, rotation, extent,
+                                       mask_dev, count_dev, s)
+                   : LaunchObb<float>(points_dev, n, center, rotation, extent,
+                                      mask_dev, count_dev, s);
 }
 
 size_t MinMaxScratchDoubles() { return 6 * (size_t)kBoundsMaxGrid + 8; }

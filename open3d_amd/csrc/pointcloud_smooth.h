@@ -57,10 +57,6 @@ int TableSmoothOpAsync(const SmoothOp& op, const int32_t* indices_dev,
                        const int64_t* row_splits_dev, int64_t n, int width,
                        int dtype, hipStream_t s);
 
-// *count_dev (zeroed by the caller) += the number of non-zero mask bytes.
-int CountMaskAsync(const uint8_t* mask_dev, int64_t n,
-                   unsigned long long* count_dev, hipStream_t s);
-
 // The three elementwise calls on normals {n,3}, in place
 // (PointCloudImpl.h:229-350). vec3: the direction / camera location, host
 // float64 {3}; it travels to the kernel by value in the point dtype.

@@ -13,6 +13,7 @@
 // of the searches in nns.hip.
 
 #include "common.h"
+#include "pointcloud_rows.h"
 #include "pointcloud_smooth_device.h"
 
 namespace o3dmi {

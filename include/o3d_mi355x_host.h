@@ -1010,6 +1010,92 @@ int o3dmi_pointcloud_min_max_bound(const void* points_dev, int64_t n,
                                    int dtype, double min_out[3],
                                    double max_out[3], o3dmi_stream_t stream);
 
+/* ---- PointCloud metrics and nearest-point distances ------------------------
+ * (t/geometry/PointCloud.cpp:1805-1836, t/geometry/kernel/Metrics.cpp;
+ * geometry/PointCloud.cpp:133-157. Upstream has no device path: it copies the
+ * clouds to the host and searches two k-d trees.) Float32 / Float64. All
+ * synchronise. The distance of a query is sqrt(d2) in the point dtype, d2 =
+ * the minimum over the target of ((dx dx) + dy dy) + dz dz with dx = query -
+ * point in the point dtype, no FMA: the d2 of every search here. The search is
+ * exact and has no radius: a group of 16 lanes walks the growing cubes of the
+ * finest level of the o3dmi_nns_knn_search index (k = 1) for a query; the
+ * queries that level cannot finish go through that search's second pass.
+ * Size limits are o3dmi_nns_knn_search's (fewer than 2^31 - 1 points a
+ * cloud). */
+
+/* ComputePointCloudDistance with the index as an extra: dist_out_dev {q} in
+ * the point dtype, idx_out_dev {q} int32 (optional) = the LOWEST original
+ * index among the nearest target points. q == 0 is O3DMI_OK with nothing
+ * written. An empty target (upstream: error), n or q negative or out of
+ * range, a NULL pointer, a dtype other than Float32 / Float64 or a NaN / Inf
+ * coordinate in either cloud: O3DMI_ERR_INVALID_ARG with the outputs
+ * untouched. */
+int o3dmi_pointcloud_nearest_distance(const void* target_dev, int64_t n,
+                                      const void* queries_dev, int64_t q,
+                                      int dtype, void* dist_out_dev,
+                                      int32_t* idx_out_dev,
+                                      o3dmi_stream_t stream);
+
+/* Metric codes: upstream's enum order (t/geometry/Geometry.h). */
+typedef enum {
+    O3DMI_METRIC_CHAMFER_DISTANCE = 0,
+    O3DMI_METRIC_HAUSDORFF_DISTANCE = 1,
+    O3DMI_METRIC_FSCORE = 2
+} o3dmi_metric_t;
+
+/* What the metrics are made of, per direction: [0] is cloud 1 -> cloud 2 (the
+ * n1 distances of upstream's distance12), [1] cloud 2 -> cloud 1.
+ *  - sum: the float64 sum of the distances in a fixed tree: consecutive runs
+ *    of 512 values are added in index order, the run sums likewise, level by
+ *    level until one value is left (the tile convention of o3dmi_plane_score).
+ *    The same bits on every run.
+ *  - max: the largest distance, widened to double.
+ *  - counts: set by the CALLER to an int64 array of 2 * n_radii entries (or
+ *    NULL: not wanted); counts[d * n_radii + r] = the number of distances of
+ *    direction d with dist < fscore_radius[r] (strict; a Float32 cloud compares
+ *    in Float32, a Float64 cloud against the radius widened to double).
+ *  - second_pass_queries: the queries the lane-group pass left to the second
+ *    pass (far from the target, or in a sparse region of it). */
+typedef struct {
+    double sum[2];
+    double max[2];
+    int64_t* counts;
+    int64_t second_pass_queries[2];
+} o3dmi_pointcloud_metrics_raw_t;
+
+/* ComputeMetricsCommon (t/geometry/kernel/Metrics.cpp:16-66) statement for
+ * statement, on sums instead of distance tensors; a pure host function. With
+ * mean12 = (float)(sum[0] / n1), mean21 = (float)(sum[1] / n2), in float:
+ *   ChamferDistance   = mean21 + mean12
+ *   HausdorffDistance = max((float)max[0], (float)max[1])
+ *   FScore at radius r: precision = (float)((double)(float)counts[r] *
+ *       (100.0 / n1)), recall likewise from counts[n_radii + r] and n2;
+ *       2 * precision * recall / (precision + recall), or 0 unless
+ *       precision + recall > 0.
+ * Values come out in the order of metrics[]; EVERY FScore entry expands to
+ * n_radii values (upstream sizes its output for one). n1 or n2 < 1, an unknown
+ * code, FScore with n_radii < 1, a negative count or a NULL pointer:
+ * O3DMI_ERR_INVALID_ARG; values_capacity below the number of values:
+ * O3DMI_ERR_CAPACITY; values_out untouched in both cases. */
+int o3dmi_metrics_from_sums(int64_t n1, int64_t n2, const double sum[2],
+                            const double max[2], const int64_t* counts,
+                            int n_radii, const int32_t* metrics, int n_metrics,
+                            float* values_out, int64_t values_capacity);
+
+/* PointCloud::ComputeMetrics: both directed nearest-point distance sets, their
+ * reduction on the device and o3dmi_metrics_from_sums. values_out is a HOST
+ * float array of values_capacity entries; raw_out (optional) receives the
+ * sums. Errors are those of o3dmi_metrics_from_sums and of
+ * o3dmi_pointcloud_nearest_distance (an empty cloud and a NaN / Inf coordinate
+ * in either cloud included), with values_out, raw_out and raw_out->counts
+ * untouched. */
+int o3dmi_pointcloud_compute_metrics(
+        const void* points1_dev, int64_t n1, const void* points2_dev,
+        int64_t n2, int dtype, const int32_t* metrics, int n_metrics,
+        const float* fscore_radius, int n_radii, float* values_out,
+        int64_t values_capacity, o3dmi_pointcloud_metrics_raw_t* raw_out,
+        o3dmi_stream_t stream);
+
 /* The per-fragment step of slac::PreprocessPointClouds (t/pipelines/slac/
  * SLACOptimizer.cpp:47-57). voxel_size > 0: VoxelDownSample ->
  * RemoveStatisticalOutliers(20, 2.0) -> EstimateNormals (KNN, 30); otherwise

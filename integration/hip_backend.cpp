@@ -520,6 +520,32 @@ static_assert(
                         value,
         "the PointCloud smoothing / boundary / normal ...HIP functions have "
         "the dispatchers' per-device signatures");
+
+// 5e'''''. PointCloud::ComputeMetrics (t/geometry/PointCloud.cpp:1805-1836)
+//    has no per-device kernel upstream: the method copies both clouds to the
+//    host and searches two k-d trees. It gains, before those copies,
+//    `if (IsHIP() && pcd2.IsHIP()) return kernel::pointcloud::ComputeMetricsHIP(
+//    GetPointPositions(), pcd2.GetPointPositions(), codes,
+//    params.fscore_radius);` with codes[i] = static_cast<int32_t>(metrics[i])
+//    (the library's codes are upstream's enum order). The result is a host
+//    Float32 tensor, as upstream's.
+core::Tensor ComputeMetricsHIP(const core::Tensor& points1,
+                               const core::Tensor& points2,
+                               const std::vector<int32_t>& metrics,
+                               const std::vector<float>& fscore_radius) {
+    int64_t n_values = 0;
+    for (int32_t m : metrics)
+        n_values += m == O3DMI_METRIC_FSCORE ? (int64_t)fscore_radius.size()
+                                             : 1;
+    std::vector<float> values((size_t)n_values);
+    O3DMI_CALL(o3dmi_pointcloud_compute_metrics(
+            points1.GetDataPtr(), points1.GetLength(), points2.GetDataPtr(),
+            points2.GetLength(), core::ToO3dmi(points1.GetDtype()),
+            metrics.data(), (int)metrics.size(), fscore_radius.data(),
+            (int)fscore_radius.size(), values.data(), n_values, nullptr,
+            core::HipStream()));
+    return core::Tensor(values, {n_values}, core::Float32);
+}
 }  // namespace pointcloud
 }  // namespace kernel
 }  // namespace geometry

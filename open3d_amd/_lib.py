@@ -180,6 +180,12 @@ class SegmentPlaneInfoC(C.Structure):
                 ("inlier_rmse", _d)]
 
 
+class MetricsRawC(C.Structure):
+    _fields_ = [("sum", _d * 2), ("max", _d * 2),
+                ("counts", C.POINTER(_i64)),
+                ("second_pass_queries", _i64 * 2)]
+
+
 class IcpAttributes(C.Structure):
     _fields_ = [("source_normals", _vp), ("source_colors", _vp),
                 ("target_colors", _vp), ("target_color_gradients", _vp),
@@ -388,6 +394,15 @@ PROTOTYPES.update({
         _i32, [_vp, _i64, _i32, _dp, _dp, _dp, _vp, C.POINTER(_i64), _vp]),
     "o3dmi_pointcloud_min_max_bound": (_i32, [_vp, _i64, _i32, _dp, _dp,
                                               _vp]),
+    "o3dmi_pointcloud_nearest_distance": (
+        _i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "o3dmi_metrics_from_sums": (
+        _i32, [_i64, _i64, _dp, _dp, C.POINTER(_i64), _i32, C.POINTER(_i32),
+               _i32, C.POINTER(_f), _i64]),
+    "o3dmi_pointcloud_compute_metrics": (
+        _i32, [_vp, _i64, _vp, _i64, _i32, C.POINTER(_i32), _i32,
+               C.POINTER(_f), _i32, C.POINTER(_f), _i64,
+               C.POINTER(MetricsRawC), _vp]),
     "o3dmi_pointcloud_smooth_laplacian": (
         _i32, [_vp, _i64, _i32, _i64, _d, _i32, _i32, _vp, _vp]),
     "o3dmi_pointcloud_smooth_taubin": (

@@ -136,6 +136,69 @@ inline NnsView<T> MakeView(const o3dmi_nns* nns) {
     return v;
 }
 
+// The square root every distance output takes, in the point dtype (float32:
+// correctly rounded under the library's build flags).
+__device__ __forceinline__ float SqrtOf(float x) { return sqrtf(x); }
+__device__ __forceinline__ double SqrtOf(double x) { return sqrt(x); }
+
+// One level of the KNN index (nns.hip, "k nearest neighbours without a
+// radius"): the bucketed grid, its cell edge and the occupied cell box.
+template <typename T>
+struct KnnGrid {
+    NnsView<T> nv;
+    double cell;
+    long long cmin[3], cmax[3];  // occupied cell box
+};
+
+// Shells a level is searched for before a query is left to a coarser one.
+constexpr int kKnnShells = 3;
+
+// ---- exact nearest point of every query (NearestSearchRun, nns.hip) ---------
+// What the first pass gets: the finest level of the KNN index as KnnSearchRun
+// builds it for k = 1. With `exhaustive` that level spans the whole cloud and
+// its box is searched in one step (no retry list then); else a query the level
+// cannot finish appends its id to retry_ids and is answered by the second pass.
+struct NearestFirstPass {
+    const o3dmi_nns* finest;
+    long long cmin[3], cmax[3];
+    int first_radius;
+    int exhaustive;
+    int* retry_ids;
+    int* retry_count;
+};
+
+template <typename T>
+inline KnnGrid<T> MakeKnnGrid(const o3dmi_nns* lv, const long long* cmin,
+                              const long long* cmax) {
+    KnnGrid<T> g;
+    g.nv = MakeView<T>(lv);
+    g.cell = lv->radius;
+    for (int a = 0; a < 3; ++a) {
+        g.cmin[a] = cmin[a];
+        g.cmax[a] = cmax[a];
+    }
+    return g;
+}
+
+// Launches the first pass over all q queries: d2_dev {q} in the point dtype
+// and idx_dev {q} (or NULL) get the slots of the queries it finishes.
+using NearestFirstPassFn = int (*)(const NearestFirstPass& fp, int dtype,
+                                   const void* queries_dev, int64_t q,
+                                   void* d2_dev, int32_t* idx_dev,
+                                   hipStream_t s);
+
+// d2_dev[i] = min over the n points of ((dx dx) + dy dy) + dz dz, dx = query -
+// point, in the point dtype; idx_dev[i] (optional) = the lowest original index
+// among the minima. Steps 1, 2 and 4 of KnnSearchRun (bounding box, cell size,
+// second-pass choice) with `first_pass` as step 3 and KnnSearchKernel with
+// knn = 1 over the retry ids as the second pass. Waits for the stream (twice
+// at least) and returns with the device drained; *second_pass_queries (optional) = the length of the retry list.
+// Size limits and their errors are o3dmi_nns_knn_search's.
+int NearestSearchRun(const void* points_dev, int64_t n, const void* queries_dev,
+                     int64_t q, int dtype, void* d2_dev, int32_t* idx_dev,
+                     NearestFirstPassFn first_pass,
+                     int64_t* second_pass_queries, hipStream_t s);
+
 // Nearest neighbour with d2 < r2 (strict), ties -> lowest original index.
 // Returns the position in the sorted array (or -1); idx/d2 by reference.
 // Distance arithmetic: nanoflann::L2_Adaptor::evalMetric for dim 3,

@@ -648,8 +648,20 @@ struct TopKOut {
     }
 };
 
-__device__ __forceinline__ float SqrtOf(float x) { return sqrtf(x); }
-__device__ __forceinline__ double SqrtOf(double x) { return sqrt(x); }
+// NearestOut: the second pass of NearestSearchRun (knn = 1): the squared
+// distance to the nearest point into slot i and, when asked, its index.
+template <typename T>
+struct NearestOut {
+    T* d2;
+    int* idx;
+    __device__ __forceinline__ void Write(const WaveTopK<T>& list,
+                                          int64_t i) const {
+        if ((threadIdx.x & 63) == 0) {
+            d2[i] = list.best_d;
+            if (idx) idx[i] = list.best_i;
+        }
+    }
+};
 
 // AvgDistanceOut: only the mean distance to the neighbours
 // (RemoveStatisticalOutliers: distance2.Sqrt().Mean({1}), t/geometry/
@@ -1126,15 +1138,8 @@ RadiusCovariancesKernel(NnsView<T> nv, const T* __restrict__ q, int64_t nq,
 // the next coarser level (the list starts over there). The
 // coarsest level spans the whole cloud in a handful of cells and is searched
 // exhaustively.
-template <typename T>
-struct KnnGrid {
-    NnsView<T> nv;
-    double cell;
-    long long cmin[3], cmax[3];  // occupied cell box
-};
-
+// (KnnGrid and kKnnShells: nns.h.)
 constexpr int kKnnMaxLevels = 12;
-constexpr int kKnnShells = 3;
 
 template <typename T>
 struct KnnPyramid {
@@ -1842,6 +1847,8 @@ int o3dmi_nns_radius_covariances(const o3dmi_nns_t* nns, const void* queries_dev
     return O3DMI_OK;
 }
 
+}  // extern "C"
+
 namespace {
 
 // Everything a KnnSearch call owns; released on every exit path (the index
@@ -1877,28 +1884,20 @@ struct KnnResources {
 
 namespace {
 
-// The KNN search behind the entry points below. With `op` the finished lists
-// go through its smoothing policy (queries are the cloud itself); else, with
-// avg_dev == NULL, the rows go to idx_dev / dist2_dev / counts_dev (TopKOut);
-// else only the mean neighbour distance of every query goes to avg_dev {q}
-// (AvgDistanceOut).
-int KnnSearchRun(const void* points_dev, int64_t n, const void* queries_dev,
-                 int64_t q, int dtype, int knn, int32_t* idx_dev,
-                 void* dist2_dev, int32_t* counts_dev, void* avg_dev,
-                 const SmoothOp* op, o3dmi_stream_t stream) {
-    O3DMI_REQUIRE(dtype == O3DMI_F32 || dtype == O3DMI_F64,
-                  "points must be Float32 or Float64");
-    O3DMI_REQUIRE(knn > 0, "knn should be larger than 0.");
-    O3DMI_REQUIRE(n > 0 && n < (1ll << 31) && points_dev, "empty dataset");
-    O3DMI_REQUIRE(q >= 0 && q < (1ll << 31) - 1, "q out of range");
-    const int k = (int)(n < (int64_t)knn ? n : (int64_t)knn);
-    O3DMI_REQUIRE(k <= kMaxKnn, "knn > 64 is not supported");
-    if (q == 0) return O3DMI_OK;
-    O3DMI_REQUIRE(queries_dev && (idx_dev || avg_dev || op), "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    KnnResources res;
-    int st;
+// What steps 1 and 2 of a KNN search leave behind: the dataset's bounding box
+// and the cell size of the finest level (res.levels[0]).
+struct KnnPlan {
+    double lo[3], ext[3];
+    double emax;    // largest extent (1 for a cloud of no extent)
+    double h;       // cell edge of the finest level
+    double target;  // points per occupied cell aimed at
+    bool single;    // one level already spans the cloud
+};
 
+// Steps 1 and 2 of KnnSearchRun / NearestSearchRun for rows of k neighbours.
+int KnnPlanFinest(const void* points_dev, int64_t n, int dtype, int k,
+                  KnnResources& res, KnnPlan& plan, hipStream_t s) {
+    int st;
     // 1. Bounding box of the dataset.
     if ((st = PoolAlloc((void**)&res.box, 64))) return st;
     unsigned* occupied = (unsigned*)(res.box + 6);
@@ -1920,7 +1919,8 @@ int KnnSearchRun(const void* points_dev, int64_t n, const void* queries_dev,
     O3DMI_HIP_CHECK(hipMemcpyAsync(hbox, res.box, sizeof(hbox),
                                    hipMemcpyDeviceToHost, s));
     O3DMI_HIP_CHECK(hipStreamSynchronize(s));
-    double lo[3], ext[3];
+    double* lo = plan.lo;
+    double* ext = plan.ext;
     for (int a = 0; a < 3; ++a) {
         lo[a] = FromOrderedKey(hbox[a]);
         const double hi = FromOrderedKey(hbox[3 + a]);
@@ -1967,16 +1967,132 @@ int KnnSearchRun(const void* points_dev, int64_t n, const void* queries_dev,
         if (h_next == h) break;
         h = h_next;
     }
+    plan.emax = emax;
+    plan.h = h;
+    plan.target = target;
+    plan.single = !(emax / h > 3.0);
+    return O3DMI_OK;
+}
+
+// The retry list of the first pass ([0] = count, [1..q] = ids); none when one
+// level spans the cloud.
+int KnnAllocRetry(KnnResources& res, const KnnPlan& plan, int64_t q,
+                  hipStream_t s) {
+    if (plan.single) return O3DMI_OK;
+    int st;
+    if ((st = PoolAlloc((void**)&res.retry, sizeof(int) * (size_t)(q + 1))))
+        return st;
+    O3DMI_HIP_CHECK(hipMemsetAsync(res.retry, 0, sizeof(int), s));
+    return O3DMI_OK;
+}
+
+// Occupied cell box of level `lv` from the dataset's bounding box.
+void KnnCellBox(const o3dmi_nns* lv, const KnnPlan& plan, long long* cmin,
+                long long* cmax) {
+    for (int a = 0; a < 3; ++a) {
+        cmin[a] = (long long)std::floor(plan.lo[a] * lv->inv_cell) - 1;
+        cmax[a] = (long long)std::floor((plan.lo[a] + plan.ext[a]) *
+                                        lv->inv_cell) + 1;
+    }
+}
+
+template <typename T>
+KnnPyramid<T> MakePyramid(const KnnResources& res, const KnnPlan& plan,
+                          int64_t n, int first_level, bool exhaustive,
+                          bool brute) {
+    KnnPyramid<T> pyr;
+    pyr.n_levels = (int)res.levels.size();
+    pyr.first_radius = 1;
+    pyr.first_level = first_level;
+    pyr.exhaustive_last = exhaustive ? 1 : 0;
+    pyr.brute = brute ? 1 : 0;
+    pyr.n_points = n;
+    for (int l = 0; l < pyr.n_levels; ++l) {
+        const o3dmi_nns* lv = res.levels[l];
+        long long cmin[3], cmax[3];
+        KnnCellBox(lv, plan, cmin, cmax);
+        pyr.level[l] = MakeKnnGrid<T>(lv, cmin, cmax);
+    }
+    return pyr;
+}
+
+// Length of the retry list once the first pass has run.
+int KnnRetryCount(const KnnResources& res, const KnnPlan& plan, int* n_retry,
+                  hipStream_t s) {
+    *n_retry = 0;
+    if (plan.single) return O3DMI_OK;
+    O3DMI_HIP_CHECK(hipMemcpyAsync(n_retry, res.retry, sizeof(int),
+                                   hipMemcpyDeviceToHost, s));
+    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
+    return O3DMI_OK;
+}
+
+// 4. Second pass: a coalesced sweep over all records when the leftovers
+// are few, else a pyramid of 4x coarser levels (built only now) whose
+// last level spans the cloud in <= 4 cells per axis and is searched
+// exhaustively. launch(first_level, exhaustive, brute, ids, count, retry_ids,
+// retry_count) is the caller's KnnSearchKernel launch.
+template <typename Launch>
+int KnnSecondPass(const void* points_dev, int64_t n, int dtype, int k,
+                  KnnResources& res, const KnnPlan& plan, int n_retry,
+                  Launch&& launch, hipStream_t s) {
+    int st;
+    double sweep_limit = 2e9;  // leftover queries x points
+    if (const char* e_ = std::getenv("O3DMI_KNN_SWEEP_LIMIT"))
+        sweep_limit = std::atof(e_);
+    const bool brute = (double)n_retry * (double)n <= sweep_limit;
+    if (n_retry > 0 && brute) {
+        if ((st = launch(0, false, true, res.retry + 1, n_retry, nullptr,
+                         nullptr)))
+            return st;
+    } else if (n_retry > 0) {
+        while ((int)res.levels.size() < kKnnMaxLevels &&
+               plan.emax / res.levels.back()->radius > 3.0) {
+            if ((st = res.AddLevel(points_dev, n, dtype,
+                                   res.levels.back()->radius * 4.0, s)))
+                return st;
+        }
+        if ((st = launch(1, true, false, res.retry + 1, n_retry, nullptr,
+                         nullptr)))
+            return st;
+    }
+    if (std::getenv("O3DMI_VERBOSE"))
+        std::fprintf(stderr,
+                     "[o3dmi] knn: n=%lld k=%d cell=%g levels=%d target=%g "
+                     "second-pass queries=%d (%s)\n",
+                     (long long)n, k, plan.h, (int)res.levels.size(),
+                     plan.target, n_retry, brute ? "sweep" : "pyramid");
+    return O3DMI_OK;
+}
+
+// The KNN search behind the entry points below. With `op` the finished lists
+// go through its smoothing policy (queries are the cloud itself); else, with
+// avg_dev == NULL, the rows go to idx_dev / dist2_dev / counts_dev (TopKOut);
+// else only the mean neighbour distance of every query goes to avg_dev {q}
+// (AvgDistanceOut).
+int KnnSearchRun(const void* points_dev, int64_t n, const void* queries_dev,
+                 int64_t q, int dtype, int knn, int32_t* idx_dev,
+                 void* dist2_dev, int32_t* counts_dev, void* avg_dev,
+                 const SmoothOp* op, o3dmi_stream_t stream) {
+    O3DMI_REQUIRE(dtype == O3DMI_F32 || dtype == O3DMI_F64,
+                  "points must be Float32 or Float64");
+    O3DMI_REQUIRE(knn > 0, "knn should be larger than 0.");
+    O3DMI_REQUIRE(n > 0 && n < (1ll << 31) && points_dev, "empty dataset");
+    O3DMI_REQUIRE(q >= 0 && q < (1ll << 31) - 1, "q out of range");
+    const int k = (int)(n < (int64_t)knn ? n : (int64_t)knn);
+    O3DMI_REQUIRE(k <= kMaxKnn, "knn > 64 is not supported");
+    if (q == 0) return O3DMI_OK;
+    O3DMI_REQUIRE(queries_dev && (idx_dev || avg_dev || op), "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    KnnResources res;
+    KnnPlan plan;
+    int st;
+    if ((st = KnnPlanFinest(points_dev, n, dtype, k, res, plan, s))) return st;
 
     // 3. First pass on the finest level alone; the queries it cannot finish
     // (too few points within kKnnShells shells: sparse regions, outliers,
     // queries away from the cloud) are collected for a second pass.
-    const bool single = !(emax / h > 3.0);  // one level already spans the cloud
-    if (!single) {
-        if ((st = PoolAlloc((void**)&res.retry, sizeof(int) * (size_t)(q + 1))))
-            return st;
-        O3DMI_HIP_CHECK(hipMemsetAsync(res.retry, 0, sizeof(int), s));
-    }
+    if ((st = KnnAllocRetry(res, plan, q, s))) return st;
     auto launch = [&](int first_level, bool exhaustive, bool brute,
                       const int* ids, int64_t count, int* retry_ids,
                       int* retry_count) -> int {
@@ -1984,24 +2100,8 @@ int KnnSearchRun(const void* points_dev, int64_t n, const void* queries_dev,
                 block(kCoopBlock);
 #define O3DMI_KNN(T)                                                           \
     do {                                                                       \
-        KnnPyramid<T> pyr;                                                     \
-        pyr.n_levels = (int)res.levels.size();                                 \
-        pyr.first_radius = 1;                                                  \
-        pyr.first_level = first_level;                                         \
-        pyr.exhaustive_last = exhaustive ? 1 : 0;                              \
-        pyr.brute = brute ? 1 : 0;                                             \
-        pyr.n_points = n;                                                      \
-        for (int l = 0; l < pyr.n_levels; ++l) {                               \
-            const o3dmi_nns* lv = res.levels[l];                               \
-            KnnGrid<T>& kg = pyr.level[l];                                     \
-            kg.nv = MakeView<T>(lv);                                           \
-            kg.cell = lv->radius;                                              \
-            for (int a = 0; a < 3; ++a) {                                      \
-                kg.cmin[a] = (long long)std::floor(lo[a] * lv->inv_cell) - 1;  \
-                kg.cmax[a] = (long long)std::floor((lo[a] + ext[a]) *          \
-                                                   lv->inv_cell) + 1;          \
-            }                                                                  \
-        }                                                                      \
+        const KnnPyramid<T> pyr =                                              \
+                MakePyramid<T>(res, plan, n, first_level, exhaustive, brute);  \
         if (op && op->kind == kSmoothLaplacian)                                \
             hipLaunchKernelGGL((KnnSearchKernel<T, LaplacianOut<T>>), grid,    \
                                block,                                          \
@@ -2036,49 +2136,77 @@ int KnnSearchRun(const void* points_dev, int64_t n, const void* queries_dev,
         O3DMI_HIP_CHECK(hipGetLastError());
         return O3DMI_OK;
     };
-    if ((st = launch(0, single, false, nullptr, q,
+    if ((st = launch(0, plan.single, false, nullptr, q,
                      res.retry ? res.retry + 1 : nullptr, res.retry)))
         return st;
     int n_retry = 0;
-    if (!single) {
-        O3DMI_HIP_CHECK(hipMemcpyAsync(&n_retry, res.retry, sizeof(int),
-                                       hipMemcpyDeviceToHost, s));
-        O3DMI_HIP_CHECK(hipStreamSynchronize(s));
-    }
-
-    // 4. Second pass: a coalesced sweep over all records when the leftovers
-    // are few, else a pyramid of 4x coarser levels (built only now) whose
-    // last level spans the cloud in <= 4 cells per axis and is searched
-    // exhaustively.
-    double sweep_limit = 2e9;  // leftover queries x points
-    if (const char* e_ = std::getenv("O3DMI_KNN_SWEEP_LIMIT"))
-        sweep_limit = std::atof(e_);
-    const bool brute = (double)n_retry * (double)n <= sweep_limit;
-    if (n_retry > 0 && brute) {
-        if ((st = launch(0, false, true, res.retry + 1, n_retry, nullptr,
-                         nullptr)))
-            return st;
-    } else if (n_retry > 0) {
-        while ((int)res.levels.size() < kKnnMaxLevels &&
-               emax / res.levels.back()->radius > 3.0) {
-            if ((st = res.AddLevel(points_dev, n, dtype,
-                                   res.levels.back()->radius * 4.0, s)))
-                return st;
-        }
-        if ((st = launch(1, true, false, res.retry + 1, n_retry, nullptr,
-                         nullptr)))
-            return st;
-    }
-    if (std::getenv("O3DMI_VERBOSE"))
-        std::fprintf(stderr,
-                     "[o3dmi] knn: n=%lld k=%d cell=%g levels=%d target=%g "
-                     "second-pass queries=%d (%s)\n",
-                     (long long)n, k, h, (int)res.levels.size(), target,
-                     n_retry, brute ? "sweep" : "pyramid");
-    return O3DMI_OK;
+    if ((st = KnnRetryCount(res, plan, &n_retry, s))) return st;
+    return KnnSecondPass(points_dev, n, dtype, k, res, plan, n_retry, launch,
+                         s);
 }
 
 }  // namespace
+
+int o3dmi::NearestSearchRun(const void* points_dev, int64_t n,
+                            const void* queries_dev, int64_t q, int dtype,
+                            void* d2_dev, int32_t* idx_dev,
+                            NearestFirstPassFn first_pass,
+                            int64_t* second_pass_queries, hipStream_t s) {
+    O3DMI_REQUIRE(dtype == O3DMI_F32 || dtype == O3DMI_F64,
+                  "points must be Float32 or Float64");
+    O3DMI_REQUIRE(n > 0 && n < (1ll << 31) && points_dev, "empty dataset");
+    O3DMI_REQUIRE(q >= 0 && q < (1ll << 31) - 1, "q out of range");
+    O3DMI_REQUIRE(first_pass != nullptr, "null argument");
+    if (second_pass_queries) *second_pass_queries = 0;
+    if (q == 0) return O3DMI_OK;
+    O3DMI_REQUIRE(queries_dev && d2_dev, "null argument");
+    KnnResources res;
+    KnnPlan plan;
+    int st;
+    if ((st = KnnPlanFinest(points_dev, n, dtype, 1, res, plan, s))) return st;
+    if ((st = KnnAllocRetry(res, plan, q, s))) return st;
+    NearestFirstPass fp;
+    fp.finest = res.levels[0];
+    KnnCellBox(fp.finest, plan, fp.cmin, fp.cmax);
+    fp.first_radius = 1;
+    fp.exhaustive = plan.single ? 1 : 0;
+    fp.retry_ids = res.retry ? res.retry + 1 : nullptr;
+    fp.retry_count = res.retry;
+    if ((st = first_pass(fp, dtype, queries_dev, q, d2_dev, idx_dev, s)))
+        return st;
+    int n_retry = 0;
+    if ((st = KnnRetryCount(res, plan, &n_retry, s))) return st;
+    auto launch = [&](int first_level, bool exhaustive, bool brute,
+                      const int* ids, int64_t count, int* retry_ids,
+                      int* retry_count) -> int {
+        const dim3 grid(GridFor(count, kCoopBlock / 64, kCUs * 16)),
+                block(kCoopBlock);
+        if (dtype == O3DMI_F64)
+            hipLaunchKernelGGL(
+                    (KnnSearchKernel<double, NearestOut<double>>), grid, block,
+                    CoopLdsBytesPerWave<double>() * (kCoopBlock / 64), s,
+                    MakePyramid<double>(res, plan, n, first_level, exhaustive,
+                                        brute),
+                    (const double*)queries_dev, count, 1, ids, retry_ids,
+                    retry_count, NearestOut<double>{(double*)d2_dev, idx_dev});
+        else
+            hipLaunchKernelGGL(
+                    (KnnSearchKernel<float, NearestOut<float>>), grid, block,
+                    CoopLdsBytesPerWave<float>() * (kCoopBlock / 64), s,
+                    MakePyramid<float>(res, plan, n, first_level, exhaustive,
+                                       brute),
+                    (const float*)queries_dev, count, 1, ids, retry_ids,
+                    retry_count, NearestOut<float>{(float*)d2_dev, idx_dev});
+        O3DMI_HIP_CHECK(hipGetLastError());
+        return O3DMI_OK;
+    };
+    st = KnnSecondPass(points_dev, n, dtype, 1, res, plan, n_retry, launch, s);
+    if (st) return st;
+    if (second_pass_queries) *second_pass_queries = n_retry;
+    return O3DMI_OK;  // (KnnResources waits before the pool gets its blocks)
+}
+
+extern "C" {
 
 // Internal form (also fills counts_dev {q} with the row width when given).
 int o3dmi_nns_knn_search_counts(const void* points_dev, int64_t n,

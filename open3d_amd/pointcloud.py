@@ -1,7 +1,7 @@
 """Mirror of t::geometry::PointCloud's selection, filter, sampling, cropping,
-smoothing, boundary, normal-orientation and segmentation methods
-(t/geometry/PointCloud.cpp:435-494, 569-854, 986-1050, 1074-1203, 1634-1720) on
-the HIP backend.
+smoothing, boundary, normal-orientation, segmentation and metrics methods
+(t/geometry/PointCloud.cpp:435-494, 569-854, 986-1050, 1074-1203, 1634-1720,
+1805-1836) on the HIP backend.
 
 A cloud is a dict of CUDA attribute tensors with "positions" ({N,3} Float32 or
 Float64) required; every other attribute has N rows of any width and dtype
@@ -348,6 +348,65 @@ def get_min_bound(attrs):
 def get_max_bound(attrs):
     """PointCloud::GetMaxBound."""
     return get_min_max_bound(attrs)[1]
+
+
+# ---- metrics and nearest-point distances ---------------------------------------
+
+class Metric:
+    """t::geometry::Metric, in upstream's enum order."""
+    ChamferDistance = 0
+    HausdorffDistance = 1
+    FScore = 2
+
+
+def compute_point_cloud_distance(attrs, target_attrs, return_index=False):
+    """PointCloud::ComputePointCloudDistance: for every point of the cloud the
+    distance to the nearest point of the target, {N} in the point dtype; with
+    return_index also the Int32 {N} index of that point (ties: the lowest)."""
+    p, t = _positions(attrs), _positions(target_attrs)
+    if p.dtype != t.dtype:
+        raise ValueError("both clouds must have the same dtype")
+    q = p.shape[0]
+    dist = torch.empty(q, dtype=p.dtype, device=p.device)
+    idx = torch.empty(q, dtype=torch.int32,
+                      device=p.device) if return_index else None
+    _lib.check(_lib.lib().o3dmi_pointcloud_nearest_distance(
+        _lib.ptr(t), t.shape[0], _lib.ptr(p), q, TORCH_TO_O3DMI[p.dtype],
+        _lib.ptr(dist), _lib.ptr(idx), stream()),
+        "compute_point_cloud_distance")
+    if return_index:
+        return dist, idx
+    return dist
+
+
+def compute_metrics(attrs1, attrs2, metrics, fscore_radius=(0.01,),
+                    return_raw=False):
+    """PointCloud::ComputeMetrics -> a CPU Float32 tensor with the values in the
+    order of `metrics` (Metric codes); every FScore entry expands to one value
+    per radius. With return_raw also a dict(sum, max, counts,
+    second_pass_queries), each with the direction 1 -> 2 first."""
+    p1, p2 = _positions(attrs1), _positions(attrs2)
+    if p1.dtype != p2.dtype:
+        raise ValueError("both clouds must have the same dtype")
+    codes = [int(m) for m in metrics]
+    radii = [float(r) for r in fscore_radius]
+    n_values = sum(len(radii) if m == Metric.FScore else 1 for m in codes)
+    values = (C.c_float * max(n_values, 1))()
+    counts = (C.c_int64 * max(2 * len(radii), 1))()
+    raw = _lib.MetricsRawC()
+    raw.counts = C.cast(counts, C.POINTER(C.c_int64))
+    _lib.check(_lib.lib().o3dmi_pointcloud_compute_metrics(
+        _lib.ptr(p1), p1.shape[0], _lib.ptr(p2), p2.shape[0],
+        TORCH_TO_O3DMI[p1.dtype], (C.c_int * max(len(codes), 1))(*codes),
+        len(codes), (C.c_float * max(len(radii), 1))(*radii), len(radii),
+        values, n_values, C.byref(raw), stream()), "compute_metrics")
+    out = torch.tensor(list(values)[:n_values], dtype=torch.float32)
+    if not return_raw:
+        return out
+    r = len(radii)
+    return out, dict(sum=list(raw.sum), max=list(raw.max),
+                     counts=[list(counts)[:r], list(counts)[r:2 * r]],
+                     second_pass_queries=list(raw.second_pass_queries))
 
 
 # ---- smoothing, boundary detection, normal orientation ------------------------

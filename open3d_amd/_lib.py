@@ -581,6 +581,10 @@ INTERNAL_PROTOTYPES = {
     "o3dmi_internal_pointcloud_smooth_from_neighbors": (
         _i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _d, _d, _vp,
                _vp, _vp, _vp]),
+    # csrc/nns.h: (index, queries, ids, nq, max_knn, idx, dist2, counts,
+    # stream)
+    "o3dmi_internal_nns_hybrid_search_wide": (
+        _i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

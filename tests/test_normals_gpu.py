@@ -77,7 +77,10 @@ def test_hybrid_search_general_k(dtype, k):
     assert np.array_equal(cnt.cpu().numpy(), want[2])
     assert np.array_equal(idx.cpu().numpy(), want[0])
     assert d2.cpu().numpy().tobytes() == want[1].tobytes()
-    assert want[2].max() == min(k, want[2].max()) and want[2].min() <= 2
+    # what this thin cloud provides: no neighbourhood of 30 at r = 0.07, so
+    # the k = 30 and k = 64 lists never fill (full lists, cuts inside ties and
+    # merges: tests/test_nns_dense_gpu.py)
+    assert want[2].max() < 30 and want[2].min() <= 2
     # the reference's own golden (cpp/tests/core/NearestNeighborSearch.cpp:321-377)
     ref_pts = np.array([[0.0, 0.0, 0.0], [0.0, 0.0, 0.1], [0.0, 0.0, 0.2],
                         [0.0, 0.1, 0.0], [0.0, 0.1, 0.1], [0.0, 0.1, 0.2],

@@ -617,6 +617,32 @@ int o3dmi_icp_doppler_accumulate(
         double doppler_scaling, double doppler_shape, double lambda_doppler,
         double* sums29_dev, o3dmi_stream_t stream);
 
+/* TransformationEstimationForGeneralizedICP::ComputeTransformation up to the
+ * reduction (legacy GeneralizedICP.cpp:104-155; Segal et al., RSS 2009). Per
+ * pair with corr >= 0, in float64 for both dtypes (widening Float32 is exact):
+ * Cs' = R Cs R^T with R_source9 the rotation the source POSITIONS have already
+ * received (host, row-major; NULL = identity), M = Ct + Cs', W = M^-1/2 through
+ * a Jacobi eigen-decomposition (the reference's M.inverse().sqrt(): the
+ * principal root of an SPD matrix is unique), d = vs - vt, J = W [-[vs]x | I],
+ * and per row i: r_i = W_i . d, w_i = RobustWeight(r_i), JtJ += w_i J_i J_i^T,
+ * Jtr += w_i J_i r_i, [27] += r_i^2 (unweighted), [28] += 1 per pair -- the
+ * 29-sum layout of o3dmi_decode_and_solve6x6. Only the upper triangle of each
+ * covariance {N,3,3} is read (the reference inverts the full matrix: an
+ * asymmetric input differs). A pair that cannot be whitened (an eigenvalue
+ * of M not > 0 or not finite: rank-deficient or NaN covariances) adds nothing
+ * to [0..28] and is counted in sums32[29]; [30] = [31] = 0 (the reference sums
+ * NaN). Robust kernel outside 0..6: O3DMI_ERR_INVALID_ARG. n == 0 or every row
+ * -1: 32 zeros. Every correspondence is range-checked on the device: an index
+ * outside [0, nt) other than -1 is O3DMI_ERR_INVALID_ARG and sums32_dev keeps
+ * its contents. The same fixed float64 reduction tree as the other seams: the
+ * same bits on every run. The call waits for the range check's verdict. */
+int o3dmi_icp_generalized_accumulate(
+        const void* src_dev, const void* src_covariances_dev,
+        const void* tgt_dev, const void* tgt_covariances_dev,
+        const int64_t* corr_dev, int64_t n, int64_t nt, int dtype,
+        const double* R_source9, int robust_kernel, double scaling_parameter,
+        double shape_parameter, double* sums32_dev, o3dmi_stream_t stream);
+
 /* ComputeFPFHFeatureCUDA (t/pipelines/kernel/FeatureImpl.h:108-296), the
  * kernel step of ComputeFPFHFeature after the neighbour search. Lists are
  * either padded {n_rows, max_nn} (indices_dev, distance2_dev) with counts_dev

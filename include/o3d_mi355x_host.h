@@ -169,7 +169,9 @@ typedef enum {
     O3DMI_ICP_POINT_TO_POINT = 1,
     O3DMI_ICP_SYMMETRIC = 2,
     O3DMI_ICP_COLORED = 3,
-    O3DMI_ICP_DOPPLER = 4 /* o3dmi_registration_multiscale_icp_doppler only */
+    O3DMI_ICP_DOPPLER = 4, /* o3dmi_registration_multiscale_icp_doppler only */
+    O3DMI_ICP_GENERALIZED = 5 /* o3dmi_registration_multiscale_icp_generalized
+                                 only */
 } o3dmi_icp_estimation_t;
 
 /* Point attributes beyond positions / target normals that some estimators
@@ -302,6 +304,71 @@ int o3dmi_registration_multiscale_icp_doppler(
         void* callback_user, o3dmi_allreduce_sum_t allreduce,
         void* allreduce_user, int64_t* correspondences_dev,
         o3dmi_registration_result_t* result, o3dmi_stream_t stream);
+
+/* TransformationEstimationForGeneralizedICP (legacy pipelines/registration/
+ * GeneralizedICP.{h,cpp}; Segal et al., "Generalized-ICP", RSS 2009): the
+ * estimator's parameters and the per-point covariances it reads. The reference
+ * has it in the legacy API only (CPU, float64, single scale). */
+typedef struct {
+    const void* source_covariances; /* device {N,3,3}, point dtype, or NULL   */
+    const void* target_covariances; /* device {N,3,3}, point dtype, or NULL   */
+    const void* source_normals;     /* device {N,3}; read when
+                                       source_covariances is NULL (the target's
+                                       normals are the call's
+                                       target_normals_dev)                    */
+    double epsilon;                 /* default 1e-3; <= 0 or non-finite:
+                                       INVALID_ARG                            */
+    int robust_kernel;              /* o3dmi robust kernel method, default L2 */
+    double scaling_parameter, shape_parameter;
+    int64_t* singular_pairs_out;    /* optional, host: sums[29] of the call's
+                                       last accumulate (pairs that could not
+                                       be whitened)                           */
+} o3dmi_icp_generalized_t;
+
+/* MultiScaleICP with TransformationEstimationForGeneralizedICP: the argument
+ * list of o3dmi_registration_multiscale_icp_doppler with `doppler` replaced by
+ * `generalized` (o3dmi_registration_multiscale_icp_ex answers
+ * O3DMI_ICP_GENERALIZED with O3DMI_ERR_INVALID_ARG). Covariances per cloud, as
+ * InitializePointCloudForGeneralizedICP (GeneralizedICP.cpp:52-80): given ->
+ * used as they are; else normals given ->
+ * o3dmi_pointcloud_covariances_from_normals; else EstimateNormals with KNN 20
+ * on the input cloud, then the same (a cloud of fewer than 3 points: that
+ * call's error, unchanged). The nine columns ride through the VoxelDownSample
+ * pyramid as three {n,3} row tables per cloud, averaged like any attribute (as
+ * the legacy VoxelDownSample does). Per iteration: search, then one launch
+ * that gathers by correspondence (o3dmi_icp_generalized_accumulate) with
+ * R_source9 = the rotation of the cumulative transformation: the level's
+ * source covariance tables are never rewritten (the reference rotates them
+ * incrementally with every Transform; equal to rounding). Sharding as for the
+ * other estimators; level_sharding slices the covariance tables with the
+ * positions. Sizes on the device (options->ns_dev / nt_dev) are
+ * O3DMI_ERR_UNSUPPORTED for a cloud whose normals would have to be
+ * estimated. */
+int o3dmi_registration_multiscale_icp_generalized(
+        const void* source_dev, int64_t ns, const void* target_dev,
+        const void* target_normals_dev, int64_t nt, int dtype, int num_scales,
+        const double* voxel_sizes, const o3dmi_icp_criteria_t* criterias,
+        const double* max_correspondence_distances,
+        const double* init_source_to_target,
+        const o3dmi_icp_generalized_t* generalized,
+        const o3dmi_icp_options_t* options, o3dmi_icp_callback_t callback,
+        void* callback_user, o3dmi_allreduce_sum_t allreduce,
+        void* allreduce_user, int64_t* correspondences_dev,
+        o3dmi_registration_result_t* result, o3dmi_stream_t stream);
+
+/* TransformationEstimationForGeneralizedICP::ComputeRMSE (GeneralizedICP.cpp:
+ * 83-102), the reference's definition kept as it is: sqrt(sum d^T W d / count)
+ * with W = (Ct + Cs)^-1/2 -- not W^2 -- over the rows with a correspondence
+ * (int64[ns], -1 = none). Covariances {N,3,3} in the point dtype, used as
+ * given (the source's are not rotated). No correspondence: 0.0, as the
+ * reference. A pair that cannot be whitened adds 0 and stays in the count. An
+ * index outside [0, nt) other than -1: O3DMI_ERR_INVALID_ARG. *rmse_out is a
+ * host double; the call synchronises. */
+int o3dmi_registration_compute_rmse_generalized(
+        const void* source_dev, const void* source_covariances_dev, int64_t ns,
+        const void* target_dev, const void* target_covariances_dev, int64_t nt,
+        int dtype, const int64_t* correspondences_dev, double* rmse_out,
+        o3dmi_stream_t stream);
 
 /* TransformationEstimation*::ComputeRMSE (TransformationEstimation.cpp:
  * 101-130 point-to-point, 160-193 point-to-plane, 229-274 symmetric, 296-378
@@ -732,6 +799,19 @@ int o3dmi_pointcloud_estimate_normals(const void* points_dev, int64_t n,
                                       int dtype, int max_nn, double radius,
                                       void* normals_dev, int has_normals,
                                       o3dmi_stream_t stream);
+
+/* InitializePointCloudForGeneralizedICP's covariances from normals (legacy
+ * GeneralizedICP.cpp:33-80): covariances {n,3,3} = Rx diag(epsilon,1,1) Rx^T
+ * with Rx = GetRotationFromE1ToX(normal), one thread per point, the
+ * reference's statements in float64 without contraction, narrowed to the point
+ * dtype once. Where e1 . x < -0.99 Rx is the identity (the reference's branch,
+ * kept); normals are not re-normalised. epsilon <= 0 or non-finite:
+ * O3DMI_ERR_INVALID_ARG (the reference does not check). Asynchronous. */
+int o3dmi_pointcloud_covariances_from_normals(const void* normals_dev,
+                                              int64_t n, int dtype,
+                                              double epsilon,
+                                              void* covariances_dev,
+                                              o3dmi_stream_t stream);
 
 /* PointCloud::EstimateColorGradients(max_nn, radius) (t/geometry/PointCloud.
  * cpp:987-1060): hybrid search when both are given, KNN search when

@@ -218,7 +218,27 @@ class IcpDoppler(C.Structure):
                 ("doppler_shape_parameter", _d)]
 
 
+class IcpGeneralized(C.Structure):
+    _fields_ = [("source_covariances", _vp), ("target_covariances", _vp),
+                ("source_normals", _vp), ("epsilon", _d),
+                ("robust_kernel", _i32), ("scaling_parameter", _d),
+                ("shape_parameter", _d),
+                ("singular_pairs_out", C.POINTER(_i64))]
+
+
 PROTOTYPES.update({
+    "o3dmi_registration_multiscale_icp_generalized": (
+        _i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _dp,
+               C.POINTER(IcpCriteria), _dp, _dp, C.POINTER(IcpGeneralized),
+               C.POINTER(IcpOptions), ICP_CALLBACK, _vp, ALLREDUCE_SUM, _vp,
+               _vp, C.POINTER(RegistrationResultC), _vp]),
+    "o3dmi_icp_generalized_accumulate": (
+        _i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _dp, _i32, _d, _d,
+               _vp, _vp]),
+    "o3dmi_registration_compute_rmse_generalized": (
+        _i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _dp, _vp]),
+    "o3dmi_pointcloud_covariances_from_normals": (
+        _i32, [_vp, _i64, _i32, _d, _vp, _vp]),
     "o3dmi_registration_multiscale_icp_doppler": (
         _i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _dp,
                C.POINTER(IcpCriteria), _dp, _dp, C.POINTER(IcpDoppler),

@@ -25,8 +25,9 @@ struct IcpCall {
     o3dmi_stream_t stream() const { return (o3dmi_stream_t)s; }
     hipEvent_t ev = nullptr;
 
-    // estimator (none of the four: point-to-point)
-    bool p2plane = false, symmetric = false, colored = false, doppler = false;
+    // estimator (none of the five: point-to-point)
+    bool p2plane = false, symmetric = false, colored = false, doppler = false,
+         generalized = false;
 
     // clouds and attributes (NULL: the estimator does not read it)
     const void *source = nullptr, *source_normals = nullptr,
@@ -36,6 +37,9 @@ struct IcpCall {
     // Doppler ICP: directions {n,3}; dopplers as column 0 of an {n,3} buffer
     // of the driver (the pyramid's levels take {n,3} attributes)
     const void *source_directions = nullptr, *source_dopplers3 = nullptr;
+    // Generalized ICP: each cloud's covariances {n,3,3} as the three {n,3} row
+    // tables of the driver
+    const void *source_cov_rows[3] = {}, *target_cov_rows[3] = {};
     int64_t ns = 0, nt = 0;
     // sizes that live on the device (o3dmi_icp_options_t)
     const int32_t *ns_dev = nullptr, *nt_dev = nullptr;
@@ -51,6 +55,8 @@ struct IcpCall {
     // inverse of the rotation and the translation
     o3dmi_icp_doppler_t dop = {};
     double R_S_to_V[9] = {}, r_v_to_s_in_V[3] = {};
+    // TransformationEstimationForGeneralizedICP's parameters
+    o3dmi_icp_generalized_t gen = {};
     int robust_kernel = 0;
     double scaling_parameter = 1.0, shape_parameter = 1.0;
 
@@ -69,10 +75,10 @@ struct IcpCall {
 // One cloud at one pyramid level: positions and its {n,3} attributes.
 // Source: normals (symmetric), colours (coloured), directions and dopplers
 // (Doppler; the dopplers in column 0); target: normals, colours, colour
-// gradients.
+// gradients; both: the three rows of the covariances (generalized).
 enum {
     kNormals = 0, kColors = 1, kGradients = 2, kDirections = 3, kDopplers = 4,
-    kCloudAttrs = 5
+    kCovRow0 = 5, kCovRow1 = 6, kCovRow2 = 7, kCloudAttrs = 8
 };
 struct CloudLevel {
     DeviceBuffer pos_buf, attr_buf[kCloudAttrs];

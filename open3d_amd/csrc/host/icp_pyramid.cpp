@@ -263,7 +263,7 @@ int BuildLevel(const IcpCall& c, CloudChain& ch, std::vector<Level>& pyr, int k,
         const CloudLevel* F =
                 k == last ? nullptr : &(pyr[(size_t)k + 1].*ch.which);
         const void* const* in_attr = F ? F->attr : ch.attr;
-        static_assert(kCloudAttrs == 5, "the attribute passes listed below");
+        static_assert(kCloudAttrs == 8, "the attribute passes listed below");
         if ((e = L.pos_buf.Alloc((size_t)ch.n * 3 * c.esz))) return e;
         for (int a = 0; a < kCloudAttrs; ++a)
             if (in_attr[a] &&
@@ -281,7 +281,10 @@ int BuildLevel(const IcpCall& c, CloudChain& ch, std::vector<Level>& pyr, int k,
                  {in_attr[1], L.attr_buf[1].p},
                  {in_attr[2], L.attr_buf[2].p},
                  {in_attr[3], L.attr_buf[3].p},
-                 {in_attr[4], L.attr_buf[4].p}},
+                 {in_attr[4], L.attr_buf[4].p},
+                 {in_attr[5], L.attr_buf[5].p},
+                 {in_attr[6], L.attr_buf[6].p},
+                 {in_attr[7], L.attr_buf[7].p}},
                 next_vs, F && !f_host, job);
         if (e) return e;
         L.pos = L.pos_buf.p;
@@ -369,21 +372,25 @@ int BuildPyramids(const IcpCall& c, std::vector<Level>& pyr,
     // -- 7 launches + one posting launch for a three-level pair of
     // pyramids instead of two chains of 8 on two streams (the source chain on
     // the caller's stream, the target chain on the side stream). Coloured ICP
-    // (three attribute passes per target level) and Doppler ICP (two per
-    // source level) keep the two chains.
+    // (three attribute passes per target level), Doppler ICP (two per
+    // source level) and generalized ICP (three per level of either cloud)
+    // keep the two chains.
     static const bool unpaired = std::getenv("O3DMI_VDS_UNPAIRED") != nullptr;
-    const bool paired = !c.colored && !c.doppler && !unpaired;
+    const bool paired =
+            !c.colored && !c.doppler && !c.generalized && !unpaired;
     hipStream_t ts = paired ? c.s : c.side;
     CloudChain src(c, c.source, c.ns, c.ns_dev, 0, c.s, &Level::source);
     src.attr[kNormals] = c.source_normals;
     src.attr[kColors] = c.source_colors;
     src.attr[kDirections] = c.source_directions;
     src.attr[kDopplers] = c.source_dopplers3;
+    for (int r = 0; r < 3; ++r) src.attr[kCovRow0 + r] = c.source_cov_rows[r];
     src.clone_input = true;
     CloudChain tgt(c, c.target, c.nt, c.nt_dev, 1, ts, &Level::target);
     tgt.attr[kNormals] = c.target_normals;
     tgt.attr[kColors] = c.target_colors;
     tgt.attr[kGradients] = c.target_gradients;
+    for (int r = 0; r < 3; ++r) tgt.attr[kCovRow0 + r] = c.target_cov_rows[r];
     tgt.needs_gradients = c.colored;
     ChainCounts &scc = src.counts, &tcc = tgt.counts;
     if ((st = scc.Init(c.num_scales, 0, c.s))) return st;

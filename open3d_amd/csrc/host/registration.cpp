@@ -24,8 +24,8 @@
 // Other estimators (o3dmi_registration_multiscale_icp_ex): the same fused
 // search launch in its point-to-point form (correspondences + raw moments),
 // then per estimator: point-to-point -> R, t from the moments on the host;
-// symmetric / coloured / Doppler -> a second launch that gathers by
-// correspondence and accumulates their 29 sums (two mailbox waits per
+// symmetric / coloured / Doppler / generalized -> a second launch that gathers
+// by correspondence and accumulates their 29 sums (two mailbox waits per
 // iteration).
 //
 // This file: the entry point, which resolves its arguments (the options
@@ -305,6 +305,11 @@ struct ScaleView {
     // {ns,1} form (the scale's scratch); the range check's device word
     void *srcdir = nullptr, *srcdop3 = nullptr, *srcdop = nullptr;
     int* bad = nullptr;
+    // generalized: the rows of the level's covariances (the source's: of this
+    // rank's slice) and their {n,3,3} form (the scale's scratch)
+    void* srccov_rows[3] = {};
+    const void* tgtcov_rows[3] = {};
+    void *srccov = nullptr, *tgtcov = nullptr;
     int64_t ns = 0, first = 0, nt = 0;
     const void *tgt = nullptr, *nrm = nullptr, *tgtc = nullptr,
                *tgtg = nullptr;
@@ -328,6 +333,10 @@ void ViewOf(const IcpCall& c, const Level& L, ScaleView& v) {
     v.srcc = at(S.attr_buf[kColors].p);
     v.srcdir = at(S.attr_buf[kDirections].p);
     v.srcdop3 = at(S.attr_buf[kDopplers].p);
+    for (int r = 0; r < 3; ++r) {
+        v.srccov_rows[r] = at(S.attr_buf[kCovRow0 + r].p);
+        v.tgtcov_rows[r] = L.target.attr[kCovRow0 + r];
+    }
     v.ns = e - b;
     v.first = b;
     v.tgt = L.target.pos;
@@ -435,19 +444,50 @@ int DopplerSums(const IcpCall& c, SumsFetcher& sums, const ScaleView& L,
     return O3DMI_OK;
 }
 
+// TransformationEstimationForGeneralizedICP::ComputeTransformation up to the
+// solve (GeneralizedICP.cpp:104-147). The level's source positions stand at
+// `current`, its covariance tables as they were built: the rotation of
+// `current` goes to the kernel (the reference rotates the covariances with
+// every Transform, PointCloud.cpp). out32[29]: the pairs that could not be
+// whitened.
+int GeneralizedSums(const IcpCall& c, SumsFetcher& sums, const ScaleView& L,
+                    const double* current, double* out32) {
+    double R[9];
+    for (int j = 0; j < 3; ++j)
+        for (int k = 0; k < 3; ++k) R[j * 3 + k] = current[j * 4 + k];
+    int e = sums.Fetch(
+            [&](double* sums_dev, double* mail_data, int* mail_flag, int seq) {
+                return o3dmi_icp_generalized_accumulate_post(
+                        L.src, L.srccov, L.tgt, L.tgtcov, L.corr, L.ns, L.nt,
+                        c.dtype, R, c.gen.robust_kernel,
+                        c.gen.scaling_parameter, c.gen.shape_parameter, 0,
+                        sums_dev, L.partials, L.bad, mail_data, mail_flag, seq,
+                        c.stream());
+            },
+            out32, kKeep, 0.0, 0.0);
+    if (e) return e;
+    O3DMI_REQUIRE(out32[28] == out32[28],
+                  "correspondence index out of range");
+    return O3DMI_OK;
+}
+
 // One iteration's update from its search: estimation.ComputeTransformation,
 // Registration.cpp:314. Point-to-point: R, t from the search pass' moments.
 // The others: 29 sums (point-to-plane: of the search pass; symmetric /
-// coloured / Doppler: of a second launch that gathers by correspondence), the 6x6
+// coloured / Doppler / generalized: of a second launch that gathers by
+// correspondence), the 6x6
 // solve, pose -> transformation. *solve_status: a failed solve (the reference
 // throws; the driver reports it after the loop); a returned error ends the
 // call at once.
 // `current`, `iteration`: the cumulative transformation before this update and
-// the iteration's index within its scale (read by the Doppler estimator only).
+// the iteration's index within its scale (read by the Doppler and the
+// generalized estimator only). *singular_pairs: the generalized estimator's
+// count of pairs that could not be whitened.
 int ComputeUpdate(const IcpCall& c, SumsFetcher& sums, const ScaleView& L,
                   const SearchResult& r, const double* current, int iteration,
-                  double* update, int* solve_status) {
-    if (!c.p2plane && !c.symmetric && !c.colored && !c.doppler) {
+                  double* update, int* solve_status, int64_t* singular_pairs) {
+    if (!c.p2plane && !c.symmetric && !c.colored && !c.doppler &&
+        !c.generalized) {
         // ComputeRtPointToPoint + RtToTransformation
         // (TransformationEstimation.cpp:150-159)
         double R[9], t[3];
@@ -509,6 +549,11 @@ int ComputeUpdate(const IcpCall& c, SumsFetcher& sums, const ScaleView& L,
         int e = DopplerSums(c, sums, L, current, iteration, gathered);
         if (e) return e;
         sums29 = gathered;
+    } else if (c.generalized) {
+        int e = GeneralizedSums(c, sums, L, current, gathered);
+        if (e) return e;
+        *singular_pairs = (int64_t)gathered[29];
+        sums29 = gathered;
     }
     double pose[6];
     float residual;
@@ -529,6 +574,7 @@ struct IcpState {
     bool converged = false;
     int iteration_count = 0;
     int status = O3DMI_OK;  // of a failed 6x6 solve: reported after the loop
+    int64_t singular_pairs = 0;  // generalized: of the last accumulate
     PendingTransform pending;
 };
 
@@ -560,7 +606,8 @@ int RunScaleIterations(const IcpCall& c, SumsFetcher& sums, NnsGuard& guard,
         if (r.sums[30] == 0) Eye4(st.T);  // Registration.cpp:56-58
         if (st.fitness <= std::numeric_limits<double>::min()) break;
         double update[16];
-        if ((e = ComputeUpdate(c, sums, L, r, st.T, it, update, &st.status)))
+        if ((e = ComputeUpdate(c, sums, L, r, st.T, it, update, &st.status,
+                               &st.singular_pairs)))
             return e;
         Matmul4(update, st.T, st.T);
         // source.Transform(update): rides in the next search launch of
@@ -628,7 +675,28 @@ int RunIcp(const IcpCall& c, IcpTimer& timer, std::vector<Level>& pyr,
                                                 L.srcdop, c.stream())))
                 return e;
         }
-        if (c.symmetric || c.colored || c.doppler) {
+        DeviceBuffer cov_buf;
+        if (c.generalized) {
+            // the level's covariances as {n,3,3}: the source's slice, the
+            // target's, and the range check's word behind them
+            const size_t sb = (size_t)L.ns * 9 * c.esz;
+            const size_t tb = (size_t)L.nt * 9 * c.esz;
+            const size_t so = (sb + 7) / 8 * 8, to = (tb + 7) / 8 * 8;
+            if ((e = cov_buf.Alloc(so + to + sizeof(int)))) return e;
+            L.srccov = cov_buf.p;
+            L.tgtcov = (char*)cov_buf.p + so;
+            L.bad = (int*)((char*)cov_buf.p + so + to);
+            O3DMI_HIP_CHECK(hipMemsetAsync(L.bad, 0, sizeof(int), c.s));
+            if ((e = o3dmi_internal_join_rows3(
+                         L.srccov_rows[0], L.srccov_rows[1], L.srccov_rows[2],
+                         L.ns, c.dtype, L.srccov, c.stream())))
+                return e;
+            if ((e = o3dmi_internal_join_rows3(
+                         L.tgtcov_rows[0], L.tgtcov_rows[1], L.tgtcov_rows[2],
+                         L.nt, c.dtype, L.tgtcov, c.stream())))
+                return e;
+        }
+        if (c.symmetric || c.colored || c.doppler || c.generalized) {
             if ((e = corr_buf.Alloc(sizeof(int64_t) * (size_t)L.ns))) return e;
             if ((e = sym_partials.Alloc(sizeof(double) * 32 * 1024)))
                 return e;
@@ -683,6 +751,8 @@ int RunIcp(const IcpCall& c, IcpTimer& timer, std::vector<Level>& pyr,
     result->converged = st.converged ? 1 : 0;
     result->num_iterations = st.iteration_count;
     result->num_correspondences = correspondences_dev ? last_ns : 0;
+    if (c.generalized && c.gen.singular_pairs_out)
+        *c.gen.singular_pairs_out = st.singular_pairs;
     return st.status;
 }
 
@@ -767,13 +837,71 @@ int ResolveDoppler(IcpCall& c, const o3dmi_icp_doppler_t* doppler) {
     return O3DMI_OK;
 }
 
-// Both entry points: `doppler` != NULL is O3DMI_ICP_DOPPLER.
+// TransformationEstimationForGeneralizedICP's constructor and argument checks.
+int ResolveGeneralized(IcpCall& c, const o3dmi_icp_generalized_t* generalized,
+                       const void* target_normals_dev) {
+    O3DMI_REQUIRE(generalized != nullptr, "generalized is null");
+    c.gen = *generalized;
+    O3DMI_REQUIRE(c.gen.epsilon > 0 && std::isfinite(c.gen.epsilon),
+                  "epsilon must be positive and finite");
+    O3DMI_REQUIRE(c.gen.robust_kernel >= 0 && c.gen.robust_kernel <= 6,
+                  "Unsupported method.");
+    const bool estimate_source =
+            !c.gen.source_covariances && !c.gen.source_normals;
+    const bool estimate_target =
+            !c.gen.target_covariances && !target_normals_dev;
+    if ((estimate_source && c.ns_dev) || (estimate_target && c.nt_dev))
+        return Unsupported(
+                "Generalized ICP: normals cannot be estimated for a cloud "
+                "whose size lives on the device");
+    return O3DMI_OK;
+}
+
+// InitializePointCloudForGeneralizedICP (GeneralizedICP.cpp:52-80) for one
+// cloud, on the call's stream: covariances given -> as they are; else from the
+// given normals; else from EstimateNormals(KNN 20). `rows`: the three {n,3}
+// row tables the pyramid carries.
+int GeneralizedCovarianceRows(const IcpCall& c, const void* points, int64_t n,
+                              const void* covariances, const void* normals,
+                              DeviceBuffer& rows, const void** rows_out) {
+    int e;
+    DeviceBuffer own_normals, own_cov;
+    if (!covariances) {
+        if (!normals) {
+            if ((e = own_normals.Alloc((size_t)n * 3 * c.esz))) return e;
+            if ((e = o3dmi_pointcloud_estimate_normals(
+                         points, n, c.dtype, 20, -1.0, own_normals.p, 0,
+                         c.stream())))
+                return e;
+            normals = own_normals.p;
+        }
+        if ((e = own_cov.Alloc((size_t)n * 9 * c.esz))) return e;
+        if ((e = o3dmi_pointcloud_covariances_from_normals(
+                     normals, n, c.dtype, c.gen.epsilon, own_cov.p,
+                     c.stream())))
+            return e;
+        covariances = own_cov.p;
+    }
+    const size_t row = (size_t)n * 3 * c.esz;
+    if ((e = rows.Alloc(3 * row))) return e;
+    for (int r = 0; r < 3; ++r) rows_out[r] = (char*)rows.p + r * row;
+    e = o3dmi_internal_split_rows3(covariances, n, c.dtype,
+                                   (void*)rows_out[0], (void*)rows_out[1],
+                                   (void*)rows_out[2], c.stream());
+    // (the temporaries above go back to the pool here)
+    if (hipStreamSynchronize(c.s) != hipSuccess && !e) e = O3DMI_ERR_HIP;
+    return e;
+}
+
+// The entry points: `doppler` != NULL is O3DMI_ICP_DOPPLER, `generalized`
+// != NULL O3DMI_ICP_GENERALIZED.
 int MultiScaleIcpEntry(
         const void* source_dev, int64_t ns, const void* target_dev,
         const void* target_normals_dev, int64_t nt, int dtype, int num_scales,
         const double* voxel_sizes, const o3dmi_icp_criteria_t* criterias,
         const double* max_dists, const double* init, int estimation,
         const o3dmi_icp_attributes_t* attrs, const o3dmi_icp_doppler_t* doppler,
+        const o3dmi_icp_generalized_t* generalized,
         const o3dmi_icp_options_t* options, int robust_kernel,
         double scaling_parameter, double shape_parameter,
         o3dmi_icp_callback_t callback, void* callback_user,
@@ -801,6 +929,7 @@ int MultiScaleIcpEntry(
     c.symmetric = estimation == O3DMI_ICP_SYMMETRIC;
     c.colored = estimation == O3DMI_ICP_COLORED;
     c.doppler = estimation == O3DMI_ICP_DOPPLER;
+    c.generalized = estimation == O3DMI_ICP_GENERALIZED;
     const bool need_tn = c.p2plane || c.symmetric || c.colored || c.doppler;
     c.source = source_dev;
     c.target = target_dev;
@@ -822,6 +951,10 @@ int MultiScaleIcpEntry(
                   "DopplerICP requires target pointcloud to have normals.");
     if (c.doppler) {
         int e = ResolveDoppler(c, doppler);
+        if (e) return e;
+    }
+    if (c.generalized) {
+        int e = ResolveGeneralized(c, generalized, target_normals_dev);
         if (e) return e;
     }
     O3DMI_REQUIRE(!c.symmetric || (c.source_normals && c.target_normals),
@@ -860,6 +993,7 @@ int MultiScaleIcpEntry(
     IcpTimer timer(c.s);  // (declared first: destroyed last)
     std::vector<Level> pyr((size_t)num_scales);
     DeviceBuffer dopplers3;  // the caller's {ns,1} dopplers as column 0 of {ns,3}
+    DeviceBuffer source_cov_rows, target_cov_rows;  // generalized
     // Declared after the pyramid so that it runs first on every exit path.
     SyncOnExit sync_on_exit{c.s};
     std::vector<NnsGuard> guards((size_t)num_scales);
@@ -872,6 +1006,17 @@ int MultiScaleIcpEntry(
                                             c.dtype, dopplers3.p, c.stream())))
             return st;
         c.source_dopplers3 = dopplers3.p;
+    }
+    if (c.generalized) {
+        if ((st = GeneralizedCovarianceRows(
+                     c, c.source, c.ns, c.gen.source_covariances,
+                     c.gen.source_normals, source_cov_rows,
+                     c.source_cov_rows)))
+            return st;
+        if ((st = GeneralizedCovarianceRows(
+                     c, c.target, c.nt, c.gen.target_covariances,
+                     target_normals_dev, target_cov_rows, c.target_cov_rows)))
+            return st;
     }
     return RunIcp(c, timer, pyr, sync_on_exit, guards, init,
                   correspondences_dev, result);
@@ -891,7 +1036,8 @@ extern "C" int o3dmi_registration_multiscale_icp_ex(
         int64_t* correspondences_dev, o3dmi_registration_result_t* result,
         o3dmi_stream_t stream) {
     // (Doppler ICP's parameters travel in o3dmi_icp_doppler_t:
-    // o3dmi_registration_multiscale_icp_doppler)
+    // o3dmi_registration_multiscale_icp_doppler; generalized ICP's in
+    // o3dmi_icp_generalized_t: o3dmi_registration_multiscale_icp_generalized)
     O3DMI_REQUIRE(estimation >= O3DMI_ICP_POINT_TO_PLANE &&
                           estimation <= O3DMI_ICP_COLORED,
                   "estimation must be point-to-plane, point-to-point, "
@@ -899,7 +1045,7 @@ extern "C" int o3dmi_registration_multiscale_icp_ex(
     return MultiScaleIcpEntry(
             source_dev, ns, target_dev, target_normals_dev, nt, dtype,
             num_scales, voxel_sizes, criterias, max_dists, init, estimation,
-            attrs, nullptr, options, robust_kernel, scaling_parameter,
+            attrs, nullptr, nullptr, options, robust_kernel, scaling_parameter,
             shape_parameter, callback, callback_user, allreduce,
             allreduce_user, correspondences_dev, result, stream);
 }
@@ -918,7 +1064,26 @@ extern "C" int o3dmi_registration_multiscale_icp_doppler(
     return MultiScaleIcpEntry(
             source_dev, ns, target_dev, target_normals_dev, nt, dtype,
             num_scales, voxel_sizes, criterias, max_dists, init,
-            O3DMI_ICP_DOPPLER, nullptr, doppler, options, O3DMI_L2_LOSS, 1.0,
-            1.0, callback, callback_user, allreduce, allreduce_user,
-            correspondences_dev, result, stream);
+            O3DMI_ICP_DOPPLER, nullptr, doppler, nullptr, options,
+            O3DMI_L2_LOSS, 1.0, 1.0, callback, callback_user, allreduce,
+            allreduce_user, correspondences_dev, result, stream);
+}
+
+extern "C" int o3dmi_registration_multiscale_icp_generalized(
+        const void* source_dev, int64_t ns, const void* target_dev,
+        const void* target_normals_dev, int64_t nt, int dtype, int num_scales,
+        const double* voxel_sizes, const o3dmi_icp_criteria_t* criterias,
+        const double* max_dists, const double* init,
+        const o3dmi_icp_generalized_t* generalized,
+        const o3dmi_icp_options_t* options, o3dmi_icp_callback_t callback,
+        void* callback_user, o3dmi_allreduce_sum_t allreduce,
+        void* allreduce_user, int64_t* correspondences_dev,
+        o3dmi_registration_result_t* result, o3dmi_stream_t stream) {
+    O3DMI_REQUIRE(generalized != nullptr, "generalized is null");
+    return MultiScaleIcpEntry(
+            source_dev, ns, target_dev, target_normals_dev, nt, dtype,
+            num_scales, voxel_sizes, criterias, max_dists, init,
+            O3DMI_ICP_GENERALIZED, nullptr, nullptr, generalized, options,
+            O3DMI_L2_LOSS, 1.0, 1.0, callback, callback_user, allreduce,
+            allreduce_user, correspondences_dev, result, stream);
 }

@@ -198,3 +198,42 @@ extern "C" int o3dmi_registration_compute_rmse(
     }
     return O3DMI_OK;
 }
+
+// TransformationEstimationForGeneralizedICP::ComputeRMSE (legacy
+// GeneralizedICP.cpp:83-102): the accumulate kernel's rmse form -- sums[0] =
+// sum d^T W d, sums[28] = the pairs.
+extern "C" int o3dmi_registration_compute_rmse_generalized(
+        const void* source_dev, const void* source_covariances_dev, int64_t ns,
+        const void* target_dev, const void* target_covariances_dev, int64_t nt,
+        int dtype, const int64_t* correspondences_dev, double* rmse_out,
+        o3dmi_stream_t stream) {
+    O3DMI_REQUIRE(rmse_out != nullptr, "rmse_out is null");
+    O3DMI_REQUIRE(dtype == O3DMI_F32 || dtype == O3DMI_F64,
+                  "Only Float32 and Float64 point clouds are supported.");
+    O3DMI_REQUIRE(source_dev && target_dev && ns > 0 && nt > 0 &&
+                          correspondences_dev,
+                  "Source and/or Target pointcloud is empty.");
+    O3DMI_REQUIRE(source_covariances_dev && target_covariances_dev,
+                  "GeneralizedICP requires both clouds to have covariances.");
+    hipStream_t s = (hipStream_t)stream;
+    DeviceBuffer sums;  // 32 sums and the range check's word
+    SyncOnExit sync_on_exit{s};
+    int st = sums.Alloc(sizeof(double) * 32 + sizeof(int));
+    if (st) return st;
+    int* bad = (int*)((double*)sums.p + 32);
+    O3DMI_HIP_CHECK(hipMemsetAsync(sums.p, 0, sizeof(double) * 32 + sizeof(int),
+                                   s));
+    st = o3dmi_icp_generalized_accumulate_post(
+            source_dev, source_covariances_dev, target_dev,
+            target_covariances_dev, correspondences_dev, ns, nt, dtype, nullptr,
+            O3DMI_L2_LOSS, 1.0, 1.0, /*rmse_form=*/1, (double*)sums.p, nullptr,
+            bad, nullptr, nullptr, 0, stream);
+    if (st) return st;
+    struct { double v[32]; int bad; } h;
+    O3DMI_HIP_CHECK(hipMemcpyAsync(&h, sums.p, sizeof(double) * 32 + sizeof(int),
+                                   hipMemcpyDeviceToHost, s));
+    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
+    O3DMI_REQUIRE(!h.bad, "correspondence index out of range");
+    *rmse_out = h.v[28] == 0 ? 0.0 : std::sqrt(h.v[0] / h.v[28]);
+    return O3DMI_OK;
+}

@@ -61,6 +61,28 @@ int o3dmi_icp_doppler_accumulate_post(
         double* sums29_dev, double* partials_dev, int* bad_dev,
         double* mail_data, int* mail_flag, int mail_seq, o3dmi_stream_t stream);
 
+// o3dmi_icp_generalized_accumulate without its wait (bad_dev as above); the
+// 32 sums, [29] = the pairs that could not be whitened. rmse_form: sums[0] =
+// sum d^T W d and [28] = the pair count only (ComputeRMSE, GeneralizedICP.cpp:
+// 83-102; R_source9 and the robust kernel are then not read).
+int o3dmi_icp_generalized_accumulate_post(
+        const void* src_dev, const void* src_covariances_dev,
+        const void* tgt_dev, const void* tgt_covariances_dev,
+        const int64_t* corr_dev, int64_t n, int64_t nt, int dtype,
+        const double* R_source9, int robust_kernel, double scaling_parameter,
+        double shape_parameter, int rmse_form, double* sums32_dev,
+        double* partials_dev, int* bad_dev, double* mail_data, int* mail_flag,
+        int mail_seq, o3dmi_stream_t stream);
+
+// {n,3,3} -> its three {n,3} row tables and back: a covariance attribute
+// through the {n,3} VoxelDownSample levels of the pyramid.
+int o3dmi_internal_split_rows3(const void* in9_dev, int64_t n, int dtype,
+                               void* row0_dev, void* row1_dev, void* row2_dev,
+                               o3dmi_stream_t stream);
+int o3dmi_internal_join_rows3(const void* row0_dev, const void* row1_dev,
+                              const void* row2_dev, int64_t n, int dtype,
+                              void* out9_dev, o3dmi_stream_t stream);
+
 // {n,1} -> column 0 of {n,3} (columns 1, 2 zero), and column 0 back: a
 // 1-column attribute through the {n,3} VoxelDownSample levels of the pyramid.
 int o3dmi_internal_pad_column(const void* in_dev, int64_t n, int dtype,

@@ -2,7 +2,7 @@
 //
 //   o3dmi_icp_p2plane_accumulate  <- ComputePosePointToPlaneCUDA (t/pipelines/kernel/
 //                                    RegistrationCUDA.cu:29-117, RegistrationImpl.h:251-287)
-//   o3dmi_icp_{p2point,symmetric,colored,doppler,information}_accumulate
+//   o3dmi_icp_{p2point,symmetric,colored,doppler,generalized,information}_accumulate
 //                                 <- the other reductions of RegistrationCUDA.cu /
 //                                    RegistrationCPU.cpp:124-493,495-735
 //   o3dmi_icp_search_accumulate   fused search + fitness/rmse sums + accumulation
@@ -30,6 +30,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "eigen3.h"
 #include "icp.h"
 #include "nns.h"
 #include "kabsch.h"
@@ -376,6 +377,108 @@ __device__ __forceinline__ void AccumulateDoppler(
     A[28] += 1.0;
 }
 
+// TransformationEstimationForGeneralizedICP (legacy GeneralizedICP.cpp:83-155;
+// Segal et al., "Generalized-ICP", RSS 2009), per pair, in float64 for both
+// point dtypes: Cs' = R Cs R^T (R: the rotation the source positions have
+// received), M = Ct + Cs', W = M^-1/2 = V diag(lambda^-1/2) V^T from the Jacobi
+// decomposition (the reference's M.inverse().sqrt(): the principal root of an
+// SPD matrix is unique). cs / ct: the upper triangles {00,01,02,11,12,22}.
+// false: an eigenvalue is not > 0 or not finite -- the pair cannot be whitened.
+struct GicpRotation { double R[9]; };
+
+__device__ __forceinline__ bool GicpWhiten(const double (&cs)[6],
+                                           const double (&ct)[6],
+                                           const GicpRotation& rot,
+                                           double (&W)[3][3]) {
+    const double* R = rot.R;
+    const double Cs[3][3] = {{cs[0], cs[1], cs[2]},
+                             {cs[1], cs[3], cs[4]},
+                             {cs[2], cs[4], cs[5]}};
+    double RC[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            RC[i][j] = R[3 * i] * Cs[0][j] + R[3 * i + 1] * Cs[1][j] +
+                       R[3 * i + 2] * Cs[2][j];
+    double M[3][3], V[3][3];
+    const int tri[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = i; j < 3; ++j) {
+            M[i][j] = ct[tri[i][j]] + (RC[i][0] * R[3 * j] +
+                                       RC[i][1] * R[3 * j + 1] +
+                                       RC[i][2] * R[3 * j + 2]);
+            M[j][i] = M[i][j];
+        }
+    JacobiEigenSym3<double>(M, V);
+    double s[3];
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double lambda = M[k][k];
+        ok = ok && lambda > 0.0 && lambda < HUGE_VAL;
+        s[k] = 1.0 / sqrt(lambda);
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = i; j < 3; ++j) {
+            W[i][j] = V[i][0] * s[0] * V[j][0] + V[i][1] * s[1] * V[j][1] +
+                      V[i][2] * s[2] * V[j][2];
+            W[j][i] = W[i][j];
+        }
+    return ok;
+}
+
+// The three weighted rows of a pair: J = W [-[vs]x | I], r_i = W_i . d,
+// A[27] += r_i^2 (unweighted, as ComputeJTJandJTr), A[28] += 1 per pair. A pair
+// that cannot be whitened adds nothing there and counts in A[29].
+// kRmse (ComputeRMSE, :83-102): A[0] += d^T W d -- W, not W^2, the reference's
+// definition -- and A[28] counts every pair, one that cannot be whitened too.
+template <bool kRmse>
+__device__ __forceinline__ void AccumulateGeneralized(
+        double (&A)[kNumSums], const double (&vs)[3], const double (&cs)[6],
+        const double (&vt)[3], const double (&ct)[6], const GicpRotation& rot,
+        const RobustParams& rp) {
+    double W[3][3];
+    const bool ok = GicpWhiten(cs, ct, rot, W);
+    // (both counts are added on every path: two separate increments under a
+    // branch become one indexed one, and with it scratch)
+    A[28] += ok || kRmse ? 1.0 : 0.0;
+    A[29] += ok ? 0.0 : 1.0;
+    if (!ok) return;
+    const double d[3] = {vs[0] - vt[0], vs[1] - vt[1], vs[2] - vt[2]};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double r = W[i][0] * d[0] + W[i][1] * d[1] + W[i][2] * d[2];
+        if (kRmse) {
+            A[0] += d[i] * r;
+            continue;
+        }
+        double J[6];
+        J[0] = W[i][1] * -vs[2] + W[i][2] * vs[1];
+        J[1] = W[i][0] * vs[2] + W[i][2] * -vs[0];
+        J[2] = W[i][0] * -vs[1] + W[i][1] * vs[0];
+        J[3] = W[i][0];
+        J[4] = W[i][1];
+        J[5] = W[i][2];
+        const double w = RobustWeight<double>(rp, r);
+        int q = 0;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+#pragma unroll
+            for (int k = 0; k <= j; ++k) {
+                A[q] += J[j] * w * J[k];
+                ++q;
+            }
+            A[21 + j] += J[j] * w * r;
+        }
+        A[27] += r * r;
+    }
+}
+
 constexpr int kReduceBlock = 256;
 
 // Reduce-scatter wave reduction (reduce_sums.h), LDS across the 4 waves, one
@@ -567,6 +670,75 @@ __global__ void TakeColumnKernel(const T* __restrict__ in3, int64_t n,
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x)
         out[i] = in3[3 * i];
+}
+
+// Gathers by correspondence, range-checked like the Doppler kernel above;
+// positions and covariances {n,3,3} are widened to float64 (exact).
+template <typename T, bool kRmse>
+__global__ void __launch_bounds__(kReduceBlock)
+GeneralizedAccumulateKernel(const T* __restrict__ src,
+                            const T* __restrict__ src_cov,
+                            const T* __restrict__ tgt,
+                            const T* __restrict__ tgt_cov,
+                            const int64_t* __restrict__ corr, int64_t n,
+                            int64_t nt, GicpRotation rot, RobustParams rp,
+                            double* __restrict__ partials,
+                            int* __restrict__ bad) {
+    double A[kNumSums];
+#pragma unroll
+    for (int k = 0; k < kNumSums; ++k) A[k] = 0;
+    bool out_of_range = false;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t c = corr[i];
+        if (c == -1) continue;
+        if (c < 0 || c >= nt) {
+            out_of_range = true;
+            continue;
+        }
+        const T* a = src_cov + 9 * i;
+        const T* b = tgt_cov + 9 * c;
+        const double vs[3] = {(double)src[3 * i], (double)src[3 * i + 1],
+                              (double)src[3 * i + 2]};
+        const double vt[3] = {(double)tgt[3 * c], (double)tgt[3 * c + 1],
+                              (double)tgt[3 * c + 2]};
+        const double cs[6] = {(double)a[0], (double)a[1], (double)a[2],
+                              (double)a[4], (double)a[5], (double)a[8]};
+        const double ct[6] = {(double)b[0], (double)b[1], (double)b[2],
+                              (double)b[4], (double)b[5], (double)b[8]};
+        AccumulateGeneralized<kRmse>(A, vs, cs, vt, ct, rot, rp);
+    }
+    if (out_of_range) atomicOr(bad, 1);
+    BlockReduceAndStore(A, partials);
+}
+
+// {n,3,3} <-> its three {n,3} row tables: how a covariance attribute rides
+// through the {n,3} VoxelDownSample levels of the ICP pyramid (every column is
+// averaged on its own, so the joined level is the {n,3,3} mean).
+template <typename T>
+__global__ void SplitRows3Kernel(const T* __restrict__ in9, int64_t n,
+                                 T* __restrict__ r0, T* __restrict__ r1,
+                                 T* __restrict__ r2) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < 3 * n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t p = i / 3, q = i % 3;
+        r0[i] = in9[9 * p + q];
+        r1[i] = in9[9 * p + 3 + q];
+        r2[i] = in9[9 * p + 6 + q];
+    }
+}
+template <typename T>
+__global__ void JoinRows3Kernel(const T* __restrict__ r0,
+                                const T* __restrict__ r1,
+                                const T* __restrict__ r2, int64_t n,
+                                T* __restrict__ out9) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < 3 * n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t p = i / 3, q = i % 3;
+        out9[9 * p + q] = r0[i];
+        out9[9 * p + 3 + q] = r1[i];
+        out9[9 * p + 6 + q] = r2[i];
+    }
 }
 
 // TransformationEstimationPointTo{Plane,Point}::ComputeRMSE
@@ -1222,6 +1394,30 @@ int AccumulateAndReduce(int64_t n, int dtype, int n_sums, double* out_dev,
     return O3DMI_OK;
 }
 
+
+// A seam with a range check: the zeroed device word, the posted work, and the
+// wait for the verdict, which is the call's status.
+template <typename Post>
+int WithRangeCheck(o3dmi_stream_t stream, Post&& post) {
+    hipStream_t s = (hipStream_t)stream;
+    int* bad = nullptr;
+    O3DMI_HIP_CHECK(hipMallocAsync((void**)&bad, sizeof(int), s));
+    int st = O3DMI_OK, host_bad = 0;
+    hipError_t e = hipMemsetAsync(bad, 0, sizeof(int), s);
+    if (e == hipSuccess) {
+        st = post(bad);
+        if (st == O3DMI_OK)
+            e = hipMemcpyAsync(&host_bad, bad, sizeof(int),
+                               hipMemcpyDeviceToHost, s);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFreeAsync(bad, s);
+    if (st != O3DMI_OK) return st;
+    O3DMI_HIP_CHECK(e);
+    O3DMI_REQUIRE(!host_bad, "correspondence index out of range");
+    return O3DMI_OK;
+}
+
 }  // namespace
 // o3dmi_preload: HIP loads this translation unit's code object at the first
 // launch of one of its kernels; asking for a kernel's attributes does it now.
@@ -1473,13 +1669,8 @@ int o3dmi_icp_doppler_accumulate(
         double doppler_scaling, double doppler_shape, double lambda_doppler,
         double* sums29_dev, o3dmi_stream_t stream) {
     O3DMI_REQUIRE(sums29_dev != nullptr, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    int* bad = nullptr;
-    O3DMI_HIP_CHECK(hipMallocAsync((void**)&bad, sizeof(int), s));
-    int st = O3DMI_OK, host_bad = 0;
-    hipError_t e = hipMemsetAsync(bad, 0, sizeof(int), s);
-    if (e == hipSuccess) {
-        st = o3dmi_icp_doppler_accumulate_post(
+    return WithRangeCheck(stream, [&](int* bad) {
+        return o3dmi_icp_doppler_accumulate_post(
                 src_dev, src_dopplers_dev, src_directions_dev, tgt_dev,
                 tgt_normals_dev, corr_dev, n, nt, dtype, R_S_to_V9,
                 r_v_to_s_in_V3, w_v_in_V3, v_v_in_V3, period,
@@ -1487,17 +1678,7 @@ int o3dmi_icp_doppler_accumulate(
                 geometric_kernel, geometric_scaling, geometric_shape,
                 doppler_kernel, doppler_scaling, doppler_shape, lambda_doppler,
                 sums29_dev, nullptr, bad, nullptr, nullptr, 0, stream);
-        if (st == O3DMI_OK)
-            e = hipMemcpyAsync(&host_bad, bad, sizeof(int),
-                               hipMemcpyDeviceToHost, s);
-    }
-    // the range check's verdict is this call's status: wait for it
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFreeAsync(bad, s);
-    if (st != O3DMI_OK) return st;
-    O3DMI_HIP_CHECK(e);
-    O3DMI_REQUIRE(!host_bad, "correspondence index out of range");
-    return O3DMI_OK;
+    });
 }
 
 // {n,1} -> column 0 of {n,3} (columns 1, 2 zero) and back: the 1-column
@@ -1529,6 +1710,115 @@ int o3dmi_internal_take_column(const void* in3_dev, int64_t n, int dtype,
         hipLaunchKernelGGL(TakeColumnKernel<float>, grid, block, 0,
                            (hipStream_t)stream, (const float*)in3_dev, n,
                            (float*)out_dev);
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
+// Internal: also posts the 32 sums to a host mailbox when mail_data != NULL;
+// bad_dev as o3dmi_icp_doppler_accumulate_post's.
+int o3dmi_icp_generalized_accumulate_post(
+        const void* src_dev, const void* src_covariances_dev,
+        const void* tgt_dev, const void* tgt_covariances_dev,
+        const int64_t* corr_dev, int64_t n, int64_t nt, int dtype,
+        const double* R_source9, int robust_kernel, double scaling_parameter,
+        double shape_parameter, int rmse_form, double* sums32_dev,
+        double* partials_dev, int* bad_dev, double* mail_data, int* mail_flag,
+        int mail_seq, o3dmi_stream_t stream) {
+    O3DMI_REQUIRE(n >= 0 && nt >= 0, "negative size");
+    O3DMI_REQUIRE(n == 0 || (src_dev && src_covariances_dev && tgt_dev &&
+                             tgt_covariances_dev && corr_dev),
+                  "null argument");
+    O3DMI_REQUIRE(bad_dev && (sums32_dev || mail_data), "null argument");
+    O3DMI_REQUIRE(dtype == O3DMI_F32 || dtype == O3DMI_F64,
+                  "points must be Float32 or Float64");
+    O3DMI_REQUIRE(robust_kernel >= 0 && robust_kernel <= 6,
+                  "Unsupported method.");
+    const RobustParams rp = MakeRobust(robust_kernel, scaling_parameter,
+                                       shape_parameter);
+    GicpRotation rot;
+    for (int k = 0; k < 9; ++k)
+        rot.R[k] = R_source9 && !rmse_form ? R_source9[k] : (k % 4 == 0);
+    hipStream_t s = (hipStream_t)stream;
+    const int g = ReduceGrid(n);
+    double* partials = partials_dev;
+    if (!partials)
+        O3DMI_HIP_CHECK(hipMallocAsync((void**)&partials,
+                                       sizeof(double) * (size_t)g * kNumSums,
+                                       s));
+    auto launch = [&](auto tag, auto rmse) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((GeneralizedAccumulateKernel<T, decltype(rmse)::value>),
+                           dim3(g), dim3(kReduceBlock), 0, s, (const T*)src_dev,
+                           (const T*)src_covariances_dev, (const T*)tgt_dev,
+                           (const T*)tgt_covariances_dev, corr_dev, n, nt, rot,
+                           rp, partials, bad_dev);
+    };
+    if (dtype == O3DMI_F64) {
+        if (rmse_form) launch(double(), std::true_type());
+        else launch(double(), std::false_type());
+    } else {
+        if (rmse_form) launch(float(), std::true_type());
+        else launch(float(), std::false_type());
+    }
+    hipLaunchKernelGGL(FinalReduceCheckedKernel, dim3(1), dim3(256), 0, s,
+                       partials, g, bad_dev, sums32_dev, 32, mail_data,
+                       mail_flag, mail_seq);
+    O3DMI_HIP_CHECK(hipGetLastError());
+    if (!partials_dev) O3DMI_HIP_CHECK(hipFreeAsync(partials, s));
+    return O3DMI_OK;
+}
+
+int o3dmi_icp_generalized_accumulate(
+        const void* src_dev, const void* src_covariances_dev,
+        const void* tgt_dev, const void* tgt_covariances_dev,
+        const int64_t* corr_dev, int64_t n, int64_t nt, int dtype,
+        const double* R_source9, int robust_kernel, double scaling_parameter,
+        double shape_parameter, double* sums32_dev, o3dmi_stream_t stream) {
+    O3DMI_REQUIRE(sums32_dev != nullptr, "null argument");
+    return WithRangeCheck(stream, [&](int* bad) {
+        return o3dmi_icp_generalized_accumulate_post(
+                src_dev, src_covariances_dev, tgt_dev, tgt_covariances_dev,
+                corr_dev, n, nt, dtype, R_source9, robust_kernel,
+                scaling_parameter, shape_parameter, 0, sums32_dev, nullptr, bad,
+                nullptr, nullptr, 0, stream);
+    });
+}
+
+int o3dmi_internal_split_rows3(const void* in9_dev, int64_t n, int dtype,
+                               void* row0_dev, void* row1_dev, void* row2_dev,
+                               o3dmi_stream_t stream) {
+    O3DMI_REQUIRE(in9_dev && row0_dev && row1_dev && row2_dev && n > 0,
+                  "null argument");
+    dim3 grid(GridFor(3 * n, kBlock)), block(kBlock);
+    if (dtype == O3DMI_F64)
+        hipLaunchKernelGGL(SplitRows3Kernel<double>, grid, block, 0,
+                           (hipStream_t)stream, (const double*)in9_dev, n,
+                           (double*)row0_dev, (double*)row1_dev,
+                           (double*)row2_dev);
+    else
+        hipLaunchKernelGGL(SplitRows3Kernel<float>, grid, block, 0,
+                           (hipStream_t)stream, (const float*)in9_dev, n,
+                           (float*)row0_dev, (float*)row1_dev,
+                           (float*)row2_dev);
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+int o3dmi_internal_join_rows3(const void* row0_dev, const void* row1_dev,
+                              const void* row2_dev, int64_t n, int dtype,
+                              void* out9_dev, o3dmi_stream_t stream) {
+    O3DMI_REQUIRE(row0_dev && row1_dev && row2_dev && out9_dev && n > 0,
+                  "null argument");
+    dim3 grid(GridFor(3 * n, kBlock)), block(kBlock);
+    if (dtype == O3DMI_F64)
+        hipLaunchKernelGGL(JoinRows3Kernel<double>, grid, block, 0,
+                           (hipStream_t)stream, (const double*)row0_dev,
+                           (const double*)row1_dev, (const double*)row2_dev, n,
+                           (double*)out9_dev);
+    else
+        hipLaunchKernelGGL(JoinRows3Kernel<float>, grid, block, 0,
+                           (hipStream_t)stream, (const float*)row0_dev,
+                           (const float*)row1_dev, (const float*)row2_dev, n,
+                           (float*)out9_dev);
     O3DMI_HIP_CHECK(hipGetLastError());
     return O3DMI_OK;
 }

@@ -221,6 +221,70 @@ __global__ void ColorGradientsKernel(const T* __restrict__ points,
     }
 }
 
+// InitializePointCloudForGeneralizedICP (legacy pipelines/registration/
+// GeneralizedICP.cpp:33-80): the covariance Rx diag(epsilon,1,1) Rx^T of a
+// point from its normal x, Rx = GetRotationFromE1ToX(x). The reference's
+// statements in float64 (this file is built without contraction), every dot
+// product summed in index order with its zero terms, narrowed to T once.
+__device__ __forceinline__ void MatMul3InOrder(const double (&a)[3][3],
+                                               const double (&b)[3][3],
+                                               double (&c)[3][3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            c[i][j] = a[i][0] * b[0][j] + a[i][1] * b[1][j] + a[i][2] * b[2][j];
+}
+
+template <typename T>
+__device__ __forceinline__ void CovarianceFromNormal(const T* normal,
+                                                     double epsilon, T* cov) {
+    const double x[3] = {(double)normal[0], (double)normal[1],
+                         (double)normal[2]};
+    const double e1[3] = {1.0, 0.0, 0.0};
+    const double v[3] = {e1[1] * x[2] - e1[2] * x[1],
+                         e1[2] * x[0] - e1[0] * x[2],
+                         e1[0] * x[1] - e1[1] * x[0]};
+    const double c = e1[0] * x[0] + e1[1] * x[1] + e1[2] * x[2];
+    double Rx[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    // (the reference's comment calls this "the same direction"; it is the
+    // opposite one, and the branch is kept as it is)
+    if (!(c < -0.99)) {
+        const double sv[3][3] = {
+                {0.0, -v[2], v[1]}, {v[2], 0.0, -v[0]}, {-v[1], v[0], 0.0}};
+        const double factor = 1 / (1 + c);
+        double sv2[3][3];
+        MatMul3InOrder(sv, sv, sv2);
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+                Rx[r][q] = (Rx[r][q] + sv[r][q]) + sv2[r][q] * factor;
+    }
+    const double D[3][3] = {
+            {epsilon, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    double RxT[3][3], P[3][3], C[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) RxT[r][q] = Rx[q][r];
+    MatMul3InOrder(Rx, D, P);
+    MatMul3InOrder(P, RxT, C);
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) cov[3 * r + q] = (T)C[r][q];
+}
+
+template <typename T>
+__global__ void CovariancesFromNormalsKernel(const T* __restrict__ normals,
+                                             int64_t n, double epsilon,
+                                             T* __restrict__ cov) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x)
+        CovarianceFromNormal<T>(normals + 3 * i, epsilon, cov + 9 * i);
+}
+
 }  // namespace
 }  // namespace o3dmi
 
@@ -328,6 +392,32 @@ int o3dmi_pointcloud_normals_from_covariances(const void* covariances_dev,
         hipLaunchKernelGGL(NormalsFromCovariancesKernel<float>, grid, block, 0,
                            s, (const float*)covariances_dev, n,
                            (float*)normals_dev, has_normals != 0);
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
+int o3dmi_pointcloud_covariances_from_normals(const void* normals_dev,
+                                              int64_t n, int dtype,
+                                              double epsilon,
+                                              void* covariances_dev,
+                                              o3dmi_stream_t stream) {
+    O3DMI_REQUIRE(dtype == O3DMI_F32 || dtype == O3DMI_F64,
+                  "normals must be Float32 or Float64");
+    O3DMI_REQUIRE(epsilon > 0 && std::isfinite(epsilon),
+                  "epsilon must be positive and finite");
+    O3DMI_REQUIRE(n >= 0, "n < 0");
+    if (n == 0) return O3DMI_OK;
+    O3DMI_REQUIRE(normals_dev && covariances_dev, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid(GridFor(n, kBlock)), block(kBlock);
+    if (dtype == O3DMI_F64)
+        hipLaunchKernelGGL(CovariancesFromNormalsKernel<double>, grid, block, 0,
+                           s, (const double*)normals_dev, n, epsilon,
+                           (double*)covariances_dev);
+    else
+        hipLaunchKernelGGL(CovariancesFromNormalsKernel<float>, grid, block, 0,
+                           s, (const float*)normals_dev, n, epsilon,
+                           (float*)covariances_dev);
     O3DMI_HIP_CHECK(hipGetLastError());
     return O3DMI_OK;
 }

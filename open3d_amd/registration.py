@@ -121,6 +121,44 @@ class TransformationEstimationForDopplerICP:
         d.doppler_shape_parameter = self.doppler_kernel.shape_parameter
 
 
+class TransformationEstimationForGeneralizedICP:
+    """Legacy pipelines/registration/GeneralizedICP.h (Segal et al.,
+    "Generalized-ICP", RSS 2009): reads a covariance {N,3,3} per point of both
+    clouds. A cloud without `covariances` gets them from its normals
+    (covariances_from_normals with `epsilon`), one without normals from
+    EstimateNormals with KNN 20 first."""
+    def __init__(self, epsilon=1e-3, kernel=None):
+        self.epsilon = epsilon
+        self.kernel = kernel or RobustKernel()
+
+
+def covariances_from_normals(normals, epsilon=1e-3):
+    """InitializePointCloudForGeneralizedICP's covariances {N,3,3} from
+    normals {N,3}: Rx diag(epsilon,1,1) Rx^T with Rx the rotation from e1 to
+    the normal (GeneralizedICP.cpp:33-80)."""
+    normals = require_cuda(normals, "normals")
+    if normals.dtype not in (torch.float32, torch.float64):
+        raise ValueError("Only Float32 and Float64 point clouds are supported.")
+    if normals.dim() != 2 or normals.shape[1] != 3:
+        raise ValueError("normals must be {N,3}")
+    out = torch.empty((normals.shape[0], 3, 3), dtype=normals.dtype,
+                      device=normals.device)
+    _lib.check(_lib.lib().o3dmi_pointcloud_covariances_from_normals(
+        _lib.ptr(normals), normals.shape[0], TORCH_TO_O3DMI[normals.dtype],
+        C.c_double(epsilon), _lib.ptr(out), stream()),
+        "covariances_from_normals")
+    return out
+
+
+def _covariances(t, name, like):
+    t = require_cuda(t, name)
+    if t.dtype != like.dtype:
+        raise ValueError("source / attribute dtype mismatch")
+    if tuple(t.shape) != (like.shape[0], 3, 3):
+        raise ValueError(name + " must be {N,3,3}")
+    return t
+
+
 def transformation_to_pose(transformation):
     """t::pipelines::kernel::TransformationToPose: 4x4 -> pose {6} (Euler
     angles, translation), float64."""
@@ -158,7 +196,8 @@ def multi_scale_icp(source, target, target_normals, voxel_sizes, criteria_list,
                     target_colors=None, target_color_gradients=None,
                     device_allreduce=None, device_counts=None,
                     level_sharding=False, source_dopplers=None,
-                    source_directions=None):
+                    source_directions=None, source_covariances=None,
+                    target_covariances=None, return_singular_pairs=False):
     """source/target/target_normals: device tensors {N,3}. `device_counts`
     (optional): (ns, nt) int32 device tensors of one element holding the LIVE
     sizes of source / target, whose tensors are then buffers of at least that
@@ -171,8 +210,20 @@ def multi_scale_icp(source, target, target_normals, voxel_sizes, criteria_list,
     level; otherwise each rank passes its shard.
     `source_normals` is read by the symmetric estimator, the colours (and the
     optional target colour gradients) by the coloured one, `source_dopplers`
-    {N,1} (or {N}) and `source_directions` {N,3} by the Doppler one."""
+    {N,1} (or {N}) and `source_directions` {N,3} by the Doppler one. The
+    generalized estimator reads `source_covariances` / `target_covariances`
+    {N,3,3}; for a cloud without them `source_normals` / `target_normals`,
+    which may both be None for it. `return_singular_pairs` (generalized only):
+    returns (result, the pairs of the last iteration that could not be
+    whitened)."""
     est = estimation_method or TransformationEstimationPointToPlane()
+    generalized = isinstance(est, TransformationEstimationForGeneralizedICP)
+    if return_singular_pairs and not generalized:
+        raise ValueError("return_singular_pairs is of the generalized "
+                         "estimator")
+    gen = _lib.IcpGeneralized()
+    singular_pairs = C.c_int64(0)
+    gen_source_normals = source_normals if generalized else None
     doppler = isinstance(est, TransformationEstimationForDopplerICP)
     dop = _lib.IcpDoppler()
     if doppler:
@@ -230,7 +281,29 @@ def multi_scale_icp(source, target, target_normals, voxel_sizes, criteria_list,
         if (source_dopplers.numel() != source.shape[0] or
                 tuple(source_directions.shape) != tuple(source.shape)):
             raise ValueError("dopplers must be {N,1} and directions {N,3}")
-    if p2point:
+    if generalized:
+        gen.epsilon = est.epsilon
+        gen.robust_kernel = int(est.kernel.type)
+        gen.scaling_parameter = est.kernel.scaling_parameter
+        gen.shape_parameter = est.kernel.shape_parameter
+        gen.singular_pairs_out = C.pointer(singular_pairs)
+        if source_covariances is not None:
+            source_covariances = _covariances(source_covariances,
+                                              "source_covariances", source)
+            gen.source_covariances = source_covariances.data_ptr()
+        if target_covariances is not None:
+            target_covariances = _covariances(target_covariances,
+                                              "target_covariances", target)
+            gen.target_covariances = target_covariances.data_ptr()
+        if gen_source_normals is not None:
+            gen_source_normals = require_cuda(gen_source_normals,
+                                              "source_normals")
+            if (gen_source_normals.dtype != source.dtype or
+                    tuple(gen_source_normals.shape) != tuple(source.shape)):
+                raise ValueError("source_normals must be {N,3} of the "
+                                 "source's dtype")
+            gen.source_normals = gen_source_normals.data_ptr()
+    if p2point or (generalized and target_normals is None):
         target_normals = None
     else:
         if target_normals is None:
@@ -300,6 +373,9 @@ def multi_scale_icp(source, target, target_normals, voxel_sizes, criteria_list,
     if doppler:
         st = _lib.lib().o3dmi_registration_multiscale_icp_doppler(
             *common, C.byref(dop), C.byref(opts), *tail)
+    elif generalized:
+        st = _lib.lib().o3dmi_registration_multiscale_icp_generalized(
+            *common, C.byref(gen), C.byref(opts), *tail)
     else:
         st = _lib.lib().o3dmi_registration_multiscale_icp_ex(
             *common,
@@ -315,6 +391,8 @@ def multi_scale_icp(source, target, target_normals, voxel_sizes, criteria_list,
     out.converged = bool(res.converged)
     out.num_iterations = res.num_iterations
     out.correspondence_set = corr[:res.num_correspondences]
+    if return_singular_pairs:
+        return out, singular_pairs.value
     return out
 
 
@@ -324,7 +402,8 @@ def icp(source, target, target_normals, max_correspondence_distance,
         source_normals=None, source_colors=None, target_colors=None,
         target_color_gradients=None, device_allreduce=None,
         device_counts=None, level_sharding=False, source_dopplers=None,
-        source_directions=None):
+        source_directions=None, source_covariances=None,
+        target_covariances=None, return_singular_pairs=False):
     """t::pipelines::registration::ICP (Registration.cpp:93-106)."""
     return multi_scale_icp(source, target, target_normals, [voxel_size],
                            [criteria or ICPConvergenceCriteria()],
@@ -334,7 +413,8 @@ def icp(source, target, target_normals, max_correspondence_distance,
                            source_colors, target_colors,
                            target_color_gradients, device_allreduce,
                            device_counts, level_sharding, source_dopplers,
-                           source_directions)
+                           source_directions, source_covariances,
+                           target_covariances, return_singular_pairs)
 
 
 def _check_pair(source, target):
@@ -474,10 +554,27 @@ def estimate_color_gradients(positions, normals, colors, max_nn=30,
 
 def compute_rmse(estimation_method, source, target, target_normals,
                  correspondences, source_normals=None, source_colors=None,
-                 target_colors=None, target_color_gradients=None):
+                 target_colors=None, target_color_gradients=None,
+                 source_covariances=None, target_covariances=None):
     """TransformationEstimation*::ComputeRMSE on device tensors (the
-    reference's definitions, see o3dmi_registration_compute_rmse)."""
+    reference's definitions, see o3dmi_registration_compute_rmse; the
+    generalized estimator's, on both clouds' covariances {N,3,3}:
+    o3dmi_registration_compute_rmse_generalized)."""
     est = estimation_method
+    if isinstance(est, TransformationEstimationForGeneralizedICP):
+        source, target = _check_pair(source, target)
+        corr = require_cuda(correspondences, "correspondences")
+        if source_covariances is None or target_covariances is None:
+            raise ValueError("GeneralizedICP requires both clouds to have "
+                             "covariances.")
+        cs = _covariances(source_covariances, "source_covariances", source)
+        ct = _covariances(target_covariances, "target_covariances", target)
+        out = np.zeros(1, np.float64)
+        _lib.check(_lib.lib().o3dmi_registration_compute_rmse_generalized(
+            _lib.ptr(source), _lib.ptr(cs), source.shape[0], _lib.ptr(target),
+            _lib.ptr(ct), target.shape[0], TORCH_TO_O3DMI[source.dtype],
+            _lib.ptr(corr), _lib.f64p(out), stream()), "compute_rmse")
+        return float(out[0])
     code = (1 if isinstance(est, TransformationEstimationPointToPoint) else
             2 if isinstance(est, TransformationEstimationSymmetric) else
             3 if isinstance(est, TransformationEstimationForColoredICP) else

@@ -25,9 +25,18 @@ struct IcpCall {
     o3dmi_stream_t stream() const { return (o3dmi_stream_t)s; }
     hipEvent_t ev = nullptr;
 
-    // estimator (none of the five: point-to-point)
-    bool p2plane = false, symmetric = false, colored = false, doppler = false,
-         generalized = false;
+    int estimation = O3DMI_ICP_POINT_TO_POINT;  // O3DMI_ICP_*
+    bool Is(int e) const { return estimation == e; }
+    // the fused search launch accumulates the point-to-plane terms itself (its
+    // index carries the target's normals); the others take its moments
+    bool SearchesPointToPlane() const { return Is(O3DMI_ICP_POINT_TO_PLANE); }
+    // a second launch per iteration gathers by correspondence
+    bool GathersByCorrespondence() const {
+        return !Is(O3DMI_ICP_POINT_TO_PLANE) && !Is(O3DMI_ICP_POINT_TO_POINT);
+    }
+    bool NeedsTargetNormals() const {
+        return !Is(O3DMI_ICP_POINT_TO_POINT) && !Is(O3DMI_ICP_GENERALIZED);
+    }
 
     // clouds and attributes (NULL: the estimator does not read it)
     const void *source = nullptr, *source_normals = nullptr,

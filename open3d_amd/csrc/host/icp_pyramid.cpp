@@ -376,8 +376,8 @@ int BuildPyramids(const IcpCall& c, std::vector<Level>& pyr,
     // source level) and generalized ICP (three per level of either cloud)
     // keep the two chains.
     static const bool unpaired = std::getenv("O3DMI_VDS_UNPAIRED") != nullptr;
-    const bool paired =
-            !c.colored && !c.doppler && !c.generalized && !unpaired;
+    const bool paired = !c.Is(O3DMI_ICP_COLORED) && !c.Is(O3DMI_ICP_DOPPLER) &&
+                        !c.Is(O3DMI_ICP_GENERALIZED) && !unpaired;
     hipStream_t ts = paired ? c.s : c.side;
     CloudChain src(c, c.source, c.ns, c.ns_dev, 0, c.s, &Level::source);
     src.attr[kNormals] = c.source_normals;
@@ -391,7 +391,7 @@ int BuildPyramids(const IcpCall& c, std::vector<Level>& pyr,
     tgt.attr[kColors] = c.target_colors;
     tgt.attr[kGradients] = c.target_gradients;
     for (int r = 0; r < 3; ++r) tgt.attr[kCovRow0 + r] = c.target_cov_rows[r];
-    tgt.needs_gradients = c.colored;
+    tgt.needs_gradients = c.Is(O3DMI_ICP_COLORED);
     ChainCounts &scc = src.counts, &tcc = tgt.counts;
     if ((st = scc.Init(c.num_scales, 0, c.s))) return st;
     if ((st = tcc.Init(c.num_scales, 1, ts))) return st;
@@ -406,7 +406,8 @@ int BuildPyramids(const IcpCall& c, std::vector<Level>& pyr,
     // build launch -> build (a 20 us hole in every tracked frame, r6a).
     NnsGuard early;  // (destroyed with a device-wide wait if not adopted)
     const CloudLevel& T0 = pyr[0].target;
-    const void* nrm0 = c.p2plane ? T0.attr[kNormals] : nullptr;
+    const void* nrm0 =
+            c.SearchesPointToPlane() ? T0.attr[kNormals] : nullptr;
     const bool early_build =
             paired && !(last == 0 && c.finest_is_input) && T0.pos;
     if (paired) {

@@ -193,7 +193,8 @@ struct IndexScheduler {
             for (; cnt < 4 && next < c.num_scales; ++cnt, ++next) {
                 const CloudLevel& Tk = pyr[(size_t)next].target;
                 pts[cnt] = Tk.pos;
-                nrm[cnt] = c.p2plane ? Tk.attr[kNormals] : nullptr;
+                nrm[cnt] = c.SearchesPointToPlane() ? Tk.attr[kNormals]
+                                                    : nullptr;
                 nn[cnt] = Tk.n;
                 rad[cnt] = c.max_dists[next];
             }
@@ -346,6 +347,56 @@ void ViewOf(const IcpCall& c, const Level& L, ScaleView& v) {
     v.nt = L.target.n;
 }
 
+// The scale's scratch of the estimators that gather by correspondence, issued
+// on the call's stream in this order: Doppler -- the level's dopplers as
+// {ns,1}; generalized -- the level's covariances as {n,3,3}, the source's
+// slice and the target's; behind either the range check's zeroed word; then
+// the correspondence set and the rows of partial sums.
+struct ScaleScratch {
+    DeviceBuffer corr, partials, tables;
+
+    int Prepare(const IcpCall& c, ScaleView& L) {
+        if (!c.GathersByCorrespondence()) return O3DMI_OK;
+        int e;
+        auto round8 = [](size_t bytes) { return (bytes + 7) / 8 * 8; };
+        // `bytes` of tables and, behind them, L.bad, zeroed
+        auto alloc_tables = [&](size_t bytes) -> int {
+            int st = tables.Alloc(bytes + sizeof(int));
+            if (st) return st;
+            L.bad = (int*)((char*)tables.p + bytes);
+            O3DMI_HIP_CHECK(hipMemsetAsync(L.bad, 0, sizeof(int), c.s));
+            return O3DMI_OK;
+        };
+        if (c.Is(O3DMI_ICP_DOPPLER)) {
+            if ((e = alloc_tables(round8((size_t)L.ns * c.esz)))) return e;
+            L.srcdop = tables.p;
+            if ((e = o3dmi_internal_take_column(L.srcdop3, L.ns, c.dtype,
+                                                L.srcdop, c.stream())))
+                return e;
+        } else if (c.Is(O3DMI_ICP_GENERALIZED)) {
+            const size_t so = round8((size_t)L.ns * 9 * c.esz);
+            const size_t to = round8((size_t)L.nt * 9 * c.esz);
+            if ((e = alloc_tables(so + to))) return e;
+            L.srccov = tables.p;
+            L.tgtcov = (char*)tables.p + so;
+            if ((e = o3dmi_internal_join_rows3(
+                         L.srccov_rows[0], L.srccov_rows[1], L.srccov_rows[2],
+                         L.ns, c.dtype, L.srccov, c.stream())))
+                return e;
+            if ((e = o3dmi_internal_join_rows3(
+                         L.tgtcov_rows[0], L.tgtcov_rows[1], L.tgtcov_rows[2],
+                         L.nt, c.dtype, L.tgtcov, c.stream())))
+                return e;
+        }
+        if ((e = corr.Alloc(sizeof(int64_t) * (size_t)L.ns))) return e;
+        if ((e = partials.Alloc(sizeof(double) * 32 * kIcpPartialRows)))
+            return e;
+        L.corr = (int64_t*)corr.p;
+        L.partials = (double*)partials.p;
+        return O3DMI_OK;
+    }
+};
+
 // The transformation the source still has to be moved by
 // (`source.Transform(...)`, Registration.cpp:322,404) -- applied by the NEXT
 // search launch itself, in place, before it searches.
@@ -375,7 +426,7 @@ int Search(const IcpCall& c, SumsFetcher& sums, o3dmi_nns_t* nns,
     const double* xf = pending.Take();
     // the fused search kernel accumulates the point-to-plane terms itself;
     // the other estimators take the point-to-point moments from it
-    const int search_mode = c.p2plane ? 0 : 1;
+    const int search_mode = c.SearchesPointToPlane() ? 0 : 1;
     int e = sums.Fetch(
             [&](double* sums_dev, double* mail_data, int* mail_flag, int seq) {
                 return o3dmi_internal_icp_transform_search_accumulate(
@@ -471,14 +522,54 @@ int GeneralizedSums(const IcpCall& c, SumsFetcher& sums, const ScaleView& L,
     return O3DMI_OK;
 }
 
+// ComputeTransformationSymmetric up to the solve, kernel/Registration.cpp:
+// 80-135: the means of the matched points (from the search pass' moments, in
+// the clouds' dtype) and the 29 sums about them.
+int SymmetricSums(const IcpCall& c, SumsFetcher& sums, const ScaleView& L,
+                  const SearchResult& r, double* ms, double* mt,
+                  double* out32) {
+    const double cnt = r.sums[15];
+    for (int k = 0; k < 3; ++k) {
+        ms[k] = r.sums[k] / cnt;
+        mt[k] = r.sums[3 + k] / cnt;
+        if (c.dtype == O3DMI_F32) {
+            ms[k] = (double)(float)ms[k];
+            mt[k] = (double)(float)mt[k];
+        }
+    }
+    return sums.Fetch(
+            [&](double* sums_dev, double* mail_data, int* mail_flag, int seq) {
+                return o3dmi_icp_symmetric_accumulate_post(
+                        L.src, L.srcn, L.tgt, L.nrm, L.corr, L.ns, c.dtype, ms,
+                        mt, c.robust_kernel, c.scaling_parameter,
+                        c.shape_parameter, sums_dev, L.partials, mail_data,
+                        mail_flag, seq, c.stream());
+            },
+            out32, 0.0, 0.0, 0.0);
+}
+
+// ComputePoseColoredICP (TransformationEstimation.cpp:420-432).
+int ColoredSums(const IcpCall& c, SumsFetcher& sums, const ScaleView& L,
+                double* out32) {
+    return sums.Fetch(
+            [&](double* sums_dev, double* mail_data, int* mail_flag, int seq) {
+                return o3dmi_icp_colored_accumulate_post(
+                        L.src, L.srcc, L.tgt, L.nrm, L.tgtc, L.tgtg, L.corr,
+                        L.ns, c.dtype, c.lambda_geometric, c.robust_kernel,
+                        c.scaling_parameter, c.shape_parameter, sums_dev,
+                        L.partials, mail_data, mail_flag, seq, c.stream());
+            },
+            out32, 0.0, 0.0, 0.0);
+}
+
 // One iteration's update from its search: estimation.ComputeTransformation,
-// Registration.cpp:314. Point-to-point: R, t from the search pass' moments.
-// The others: 29 sums (point-to-plane: of the search pass; symmetric /
-// coloured / Doppler / generalized: of a second launch that gathers by
-// correspondence), the 6x6
-// solve, pose -> transformation. *solve_status: a failed solve (the reference
-// throws; the driver reports it after the loop); a returned error ends the
-// call at once.
+// Registration.cpp:314, in three steps. Point-to-point: R, t from the search
+// pass' moments, and done. The others: their 29 sums -- point-to-plane: of the
+// search pass; symmetric / coloured / Doppler / generalized: of a second
+// launch that gathers by correspondence -- then the 6x6 solve and pose ->
+// transformation (symmetric: the half-angle form about the means).
+// *solve_status: a failed solve (the reference throws; the driver reports it
+// after the loop); a returned error ends the call at once.
 // `current`, `iteration`: the cumulative transformation before this update and
 // the iteration's index within its scale (read by the Doppler and the
 // generalized estimator only). *singular_pairs: the generalized estimator's
@@ -486,8 +577,7 @@ int GeneralizedSums(const IcpCall& c, SumsFetcher& sums, const ScaleView& L,
 int ComputeUpdate(const IcpCall& c, SumsFetcher& sums, const ScaleView& L,
                   const SearchResult& r, const double* current, int iteration,
                   double* update, int* solve_status, int64_t* singular_pairs) {
-    if (!c.p2plane && !c.symmetric && !c.colored && !c.doppler &&
-        !c.generalized) {
+    if (c.Is(O3DMI_ICP_POINT_TO_POINT)) {
         // ComputeRtPointToPoint + RtToTransformation
         // (TransformationEstimation.cpp:150-159)
         double R[9], t[3];
@@ -500,67 +590,33 @@ int ComputeUpdate(const IcpCall& c, SumsFetcher& sums, const ScaleView& L,
         }
         return O3DMI_OK;
     }
-    const double* sums29 = r.sums;
     double gathered[32], ms[3], mt[3];
-    if (c.symmetric) {
-        // ComputeTransformationSymmetric, kernel/Registration.cpp:80-135:
-        // means of the matched points (from the search pass' moments), 29
-        // sums about them, solve, half-angle pose -> transformation.
-        const double cnt = r.sums[15];
-        for (int k = 0; k < 3; ++k) {
-            ms[k] = r.sums[k] / cnt;
-            mt[k] = r.sums[3 + k] / cnt;
-        }
-        if (c.dtype == O3DMI_F32)
-            for (int k = 0; k < 3; ++k) {
-                ms[k] = (double)(float)ms[k];
-                mt[k] = (double)(float)mt[k];
-            }
-        int e = sums.Fetch(
-                [&](double* sums_dev, double* mail_data, int* mail_flag,
-                    int seq) {
-                    return o3dmi_icp_symmetric_accumulate_post(
-                            L.src, L.srcn, L.tgt, L.nrm, L.corr, L.ns, c.dtype,
-                            ms, mt, c.robust_kernel, c.scaling_parameter,
-                            c.shape_parameter, sums_dev, L.partials, mail_data,
-                            mail_flag, seq, c.stream());
-                },
-                gathered, 0.0, 0.0, 0.0);
-        if (e) return e;
-        sums29 = gathered;
-    } else if (c.colored) {
-        // ComputePoseColoredICP + PoseToTransformation
-        // (TransformationEstimation.cpp:420-432)
-        int e = sums.Fetch(
-                [&](double* sums_dev, double* mail_data, int* mail_flag,
-                    int seq) {
-                    return o3dmi_icp_colored_accumulate_post(
-                            L.src, L.srcc, L.tgt, L.nrm, L.tgtc, L.tgtg, L.corr,
-                            L.ns, c.dtype, c.lambda_geometric, c.robust_kernel,
-                            c.scaling_parameter, c.shape_parameter, sums_dev,
-                            L.partials, mail_data, mail_flag, seq, c.stream());
-                },
-                gathered, 0.0, 0.0, 0.0);
-        if (e) return e;
-        sums29 = gathered;
-    } else if (c.doppler) {
-        // ComputePoseDopplerICP + PoseToTransformation
-        // (TransformationEstimation.cpp:469-519)
-        int e = DopplerSums(c, sums, L, current, iteration, gathered);
-        if (e) return e;
-        sums29 = gathered;
-    } else if (c.generalized) {
-        int e = GeneralizedSums(c, sums, L, current, gathered);
-        if (e) return e;
-        *singular_pairs = (int64_t)gathered[29];
-        sums29 = gathered;
+    int e = O3DMI_OK;
+    switch (c.estimation) {
+        case O3DMI_ICP_SYMMETRIC:
+            e = SymmetricSums(c, sums, L, r, ms, mt, gathered);
+            break;
+        case O3DMI_ICP_COLORED:
+            e = ColoredSums(c, sums, L, gathered);
+            break;
+        case O3DMI_ICP_DOPPLER:
+            // ComputePoseDopplerICP (TransformationEstimation.cpp:469-519)
+            e = DopplerSums(c, sums, L, current, iteration, gathered);
+            break;
+        case O3DMI_ICP_GENERALIZED:
+            e = GeneralizedSums(c, sums, L, current, gathered);
+            if (!e) *singular_pairs = (int64_t)gathered[29];
+            break;
     }
+    if (e) return e;
+    // (point-to-plane: the search pass' own sums)
+    const double* sums29 = c.GathersByCorrespondence() ? gathered : r.sums;
     double pose[6];
     float residual;
     int inlier_count;
-    int e = o3dmi_decode_and_solve6x6(sums29, pose, &residual, &inlier_count);
+    e = o3dmi_decode_and_solve6x6(sums29, pose, &residual, &inlier_count);
     if (e) *solve_status = e;
-    if (c.symmetric)
+    if (c.Is(O3DMI_ICP_SYMMETRIC))
         o3dmi_symmetric_pose_to_transformation(pose, ms, mt, update);
     else
         o3dmi_pose_to_transformation(pose, update);
@@ -614,8 +670,9 @@ int RunScaleIterations(const IcpCall& c, SumsFetcher& sums, NnsGuard& guard,
         // this scale (a scale that ends here has no further use for its
         // source cloud)
         st.pending.Set(update);
-        if (c.symmetric && (e = o3dmi_transform_normals(update, L.srcn, L.ns,
-                                                        c.dtype, c.stream())))
+        if (c.Is(O3DMI_ICP_SYMMETRIC) &&
+            (e = o3dmi_transform_normals(update, L.srcn, L.ns, c.dtype,
+                                         c.stream())))
             return e;
         if (c.callback)
             c.callback(st.iteration_count + it, scale_idx, it, st.inlier_rmse,
@@ -658,51 +715,12 @@ int RunIcp(const IcpCall& c, IcpTimer& timer, std::vector<Level>& pyr,
         // source_down_pyramid[scale].Transform(result.transformation_) :404
         // (positions and, when the estimator reads them, normals)
         st.pending.Set(st.T);
-        if (c.symmetric && (e = o3dmi_transform_normals(st.T, L.srcn, L.ns,
-                                                        c.dtype, c.stream())))
+        if (c.Is(O3DMI_ICP_SYMMETRIC) &&
+            (e = o3dmi_transform_normals(st.T, L.srcn, L.ns, c.dtype,
+                                         c.stream())))
             return e;
-        DeviceBuffer corr_buf, sym_partials, doppler_buf;
-        if (c.doppler) {
-            // the level's dopplers as {ns,1}, and the range check's word
-            // behind them
-            const size_t bytes = (size_t)L.ns * c.esz;
-            const size_t word = (bytes + 7) / 8 * 8;
-            if ((e = doppler_buf.Alloc(word + sizeof(int)))) return e;
-            L.srcdop = doppler_buf.p;
-            L.bad = (int*)((char*)doppler_buf.p + word);
-            O3DMI_HIP_CHECK(hipMemsetAsync(L.bad, 0, sizeof(int), c.s));
-            if ((e = o3dmi_internal_take_column(L.srcdop3, L.ns, c.dtype,
-                                                L.srcdop, c.stream())))
-                return e;
-        }
-        DeviceBuffer cov_buf;
-        if (c.generalized) {
-            // the level's covariances as {n,3,3}: the source's slice, the
-            // target's, and the range check's word behind them
-            const size_t sb = (size_t)L.ns * 9 * c.esz;
-            const size_t tb = (size_t)L.nt * 9 * c.esz;
-            const size_t so = (sb + 7) / 8 * 8, to = (tb + 7) / 8 * 8;
-            if ((e = cov_buf.Alloc(so + to + sizeof(int)))) return e;
-            L.srccov = cov_buf.p;
-            L.tgtcov = (char*)cov_buf.p + so;
-            L.bad = (int*)((char*)cov_buf.p + so + to);
-            O3DMI_HIP_CHECK(hipMemsetAsync(L.bad, 0, sizeof(int), c.s));
-            if ((e = o3dmi_internal_join_rows3(
-                         L.srccov_rows[0], L.srccov_rows[1], L.srccov_rows[2],
-                         L.ns, c.dtype, L.srccov, c.stream())))
-                return e;
-            if ((e = o3dmi_internal_join_rows3(
-                         L.tgtcov_rows[0], L.tgtcov_rows[1], L.tgtcov_rows[2],
-                         L.nt, c.dtype, L.tgtcov, c.stream())))
-                return e;
-        }
-        if (c.symmetric || c.colored || c.doppler || c.generalized) {
-            if ((e = corr_buf.Alloc(sizeof(int64_t) * (size_t)L.ns))) return e;
-            if ((e = sym_partials.Alloc(sizeof(double) * 32 * 1024)))
-                return e;
-            L.corr = (int64_t*)corr_buf.p;
-            L.partials = (double*)sym_partials.p;
-        }
+        ScaleScratch scratch;
+        if ((e = scratch.Prepare(c, L))) return e;
         // target_nns.HybridIndex(max_correspondence_distance) :406-412:
         // built behind the target pyramid, the later scales' in the shadow of
         // the first scale's searches
@@ -751,7 +769,7 @@ int RunIcp(const IcpCall& c, IcpTimer& timer, std::vector<Level>& pyr,
     result->converged = st.converged ? 1 : 0;
     result->num_iterations = st.iteration_count;
     result->num_correspondences = correspondences_dev ? last_ns : 0;
-    if (c.generalized && c.gen.singular_pairs_out)
+    if (c.Is(O3DMI_ICP_GENERALIZED) && c.gen.singular_pairs_out)
         *c.gen.singular_pairs_out = st.singular_pairs;
     return st.status;
 }
@@ -925,17 +943,14 @@ int MultiScaleIcpEntry(
                   "Only Float32 and Float64 point clouds are supported.");
     O3DMI_REQUIRE(source_dev && target_dev && ns > 0 && nt > 0,
                   "Source and/or Target pointcloud is empty.");
-    c.p2plane = estimation == O3DMI_ICP_POINT_TO_PLANE;
-    c.symmetric = estimation == O3DMI_ICP_SYMMETRIC;
-    c.colored = estimation == O3DMI_ICP_COLORED;
-    c.doppler = estimation == O3DMI_ICP_DOPPLER;
-    c.generalized = estimation == O3DMI_ICP_GENERALIZED;
-    const bool need_tn = c.p2plane || c.symmetric || c.colored || c.doppler;
+    c.estimation = estimation;
+    const bool symmetric = c.Is(O3DMI_ICP_SYMMETRIC),
+               colored = c.Is(O3DMI_ICP_COLORED);
     c.source = source_dev;
     c.target = target_dev;
-    c.target_normals = need_tn ? target_normals_dev : nullptr;
-    if (c.symmetric && attrs) c.source_normals = attrs->source_normals;
-    if (c.colored && attrs) {
+    c.target_normals = c.NeedsTargetNormals() ? target_normals_dev : nullptr;
+    if (symmetric && attrs) c.source_normals = attrs->source_normals;
+    if (colored && attrs) {
         c.source_colors = attrs->source_colors;
         c.target_colors = attrs->target_colors;
         c.target_gradients = attrs->target_color_gradients;
@@ -945,22 +960,23 @@ int MultiScaleIcpEntry(
     // 293-299
     if (!(c.lambda_geometric >= 0 && c.lambda_geometric <= 1.0))
         c.lambda_geometric = 0.968;
-    O3DMI_REQUIRE(!(c.p2plane || c.colored) || c.target_normals != nullptr,
+    O3DMI_REQUIRE(!(c.SearchesPointToPlane() || colored) ||
+                          c.target_normals != nullptr,
                   "Target pointcloud missing normals attribute.");
-    O3DMI_REQUIRE(!c.doppler || c.target_normals != nullptr,
+    O3DMI_REQUIRE(!c.Is(O3DMI_ICP_DOPPLER) || c.target_normals != nullptr,
                   "DopplerICP requires target pointcloud to have normals.");
-    if (c.doppler) {
+    if (c.Is(O3DMI_ICP_DOPPLER)) {
         int e = ResolveDoppler(c, doppler);
         if (e) return e;
     }
-    if (c.generalized) {
+    if (c.Is(O3DMI_ICP_GENERALIZED)) {
         int e = ResolveGeneralized(c, generalized, target_normals_dev);
         if (e) return e;
     }
-    O3DMI_REQUIRE(!c.symmetric || (c.source_normals && c.target_normals),
+    O3DMI_REQUIRE(!symmetric || (c.source_normals && c.target_normals),
                   "SymmetricICP requires both source and target to have "
                   "normals.");
-    O3DMI_REQUIRE(!c.colored || (c.source_colors && c.target_colors),
+    O3DMI_REQUIRE(!colored || (c.source_colors && c.target_colors),
                   "Source and/or Target pointcloud missing colors attribute.");
     O3DMI_REQUIRE(num_scales > 0 && voxel_sizes && criterias && max_dists,
                   "Size of criterias, voxel_size, max_correspondence_distances "
@@ -1000,14 +1016,14 @@ int MultiScaleIcpEntry(
     int st = ResolveSizesAndStreams(c);
     sync_on_exit.side = c.side;
     if (st) return st;
-    if (c.doppler) {
+    if (c.Is(O3DMI_ICP_DOPPLER)) {
         if ((st = dopplers3.Alloc((size_t)c.ns * 3 * c.esz))) return st;
         if ((st = o3dmi_internal_pad_column(c.dop.source_dopplers, c.ns,
                                             c.dtype, dopplers3.p, c.stream())))
             return st;
         c.source_dopplers3 = dopplers3.p;
     }
-    if (c.generalized) {
+    if (c.Is(O3DMI_ICP_GENERALIZED)) {
         if ((st = GeneralizedCovarianceRows(
                      c, c.source, c.ns, c.gen.source_covariances,
                      c.gen.source_normals, source_cov_rows,

@@ -5,6 +5,12 @@
 
 #include "common.h"
 
+namespace o3dmi {
+// Rows of kNumSums partial sums in a caller's `partials_dev`: at least the
+// largest grid of the gather kernels (icp.hip ReduceGrid checks it).
+constexpr int kIcpPartialRows = 1024;
+}  // namespace o3dmi
+
 extern "C" {
 
 // o3dmi_icp_search_accumulate[_p2point] (`estimation` 0 / 1) that also posts

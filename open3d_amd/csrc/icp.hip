@@ -489,148 +489,49 @@ __device__ __forceinline__ void BlockReduceAndStore(double (&A)[kNumSums],
     BlockSumAndStore<kNumSums>(A, partials);
 }
 
-__global__ void FinalReduceKernel(const double* __restrict__ partials,
-                                  int n_rows, double* __restrict__ out,
-                                  int n_out, double* mail_data, int* mail_flag,
-                                  int mail_seq) {
-    // one wave per output column would waste lanes; 32 columns x 8 row-lanes.
-    __shared__ double lds[8][kNumSums];
-    int col = threadIdx.x % kNumSums;
-    int rl = threadIdx.x / kNumSums;  // 0..7
-    double v = 0;
-    for (int r = rl; r < n_rows; r += 8) v += partials[(int64_t)r * kNumSums + col];
-    lds[rl][col] = v;
-    __syncthreads();
-    if (threadIdx.x < n_out) {
-        double s = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s += lds[k][threadIdx.x];
-        if (out) out[threadIdx.x] = s;
-        if (mail_data) mail_data[threadIdx.x] = s;
-    }
-    // Host mailbox (mailbox.h): the driver spins on the sequence word instead
-    // of a copy + stream synchronise per iteration.
-    if (mail_flag) MailboxPublish(mail_flag, mail_seq);
-}
-
-template <typename T>
-__global__ void __launch_bounds__(kReduceBlock)
-P2PlaneAccumulateKernel(const T* __restrict__ src, const T* __restrict__ tgt,
-                        const T* __restrict__ tgt_n,
-                        const int64_t* __restrict__ corr, int64_t n,
-                        RobustParams rp, double* __restrict__ partials) {
-    double A[kNumSums];
-#pragma unroll
-    for (int k = 0; k < kNumSums; ++k) A[k] = 0;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        int64_t c = corr[i];
-        if (c == -1) continue;
-        AccumulateP2Plane<T>(A, src[3 * i + 0], src[3 * i + 1], src[3 * i + 2],
-                             tgt[3 * c + 0], tgt[3 * c + 1], tgt[3 * c + 2],
-                             tgt_n[3 * c + 0], tgt_n[3 * c + 1],
-                             tgt_n[3 * c + 2], rp);
-    }
-    BlockReduceAndStore(A, partials);
-}
-
-template <typename T>
-__global__ void __launch_bounds__(kReduceBlock)
-SymmetricAccumulateKernel(const T* __restrict__ src, const T* __restrict__ src_n,
-                          const T* __restrict__ tgt, const T* __restrict__ tgt_n,
-                          const int64_t* __restrict__ corr, int64_t n,
-                          Means3<T> mean, RobustParams rp,
-                          double* __restrict__ partials) {
-    double A[kNumSums];
-#pragma unroll
-    for (int k = 0; k < kNumSums; ++k) A[k] = 0;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        int64_t c = corr[i];
-        if (c == -1) continue;
-        AccumulateSymmetric<T>(A, src[3 * i + 0], src[3 * i + 1], src[3 * i + 2],
-                               tgt[3 * c + 0], tgt[3 * c + 1], tgt[3 * c + 2],
-                               src_n[3 * i + 0], src_n[3 * i + 1],
-                               src_n[3 * i + 2], tgt_n[3 * c + 0],
-                               tgt_n[3 * c + 1], tgt_n[3 * c + 2], mean, rp);
-    }
-    BlockReduceAndStore(A, partials);
-}
-
-template <typename T>
-__global__ void __launch_bounds__(kReduceBlock)
-ColoredAccumulateKernel(const T* __restrict__ src, const T* __restrict__ src_c,
-                        const T* __restrict__ tgt, const T* __restrict__ tgt_n,
-                        const T* __restrict__ tgt_c, const T* __restrict__ tgt_g,
-                        const int64_t* __restrict__ corr, int64_t n,
-                        T sqrt_lambda_geometric, T sqrt_lambda_photometric,
-                        RobustParams rp, double* __restrict__ partials) {
-    double A[kNumSums];
-#pragma unroll
-    for (int k = 0; k < kNumSums; ++k) A[k] = 0;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        int64_t c = corr[i];
-        if (c == -1) continue;
-        const T vs[3] = {src[3 * i], src[3 * i + 1], src[3 * i + 2]};
-        const T cs[3] = {src_c[3 * i], src_c[3 * i + 1], src_c[3 * i + 2]};
-        const T vt[3] = {tgt[3 * c], tgt[3 * c + 1], tgt[3 * c + 2]};
-        const T nt[3] = {tgt_n[3 * c], tgt_n[3 * c + 1], tgt_n[3 * c + 2]};
-        const T ct[3] = {tgt_c[3 * c], tgt_c[3 * c + 1], tgt_c[3 * c + 2]};
-        const T dit[3] = {tgt_g[3 * c], tgt_g[3 * c + 1], tgt_g[3 * c + 2]};
-        AccumulateColored<T>(A, vs, cs, vt, nt, ct, dit, sqrt_lambda_geometric,
-                             sqrt_lambda_photometric, rp);
-    }
-    BlockReduceAndStore(A, partials);
-}
-
-// Every correspondence index is range-checked against the target's size: an
-// index outside [0, nt) (other than -1) raises *bad and is skipped; the
-// checked final pass below then delivers nothing.
-template <typename T>
-__global__ void __launch_bounds__(kReduceBlock)
-DopplerAccumulateKernel(const T* __restrict__ src,
-                        const T* __restrict__ src_dopplers,
-                        const T* __restrict__ src_directions,
-                        const T* __restrict__ tgt, const T* __restrict__ tgt_n,
-                        const int64_t* __restrict__ corr, int64_t n, int64_t nt,
-                        DopplerParams<T> dp, RobustParams rp_geometric,
-                        RobustParams rp_doppler, double* __restrict__ partials,
-                        int* __restrict__ bad) {
+// The frame of every gather kernel: zero the sums, grid-stride over the n
+// source rows, skip a row without a correspondence (-1), let `term(A, i, c)`
+// load row i and its target row c and add the estimator's terms, then one row
+// of partial sums per workgroup. kChecked: an index outside [0, nt) (other
+// than -1) raises *bad and is skipped; the checked final pass below then
+// delivers nothing.
+template <bool kChecked, typename Term>
+__device__ __forceinline__ void GatherAccumulate(
+        const int64_t* __restrict__ corr, int64_t n, int64_t nt,
+        int* __restrict__ bad, double* __restrict__ partials, Term&& term) {
     double A[kNumSums];
 #pragma unroll
     for (int k = 0; k < kNumSums; ++k) A[k] = 0;
     bool out_of_range = false;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x) {
+    // (every gather kernel is launched with kReduceBlock threads)
+    for (int64_t i = blockIdx.x * (int64_t)kReduceBlock + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * kReduceBlock) {
         const int64_t c = corr[i];
         if (c == -1) continue;
-        if (c < 0 || c >= nt) {
+        if (kChecked && (c < 0 || c >= nt)) {
             out_of_range = true;
             continue;
         }
-        const T ps[3] = {src[3 * i], src[3 * i + 1], src[3 * i + 2]};
-        const T ds[3] = {src_directions[3 * i], src_directions[3 * i + 1],
-                         src_directions[3 * i + 2]};
-        const T pt[3] = {tgt[3 * c], tgt[3 * c + 1], tgt[3 * c + 2]};
-        const T nrm[3] = {tgt_n[3 * c], tgt_n[3 * c + 1], tgt_n[3 * c + 2]};
-        AccumulateDoppler<T>(A, ps, src_dopplers[i], ds, pt, nrm, dp,
-                             rp_geometric, rp_doppler);
+        term(A, i, c);
     }
-    if (out_of_range) atomicOr(bad, 1);
+    if (kChecked && out_of_range) atomicOr(bad, 1);
     BlockReduceAndStore(A, partials);
 }
 
-// FinalReduceKernel behind a range check: with *bad set `out` keeps its
-// previous contents and a mailbox receives NaN in every value (the driver
-// turns that into O3DMI_ERR_INVALID_ARG).
-__global__ void FinalReduceCheckedKernel(const double* __restrict__ partials,
-                                         int n_rows, const int* __restrict__ bad,
-                                         double* __restrict__ out, int n_out,
-                                         double* mail_data, int* mail_flag,
-                                         int mail_seq) {
+// The single-workgroup final pass over the rows. kChecked: behind a range
+// check -- with *bad set `out` keeps its previous contents and a mailbox
+// receives NaN in every value (the driver turns that into
+// O3DMI_ERR_INVALID_ARG); the unchecked form never reads `bad`.
+template <bool kChecked>
+__device__ __forceinline__ void FinalReduce(const double* __restrict__ partials,
+                                            int n_rows, const int* bad,
+                                            double* __restrict__ out, int n_out,
+                                            double* mail_data, int* mail_flag,
+                                            int mail_seq) {
+    // one wave per output column would waste lanes; 32 columns x 8 row-lanes.
     __shared__ double lds[8][kNumSums];
-    const bool is_bad = *bad != 0;
+    bool is_bad = false;
+    if constexpr (kChecked) is_bad = *bad != 0;
     int col = threadIdx.x % kNumSums;
     int rl = threadIdx.x / kNumSums;  // 0..7
     double v = 0;
@@ -647,7 +548,103 @@ __global__ void FinalReduceCheckedKernel(const double* __restrict__ partials,
                                                       0x7ff8000000000000ll)
                                             : s;
     }
+    // Host mailbox (mailbox.h): the driver spins on the sequence word instead
+    // of a copy + stream synchronise per iteration.
     if (mail_flag) MailboxPublish(mail_flag, mail_seq);
+}
+
+__global__ void FinalReduceKernel(const double* __restrict__ partials,
+                                  int n_rows, double* __restrict__ out,
+                                  int n_out, double* mail_data, int* mail_flag,
+                                  int mail_seq) {
+    FinalReduce<false>(partials, n_rows, nullptr, out, n_out, mail_data,
+                       mail_flag, mail_seq);
+}
+
+__global__ void FinalReduceCheckedKernel(const double* __restrict__ partials,
+                                         int n_rows, const int* __restrict__ bad,
+                                         double* __restrict__ out, int n_out,
+                                         double* mail_data, int* mail_flag,
+                                         int mail_seq) {
+    FinalReduce<true>(partials, n_rows, bad, out, n_out, mail_data, mail_flag,
+                      mail_seq);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kReduceBlock)
+P2PlaneAccumulateKernel(const T* __restrict__ src, const T* __restrict__ tgt,
+                        const T* __restrict__ tgt_n,
+                        const int64_t* __restrict__ corr, int64_t n,
+                        RobustParams rp, double* __restrict__ partials) {
+    auto term = [&](double (&A)[kNumSums], int64_t i, int64_t c) {
+        AccumulateP2Plane<T>(A, src[3 * i + 0], src[3 * i + 1], src[3 * i + 2],
+                             tgt[3 * c + 0], tgt[3 * c + 1], tgt[3 * c + 2],
+                             tgt_n[3 * c + 0], tgt_n[3 * c + 1],
+                             tgt_n[3 * c + 2], rp);
+    };
+    GatherAccumulate<false>(corr, n, 0, nullptr, partials, term);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kReduceBlock)
+SymmetricAccumulateKernel(const T* __restrict__ src, const T* __restrict__ src_n,
+                          const T* __restrict__ tgt, const T* __restrict__ tgt_n,
+                          const int64_t* __restrict__ corr, int64_t n,
+                          Means3<T> mean, RobustParams rp,
+                          double* __restrict__ partials) {
+    auto term = [&](double (&A)[kNumSums], int64_t i, int64_t c) {
+        AccumulateSymmetric<T>(A, src[3 * i + 0], src[3 * i + 1], src[3 * i + 2],
+                               tgt[3 * c + 0], tgt[3 * c + 1], tgt[3 * c + 2],
+                               src_n[3 * i + 0], src_n[3 * i + 1],
+                               src_n[3 * i + 2], tgt_n[3 * c + 0],
+                               tgt_n[3 * c + 1], tgt_n[3 * c + 2], mean, rp);
+    };
+    GatherAccumulate<false>(corr, n, 0, nullptr, partials, term);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kReduceBlock)
+ColoredAccumulateKernel(const T* __restrict__ src, const T* __restrict__ src_c,
+                        const T* __restrict__ tgt, const T* __restrict__ tgt_n,
+                        const T* __restrict__ tgt_c, const T* __restrict__ tgt_g,
+                        const int64_t* __restrict__ corr, int64_t n,
+                        T sqrt_lambda_geometric, T sqrt_lambda_photometric,
+                        RobustParams rp, double* __restrict__ partials) {
+    auto term = [&](double (&A)[kNumSums], int64_t i, int64_t c) {
+        const T vs[3] = {src[3 * i], src[3 * i + 1], src[3 * i + 2]};
+        const T cs[3] = {src_c[3 * i], src_c[3 * i + 1], src_c[3 * i + 2]};
+        const T vt[3] = {tgt[3 * c], tgt[3 * c + 1], tgt[3 * c + 2]};
+        const T nt[3] = {tgt_n[3 * c], tgt_n[3 * c + 1], tgt_n[3 * c + 2]};
+        const T ct[3] = {tgt_c[3 * c], tgt_c[3 * c + 1], tgt_c[3 * c + 2]};
+        const T dit[3] = {tgt_g[3 * c], tgt_g[3 * c + 1], tgt_g[3 * c + 2]};
+        AccumulateColored<T>(A, vs, cs, vt, nt, ct, dit, sqrt_lambda_geometric,
+                             sqrt_lambda_photometric, rp);
+    };
+    GatherAccumulate<false>(corr, n, 0, nullptr, partials, term);
+}
+
+// Every correspondence index is range-checked against the target's size (the
+// checked frame).
+template <typename T>
+__global__ void __launch_bounds__(kReduceBlock)
+DopplerAccumulateKernel(const T* __restrict__ src,
+                        const T* __restrict__ src_dopplers,
+                        const T* __restrict__ src_directions,
+                        const T* __restrict__ tgt, const T* __restrict__ tgt_n,
+                        const int64_t* __restrict__ corr, int64_t n, int64_t nt,
+                        DopplerParams<T> dp, RobustParams rp_geometric,
+                        RobustParams rp_doppler, double* __restrict__ partials,
+                        int* __restrict__ bad) {
+    auto term = [&](double (&A)[kNumSums], int64_t i, int64_t c) {
+        const T ps[3] = {src[3 * i], src[3 * i + 1], src[3 * i + 2]};
+        const T ds[3] = {src_directions[3 * i], src_directions[3 * i + 1],
+                         src_directions[3 * i + 2]};
+        const T pt[3] = {tgt[3 * c], tgt[3 * c + 1], tgt[3 * c + 2]};
+        const T nrm[3] = {tgt_n[3 * c], tgt_n[3 * c + 1], tgt_n[3 * c + 2]};
+        AccumulateDoppler<T>(A, ps, src_dopplers[i], ds, pt, nrm, dp,
+                             rp_geometric, rp_doppler);
+    };
+    GatherAccumulate<true>(corr, n, nt, bad, partials, term);
 }
 
 // {n,1} <-> column 0 of an {n,3} attribute: how a 1-column attribute rides
@@ -684,18 +681,7 @@ GeneralizedAccumulateKernel(const T* __restrict__ src,
                             int64_t nt, GicpRotation rot, RobustParams rp,
                             double* __restrict__ partials,
                             int* __restrict__ bad) {
-    double A[kNumSums];
-#pragma unroll
-    for (int k = 0; k < kNumSums; ++k) A[k] = 0;
-    bool out_of_range = false;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t c = corr[i];
-        if (c == -1) continue;
-        if (c < 0 || c >= nt) {
-            out_of_range = true;
-            continue;
-        }
+    auto term = [&](double (&A)[kNumSums], int64_t i, int64_t c) {
         const T* a = src_cov + 9 * i;
         const T* b = tgt_cov + 9 * c;
         const double vs[3] = {(double)src[3 * i], (double)src[3 * i + 1],
@@ -707,9 +693,8 @@ GeneralizedAccumulateKernel(const T* __restrict__ src,
         const double ct[6] = {(double)b[0], (double)b[1], (double)b[2],
                               (double)b[4], (double)b[5], (double)b[8]};
         AccumulateGeneralized<kRmse>(A, vs, cs, vt, ct, rot, rp);
-    }
-    if (out_of_range) atomicOr(bad, 1);
-    BlockReduceAndStore(A, partials);
+    };
+    GatherAccumulate<true>(corr, n, nt, bad, partials, term);
 }
 
 // {n,3,3} <-> its three {n,3} row tables: how a covariance attribute rides
@@ -752,13 +737,7 @@ ResidualSquaresKernel(const T* __restrict__ src, const T* __restrict__ tgt,
                       const T* __restrict__ tgt_n,
                       const int64_t* __restrict__ corr, int64_t n,
                       double* __restrict__ partials) {
-    double A[kNumSums];
-#pragma unroll
-    for (int k = 0; k < kNumSums; ++k) A[k] = 0;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        int64_t c = corr[i];
-        if (c == -1) continue;
+    auto term = [&](double (&A)[kNumSums], int64_t i, int64_t c) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             T e = src[3 * i + k] - tgt[3 * c + k];
@@ -766,8 +745,8 @@ ResidualSquaresKernel(const T* __restrict__ src, const T* __restrict__ tgt,
             A[0] += (double)(e * e);
         }
         A[1] += 1.0;
-    }
-    BlockReduceAndStore(A, partials);
+    };
+    GatherAccumulate<false>(corr, n, 0, nullptr, partials, term);
 }
 
 template <typename T>
@@ -775,17 +754,11 @@ __global__ void __launch_bounds__(kReduceBlock)
 P2PointAccumulateKernel(const T* __restrict__ src, const T* __restrict__ tgt,
                         const int64_t* __restrict__ corr, int64_t n,
                         double* __restrict__ partials) {
-    double A[kNumSums];
-#pragma unroll
-    for (int k = 0; k < kNumSums; ++k) A[k] = 0;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        int64_t c = corr[i];
-        if (c == -1) continue;
+    auto term = [&](double (&A)[kNumSums], int64_t i, int64_t c) {
         AccumulateP2Point<T>(A, src[3 * i + 0], src[3 * i + 1], src[3 * i + 2],
                              tgt[3 * c + 0], tgt[3 * c + 1], tgt[3 * c + 2]);
-    }
-    BlockReduceAndStore(A, partials);
+    };
+    GatherAccumulate<false>(corr, n, 0, nullptr, partials, term);
 }
 
 template <typename T>
@@ -793,17 +766,11 @@ __global__ void __launch_bounds__(kReduceBlock)
 InformationAccumulateKernel(const T* __restrict__ tgt,
                             const int64_t* __restrict__ corr, int64_t n,
                             double* __restrict__ partials) {
-    double A[kNumSums];
-#pragma unroll
-    for (int k = 0; k < kNumSums; ++k) A[k] = 0;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        int64_t c = corr[i];
-        if (c == -1) continue;
+    auto term = [&](double (&A)[kNumSums], int64_t i, int64_t c) {
         AccumulateInformation<T>(A, tgt[3 * c + 0], tgt[3 * c + 1],
                                  tgt[3 * c + 2]);
-    }
-    BlockReduceAndStore(A, partials);
+    };
+    GatherAccumulate<false>(corr, n, 0, nullptr, partials, term);
 }
 
 // TransformImpl.h:19-44
@@ -1362,9 +1329,17 @@ int ReduceGrid(int64_t n) {
     // and the final pass (a single workgroup, linear in the row count) reads
     // <= 512 partial rows.
     int64_t cap = (int64_t)kCUs * 2;
+    static_assert(kIcpPartialRows >= kCUs * 2, "rows of the driver's partials");
     if (g > cap) g = cap;
     if (g < 1) g = 1;
     return (int)g;
+}
+
+// f(T()) with T the element type of the C ABI's `dtype`.
+template <typename F>
+void DispatchFloat(int dtype, F&& f) {
+    if (dtype == O3DMI_F64) f(double());
+    else f(float());
 }
 
 // The frame of the gather-and-accumulate entry points: `launch(T(), partials,
@@ -1372,10 +1347,12 @@ int ReduceGrid(int64_t n) {
 // row of kNumSums partial sums per workgroup; the single-workgroup final pass
 // then sums the rows into out_dev[0..n_sums) (and / or a host mailbox,
 // mailbox.h). partials_dev: the caller's rows (>= ReduceGrid rows), NULL:
-// allocated here, stream-ordered.
+// allocated here, stream-ordered. bad_dev: the range check's device word of a
+// checked accumulate kernel (the final pass is then the checked one), else
+// NULL.
 template <typename Launch>
 int AccumulateAndReduce(int64_t n, int dtype, int n_sums, double* out_dev,
-                        double* partials_dev, double* mail_data,
+                        double* partials_dev, int* bad_dev, double* mail_data,
                         int* mail_flag, int mail_seq, o3dmi_stream_t stream,
                         Launch&& launch) {
     hipStream_t s = (hipStream_t)stream;
@@ -1385,15 +1362,65 @@ int AccumulateAndReduce(int64_t n, int dtype, int n_sums, double* out_dev,
         O3DMI_HIP_CHECK(hipMallocAsync((void**)&partials,
                                        sizeof(double) * (size_t)g * kNumSums,
                                        s));
-    if (dtype == O3DMI_F64) launch(double(), partials, g, s);
-    else launch(float(), partials, g, s);
-    hipLaunchKernelGGL(FinalReduceKernel, dim3(1), dim3(256), 0, s, partials, g,
-                       out_dev, n_sums, mail_data, mail_flag, mail_seq);
+    DispatchFloat(dtype, [&](auto t) { launch(t, partials, g, s); });
+    if (bad_dev)
+        hipLaunchKernelGGL(FinalReduceCheckedKernel, dim3(1), dim3(256), 0, s,
+                           partials, g, bad_dev, out_dev, n_sums, mail_data,
+                           mail_flag, mail_seq);
+    else
+        hipLaunchKernelGGL(FinalReduceKernel, dim3(1), dim3(256), 0, s,
+                           partials, g, out_dev, n_sums, mail_data, mail_flag,
+                           mail_seq);
     O3DMI_HIP_CHECK(hipGetLastError());
     if (!partials_dev) O3DMI_HIP_CHECK(hipFreeAsync(partials, s));
     return O3DMI_OK;
 }
 
+
+// DopplerAccumulateKernel's by-value parameters from the float64 arguments of
+// the C ABI, every one narrowed to the clouds' type T first.
+template <typename T>
+DopplerParams<T> MakeDopplerParams(const double* R_S_to_V9,
+                                   const double* r_v_to_s_in_V3,
+                                   const double* w_v_in_V3,
+                                   const double* v_v_in_V3, double period,
+                                   int reject_dynamic_outliers,
+                                   double doppler_outlier_threshold,
+                                   double lambda_doppler) {
+    DopplerParams<T> dp;
+    T w_v_in_V[3], v_v_in_V[3];
+    for (int k = 0; k < 9; ++k) dp.R_S_to_V[k] = (T)R_S_to_V9[k];
+    for (int k = 0; k < 3; ++k) {
+        dp.r_v_to_s_in_V[k] = (T)r_v_to_s_in_V3[k];
+        w_v_in_V[k] = (T)w_v_in_V3[k];
+        v_v_in_V[k] = (T)v_v_in_V3[k];
+    }
+    // PreComputeForDopplerICP (RegistrationImpl.h:525-541), in T:
+    // v_s_in_V = v_v_in_V + w_v_in_V x r_v_to_s_in_V, v_s_in_S = R v_s_in_V
+    const T* r = dp.r_v_to_s_in_V;
+    T v_s_in_V[3];
+    v_s_in_V[0] = w_v_in_V[1] * r[2] - w_v_in_V[2] * r[1];
+    v_s_in_V[1] = w_v_in_V[2] * r[0] - w_v_in_V[0] * r[2];
+    v_s_in_V[2] = w_v_in_V[0] * r[1] - w_v_in_V[1] * r[0];
+    v_s_in_V[0] += v_v_in_V[0];
+    v_s_in_V[1] += v_v_in_V[1];
+    v_s_in_V[2] += v_v_in_V[2];
+    const T* R = dp.R_S_to_V;
+    dp.v_s_in_S[0] = R[0] * v_s_in_V[0] + R[1] * v_s_in_V[1] +
+                     R[2] * v_s_in_V[2];
+    dp.v_s_in_S[1] = R[3] * v_s_in_V[0] + R[4] * v_s_in_V[1] +
+                     R[5] * v_s_in_V[2];
+    dp.v_s_in_S[2] = R[6] * v_s_in_V[0] + R[7] * v_s_in_V[1] +
+                     R[8] * v_s_in_V[2];
+    // ComputePoseDopplerICPCPU, RegistrationCPU.cpp:454-458: the square
+    // roots are float64, then narrowed; the division is in T
+    dp.sqrt_lambda_geometric = (T)std::sqrt(1.0 - (T)lambda_doppler);
+    dp.sqrt_lambda_doppler = (T)std::sqrt(lambda_doppler);
+    dp.sqrt_lambda_doppler_by_dt = dp.sqrt_lambda_doppler / (T)period;
+    dp.doppler_outlier_threshold = (T)doppler_outlier_threshold;
+    dp.reject_dynamic_outliers = reject_dynamic_outliers ? 1 : 0;
+    return dp;
+}
 
 // A seam with a range check: the zeroed device word, the posted work, and the
 // wait for the verdict, which is the call's status.
@@ -1448,7 +1475,8 @@ int o3dmi_icp_p2plane_accumulate(const void* src_dev, const void* tgt_dev,
     RobustParams rp = MakeRobust(robust_kernel, scaling_parameter,
                                  shape_parameter);
     return AccumulateAndReduce(
-            n, dtype, 29, sums29_dev, nullptr, nullptr, nullptr, 0, stream,
+            n, dtype, 29, sums29_dev, nullptr, nullptr, nullptr, nullptr, 0,
+            stream,
             [&](auto t, double* partials, int g, hipStream_t s) {
                 using T = decltype(t);
                 hipLaunchKernelGGL(P2PlaneAccumulateKernel<T>, dim3(g),
@@ -1469,7 +1497,8 @@ int o3dmi_icp_residual_squares(const void* src_dev, const void* tgt_dev,
     O3DMI_REQUIRE(dtype == O3DMI_F32 || dtype == O3DMI_F64,
                   "points must be Float32 or Float64");
     return AccumulateAndReduce(
-            n, dtype, 2, sums2_dev, nullptr, nullptr, nullptr, 0, stream,
+            n, dtype, 2, sums2_dev, nullptr, nullptr, nullptr, nullptr, 0,
+            stream,
             [&](auto t, double* partials, int g, hipStream_t s) {
                 using T = decltype(t);
 #define O3DMI_RESID(P)                                                         \
@@ -1491,7 +1520,8 @@ int o3dmi_icp_p2point_accumulate(const void* src_dev, const void* tgt_dev,
     O3DMI_REQUIRE(dtype == O3DMI_F32 || dtype == O3DMI_F64,
                   "points must be Float32 or Float64");
     return AccumulateAndReduce(
-            n, dtype, 16, sums16_dev, nullptr, nullptr, nullptr, 0, stream,
+            n, dtype, 16, sums16_dev, nullptr, nullptr, nullptr, nullptr, 0,
+            stream,
             [&](auto t, double* partials, int g, hipStream_t s) {
                 using T = decltype(t);
                 hipLaunchKernelGGL(P2PointAccumulateKernel<T>, dim3(g),
@@ -1525,8 +1555,8 @@ int o3dmi_icp_colored_accumulate_post(
     const double slg = std::sqrt(lambda_geometric);
     const double slp = std::sqrt(1.0 - lambda_geometric);
     return AccumulateAndReduce(
-            n, dtype, 29, sums29_dev, partials_dev, mail_data, mail_flag,
-            mail_seq, stream,
+            n, dtype, 29, sums29_dev, partials_dev, nullptr, mail_data,
+            mail_flag, mail_seq, stream,
             [&](auto t, double* partials, int g, hipStream_t s) {
                 using T = decltype(t);
                 hipLaunchKernelGGL(ColoredAccumulateKernel<T>, dim3(g),
@@ -1599,62 +1629,22 @@ int o3dmi_icp_doppler_accumulate_post(
                                         geometric_shape);
     const RobustParams rpd = MakeRobust(doppler_kernel, doppler_scaling,
                                         doppler_shape);
-    hipStream_t s = (hipStream_t)stream;
-    const int g = ReduceGrid(n);
-    double* partials = partials_dev;
-    if (!partials)
-        O3DMI_HIP_CHECK(hipMallocAsync((void**)&partials,
-                                       sizeof(double) * (size_t)g * kNumSums,
-                                       s));
-    auto launch = [&](auto tag) {
-        using T = decltype(tag);
-        DopplerParams<T> dp;
-        T w_v_in_V[3], v_v_in_V[3];
-        for (int k = 0; k < 9; ++k) dp.R_S_to_V[k] = (T)R_S_to_V9[k];
-        for (int k = 0; k < 3; ++k) {
-            dp.r_v_to_s_in_V[k] = (T)r_v_to_s_in_V3[k];
-            w_v_in_V[k] = (T)w_v_in_V3[k];
-            v_v_in_V[k] = (T)v_v_in_V3[k];
-        }
-        // PreComputeForDopplerICP (RegistrationImpl.h:525-541), in T:
-        // v_s_in_V = v_v_in_V + w_v_in_V x r_v_to_s_in_V, v_s_in_S = R v_s_in_V
-        const T* r = dp.r_v_to_s_in_V;
-        T v_s_in_V[3];
-        v_s_in_V[0] = w_v_in_V[1] * r[2] - w_v_in_V[2] * r[1];
-        v_s_in_V[1] = w_v_in_V[2] * r[0] - w_v_in_V[0] * r[2];
-        v_s_in_V[2] = w_v_in_V[0] * r[1] - w_v_in_V[1] * r[0];
-        v_s_in_V[0] += v_v_in_V[0];
-        v_s_in_V[1] += v_v_in_V[1];
-        v_s_in_V[2] += v_v_in_V[2];
-        const T* R = dp.R_S_to_V;
-        dp.v_s_in_S[0] = R[0] * v_s_in_V[0] + R[1] * v_s_in_V[1] +
-                         R[2] * v_s_in_V[2];
-        dp.v_s_in_S[1] = R[3] * v_s_in_V[0] + R[4] * v_s_in_V[1] +
-                         R[5] * v_s_in_V[2];
-        dp.v_s_in_S[2] = R[6] * v_s_in_V[0] + R[7] * v_s_in_V[1] +
-                         R[8] * v_s_in_V[2];
-        // ComputePoseDopplerICPCPU, RegistrationCPU.cpp:454-458: the square
-        // roots are float64, then narrowed; the division is in T
-        dp.sqrt_lambda_geometric = (T)std::sqrt(1.0 - (T)lambda_doppler);
-        dp.sqrt_lambda_doppler = (T)std::sqrt(lambda_doppler);
-        dp.sqrt_lambda_doppler_by_dt = dp.sqrt_lambda_doppler / (T)period;
-        dp.doppler_outlier_threshold = (T)doppler_outlier_threshold;
-        dp.reject_dynamic_outliers = reject_dynamic_outliers ? 1 : 0;
-        hipLaunchKernelGGL(DopplerAccumulateKernel<T>, dim3(g),
-                           dim3(kReduceBlock), 0, s, (const T*)src_dev,
-                           (const T*)src_dopplers_dev,
-                           (const T*)src_directions_dev, (const T*)tgt_dev,
-                           (const T*)tgt_normals_dev, corr_dev, n, nt, dp, rpg,
-                           rpd, partials, bad_dev);
-    };
-    if (dtype == O3DMI_F64) launch(double());
-    else launch(float());
-    hipLaunchKernelGGL(FinalReduceCheckedKernel, dim3(1), dim3(256), 0, s,
-                       partials, g, bad_dev, sums29_dev, 29, mail_data,
-                       mail_flag, mail_seq);
-    O3DMI_HIP_CHECK(hipGetLastError());
-    if (!partials_dev) O3DMI_HIP_CHECK(hipFreeAsync(partials, s));
-    return O3DMI_OK;
+    return AccumulateAndReduce(
+            n, dtype, 29, sums29_dev, partials_dev, bad_dev, mail_data,
+            mail_flag, mail_seq, stream,
+            [&](auto t, double* partials, int g, hipStream_t s) {
+                using T = decltype(t);
+                hipLaunchKernelGGL(
+                        DopplerAccumulateKernel<T>, dim3(g), dim3(kReduceBlock),
+                        0, s, (const T*)src_dev, (const T*)src_dopplers_dev,
+                        (const T*)src_directions_dev, (const T*)tgt_dev,
+                        (const T*)tgt_normals_dev, corr_dev, n, nt,
+                        MakeDopplerParams<T>(
+                                R_S_to_V9, r_v_to_s_in_V3, w_v_in_V3, v_v_in_V3,
+                                period, reject_dynamic_outliers,
+                                doppler_outlier_threshold, lambda_doppler),
+                        rpg, rpd, partials, bad_dev);
+            });
 }
 
 int o3dmi_icp_doppler_accumulate(
@@ -1687,14 +1677,12 @@ int o3dmi_internal_pad_column(const void* in_dev, int64_t n, int dtype,
                               void* out3_dev, o3dmi_stream_t stream) {
     O3DMI_REQUIRE(in_dev && out3_dev && n > 0, "null argument");
     dim3 grid(GridFor(n, kBlock)), block(kBlock);
-    if (dtype == O3DMI_F64)
-        hipLaunchKernelGGL(PadColumnKernel<double>, grid, block, 0,
-                           (hipStream_t)stream, (const double*)in_dev, n,
-                           (double*)out3_dev);
-    else
-        hipLaunchKernelGGL(PadColumnKernel<float>, grid, block, 0,
-                           (hipStream_t)stream, (const float*)in_dev, n,
-                           (float*)out3_dev);
+    DispatchFloat(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(PadColumnKernel<T>, grid, block, 0,
+                           (hipStream_t)stream, (const T*)in_dev, n,
+                           (T*)out3_dev);
+    });
     O3DMI_HIP_CHECK(hipGetLastError());
     return O3DMI_OK;
 }
@@ -1702,14 +1690,12 @@ int o3dmi_internal_take_column(const void* in3_dev, int64_t n, int dtype,
                                void* out_dev, o3dmi_stream_t stream) {
     O3DMI_REQUIRE(in3_dev && out_dev && n > 0, "null argument");
     dim3 grid(GridFor(n, kBlock)), block(kBlock);
-    if (dtype == O3DMI_F64)
-        hipLaunchKernelGGL(TakeColumnKernel<double>, grid, block, 0,
-                           (hipStream_t)stream, (const double*)in3_dev, n,
-                           (double*)out_dev);
-    else
-        hipLaunchKernelGGL(TakeColumnKernel<float>, grid, block, 0,
-                           (hipStream_t)stream, (const float*)in3_dev, n,
-                           (float*)out_dev);
+    DispatchFloat(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(TakeColumnKernel<T>, grid, block, 0,
+                           (hipStream_t)stream, (const T*)in3_dev, n,
+                           (T*)out_dev);
+    });
     O3DMI_HIP_CHECK(hipGetLastError());
     return O3DMI_OK;
 }
@@ -1738,34 +1724,23 @@ int o3dmi_icp_generalized_accumulate_post(
     GicpRotation rot;
     for (int k = 0; k < 9; ++k)
         rot.R[k] = R_source9 && !rmse_form ? R_source9[k] : (k % 4 == 0);
-    hipStream_t s = (hipStream_t)stream;
-    const int g = ReduceGrid(n);
-    double* partials = partials_dev;
-    if (!partials)
-        O3DMI_HIP_CHECK(hipMallocAsync((void**)&partials,
-                                       sizeof(double) * (size_t)g * kNumSums,
-                                       s));
-    auto launch = [&](auto tag, auto rmse) {
-        using T = decltype(tag);
-        hipLaunchKernelGGL((GeneralizedAccumulateKernel<T, decltype(rmse)::value>),
-                           dim3(g), dim3(kReduceBlock), 0, s, (const T*)src_dev,
-                           (const T*)src_covariances_dev, (const T*)tgt_dev,
-                           (const T*)tgt_covariances_dev, corr_dev, n, nt, rot,
-                           rp, partials, bad_dev);
-    };
-    if (dtype == O3DMI_F64) {
-        if (rmse_form) launch(double(), std::true_type());
-        else launch(double(), std::false_type());
-    } else {
-        if (rmse_form) launch(float(), std::true_type());
-        else launch(float(), std::false_type());
-    }
-    hipLaunchKernelGGL(FinalReduceCheckedKernel, dim3(1), dim3(256), 0, s,
-                       partials, g, bad_dev, sums32_dev, 32, mail_data,
-                       mail_flag, mail_seq);
-    O3DMI_HIP_CHECK(hipGetLastError());
-    if (!partials_dev) O3DMI_HIP_CHECK(hipFreeAsync(partials, s));
-    return O3DMI_OK;
+    return AccumulateAndReduce(
+            n, dtype, 32, sums32_dev, partials_dev, bad_dev, mail_data,
+            mail_flag, mail_seq, stream,
+            [&](auto t, double* partials, int g, hipStream_t s) {
+                using T = decltype(t);
+                auto launch = [&](auto rmse) {
+                    constexpr bool kRmse = decltype(rmse)::value;
+                    hipLaunchKernelGGL(
+                            (GeneralizedAccumulateKernel<T, kRmse>), dim3(g),
+                            dim3(kReduceBlock), 0, s, (const T*)src_dev,
+                            (const T*)src_covariances_dev, (const T*)tgt_dev,
+                            (const T*)tgt_covariances_dev, corr_dev, n, nt, rot,
+                            rp, partials, bad_dev);
+                };
+                if (rmse_form) launch(std::true_type());
+                else launch(std::false_type());
+            });
 }
 
 int o3dmi_icp_generalized_accumulate(
@@ -1790,16 +1765,12 @@ int o3dmi_internal_split_rows3(const void* in9_dev, int64_t n, int dtype,
     O3DMI_REQUIRE(in9_dev && row0_dev && row1_dev && row2_dev && n > 0,
                   "null argument");
     dim3 grid(GridFor(3 * n, kBlock)), block(kBlock);
-    if (dtype == O3DMI_F64)
-        hipLaunchKernelGGL(SplitRows3Kernel<double>, grid, block, 0,
-                           (hipStream_t)stream, (const double*)in9_dev, n,
-                           (double*)row0_dev, (double*)row1_dev,
-                           (double*)row2_dev);
-    else
-        hipLaunchKernelGGL(SplitRows3Kernel<float>, grid, block, 0,
-                           (hipStream_t)stream, (const float*)in9_dev, n,
-                           (float*)row0_dev, (float*)row1_dev,
-                           (float*)row2_dev);
+    DispatchFloat(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(SplitRows3Kernel<T>, grid, block, 0,
+                           (hipStream_t)stream, (const T*)in9_dev, n,
+                           (T*)row0_dev, (T*)row1_dev, (T*)row2_dev);
+    });
     O3DMI_HIP_CHECK(hipGetLastError());
     return O3DMI_OK;
 }
@@ -1809,16 +1780,13 @@ int o3dmi_internal_join_rows3(const void* row0_dev, const void* row1_dev,
     O3DMI_REQUIRE(row0_dev && row1_dev && row2_dev && out9_dev && n > 0,
                   "null argument");
     dim3 grid(GridFor(3 * n, kBlock)), block(kBlock);
-    if (dtype == O3DMI_F64)
-        hipLaunchKernelGGL(JoinRows3Kernel<double>, grid, block, 0,
-                           (hipStream_t)stream, (const double*)row0_dev,
-                           (const double*)row1_dev, (const double*)row2_dev, n,
-                           (double*)out9_dev);
-    else
-        hipLaunchKernelGGL(JoinRows3Kernel<float>, grid, block, 0,
-                           (hipStream_t)stream, (const float*)row0_dev,
-                           (const float*)row1_dev, (const float*)row2_dev, n,
-                           (float*)out9_dev);
+    DispatchFloat(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(JoinRows3Kernel<T>, grid, block, 0,
+                           (hipStream_t)stream, (const T*)row0_dev,
+                           (const T*)row1_dev, (const T*)row2_dev, n,
+                           (T*)out9_dev);
+    });
     O3DMI_HIP_CHECK(hipGetLastError());
     return O3DMI_OK;
 }
@@ -1842,8 +1810,8 @@ int o3dmi_icp_symmetric_accumulate_post(
     RobustParams rp = MakeRobust(robust_kernel, scaling_parameter,
                                  shape_parameter);
     return AccumulateAndReduce(
-            n, dtype, 29, sums29_dev, partials_dev, mail_data, mail_flag,
-            mail_seq, stream,
+            n, dtype, 29, sums29_dev, partials_dev, nullptr, mail_data,
+            mail_flag, mail_seq, stream,
             [&](auto t, double* partials, int g, hipStream_t s) {
                 using T = decltype(t);
                 Means3<T> m;
@@ -1880,7 +1848,8 @@ int o3dmi_icp_information_accumulate(const void* tgt_dev,
     O3DMI_REQUIRE(dtype == O3DMI_F32 || dtype == O3DMI_F64,
                   "points must be Float32 or Float64");
     return AccumulateAndReduce(
-            n, dtype, 21, sums21_dev, nullptr, nullptr, nullptr, 0, stream,
+            n, dtype, 21, sums21_dev, nullptr, nullptr, nullptr, nullptr, 0,
+            stream,
             [&](auto t, double* partials, int g, hipStream_t s) {
                 using T = decltype(t);
                 hipLaunchKernelGGL(InformationAccumulateKernel<T>, dim3(g),
@@ -2036,17 +2005,13 @@ int o3dmi_transform_points(const double* transformation, void* points_dev,
     if (n == 0) return O3DMI_OK;
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(GridFor(n, kBlock)), block(kBlock);
-    if (dtype == O3DMI_F64) {
-        Mat4<double> t;
-        for (int i = 0; i < 16; ++i) t.m[i] = transformation[i];
-        hipLaunchKernelGGL(TransformPointsKernel<double>, grid, block, 0, s, t,
-                           (double*)points_dev, n);
-    } else {
-        Mat4<float> t;
-        for (int i = 0; i < 16; ++i) t.m[i] = (float)transformation[i];
-        hipLaunchKernelGGL(TransformPointsKernel<float>, grid, block, 0, s, t,
-                           (float*)points_dev, n);
-    }
+    DispatchFloat(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        Mat4<T> t;
+        for (int i = 0; i < 16; ++i) t.m[i] = (T)transformation[i];
+        hipLaunchKernelGGL(TransformPointsKernel<T>, grid, block, 0, s, t,
+                           (T*)points_dev, n);
+    });
     O3DMI_HIP_CHECK(hipGetLastError());
     return O3DMI_OK;
 }
@@ -2059,17 +2024,13 @@ int o3dmi_transform_normals(const double* transformation, void* normals_dev,
     if (n == 0) return O3DMI_OK;
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(GridFor(n, kBlock)), block(kBlock);
-    if (dtype == O3DMI_F64) {
-        Mat4<double> t;
-        for (int i = 0; i < 16; ++i) t.m[i] = transformation[i];
-        hipLaunchKernelGGL(TransformNormalsKernel<double>, grid, block, 0, s,
-                           t, (double*)normals_dev, n);
-    } else {
-        Mat4<float> t;
-        for (int i = 0; i < 16; ++i) t.m[i] = (float)transformation[i];
-        hipLaunchKernelGGL(TransformNormalsKernel<float>, grid, block, 0, s, t,
-                           (float*)normals_dev, n);
-    }
+    DispatchFloat(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        Mat4<T> t;
+        for (int i = 0; i < 16; ++i) t.m[i] = (T)transformation[i];
+        hipLaunchKernelGGL(TransformNormalsKernel<T>, grid, block, 0, s, t,
+                           (T*)normals_dev, n);
+    });
     O3DMI_HIP_CHECK(hipGetLastError());
     return O3DMI_OK;
 }

@@ -378,6 +378,14 @@ int o3dmi_vbg_extract_mesh(o3dmi_hash_t* block_hash, const int32_t* indices_dev,
                            o3dmi_stream_t stream);
 /* Ascending in-place sort of int32 indices (synchronises). */
 int o3dmi_sort_indices(int32_t* indices_dev, int64_t n, o3dmi_stream_t stream);
+/* Stable ascending sort of n (key, value) pairs of uint32 by the low key_bits
+ * bits of the key, in place from the caller's view: pairs whose keys agree in
+ * those bits keep their input order, on every run (a least-significant-digit
+ * radix sort whose ranks follow the index, never the arrival order; scratch
+ * comes from the pool). The bits above key_bits are carried along and ignored.
+ * n < 2^31, key_bits in [0, 32] (0: nothing moves). Synchronises. */
+int o3dmi_sort_pairs_u32(uint32_t* keys_dev, uint32_t* vals_dev, int64_t n,
+                         int key_bits, o3dmi_stream_t stream);
 
 /* UnprojectCUDA (t/geometry/kernel/PointCloudImpl.h:42-143): strided depth ->
  * compacted world points. points_dev holds (rows/stride)*(cols/stride) x 3

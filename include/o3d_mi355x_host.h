@@ -1874,6 +1874,145 @@ const char* o3dmi_vbg_attribute_name(const o3dmi_vbg_t* g, int i);
 float o3dmi_vbg_voxel_size(const o3dmi_vbg_t* g);
 int64_t o3dmi_vbg_block_resolution(const o3dmi_vbg_t* g);
 
+/* ---- TriangleMesh operators --------------------------------------------------
+ * (t/geometry/kernel/TriangleMeshImpl.h, TriangleMeshCPU.cpp:22-56; the host
+ * loops of t/geometry/TriangleMesh.cpp:1221-1452 and 1826-1864; legacy
+ * geometry/TriangleMesh.cpp:1459-1528.) A mesh is positions {v,3} in `dtype`
+ * (O3DMI_F32 / O3DMI_F64) and triangles {m,3} in `index_dtype` (O3DMI_I32 /
+ * O3DMI_I64, narrowed on load). v < 2^31, m <= 2^29. Common rules:
+ *  - EVERY triangle index is range-checked on the device before anything is
+ *    written: an index outside [0, v) is O3DMI_ERR_INVALID_ARG with every
+ *    output untouched (upstream reads out of bounds).
+ *  - m == 0 or v == 0 is legal wherever upstream returns an empty or zero
+ *    result.
+ *  - Arithmetic is in the position dtype without contraction.
+ *  - A NULL pointer where one is needed, a dtype outside the two, v or m out
+ *    of range: O3DMI_ERR_INVALID_ARG before anything is allocated.
+ * All synchronise. */
+
+/* ComputeTriangleNormalsCPU / CUDA: normals_out {m,3} = cross_3x1(p2 - p1,
+ * p3 - p1) (core/linalg/kernel/Matrix.h:63-73), NOT normalised: normalising
+ * is a second call, as upstream. */
+int o3dmi_trianglemesh_compute_triangle_normals(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* triangles_dev, int64_t m, int index_dtype,
+        void* normals_out_dev, o3dmi_stream_t stream);
+
+/* ComputeTriangleAreasCPU / CUDA: areas_out {m} = 0.5 * sqrt((t0 t0 + t1 t1) +
+ * t2 t2) of the same cross product. */
+int o3dmi_trianglemesh_compute_triangle_areas(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* triangles_dev, int64_t m, int index_dtype,
+        void* areas_out_dev, o3dmi_stream_t stream);
+
+/* TriangleMesh::GetSurfaceArea: *area_out = the float64 sum of those areas in
+ * the fixed tree of o3dmi_pointcloud_compute_metrics (runs of 512 in index
+ * order, the run sums likewise). Upstream: Sum({0}) in the dtype, order
+ * unspecified. m == 0 gives 0. */
+int o3dmi_trianglemesh_surface_area(const void* positions_dev, int64_t v,
+                                    int dtype, const void* triangles_dev,
+                                    int64_t m, int index_dtype,
+                                    double* area_out, o3dmi_stream_t stream);
+
+/* NormalizeNormalsCPU / CUDA (TriangleMeshImpl.h:40-69), in place on
+ * normals_dev {n,3}: norm = sqrt((x x + y y) + z z); the row is divided when
+ * norm > 0. THE MESH RULE, NOT THE POINTCLOUD ONE: a row whose x is NaN is
+ * left exactly as it is (upstream assigns (0, 0, 1) to locals it never
+ * stores). */
+int o3dmi_trianglemesh_normalize_normals(void* normals_dev, int64_t n,
+                                         int dtype, o3dmi_stream_t stream);
+
+/* ComputeVertexNormalsCPU bit for bit: component c of vertex u of
+ * vertex_normals_out {v,3} is ((0 + n_a[c]) + n_b[c]) + ... in `dtype` over
+ * the corners 3 t + k that name u, in ascending corner order (a triangle that
+ * lists a vertex twice adds twice; an unreferenced vertex is +0). No float
+ * atomics: the corners are stable-sorted by vertex and every vertex's list is
+ * walked in order. The same bits on every run. */
+int o3dmi_trianglemesh_compute_vertex_normals(
+        const void* triangles_dev, int64_t m, int index_dtype,
+        const void* triangle_normals_dev, int dtype, int64_t v,
+        void* vertex_normals_out_dev, o3dmi_stream_t stream);
+
+/* TriangleMesh::ComputeVertexNormals(normalized): triangle normals (not
+ * normalised), the sum above, then o3dmi_trianglemesh_normalize_normals when
+ * `normalized`. triangle_normals_out_dev {m,3} is optional (NULL: pooled
+ * scratch). */
+int o3dmi_trianglemesh_vertex_normals(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* triangles_dev, int64_t m, int index_dtype,
+        void* triangle_normals_out_dev, void* vertex_normals_out_dev,
+        int normalized, o3dmi_stream_t stream);
+
+/* TriangleMesh::GetNonManifoldEdges. Edge slot 3 t + k is the ordered pair
+ * (lo, hi) of (v_k, v_(k+1)%3); an edge's multiplicity is its number of slots
+ * (upstream's GetEdgeToTrianglesMap: a triangle (6,6,7) gives (6,6) once and
+ * (6,7) twice). Emits the edges of multiplicity > 2 (allow_boundary_edges) or
+ * != 2 into edges_out_dev {capacity,2} in the index dtype, in ASCENDING
+ * (lo, hi) ORDER (upstream: unordered_map iteration order), and their number
+ * into *n_edges_out. capacity < 0 only counts; 0 <= capacity < the number is
+ * O3DMI_ERR_CAPACITY with nothing written (*n_edges_out is still set). */
+int o3dmi_trianglemesh_get_non_manifold_edges(
+        const void* triangles_dev, int64_t m, int index_dtype, int64_t v,
+        int allow_boundary_edges, void* edges_out_dev, int64_t capacity,
+        int64_t* n_edges_out, o3dmi_stream_t stream);
+
+/* Legacy TriangleMesh::ClusterConnectedTriangles. Two triangles are adjacent
+ * when they share an edge of the table above (a shared vertex alone does not
+ * connect them); clusters are the connected components, NUMBERED BY THEIR
+ * LOWEST TRIANGLE INDEX, which is the order in which the legacy loop meets
+ * their seeds: labels_out_dev int32 {m} equals upstream's.
+ * cluster_n_triangles_out_dev int64 {capacity} and cluster_area_out_dev
+ * float64 {capacity} are optional (NULL). *n_clusters_out is always set;
+ * capacity < 0 only counts and 0 <= capacity < the count is
+ * O3DMI_ERR_CAPACITY, both with nothing written, labels_out_dev included (a
+ * caller who wants the labels alone passes capacity = m). A triangle's area is
+ * 0.5 |(p0 - p1) x (p0 - p2)| in float64 from the positions widened (legacy
+ * is float64
+ * throughout); a cluster's area adds its triangles in ascending triangle
+ * index, runs of 512 members first, the run sums in order then (upstream:
+ * BFS order; equal to rounding). positions_dev may be NULL when no area is
+ * wanted. m == 0: zero clusters, O3DMI_OK. */
+int o3dmi_trianglemesh_cluster_connected_triangles(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* triangles_dev, int64_t m, int index_dtype,
+        int32_t* labels_out_dev, int64_t* n_clusters_out,
+        int64_t* cluster_n_triangles_out_dev, double* cluster_area_out_dev,
+        int64_t capacity, o3dmi_stream_t stream);
+
+/* The selections share one chain: a vertex mask, its exclusive prefix sum (the
+ * new index of a kept vertex: upstream's UpdateTriangleIndicesByVertexMask) and
+ * the remap of the kept triangles, which keep their input order; kept
+ * vertices keep ascending original index. Masks are uint8 {v} / {m} holding
+ * 0 / 1 and go to o3dmi_pointcloud_select_by_mask for the attribute rows of
+ * the vertices and of the triangles. triangles_out_dev holds m rows in the
+ * index dtype. */
+
+/* TriangleMesh::SelectFacesByMask: keeps the triangles with tri_mask_dev != 0
+ * and the vertices they name. */
+int o3dmi_trianglemesh_select_faces_by_mask(
+        const void* triangles_dev, int64_t m, int index_dtype, int64_t v,
+        const uint8_t* tri_mask_dev, uint8_t* vertex_mask_out_dev,
+        void* triangles_out_dev, int64_t* n_triangles_out,
+        int64_t* n_vertices_out, o3dmi_stream_t stream);
+
+/* TriangleMesh::SelectByIndex: keeps the vertices named by indices_dev int64
+ * {k} (duplicates count once; an index outside [0, v) is ignored and counted
+ * in *n_ignored_out, as upstream warns and continues) and the triangles all
+ * three of whose vertices are kept (tri_mask_out_dev {m}). */
+int o3dmi_trianglemesh_select_by_index(
+        const void* triangles_dev, int64_t m, int index_dtype, int64_t v,
+        const int64_t* indices_dev, int64_t k, uint8_t* vertex_mask_out_dev,
+        uint8_t* tri_mask_out_dev, void* triangles_out_dev,
+        int64_t* n_triangles_out, int64_t* n_vertices_out,
+        int64_t* n_ignored_out, o3dmi_stream_t stream);
+
+/* TriangleMesh::RemoveUnreferencedVertices: SelectFacesByMask with every
+ * triangle kept. */
+int o3dmi_trianglemesh_remove_unreferenced_vertices(
+        const void* triangles_dev, int64_t m, int index_dtype, int64_t v,
+        uint8_t* vertex_mask_out_dev, void* triangles_out_dev,
+        int64_t* n_vertices_out, o3dmi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@
 #include "open3d/core/nns/NeighborSearchCommon.h"
 #include "open3d/t/geometry/kernel/PointCloud.h"
 #include "open3d/t/geometry/kernel/Transform.h"
+#include "open3d/t/geometry/kernel/TriangleMesh.h"
 #include "open3d/t/geometry/kernel/VoxelBlockGrid.h"
 #include "open3d/t/pipelines/kernel/RegistrationImpl.h"
 #include "open3d/t/pipelines/registration/RobustKernel.h"
@@ -547,6 +548,59 @@ core::Tensor ComputeMetricsHIP(const core::Tensor& points1,
     return core::Tensor(values, {n_values}, core::Float32);
 }
 }  // namespace pointcloud
+
+// 5e. beside NormalizeNormalsCUDA ... ComputeTriangleAreasCUDA
+//    (t/geometry/kernel/TriangleMesh.h:60-73; the dispatchers in
+//    t/geometry/TriangleMesh.cpp:198-360 gain `else if (IsHIP()) {
+//    kernel::trianglemesh::...HIP(...); }`). The outputs are the tensors the
+//    dispatchers allocate; ComputeVertexNormals' arrives zeroed and is
+//    overwritten with the sum of upstream's CPU loop.
+namespace trianglemesh {
+void NormalizeNormalsHIP(core::Tensor& normals) {
+    O3DMI_CALL(o3dmi_trianglemesh_normalize_normals(
+            normals.GetDataPtr(), normals.GetLength(),
+            core::ToO3dmi(normals.GetDtype()), core::HipStream()));
+}
+void ComputeTriangleNormalsHIP(const core::Tensor& vertices,
+                               const core::Tensor& triangles,
+                               core::Tensor& normals) {
+    O3DMI_CALL(o3dmi_trianglemesh_compute_triangle_normals(
+            vertices.GetDataPtr(), vertices.GetLength(),
+            core::ToO3dmi(normals.GetDtype()), triangles.GetDataPtr(),
+            triangles.GetLength(), core::ToO3dmi(triangles.GetDtype()),
+            normals.GetDataPtr(), core::HipStream()));
+}
+void ComputeVertexNormalsHIP(const core::Tensor& triangles,
+                             const core::Tensor& triangle_normals,
+                             core::Tensor& vertex_normals) {
+    O3DMI_CALL(o3dmi_trianglemesh_compute_vertex_normals(
+            triangles.GetDataPtr(), triangles.GetLength(),
+            core::ToO3dmi(triangles.GetDtype()), triangle_normals.GetDataPtr(),
+            core::ToO3dmi(vertex_normals.GetDtype()),
+            vertex_normals.GetLength(), vertex_normals.GetDataPtr(),
+            core::HipStream()));
+}
+void ComputeTriangleAreasHIP(const core::Tensor& vertices,
+                             const core::Tensor& triangles,
+                             core::Tensor& triangle_areas) {
+    O3DMI_CALL(o3dmi_trianglemesh_compute_triangle_areas(
+            vertices.GetDataPtr(), vertices.GetLength(),
+            core::ToO3dmi(triangle_areas.GetDtype()), triangles.GetDataPtr(),
+            triangles.GetLength(), core::ToO3dmi(triangles.GetDtype()),
+            triangle_areas.GetDataPtr(), core::HipStream()));
+}
+static_assert(
+        std::is_same<decltype(&NormalizeNormalsHIP),
+                     decltype(&NormalizeNormalsCPU)>::value &&
+                std::is_same<decltype(&ComputeTriangleNormalsHIP),
+                             decltype(&ComputeTriangleNormalsCPU)>::value &&
+                std::is_same<decltype(&ComputeVertexNormalsHIP),
+                             decltype(&ComputeVertexNormalsCPU)>::value &&
+                std::is_same<decltype(&ComputeTriangleAreasHIP),
+                             decltype(&ComputeTriangleAreasCPU)>::value,
+        "the TriangleMesh ...HIP functions have the dispatchers' per-device "
+        "signatures");
+}  // namespace trianglemesh
 }  // namespace kernel
 }  // namespace geometry
 

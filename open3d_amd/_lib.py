@@ -578,6 +578,34 @@ PROTOTYPES.update({
                                     C.POINTER(_i64), _vp]),
     "o3dmi_vbg_merge_frame_sharded": (_i32, [_vp, _vp, _vp]),
     "o3dmi_vbg_allgather_owned_blocks": (_i32, [_vp, _vp, _vp]),
+    # include/o3d_mi355x.h
+    "o3dmi_sort_pairs_u32": (_i32, [_vp, _vp, _i64, _i32, _vp]),
+    # TriangleMesh operators: (positions, v, dtype, triangles, m, index_dtype,
+    # ...) wherever a call takes positions
+    "o3dmi_trianglemesh_compute_triangle_normals": (
+        _i32, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp]),
+    "o3dmi_trianglemesh_compute_triangle_areas": (
+        _i32, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp]),
+    "o3dmi_trianglemesh_surface_area": (
+        _i32, [_vp, _i64, _i32, _vp, _i64, _i32, _dp, _vp]),
+    "o3dmi_trianglemesh_normalize_normals": (_i32, [_vp, _i64, _i32, _vp]),
+    "o3dmi_trianglemesh_compute_vertex_normals": (
+        _i32, [_vp, _i64, _i32, _vp, _i32, _i64, _vp, _vp]),
+    "o3dmi_trianglemesh_vertex_normals": (
+        _i32, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _i32, _vp]),
+    "o3dmi_trianglemesh_get_non_manifold_edges": (
+        _i32, [_vp, _i64, _i32, _i64, _i32, _vp, _i64, C.POINTER(_i64), _vp]),
+    "o3dmi_trianglemesh_cluster_connected_triangles": (
+        _i32, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, C.POINTER(_i64), _vp,
+               _vp, _i64, _vp]),
+    "o3dmi_trianglemesh_select_faces_by_mask": (
+        _i32, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, C.POINTER(_i64),
+               C.POINTER(_i64), _vp]),
+    "o3dmi_trianglemesh_select_by_index": (
+        _i32, [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _vp, _vp,
+               C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _vp]),
+    "o3dmi_trianglemesh_remove_unreferenced_vertices": (
+        _i32, [_vp, _i64, _i32, _i64, _vp, _vp, C.POINTER(_i64), _vp]),
 })
 
 # o3dmi_transport_t (include/o3d_mi355x_host.h): the caller-provided collectives

@@ -1,0 +1,284 @@
+"""Mirror of t::geometry::TriangleMesh's normal, area, selection and
+connectivity methods (t/geometry/TriangleMesh.cpp:198-404, 1221-1452,
+1826-1864) and of legacy ClusterConnectedTriangles (geometry/TriangleMesh.cpp:
+1459-1528) on the HIP backend.
+
+A mesh is the dict VoxelBlockGrid.extract_triangle_mesh returns: "positions"
+({V,3} Float32 or Float64) and "indices" ({M,3} Int32 or Int64) on the device,
+further vertex attributes under their own names ("normals", "colors", ...)
+and triangle attributes under a "triangle_" prefix ("triangle_normals",
+"triangle_areas", ...). Every function returns a new dict; the input is left
+as it was.
+"""
+import ctypes as C
+
+import torch
+
+from . import _lib
+from . import pointcloud as _pc
+from .core import TORCH_TO_O3DMI, require_cuda, stream
+
+TRIANGLE_PREFIX = "triangle_"
+
+
+def _positions(mesh):
+    if "positions" not in mesh:
+        raise ValueError('a mesh needs "positions"')
+    p = require_cuda(mesh["positions"], "positions")
+    if p.dim() != 2 or p.shape[1] != 3 or p.dtype not in (torch.float32,
+                                                          torch.float64):
+        raise ValueError("positions must be {V,3} Float32 or Float64")
+    return p
+
+
+def _indices(mesh, p):
+    t = mesh.get("indices")
+    if t is None:
+        return torch.empty((0, 3), dtype=torch.int64, device=p.device)
+    t = require_cuda(t, "indices")
+    if t.dim() != 2 or t.shape[1] != 3 or t.dtype not in (torch.int32,
+                                                          torch.int64):
+        raise ValueError("indices must be {M,3} Int32 or Int64")
+    return t
+
+
+def _mesh_args(mesh):
+    """-> (positions, indices, the six leading arguments of a mesh call)."""
+    p = _positions(mesh)
+    t = _indices(mesh, p)
+    return p, t, (_lib.ptr(p), p.shape[0], TORCH_TO_O3DMI[p.dtype],
+                  _lib.ptr(t), t.shape[0], TORCH_TO_O3DMI[t.dtype])
+
+
+def _index_args(p, t):
+    return (_lib.ptr(t), t.shape[0], TORCH_TO_O3DMI[t.dtype], p.shape[0])
+
+
+def _split(mesh):
+    """-> (vertex attributes, triangle attributes with "indices")."""
+    vertex, triangle = {}, {}
+    for name, value in mesh.items():
+        if name == "indices" or name.startswith(TRIANGLE_PREFIX):
+            triangle[name] = value
+        else:
+            vertex[name] = value
+    return vertex, triangle
+
+
+def _normalize(t):
+    if t.shape[0]:
+        _lib.check(_lib.lib().o3dmi_trianglemesh_normalize_normals(
+            _lib.ptr(t), t.shape[0], TORCH_TO_O3DMI[t.dtype], stream()),
+            "normalize_normals")
+    return t
+
+
+def normalize_normals(mesh):
+    """TriangleMesh::NormalizeNormals: the vertex and the triangle normals the
+    mesh has, by upstream's mesh rule (a row whose x is NaN stays as it is)."""
+    out = dict(mesh)
+    for name in ("normals", TRIANGLE_PREFIX + "normals"):
+        if name in out:
+            out[name] = _normalize(
+                require_cuda(out[name], name).contiguous().clone())
+    return out
+
+
+def compute_triangle_normals(mesh, normalized=True):
+    """TriangleMesh::ComputeTriangleNormals -> mesh with "triangle_normals"
+    (and, when normalized, every normal of the mesh normalised, as
+    upstream)."""
+    p, t, args = _mesh_args(mesh)
+    out = dict(mesh)
+    if p.shape[0] == 0 or "indices" not in mesh:
+        return out
+    normals = torch.empty((t.shape[0], 3), dtype=p.dtype, device=p.device)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_compute_triangle_normals(
+        *args, _lib.ptr(normals), stream()), "compute_triangle_normals")
+    out[TRIANGLE_PREFIX + "normals"] = normals
+    return normalize_normals(out) if normalized else out
+
+
+def compute_vertex_normals(mesh, normalized=True):
+    """TriangleMesh::ComputeVertexNormals -> mesh with "triangle_normals" and
+    "normals": the sum of upstream's CPU loop, bit for bit."""
+    p, t, args = _mesh_args(mesh)
+    out = dict(mesh)
+    if p.shape[0] == 0 or "indices" not in mesh:
+        return out
+    tn = torch.empty((t.shape[0], 3), dtype=p.dtype, device=p.device)
+    vn = torch.empty((p.shape[0], 3), dtype=p.dtype, device=p.device)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_vertex_normals(
+        *args, _lib.ptr(tn), _lib.ptr(vn), 0, stream()),
+        "compute_vertex_normals")
+    out[TRIANGLE_PREFIX + "normals"] = tn
+    out["normals"] = vn
+    return normalize_normals(out) if normalized else out
+
+
+def _areas(mesh):
+    p, t, args = _mesh_args(mesh)
+    areas = torch.empty(t.shape[0], dtype=p.dtype, device=p.device)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_compute_triangle_areas(
+        *args, _lib.ptr(areas), stream()), "compute_triangle_areas")
+    return areas
+
+
+def compute_triangle_areas(mesh):
+    """TriangleMesh::ComputeTriangleAreas -> mesh with "triangle_areas" ({0}
+    for a mesh without triangles; areas the mesh already has are kept)."""
+    out = dict(mesh)
+    if _positions(mesh).shape[0] == 0 or TRIANGLE_PREFIX + "areas" in mesh:
+        return out
+    out[TRIANGLE_PREFIX + "areas"] = _areas(mesh)
+    return out
+
+
+def get_surface_area(mesh):
+    """TriangleMesh::GetSurfaceArea as a float64 sum in a fixed order."""
+    _, _, args = _mesh_args(mesh)
+    area = C.c_double(0)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_surface_area(
+        *args, C.byref(area), stream()), "get_surface_area")
+    return area.value
+
+
+def _select_rows(rows, mask8):
+    """Stable compaction of equally long attribute tensors by a uint8 mask
+    (o3dmi_pointcloud_select_by_mask, up to MAX_ATTRS attributes a launch)."""
+    names = list(rows)
+    n = mask8.shape[0]
+    out = {}
+    for g in range(0, len(names), _pc.MAX_ATTRS):
+        group = names[g:g + _pc.MAX_ATTRS]
+        ins = [require_cuda(rows[k], k).contiguous() for k in group]
+        for k, t in zip(group, ins):
+            if t.dim() < 1 or t.shape[0] != n:
+                raise ValueError("attribute %r must have %d rows" % (k, n))
+        outs = [torch.empty_like(t) for t in ins]
+        m = C.c_int64(0)
+        a_in, widths, a_out = _pc._tables(ins, outs)
+        _lib.check(_lib.lib().o3dmi_pointcloud_select_by_mask(
+            n, _lib.ptr(mask8), 0, len(group), a_in, widths, a_out,
+            C.byref(m), stream()), "select_by_mask")
+        for k, t in zip(group, outs):
+            out[k] = t[:m.value]
+    return out
+
+
+def _selected(mesh, vertex_mask, tri_mask, triangles, n_tri, copy_attributes):
+    """The mesh of a selection: positions and indices always, the other
+    attributes with copy_attributes (CopyAttributesByMasks)."""
+    vertex, triangle = _split(mesh)
+    triangle.pop("indices", None)
+    if not copy_attributes:
+        vertex = {"positions": vertex["positions"]}
+        triangle = {}
+    out = _select_rows(vertex, vertex_mask)
+    if "indices" in mesh:
+        out.update(_select_rows(triangle, tri_mask))
+        out["indices"] = triangles[:n_tri]
+    return out
+
+
+def select_faces_by_mask(mesh, mask):
+    """TriangleMesh::SelectFacesByMask: the triangles with mask set, in input
+    order, and the vertices they name, renumbered."""
+    p = _positions(mesh)
+    if "indices" not in mesh:
+        return {}
+    t = _indices(mesh, p)
+    m = t.shape[0]
+    mask = require_cuda(mask, "mask")
+    if mask.dtype not in (torch.bool, torch.uint8) or mask.shape != (m,):
+        raise ValueError("mask must be a bool {M} tensor")
+    m8 = mask.view(torch.uint8)
+    vmask = torch.empty(p.shape[0], dtype=torch.uint8, device=p.device)
+    tris = torch.empty_like(t)
+    n_tri, n_vert = C.c_int64(0), C.c_int64(0)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_select_faces_by_mask(
+        *_index_args(p, t), _lib.ptr(m8), _lib.ptr(vmask), _lib.ptr(tris),
+        C.byref(n_tri), C.byref(n_vert), stream()), "select_faces_by_mask")
+    return _selected(mesh, vmask, m8, tris, n_tri.value, True)
+
+
+def select_by_index(mesh, indices, copy_attributes=True):
+    """TriangleMesh::SelectByIndex: the vertices named by `indices` (an index
+    out of range is ignored, as upstream warns and continues) and the
+    triangles all of whose vertices are kept. No index: the empty mesh."""
+    p = _positions(mesh)
+    indices = require_cuda(indices, "indices")
+    if indices.dim() != 1 or indices.dtype not in (torch.int32, torch.int64):
+        raise ValueError("indices must be an integer {K} tensor")
+    if indices.shape[0] == 0:
+        return {}
+    indices = indices.to(torch.int64)
+    t = _indices(mesh, p)
+    vmask = torch.empty(p.shape[0], dtype=torch.uint8, device=p.device)
+    tmask = torch.empty(t.shape[0], dtype=torch.uint8, device=p.device)
+    tris = torch.empty_like(t)
+    n_tri, n_vert, n_ign = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_select_by_index(
+        *_index_args(p, t), _lib.ptr(indices), indices.shape[0],
+        _lib.ptr(vmask), _lib.ptr(tmask), _lib.ptr(tris), C.byref(n_tri),
+        C.byref(n_vert), C.byref(n_ign), stream()), "select_by_index")
+    out = _selected(mesh, vmask, tmask, tris, n_tri.value, copy_attributes)
+    if "indices" in out and n_tri.value == 0:
+        # upstream sets no triangle indices when none survives
+        out = {k: v for k, v in out.items()
+               if k != "indices" and not k.startswith(TRIANGLE_PREFIX)}
+    return out
+
+
+def remove_unreferenced_vertices(mesh):
+    """TriangleMesh::RemoveUnreferencedVertices: the vertices no triangle
+    names leave; a mesh without triangles loses every vertex."""
+    p = _positions(mesh)
+    if p.shape[0] == 0:
+        return dict(mesh)
+    t = _indices(mesh, p)
+    vmask = torch.empty(p.shape[0], dtype=torch.uint8, device=p.device)
+    tris = torch.empty_like(t)
+    n_vert = C.c_int64(0)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_remove_unreferenced_vertices(
+        *_index_args(p, t), _lib.ptr(vmask), _lib.ptr(tris), C.byref(n_vert),
+        stream()), "remove_unreferenced_vertices")
+    vertex, triangle = _split(mesh)
+    out = _select_rows(vertex, vmask)
+    out.update(triangle)
+    if "indices" in mesh:
+        out["indices"] = tris
+    return out
+
+
+def get_non_manifold_edges(mesh, allow_boundary_edges=True):
+    """TriangleMesh::GetNonManifoldEdges -> {E,2} in the index dtype, in
+    ascending (lo, hi) order (upstream: its hash map's order)."""
+    p = _positions(mesh)
+    t = _indices(mesh, p)
+    args = _index_args(p, t) + (int(bool(allow_boundary_edges)),)
+    n = C.c_int64(0)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_get_non_manifold_edges(
+        *args, None, -1, C.byref(n), stream()), "get_non_manifold_edges")
+    edges = torch.empty((n.value, 2), dtype=t.dtype, device=p.device)
+    if n.value:
+        _lib.check(_lib.lib().o3dmi_trianglemesh_get_non_manifold_edges(
+            *args, _lib.ptr(edges), n.value, C.byref(n), stream()),
+            "get_non_manifold_edges")
+    return edges
+
+
+def cluster_connected_triangles(mesh):
+    """Legacy TriangleMesh::ClusterConnectedTriangles -> (labels int32 {M},
+    n_triangles int64 {C}, areas float64 {C}); clusters are numbered by their
+    lowest triangle index, as upstream's loop numbers them."""
+    p, t, args = _mesh_args(mesh)
+    m = t.shape[0]
+    labels = torch.empty(m, dtype=torch.int32, device=p.device)
+    counts = torch.empty(m, dtype=torch.int64, device=p.device)
+    areas = torch.empty(m, dtype=torch.float64, device=p.device)
+    n = C.c_int64(0)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_cluster_connected_triangles(
+        *args, _lib.ptr(labels), C.byref(n), _lib.ptr(counts),
+        _lib.ptr(areas), m, stream()), "cluster_connected_triangles")
+    return labels, counts[:n.value], areas[:n.value]

@@ -2013,6 +2013,134 @@ int o3dmi_trianglemesh_remove_unreferenced_vertices(
         uint8_t* vertex_mask_out_dev, void* triangles_out_dev,
         int64_t* n_vertices_out, o3dmi_stream_t stream);
 
+/* ---- TriangleMesh sampling, closest points and metrics -----------------------
+ * (t/geometry/TriangleMesh.cpp:1866-1967, kernel/TriangleMeshCPU.cpp:75-186,
+ * t/geometry/RaycastingScene.cpp:206-353 and 1464-1517. Upstream runs all of
+ * it on the host: a sequential sampling loop and Embree point queries.) The
+ * mesh rules above hold. All synchronise. */
+
+/* The draw of sampled point j >= 0, a pure host function of (seed, j), in
+ * uint64 arithmetic that wraps: h_k = SplitMix64(seed + 0x9E3779B97F4A7C15 *
+ * (3 j + k + 1)), k = 0, 1, 2 (the finaliser of o3dmi_sample_index), and
+ *   *u_out  = (double)(h_0 >> 11) * 2^-53, which picks the triangle,
+ *   *r1_out = (float)(h_1 >> 40) * 2^-24,
+ *   *r2_out = (float)(h_2 >> 40) * 2^-24,
+ * all in [0, 1) and exact. */
+int o3dmi_mesh_sample_draw(uint64_t seed, int64_t j, double* u_out,
+                           float* r1_out, float* r2_out);
+
+/* TriangleMesh::SamplePointsUniformly, every point a pure function of the
+ * mesh, seed and its index (upstream: a global Mersenne engine and
+ * std::discrete_distribution).
+ *  - The triangle. The areas are those of
+ *    o3dmi_trianglemesh_compute_triangle_areas, widened to double. Level 0 is
+ *    the areas in consecutive groups of 512, P[i] the inclusive prefix inside
+ *    i's group, added in index order; level k + 1 holds each group's last
+ *    prefix, grouped the same way, until one group is left. A = the top
+ *    group's last prefix, x = u * A. From the top: in the current group the
+ *    first i with x < P[i] (none, by rounding: the last i whose own value is
+ *    > 0); x -= the prefix before i; on to group i one level down. No
+ *    floating-point scan across groups, and A TRIANGLE OF AREA 0 IS NEVER
+ *    DRAWN.
+ *  - The point, upstream's statements without contraction: wts = {1 -
+ *    sqrt(r1), sqrt(r1) * (1 - r2), sqrt(r1) * r2} in float, out[c] = (wts[0]
+ *    * a[c] + wts[1] * b[c]) + wts[2] * c[c] in the position dtype (a float
+ *    times a double widens).
+ *  - normals_out_dev {n,3} (optional): vertex_normals_dev {v,3} mixed the
+ *    same way when given, else triangle_normals_dev {m,3} copied; both in the
+ *    position dtype. colors_out_dev {n,3} float (optional): vertex_colors_dev
+ *    {v,3} of color_dtype O3DMI_F32, or O3DMI_U8 / O3DMI_U16 divided by 255 /
+ *    65535 in float first, mixed in float. triangles_out_dev int32 {n}
+ *    (optional): the triangle of every point. The albedo / texture_uvs path
+ *    is not offered.
+ * number_of_points <= 0 or >= 2^31, m == 0, v == 0, an area that is not
+ * finite, A not finite or not > 0, an output wanted without its input, a NULL
+ * pointer: O3DMI_ERR_INVALID_ARG with the outputs untouched. */
+int o3dmi_trianglemesh_sample_points_uniformly(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* triangles_dev, int64_t m, int index_dtype,
+        int64_t number_of_points, uint64_t seed,
+        const void* vertex_normals_dev, const void* triangle_normals_dev,
+        const void* vertex_colors_dev, int color_dtype, void* points_out_dev,
+        void* normals_out_dev, float* colors_out_dev,
+        int32_t* triangles_out_dev, o3dmi_stream_t stream);
+
+/* Closest points on a mesh: RaycastingScene::ComputeClosestPoints /
+ * ComputeDistance for one triangle geometry. Float32 positions and queries
+ * only, as upstream's scene (Float64: O3DMI_ERR_UNSUPPORTED).
+ *
+ * The distance of a query q to a triangle t = (a, b, c), in float without
+ * contraction, every dot product (x x + y y) + z z: p, u, v = upstream's
+ * closestPointTriangle branch for branch; e2 = ((dx dx) + dy dy) + dz dz of
+ * q - p; b2 = the same expression on the per-axis gap max(lo - q, q - hi, 0)
+ * between q and t's own bounding box; d2(q, t) = max(e2, b2), a NaN e2 (a
+ * degenerate triangle) staying NaN. The clamp by b2 makes pruning on box
+ * distances exact (closestPointTriangle has no error bound on slivers) and
+ * changes e2 only where it is a rounding artefact.
+ *
+ * The result of a query is the minimum of d2 over ALL triangles, the LOWEST
+ * triangle index on equal d2 (upstream: the first in Embree's traversal
+ * order): a pure function of mesh and query, whatever the tree. Outputs, each
+ * optional (NULL): points {q,3}; primitive_ids uint32 {q}; primitive_uvs
+ * {q,2}; primitive_normals {q,3} = cross(b - a, c - a) of the winner divided
+ * by its norm sqrt((x x + y y) + z z) when that is > 0; distance {q} =
+ * sqrt(d2). When no triangle has a non-NaN d2: id 0xFFFFFFFF, distance +inf,
+ * the other rows 0 (upstream leaves them uninitialised).
+ *
+ * The structure is a linear BVH: 30-bit Morton codes of the triangle boxes'
+ * centres in the box of the referenced vertices, the stable pair sort, a
+ * Karras radix tree over (code, sorted position), boxes refitted bottom-up.
+ * The handle owns copies of what it needs: the caller may free the mesh.
+ * A triangle index out of range, a NaN / Inf vertex or query coordinate,
+ * m == 0, a NULL pointer, a negative count: O3DMI_ERR_INVALID_ARG with the
+ * outputs untouched. q == 0 is O3DMI_OK with nothing written. */
+typedef struct o3dmi_mesh_bvh o3dmi_mesh_bvh_t;
+int o3dmi_mesh_bvh_create(const void* positions_dev, int64_t v, int dtype,
+                          const void* triangles_dev, int64_t m,
+                          int index_dtype, o3dmi_mesh_bvh_t** bvh_out,
+                          o3dmi_stream_t stream);
+int o3dmi_mesh_bvh_destroy(o3dmi_mesh_bvh_t* bvh);
+int o3dmi_mesh_bvh_closest_points(const o3dmi_mesh_bvh_t* bvh,
+                                  const void* queries_dev, int64_t q,
+                                  int dtype, void* points_out_dev,
+                                  uint32_t* primitive_ids_out_dev,
+                                  void* primitive_uvs_out_dev,
+                                  void* primitive_normals_out_dev,
+                                  void* distance_out_dev,
+                                  o3dmi_stream_t stream);
+/* The one-shot forms: build, query, free. `dtype` is that of the positions
+ * and of the queries. */
+int o3dmi_trianglemesh_closest_points(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* triangles_dev, int64_t m, int index_dtype,
+        const void* queries_dev, int64_t q, void* points_out_dev,
+        uint32_t* primitive_ids_out_dev, void* primitive_uvs_out_dev,
+        void* primitive_normals_out_dev, void* distance_out_dev,
+        o3dmi_stream_t stream);
+int o3dmi_trianglemesh_compute_distance(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* triangles_dev, int64_t m, int index_dtype,
+        const void* queries_dev, int64_t q, void* distance_out_dev,
+        o3dmi_stream_t stream);
+
+/* TriangleMesh::ComputeMetrics: n_sampled_points points on either mesh
+ * (o3dmi_trianglemesh_sample_points_uniformly; MESH 1 WITH `seed`, MESH 2
+ * WITH seed + 1), distance12 = the samples of mesh 1 against mesh 2 and
+ * distance21 likewise (the d2 above), the reduction of
+ * o3dmi_pointcloud_compute_metrics on the device and o3dmi_metrics_from_sums
+ * with n1 = n2 = n_sampled_points. Float32 meshes only (upstream's chain
+ * throws on Float64 at the scene). values_out is a HOST array; raw_out
+ * (optional) receives the sums, second_pass_queries = 0. Errors are those of
+ * the parts, raised before any output is written. */
+int o3dmi_trianglemesh_compute_metrics(
+        const void* positions1_dev, int64_t v1, const void* triangles1_dev,
+        int64_t m1, int index_dtype1, const void* positions2_dev, int64_t v2,
+        const void* triangles2_dev, int64_t m2, int index_dtype2, int dtype,
+        const int32_t* metrics, int n_metrics, const float* fscore_radius,
+        int n_radii, int64_t n_sampled_points, uint64_t seed,
+        float* values_out, int64_t values_capacity,
+        o3dmi_pointcloud_metrics_raw_t* raw_out, o3dmi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

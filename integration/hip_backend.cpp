@@ -600,6 +600,101 @@ static_assert(
                              decltype(&ComputeTriangleAreasCPU)>::value,
         "the TriangleMesh ...HIP functions have the dispatchers' per-device "
         "signatures");
+
+// 5e (continued). TriangleMesh::SamplePointsUniformly (t/geometry/
+//    TriangleMesh.cpp:1866-1937), RaycastingScene::ComputeClosestPoints /
+//    ComputeDistance for one triangle geometry (RaycastingScene.cpp:
+//    1464-1517) and TriangleMesh::ComputeMetrics (:1939-1967) have no
+//    per-device kernel upstream: each copies to the host first. Each gains a
+//    HIP branch in front of those copies (INTEGRATION 5e''''''). `seed` is
+//    drawn once per call from utility::random.
+//    points / normals / colors: the tensors the method allocates ({n,3};
+//    normals and colors may be empty), vertex_normals / triangle_normals /
+//    vertex_colors the inputs SamplePointsUniformly selects (empty: unused).
+void SamplePointsUniformlyHIP(const core::Tensor& triangles,
+                              const core::Tensor& vertices,
+                              const core::Tensor& vertex_normals,
+                              const core::Tensor& vertex_colors,
+                              const core::Tensor& triangle_normals,
+                              uint64_t seed, core::Tensor& points,
+                              core::Tensor& normals, core::Tensor& colors) {
+    auto ptr = [](const core::Tensor& t) -> const void* {
+        return t.NumElements() > 0 ? t.GetDataPtr() : nullptr;
+    };
+    O3DMI_CALL(o3dmi_trianglemesh_sample_points_uniformly(
+            vertices.GetDataPtr(), vertices.GetLength(),
+            core::ToO3dmi(vertices.GetDtype()), triangles.GetDataPtr(),
+            triangles.GetLength(), core::ToO3dmi(triangles.GetDtype()),
+            points.GetLength(), seed, ptr(vertex_normals),
+            ptr(triangle_normals), ptr(vertex_colors),
+            vertex_colors.NumElements() > 0
+                    ? core::ToO3dmi(vertex_colors.GetDtype())
+                    : O3DMI_F32,
+            points.GetDataPtr(),
+            normals.NumElements() > 0 ? normals.GetDataPtr() : nullptr,
+            colors.NumElements() > 0 ? colors.GetDataPtr<float>() : nullptr,
+            nullptr, core::HipStream()));
+}
+
+//    RaycastingScene::Impl keeps the handle: AddTriangles creates it,
+//    the destructor destroys it.
+o3dmi_mesh_bvh_t* MeshBvhCreateHIP(const core::Tensor& vertices,
+                                   const core::Tensor& triangles) {
+    o3dmi_mesh_bvh_t* bvh = nullptr;
+    O3DMI_CALL(o3dmi_mesh_bvh_create(
+            vertices.GetDataPtr(), vertices.GetLength(),
+            core::ToO3dmi(vertices.GetDtype()), triangles.GetDataPtr(),
+            triangles.GetLength(), core::ToO3dmi(triangles.GetDtype()), &bvh,
+            core::HipStream()));
+    return bvh;
+}
+void MeshBvhDestroyHIP(o3dmi_mesh_bvh_t* bvh) {
+    O3DMI_CALL(o3dmi_mesh_bvh_destroy(bvh));
+}
+//    query_points {..,3} Float32, contiguous; every output has its leading
+//    dimensions and may be empty (ComputeDistance passes `distance` alone).
+void MeshClosestPointsHIP(const o3dmi_mesh_bvh_t* bvh,
+                          const core::Tensor& query_points,
+                          core::Tensor& points, core::Tensor& primitive_ids,
+                          core::Tensor& primitive_uvs,
+                          core::Tensor& primitive_normals,
+                          core::Tensor& distance) {
+    auto ptr = [](core::Tensor& t) -> void* {
+        return t.NumElements() > 0 ? t.GetDataPtr() : nullptr;
+    };
+    O3DMI_CALL(o3dmi_mesh_bvh_closest_points(
+            bvh, query_points.GetDataPtr(), query_points.NumElements() / 3,
+            core::ToO3dmi(query_points.GetDtype()), ptr(points),
+            (uint32_t*)ptr(primitive_ids), ptr(primitive_uvs),
+            ptr(primitive_normals), ptr(distance), core::HipStream()));
+}
+
+//    codes[i] = static_cast<int32_t>(metrics[i]); the result is a host
+//    Float32 tensor, as upstream's.
+core::Tensor ComputeMetricsHIP(const core::Tensor& vertices1,
+                               const core::Tensor& triangles1,
+                               const core::Tensor& vertices2,
+                               const core::Tensor& triangles2,
+                               const std::vector<int32_t>& metrics,
+                               const std::vector<float>& fscore_radius,
+                               int64_t n_sampled_points, uint64_t seed) {
+    int64_t n_values = 0;
+    for (int32_t m : metrics)
+        n_values += m == O3DMI_METRIC_FSCORE ? (int64_t)fscore_radius.size()
+                                             : 1;
+    std::vector<float> values((size_t)n_values);
+    O3DMI_CALL(o3dmi_trianglemesh_compute_metrics(
+            vertices1.GetDataPtr(), vertices1.GetLength(),
+            triangles1.GetDataPtr(), triangles1.GetLength(),
+            core::ToO3dmi(triangles1.GetDtype()), vertices2.GetDataPtr(),
+            vertices2.GetLength(), triangles2.GetDataPtr(),
+            triangles2.GetLength(), core::ToO3dmi(triangles2.GetDtype()),
+            core::ToO3dmi(vertices1.GetDtype()), metrics.data(),
+            (int)metrics.size(), fscore_radius.data(),
+            (int)fscore_radius.size(), n_sampled_points, seed, values.data(),
+            n_values, nullptr, core::HipStream()));
+    return core::Tensor(values, {n_values}, core::Float32);
+}
 }  // namespace trianglemesh
 }  // namespace kernel
 }  // namespace geometry

@@ -606,6 +606,25 @@ PROTOTYPES.update({
                C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "o3dmi_trianglemesh_remove_unreferenced_vertices": (
         _i32, [_vp, _i64, _i32, _i64, _vp, _vp, C.POINTER(_i64), _vp]),
+    "o3dmi_mesh_sample_draw": (
+        _i32, [C.c_uint64, _i64, _dp, C.POINTER(_f), C.POINTER(_f)]),
+    "o3dmi_trianglemesh_sample_points_uniformly": (
+        _i32, [_vp, _i64, _i32, _vp, _i64, _i32, _i64, C.c_uint64, _vp, _vp,
+               _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "o3dmi_mesh_bvh_create": (
+        _i32, [_vp, _i64, _i32, _vp, _i64, _i32, C.POINTER(_vp), _vp]),
+    "o3dmi_mesh_bvh_destroy": (_i32, [_vp]),
+    "o3dmi_mesh_bvh_closest_points": (
+        _i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "o3dmi_trianglemesh_closest_points": (
+        _i32, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp,
+               _vp, _vp, _vp]),
+    "o3dmi_trianglemesh_compute_distance": (
+        _i32, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _i64, _vp, _vp]),
+    "o3dmi_trianglemesh_compute_metrics": (
+        _i32, [_vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _i32, _i32,
+               C.POINTER(_i32), _i32, C.POINTER(_f), _i32, _i64, C.c_uint64,
+               C.POINTER(_f), _i64, C.POINTER(MetricsRawC), _vp]),
 })
 
 # o3dmi_transport_t (include/o3d_mi355x_host.h): the caller-provided collectives
@@ -633,6 +652,11 @@ INTERNAL_PROTOTYPES = {
     # stream)
     "o3dmi_internal_nns_hybrid_search_wide": (
         _i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    # csrc/mesh_bvh.h: (handle, queries, q, points, ids, uvs, normals,
+    # distance, sort_queries, visits[2], stream)
+    "o3dmi_internal_mesh_bvh_query": (
+        _i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32,
+               C.POINTER(C.c_uint64), _vp]),
 }
 
 _lib = None

@@ -9,49 +9,12 @@
 
 #include "../scan.h"
 #include "../sort.h"
-#include "../trianglemesh.h"
 #include "o3d_mi355x_host.h"
-#include "pointcloud_call.h"
+#include "trianglemesh_call.h"
 
 using namespace o3dmi;
 
 namespace {
-
-int CheckSizes(int64_t v, int64_t m, int index_dtype) {
-    O3DMI_REQUIRE(index_dtype == O3DMI_I32 || index_dtype == O3DMI_I64,
-                  "triangles must be Int32 or Int64");
-    O3DMI_REQUIRE(v >= 0 && v < (1ll << 31), "v out of range (< 2^31)");
-    O3DMI_REQUIRE(m >= 0 && m <= kMeshMaxTriangles,
-                  "m out of range (<= 2^29 triangles)");
-    return O3DMI_OK;
-}
-
-int CheckFloat(int dtype) {
-    O3DMI_REQUIRE(dtype == O3DMI_F32 || dtype == O3DMI_F64,
-                  "positions and normals must be Float32 or Float64");
-    return O3DMI_OK;
-}
-
-// The triangle list as checked int32: the caller's array, or its narrowed
-// copy. One launch, one download.
-int LoadTriangles(PoolScratch& pool, Words* w, const void* triangles_dev,
-                  int64_t m, int index_dtype, int64_t v, const int32_t** tri) {
-    int32_t* narrowed = nullptr;
-    int st = O3DMI_OK;
-    if (index_dtype == O3DMI_I64 &&
-        (st = pool.Alloc(&narrowed, sizeof(int32_t) * 3 * (size_t)m)))
-        return st;
-    st = CheckTrianglesAsync(triangles_dev, m, index_dtype, v, narrowed,
-                             &w->bad, pool.s);
-    if (st) return st;
-    int bad = 0;
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&bad, &w->bad, sizeof(int),
-                                   hipMemcpyDeviceToHost, pool.s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(pool.s));
-    O3DMI_REQUIRE(!bad, "triangle index outside [0, v)");
-    *tri = narrowed ? narrowed : (const int32_t*)triangles_dev;
-    return O3DMI_OK;
-}
 
 // The arguments of a call on positions and triangles.
 int CheckMesh(const void* positions_dev, int64_t v, int dtype,
@@ -168,7 +131,103 @@ int SelectFaces(const void* triangles_dev, int64_t m, int index_dtype,
 
 }  // namespace
 
+namespace o3dmi {
+
+int SampleMeshChecked(const void* positions_dev, int64_t v, int dtype,
+                      const void* triangles_dev, int64_t m, int index_dtype,
+                      int64_t n, uint64_t seed, MeshSampleIO io,
+                      hipStream_t s) {
+    PoolScratch pool(s);
+    Words* w = nullptr;
+    const int32_t* tri = nullptr;
+    void* areas = nullptr;
+    double* prefix = nullptr;
+    int st = AllocWords(pool, &w);
+    if (st) return st;
+    if ((st = LoadTriangles(pool, w, triangles_dev, m, index_dtype, v, &tri)))
+        return st;
+    if ((st = pool.Alloc(&areas, ElemSize(dtype) * (size_t)m))) return st;
+    if ((st = pool.Alloc(&prefix, sizeof(double) * MeshPrefixDoubles(m))))
+        return st;
+    if ((st = TriangleAreasAsync(positions_dev, dtype, tri, m, areas, s)))
+        return st;
+    MeshPrefixTree tree;
+    if ((st = MeshPrefixTreeAsync(areas, m, dtype, prefix, &tree, &w->bad, s)))
+        return st;
+    int bad = 0;
+    double total = 0;
+    O3DMI_HIP_CHECK(hipMemcpyAsync(&bad, &w->bad, sizeof(int),
+                                   hipMemcpyDeviceToHost, s));
+    O3DMI_HIP_CHECK(hipMemcpyAsync(
+            &total,
+            tree.prefix[tree.levels - 1] + (tree.size[tree.levels - 1] - 1),
+            sizeof(double), hipMemcpyDeviceToHost, s));
+    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
+    O3DMI_REQUIRE(!bad, "sample points: a triangle area is not finite");
+    O3DMI_REQUIRE(total - total == 0 && total > 0,
+                  "sample points: the surface area is not finite and > 0");
+    io.positions = positions_dev;
+    io.tri = tri;
+    if ((st = MeshSamplePointsAsync(tree, areas, dtype, io, n, seed, s)))
+        return st;
+    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
+    return O3DMI_OK;
+}
+
+}  // namespace o3dmi
+
 extern "C" {
+
+int o3dmi_mesh_sample_draw(uint64_t seed, int64_t j, double* u_out,
+                           float* r1_out, float* r2_out) {
+    O3DMI_REQUIRE(j >= 0, "j < 0");
+    O3DMI_REQUIRE(u_out && r1_out && r2_out, "null argument");
+    const MeshSampleDraw d = DrawMeshSample(seed, (uint64_t)j);
+    *u_out = d.u;
+    *r1_out = d.r1;
+    *r2_out = d.r2;
+    return O3DMI_OK;
+}
+
+int o3dmi_trianglemesh_sample_points_uniformly(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* triangles_dev, int64_t m, int index_dtype,
+        int64_t number_of_points, uint64_t seed,
+        const void* vertex_normals_dev, const void* triangle_normals_dev,
+        const void* vertex_colors_dev, int color_dtype, void* points_out_dev,
+        void* normals_out_dev, float* colors_out_dev,
+        int32_t* triangles_out_dev, o3dmi_stream_t stream) {
+    int st = CheckFloat(dtype);
+    if (!st) st = CheckSizes(v, m, index_dtype);
+    if (st) return st;
+    O3DMI_REQUIRE(number_of_points > 0, "number_of_points <= 0");
+    O3DMI_REQUIRE(number_of_points < (1ll << 31),
+                  "number_of_points out of range (< 2^31)");
+    O3DMI_REQUIRE(m > 0, "Input mesh has no triangles. Cannot sample points.");
+    O3DMI_REQUIRE(v > 0, "Input mesh is empty. Cannot sample points.");
+    O3DMI_REQUIRE(positions_dev && triangles_dev && points_out_dev,
+                  "null argument");
+    O3DMI_REQUIRE(!normals_out_dev || vertex_normals_dev ||
+                          triangle_normals_dev,
+                  "null argument: normals wanted, none given");
+    O3DMI_REQUIRE(!colors_out_dev || vertex_colors_dev,
+                  "null argument: colours wanted, none given");
+    O3DMI_REQUIRE(!colors_out_dev || color_dtype == O3DMI_F32 ||
+                          color_dtype == O3DMI_U8 || color_dtype == O3DMI_U16,
+                  "vertex colours must be Float32, UInt8 or UInt16");
+    MeshSampleIO io = {};
+    io.vertex_normals = vertex_normals_dev;
+    io.triangle_normals = triangle_normals_dev;
+    io.vertex_colors = vertex_colors_dev;
+    io.color_dtype = color_dtype;
+    io.points_out = points_out_dev;
+    io.normals_out = normals_out_dev;
+    io.colors_out = colors_out_dev;
+    io.triangles_out = triangles_out_dev;
+    return SampleMeshChecked(positions_dev, v, dtype, triangles_dev, m,
+                             index_dtype, number_of_points, seed, io,
+                             (hipStream_t)stream);
+}
 
 int o3dmi_trianglemesh_compute_triangle_normals(
         const void* positions_dev, int64_t v, int dtype,

@@ -1,0 +1,49 @@
+// The call scaffold the TriangleMesh drivers (trianglemesh.cpp, mesh_bvh.cpp)
+// share: the size and dtype checks and the checked int32 triangle list.
+#pragma once
+
+#include "../trianglemesh.h"
+#include "pointcloud_call.h"
+
+namespace o3dmi {
+namespace {  // every driver gets its own copy: the library exports none of it
+
+inline int CheckSizes(int64_t v, int64_t m, int index_dtype) {
+    O3DMI_REQUIRE(index_dtype == O3DMI_I32 || index_dtype == O3DMI_I64,
+                  "triangles must be Int32 or Int64");
+    O3DMI_REQUIRE(v >= 0 && v < (1ll << 31), "v out of range (< 2^31)");
+    O3DMI_REQUIRE(m >= 0 && m <= kMeshMaxTriangles,
+                  "m out of range (<= 2^29 triangles)");
+    return O3DMI_OK;
+}
+
+inline int CheckFloat(int dtype) {
+    O3DMI_REQUIRE(dtype == O3DMI_F32 || dtype == O3DMI_F64,
+                  "positions and normals must be Float32 or Float64");
+    return O3DMI_OK;
+}
+
+// The triangle list as checked int32: the caller's array, or its narrowed
+// copy. One launch, one download.
+inline int LoadTriangles(PoolScratch& pool, Words* w, const void* triangles_dev,
+                         int64_t m, int index_dtype, int64_t v,
+                         const int32_t** tri) {
+    int32_t* narrowed = nullptr;
+    int st = O3DMI_OK;
+    if (index_dtype == O3DMI_I64 &&
+        (st = pool.Alloc(&narrowed, sizeof(int32_t) * 3 * (size_t)m)))
+        return st;
+    st = CheckTrianglesAsync(triangles_dev, m, index_dtype, v, narrowed,
+                             &w->bad, pool.s);
+    if (st) return st;
+    int bad = 0;
+    O3DMI_HIP_CHECK(hipMemcpyAsync(&bad, &w->bad, sizeof(int),
+                                   hipMemcpyDeviceToHost, pool.s));
+    O3DMI_HIP_CHECK(hipStreamSynchronize(pool.s));
+    O3DMI_REQUIRE(!bad, "triangle index outside [0, v)");
+    *tri = narrowed ? narrowed : (const int32_t*)triangles_dev;
+    return O3DMI_OK;
+}
+
+}  // namespace
+}  // namespace o3dmi

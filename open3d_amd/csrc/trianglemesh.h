@@ -10,6 +10,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "ransac.h"  // SplitMix64
+
 namespace o3dmi {
 
 constexpr int64_t kMeshMaxTriangles = 1ll << 29;  // 3 m corners < 2^31
@@ -47,6 +49,88 @@ int NormalizeMeshNormalsAsync(void* normals_dev, int64_t n, int dtype,
 size_t RunSumScratchDoubles(int64_t n);
 int RunSumTreeAsync(const void* values_dev, int64_t n, int dtype,
                     double* sums_dev, const double** total_dev, hipStream_t s);
+
+// ---- uniform sampling (trianglemesh_sample.hip) --------------------------------
+// The draw of point j, a pure function of (seed, j), in uint64 arithmetic
+// (everything wraps): h_k = SplitMix64(seed + 0x9E3779B97F4A7C15 * (3 j + k +
+// 1)) for k = 0, 1, 2 (ransac.h), and
+//   u  = (double)(h_0 >> 11) * 2^-53   in [0, 1), picks the triangle,
+//   r1 = (float)(h_1 >> 40) * 2^-24    in [0, 1),
+//   r2 = (float)(h_2 >> 40) * 2^-24    in [0, 1).
+// Both conversions and both products are exact.
+struct MeshSampleDraw {
+    double u;
+    float r1, r2;
+};
+__host__ __device__ inline MeshSampleDraw DrawMeshSample(uint64_t seed,
+                                                         uint64_t j) {
+    const uint64_t c = 3ull * j;
+    const uint64_t g = 0x9E3779B97F4A7C15ull;
+    MeshSampleDraw d;
+    d.u = (double)(SplitMix64(seed + g * (c + 1ull)) >> 11) *
+          (1.0 / 9007199254740992.0);
+    d.r1 = (float)(SplitMix64(seed + g * (c + 2ull)) >> 40) *
+           (1.0f / 16777216.0f);
+    d.r2 = (float)(SplitMix64(seed + g * (c + 3ull)) >> 40) *
+           (1.0f / 16777216.0f);
+    return d;
+}
+
+// The prefix tree of the triangle choice. Level 0 holds the m areas widened to
+// double, in consecutive groups of kMeshRun: prefix[0][i] is the inclusive
+// prefix of i's group, added in index order. Level k + 1 holds every group's
+// last prefix of level k, grouped the same way, until a level is one group
+// (m <= 2^29: at most 4 levels). The shape of RunSumTreeAsync with the
+// prefixes kept; a group's prefixes are sums of non-negative values in order,
+// hence monotone.
+constexpr int kMeshPrefixLevels = 4;
+struct MeshPrefixTree {
+    int levels;
+    int64_t size[kMeshPrefixLevels];
+    double* prefix[kMeshPrefixLevels];
+};
+size_t MeshPrefixDoubles(int64_t m);
+// Lays the tree out in prefix_dev (MeshPrefixDoubles(m) doubles) and fills it.
+// *bad_dev |= 1 for an area that is not finite. The total area is
+// tree->prefix[levels - 1][size[levels - 1] - 1].
+int MeshPrefixTreeAsync(const void* areas_dev, int64_t m, int dtype,
+                        double* prefix_dev, MeshPrefixTree* tree, int* bad_dev,
+                        hipStream_t s);
+
+// What a sampled point is mixed from; every pointer but positions / tri may be
+// NULL. vertex_normals win over triangle_normals (both in the position dtype);
+// colors are {v,3} of color_dtype O3DMI_F32 / O3DMI_U8 / O3DMI_U16.
+struct MeshSampleIO {
+    const void* positions;
+    const int32_t* tri;
+    const void* vertex_normals;
+    const void* triangle_normals;
+    const void* vertex_colors;
+    int color_dtype;
+    void* points_out;        // {n,3} position dtype
+    void* normals_out;       // {n,3} position dtype
+    float* colors_out;       // {n,3}
+    int32_t* triangles_out;  // {n}: the triangle of every point
+};
+// Point j < n: x = u * total; from the top level down, in the current group
+// the first i with x < prefix[i] (none, by rounding: the last i whose own
+// value is > 0), x -= the prefix before i, then group i one level down. A
+// triangle of area 0 is never drawn. Then TriangleMeshCPU.cpp:137-182 with
+// that triangle: wts = {1 - sqrt(r1), sqrt(r1) (1 - r2), sqrt(r1) r2} in
+// float, out[c] = (wts[0] a[c] + wts[1] b[c]) + wts[2] c[c] (mix_3x3; a float
+// times a double widens).
+int MeshSamplePointsAsync(const MeshPrefixTree& tree, const void* areas_dev,
+                          int dtype, const MeshSampleIO& io, int64_t n,
+                          uint64_t seed, hipStream_t s);
+
+// SamplePointsUniformly on the caller's stream for a mesh whose arguments
+// were checked (host/trianglemesh.cpp): the triangle range check, the areas,
+// the tree, the error downloads (one wait), then the points. io.tri is
+// ignored (the checked list is used).
+int SampleMeshChecked(const void* positions_dev, int64_t v, int dtype,
+                      const void* triangles_dev, int64_t m, int index_dtype,
+                      int64_t n, uint64_t seed, MeshSampleIO io,
+                      hipStream_t s);
 
 // ---- vertex -> corners --------------------------------------------------------
 // The 3 m corner ids 3 t + k sorted stably by the vertex they name:

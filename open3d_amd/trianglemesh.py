@@ -1,7 +1,9 @@
 """Mirror of t::geometry::TriangleMesh's normal, area, selection and
 connectivity methods (t/geometry/TriangleMesh.cpp:198-404, 1221-1452,
-1826-1864) and of legacy ClusterConnectedTriangles (geometry/TriangleMesh.cpp:
-1459-1528) on the HIP backend.
+1826-1864), of legacy ClusterConnectedTriangles (geometry/TriangleMesh.cpp:
+1459-1528), of SamplePointsUniformly and ComputeMetrics (t/geometry/
+TriangleMesh.cpp:1866-1967) and of RaycastingScene's closest-point queries for
+one mesh (MeshBVH) on the HIP backend.
 
 A mesh is the dict VoxelBlockGrid.extract_triangle_mesh returns: "positions"
 ({V,3} Float32 or Float64) and "indices" ({M,3} Int32 or Int64) on the device,
@@ -282,3 +284,158 @@ def cluster_connected_triangles(mesh):
         *args, _lib.ptr(labels), C.byref(n), _lib.ptr(counts),
         _lib.ptr(areas), m, stream()), "cluster_connected_triangles")
     return labels, counts[:n.value], areas[:n.value]
+
+
+# ---- sampling, closest points, metrics ----------------------------------------
+
+_COLOR_CODES = {torch.float32: 0, torch.uint8: 3, torch.uint16: 2}
+
+
+def sample_points_uniformly(mesh, number_of_points, use_triangle_normal=False,
+                            seed=0):
+    """TriangleMesh::SamplePointsUniformly -> a point cloud dict: "positions",
+    "normals" when the mesh has vertex normals (or use_triangle_normal: the
+    triangle's normal, computed first if absent) and Float32 "colors" when it
+    has vertex colors. Point j is a pure function of (mesh, seed, j); a
+    triangle of area 0 is never drawn. Textures are not sampled."""
+    p, t, args = _mesh_args(mesh)
+    n = int(number_of_points)
+    if n <= 0:
+        raise ValueError("number_of_points <= 0")
+    if p.shape[0] == 0:
+        raise ValueError("Input mesh is empty. Cannot sample points.")
+    if "indices" not in mesh or t.shape[0] == 0:
+        raise ValueError("Input mesh has no triangles. Cannot sample points.")
+    vn = tn = colors = None
+    if use_triangle_normal:
+        name = TRIANGLE_PREFIX + "normals"
+        if name not in mesh:
+            mesh = compute_triangle_normals(mesh, normalized=True)
+        tn = require_cuda(mesh[name], name).to(p.dtype).contiguous()
+        if tn.shape != (t.shape[0], 3):
+            raise ValueError("triangle_normals must be {M,3}")
+    elif "normals" in mesh:
+        vn = require_cuda(mesh["normals"], "normals").to(p.dtype).contiguous()
+        if vn.shape != p.shape:
+            raise ValueError("normals must be {V,3}")
+    if "colors" in mesh:
+        colors = require_cuda(mesh["colors"], "colors")
+        if colors.dtype not in _COLOR_CODES:
+            colors = colors.to(torch.float32)
+        colors = colors.contiguous()
+        if colors.shape != p.shape:
+            raise ValueError("colors must be {V,3}")
+    out = {"positions": torch.empty((n, 3), dtype=p.dtype, device=p.device)}
+    if vn is not None or tn is not None:
+        out["normals"] = torch.empty((n, 3), dtype=p.dtype, device=p.device)
+    if colors is not None:
+        out["colors"] = torch.empty((n, 3), dtype=torch.float32,
+                                    device=p.device)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_sample_points_uniformly(
+        *args, n, int(seed) & (2 ** 64 - 1), _lib.ptr(vn), _lib.ptr(tn),
+        _lib.ptr(colors),
+        _COLOR_CODES[colors.dtype] if colors is not None else 0,
+        _lib.ptr(out["positions"]), _lib.ptr(out.get("normals")),
+        _lib.ptr(out.get("colors")), None, stream()),
+        "sample_points_uniformly")
+    return out
+
+
+class MeshBVH:
+    """The closest-point queries of RaycastingScene for one triangle mesh
+    (Float32): a linear BVH on the device that owns its copies of the mesh.
+    The answer to a query is the minimum over all triangles, the lowest index
+    on ties, whatever the tree."""
+
+    def __init__(self, mesh):
+        p, t, args = _mesh_args(mesh)
+        handle = C.c_void_p()
+        _lib.check(_lib.lib().o3dmi_mesh_bvh_create(
+            *args, C.byref(handle), stream()), "MeshBVH")
+        self._handle = handle
+        self._device = p.device
+
+    def close(self):
+        if self._handle is not None:
+            _lib.lib().o3dmi_mesh_bvh_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _queries(self, points):
+        points = require_cuda(points, "query_points")
+        if points.dim() < 1 or points.shape[-1] != 3:
+            raise ValueError("query_points must have shape {..., 3}")
+        return points.reshape(-1, 3).contiguous(), tuple(points.shape[:-1])
+
+    def compute_closest_points(self, points):
+        """-> dict(points {..,3}, geometry_ids {..} (all 0), primitive_ids
+        {..} uint32, primitive_uvs {..,2}, primitive_normals {..,3}), as
+        RaycastingScene::ComputeClosestPoints."""
+        flat, lead = self._queries(points)
+        q, dev = flat.shape[0], flat.device
+        out = {
+            "points": torch.empty((q, 3), dtype=torch.float32, device=dev),
+            "primitive_ids": torch.empty(q, dtype=torch.uint32, device=dev),
+            "primitive_uvs": torch.empty((q, 2), dtype=torch.float32,
+                                         device=dev),
+            "primitive_normals": torch.empty((q, 3), dtype=torch.float32,
+                                             device=dev),
+        }
+        _lib.check(_lib.lib().o3dmi_mesh_bvh_closest_points(
+            self._handle, _lib.ptr(flat), q, TORCH_TO_O3DMI[flat.dtype],
+            _lib.ptr(out["points"]), _lib.ptr(out["primitive_ids"]),
+            _lib.ptr(out["primitive_uvs"]),
+            _lib.ptr(out["primitive_normals"]), None, stream()),
+            "compute_closest_points")
+        out["geometry_ids"] = torch.zeros(q, dtype=torch.uint32, device=dev)
+        return {k: v.reshape(lead + tuple(v.shape[1:]))
+                for k, v in out.items()}
+
+    def compute_distance(self, points):
+        """RaycastingScene::ComputeDistance -> {..} Float32."""
+        flat, lead = self._queries(points)
+        q = flat.shape[0]
+        dist = torch.empty(q, dtype=torch.float32, device=flat.device)
+        _lib.check(_lib.lib().o3dmi_mesh_bvh_closest_points(
+            self._handle, _lib.ptr(flat), q, TORCH_TO_O3DMI[flat.dtype], None,
+            None, None, None, _lib.ptr(dist), stream()), "compute_distance")
+        return dist.reshape(lead)
+
+
+def compute_metrics(mesh1, mesh2, metrics, fscore_radius=(0.01,),
+                    n_sampled_points=1000, seed=0, return_raw=False):
+    """TriangleMesh::ComputeMetrics -> a CPU Float32 tensor with the values in
+    the order of `metrics` (pointcloud.Metric codes; every FScore entry expands
+    to one value per radius). Mesh 1 is sampled with `seed`, mesh 2 with
+    seed + 1. With return_raw also dict(sum, max, counts), each with the
+    direction 1 -> 2 first. Float32 meshes."""
+    p1, t1, _ = _mesh_args(mesh1)
+    p2, t2, _ = _mesh_args(mesh2)
+    if p1.dtype != p2.dtype:
+        raise ValueError("both meshes must have the same dtype")
+    codes = [int(m) for m in metrics]
+    radii = [float(r) for r in fscore_radius]
+    n_values = sum(len(radii) if m == _pc.Metric.FScore else 1 for m in codes)
+    values = (C.c_float * max(n_values, 1))()
+    counts = (C.c_int64 * max(2 * len(radii), 1))()
+    raw = _lib.MetricsRawC()
+    raw.counts = C.cast(counts, C.POINTER(C.c_int64))
+    _lib.check(_lib.lib().o3dmi_trianglemesh_compute_metrics(
+        _lib.ptr(p1), p1.shape[0], _lib.ptr(t1), t1.shape[0],
+        TORCH_TO_O3DMI[t1.dtype], _lib.ptr(p2), p2.shape[0], _lib.ptr(t2),
+        t2.shape[0], TORCH_TO_O3DMI[t2.dtype], TORCH_TO_O3DMI[p1.dtype],
+        (C.c_int * max(len(codes), 1))(*codes), len(codes),
+        (C.c_float * max(len(radii), 1))(*radii), len(radii),
+        int(n_sampled_points), int(seed) & (2 ** 64 - 1), values, n_values,
+        C.byref(raw), stream()), "compute_metrics")
+    out = torch.tensor(list(values)[:n_values], dtype=torch.float32)
+    if not return_raw:
+        return out
+    r = len(radii)
+    return out, dict(sum=list(raw.sum), max=list(raw.max),
+                     counts=[list(counts)[:r], list(counts)[r:2 * r]])

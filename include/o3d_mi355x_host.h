@@ -2141,6 +2141,142 @@ int o3dmi_trianglemesh_compute_metrics(
         float* values_out, int64_t values_capacity,
         o3dmi_pointcloud_metrics_raw_t* raw_out, o3dmi_stream_t stream);
 
+/* ---- Ray queries on a mesh ----------------------------------------------------
+ * RaycastingScene::CastRays, TestOcclusions, CountIntersections,
+ * ListIntersections, ComputeOccupancy, ComputeSignedDistance and
+ * CreateRaysPinhole (t/geometry/RaycastingScene.cpp:486-1100, 1325-1462,
+ * 1520-1674) for one triangle geometry, on the tree of o3dmi_mesh_bvh_create.
+ * Upstream runs them on the host through Embree, whose intersector and
+ * traversal order cannot be matched bit for bit; as for the closest points,
+ * every answer here is a PURE FUNCTION OF THE MESH AND THE RAY, the same for
+ * any tree, traversal order and launch shape. Float32 only (Float64:
+ * O3DMI_ERR_UNSUPPORTED). All synchronise.
+ *
+ * A ray is six floats (o, d); d is not normalised and t is in units of |d|.
+ * The pair of a ray with range (tnear, tfar] and a triangle t = (a, b, c), in
+ * float without contraction, every dot product (x x + y y) + z z:
+ *   e1 = b - a, e2 = c - a, p = d x e2, det = e1 . p; a miss when det == 0 or
+ *   det is NaN (a degenerate triangle, a zero direction); no back-face
+ *   culling; inv = 1 / det, s = o - a, u = (s . p) inv, q = s x e1,
+ *   v = (d . q) inv, t_e = (e2 . q) inv; hit_e = u >= 0 && v >= 0 &&
+ *   u + v <= 1 (u weighs vertex 1 and v vertex 2, as primitive_uvs above).
+ *   The slab interval of t's own bounding box: per axis with d_k != 0,
+ *   (lo_k - o_k) / d_k and (hi_k - o_k) / d_k (divisions), their min entering
+ *   and their max leaving; an axis with d_k == 0 empties the interval when
+ *   o_k is outside [lo_k, hi_k]; T0 = max(the entries, tnear), T1 = min(the
+ *   exits, tfar).
+ *   The pair HITS iff hit_e && T0 <= T1 && t_e > tnear && t_e <= tfar (a ray
+ *   that starts on the surface does not hit it at t = 0), with the parameter
+ *   t = min(max(t_e, T0), T1), a zero made positive. The clamp makes pruning
+ *   on node boxes exact (subtract, divide, min and max are monotone, so a
+ *   containing box's interval contains t) and moves t_e only where it already
+ *   disagrees with the triangle's own box.
+ * Moeller-Trumbore is not watertight: a ray through a shared edge can be
+ * counted twice or not at all, which is why upstream votes with three rays.
+ *
+ * A NaN / Inf ray or point component, a NaN tnear / tfar, a NULL pointer, a
+ * negative count: O3DMI_ERR_INVALID_ARG with the outputs untouched (upstream:
+ * undefined). q == 0 is O3DMI_OK with nothing written. */
+
+#define O3DMI_RAYCAST_INVALID_ID 0xFFFFFFFFu
+
+/* CastRays (tnear = 0, tfar = +inf): the minimum t over the hitting pairs, the
+ * LOWEST triangle index on equal t (upstream: Embree's first). Outputs, each
+ * optional (NULL): t_hit {q}; geometry_ids uint32 {q} (0); primitive_ids
+ * uint32 {q}; primitive_uvs {q,2} recomputed from the winner;
+ * primitive_normals {q,3} = cross(b - a, c - a) by the closest points' rule.
+ * No hit: t_hit +inf, both ids O3DMI_RAYCAST_INVALID_ID, the other rows 0. */
+int o3dmi_mesh_bvh_cast_rays(const o3dmi_mesh_bvh_t* bvh, const void* rays_dev,
+                             int64_t q, int dtype, void* t_hit_out_dev,
+                             uint32_t* geometry_ids_out_dev,
+                             uint32_t* primitive_ids_out_dev,
+                             void* primitive_uvs_out_dev,
+                             void* primitive_normals_out_dev,
+                             o3dmi_stream_t stream);
+
+/* TestOcclusions: occluded_out_dev uint8 {q} = 1 when a pair hits within
+ * (tnear, tfar], else 0. */
+int o3dmi_mesh_bvh_test_occlusions(const o3dmi_mesh_bvh_t* bvh,
+                                   const void* rays_dev, int64_t q, int dtype,
+                                   float tnear, float tfar,
+                                   uint8_t* occluded_out_dev,
+                                   o3dmi_stream_t stream);
+
+/* CountIntersections: counts_out_dev int32 {q} = the number of DISTINCT
+ * VALUES OF t among the hitting pairs on (0, +inf] (upstream: one more
+ * whenever a candidate's t differs from the previous candidate's in Embree's
+ * traversal order, which approximates that number and is not a function of
+ * the input). A duplicated triangle does not raise the count. */
+int o3dmi_mesh_bvh_count_intersections(const o3dmi_mesh_bvh_t* bvh,
+                                       const void* rays_dev, int64_t q,
+                                       int dtype, int32_t* counts_out_dev,
+                                       o3dmi_stream_t stream);
+
+/* ListIntersections: one entry per distinct t, IN ASCENDING t PER RAY, with
+ * the lowest triangle index at that t (upstream: Embree's order). The entries
+ * of ray i are [ray_splits[i], ray_splits[i + 1]). ray_splits_out_dev int64
+ * {q + 1} (optional) and *total_out = ray_splits[q] are always written;
+ * capacity < 0 only counts; 0 <= capacity < the total is O3DMI_ERR_CAPACITY
+ * with nothing else written; a total above 2^31 - 1 is
+ * O3DMI_ERR_UNSUPPORTED. The entry arrays hold `capacity` rows, each optional
+ * (NULL): ray_ids int64, t_hit, geometry_ids uint32 (0), primitive_ids uint32,
+ * primitive_uvs {.,2} (upstream: uint32 ray_splits and ray_ids). */
+int o3dmi_mesh_bvh_list_intersections(
+        const o3dmi_mesh_bvh_t* bvh, const void* rays_dev, int64_t q,
+        int dtype, int64_t* ray_splits_out_dev, int64_t capacity,
+        int64_t* total_out, int64_t* ray_ids_out_dev, void* t_hit_out_dev,
+        uint32_t* geometry_ids_out_dev, uint32_t* primitive_ids_out_dev,
+        void* primitive_uvs_out_dev, o3dmi_stream_t stream);
+
+/* VoteInsideOutside's ray directions on the host: out[3 j + k] = 1 + r, r
+ * drawn with upstream's statements (std::mt19937 gen(42),
+ * std::uniform_real_distribution<float>(-0.001, 0.001)) in the column-major
+ * order of upstream's 3 x nsamples matrix, so direction j is out[3 j .. 3 j +
+ * 2]. nsamples must be odd and >= 1, here and below. */
+int o3dmi_raycast_vote_directions(int nsamples, float* out);
+
+/* ComputeOccupancy / ComputeSignedDistance: a point is inside when more than
+ * nsamples / 2 of its rays (the point, direction j) have an odd count.
+ * Occupancy is 1 inside and 0 outside; the signed distance is the closest
+ * points' distance times -1 inside and +1 outside. The rays of a point run in
+ * neighbouring lanes of one wave and the vote is written directly:
+ * upstream's {nsamples q, 6} ray tensor and its count tensor never exist. */
+int o3dmi_mesh_bvh_compute_occupancy(const o3dmi_mesh_bvh_t* bvh,
+                                     const void* points_dev, int64_t q,
+                                     int dtype, int nsamples,
+                                     void* occupancy_out_dev,
+                                     o3dmi_stream_t stream);
+int o3dmi_mesh_bvh_compute_signed_distance(const o3dmi_mesh_bvh_t* bvh,
+                                           const void* points_dev, int64_t q,
+                                           int dtype, int nsamples,
+                                           void* distance_out_dev,
+                                           o3dmi_stream_t stream);
+
+/* CreateRaysPinhole: intrinsic (3 x 3) and extrinsic (4 x 4) are row-major
+ * HOST doubles. K^-1 (the adjugate over the determinant), R^T, C = -(R^T t)
+ * and R^T K^-1 are formed in double, every sum (x + y) + z, and narrowed
+ * once (upstream: Eigen's inverse). rays_out_dev {height, width, 6} float:
+ * C and the rows (m0 (x + 0.5) + m1 (y + 0.5)) + m2 of R^T K^-1. A matrix
+ * that is not finite or whose K is singular: O3DMI_ERR_INVALID_ARG. */
+int o3dmi_create_rays_pinhole(const double* intrinsic, const double* extrinsic,
+                              int width, int height, void* rays_out_dev,
+                              o3dmi_stream_t stream);
+
+/* The one-shot forms: build, query, free. `dtype` is that of the positions
+ * and of the rays / points. */
+int o3dmi_trianglemesh_cast_rays(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* triangles_dev, int64_t m, int index_dtype,
+        const void* rays_dev, int64_t q, void* t_hit_out_dev,
+        uint32_t* geometry_ids_out_dev, uint32_t* primitive_ids_out_dev,
+        void* primitive_uvs_out_dev, void* primitive_normals_out_dev,
+        o3dmi_stream_t stream);
+int o3dmi_trianglemesh_compute_signed_distance(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* triangles_dev, int64_t m, int index_dtype,
+        const void* points_dev, int64_t q, int nsamples,
+        void* distance_out_dev, o3dmi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

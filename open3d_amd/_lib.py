@@ -625,6 +625,27 @@ PROTOTYPES.update({
         _i32, [_vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _i32, _i32,
                C.POINTER(_i32), _i32, C.POINTER(_f), _i32, _i64, C.c_uint64,
                C.POINTER(_f), _i64, C.POINTER(MetricsRawC), _vp]),
+    # ray queries: (handle, rays, q, dtype, ...)
+    "o3dmi_mesh_bvh_cast_rays": (
+        _i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "o3dmi_mesh_bvh_test_occlusions": (
+        _i32, [_vp, _vp, _i64, _i32, _f, _f, _vp, _vp]),
+    "o3dmi_mesh_bvh_count_intersections": (
+        _i32, [_vp, _vp, _i64, _i32, _vp, _vp]),
+    "o3dmi_mesh_bvh_list_intersections": (
+        _i32, [_vp, _vp, _i64, _i32, _vp, _i64, C.POINTER(_i64), _vp, _vp,
+               _vp, _vp, _vp, _vp]),
+    "o3dmi_raycast_vote_directions": (_i32, [_i32, C.POINTER(_f)]),
+    "o3dmi_mesh_bvh_compute_occupancy": (
+        _i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "o3dmi_mesh_bvh_compute_signed_distance": (
+        _i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "o3dmi_create_rays_pinhole": (_i32, [_dp, _dp, _i32, _i32, _vp, _vp]),
+    "o3dmi_trianglemesh_cast_rays": (
+        _i32, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp,
+               _vp, _vp, _vp]),
+    "o3dmi_trianglemesh_compute_signed_distance": (
+        _i32, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp]),
 })
 
 # o3dmi_transport_t (include/o3d_mi355x_host.h): the caller-provided collectives
@@ -657,6 +678,12 @@ INTERNAL_PROTOTYPES = {
     "o3dmi_internal_mesh_bvh_query": (
         _i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32,
                C.POINTER(C.c_uint64), _vp]),
+    # csrc/mesh_bvh.h: (handle, kind, rays, q, tnear, tfar, t_hit,
+    # geometry_ids, primitive_ids, uvs, normals, occluded, counts, sort_rays,
+    # visits[2], stream)
+    "o3dmi_internal_mesh_bvh_ray_query": (
+        _i32, [_vp, _i32, _vp, _i64, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp,
+               _vp, _i32, C.POINTER(C.c_uint64), _vp]),
 }
 
 _lib = None

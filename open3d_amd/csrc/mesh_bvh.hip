@@ -2,8 +2,10 @@
 // (mesh_bvh.h). Build: the scene box, a 30-bit Morton code per triangle, the
 // stable pair sort (sort.h), a Karras radix tree over (code, sorted position)
 // and a bottom-up refit with one arrival counter per inner node. Query: one
-// lane per query, near child first, the far child on a stack in LDS. The
-// result does not depend on the tree: see the header.
+// lane per query, near child first, the far child on a stack in LDS. Ray
+// queries: the same walk with slab intervals for box distances, one template
+// with a policy per kind (closest, any, next above a given t; count, list
+// and vote iterate the last). No result depends on the tree: see the header.
 #include "mesh_bvh.h"
 
 #include "common.h"
@@ -503,6 +505,379 @@ ClosestPointKernel(MeshBvhView bvh, const float* __restrict__ queries,
     }
 }
 
+// ---- ray queries ----------------------------------------------------------------
+struct Ray {
+    float o[3], d[3];
+};
+
+__device__ __forceinline__ Ray LoadRay(const float* __restrict__ rays,
+                                       int64_t i) {
+    Ray r;
+    for (int k = 0; k < 3; ++k) {
+        r.o[k] = rays[6 * i + k];
+        r.d[k] = rays[6 * i + 3 + k];
+    }
+    return r;
+}
+
+// The slab interval [T0, T1] of the header; false when it is empty.
+__device__ __forceinline__ bool Slab(const Ray& r, const float lo[3],
+                                     const float hi[3], float tnear,
+                                     float tfar, float* T0, float* T1) {
+    float t0 = tnear, t1 = tfar;
+    bool inside = true;
+    for (int k = 0; k < 3; ++k) {
+        if (r.d[k] != 0.0f) {
+            const float a = (lo[k] - r.o[k]) / r.d[k];
+            const float b = (hi[k] - r.o[k]) / r.d[k];
+            t0 = fmaxf(t0, fminf(a, b));
+            t1 = fminf(t1, fmaxf(a, b));
+        } else if (r.o[k] < lo[k] || r.o[k] > hi[k]) {
+            inside = false;
+        }
+    }
+    *T0 = t0;
+    *T1 = t1;
+    return inside && t0 <= t1;
+}
+
+__device__ __forceinline__ void Cross3(const float x[3], const float y[3],
+                                       float out[3]) {
+    out[0] = x[1] * y[2] - x[2] * y[1];
+    out[1] = x[2] * y[0] - x[0] * y[2];
+    out[2] = x[0] * y[1] - x[1] * y[0];
+}
+
+// The pair of the header: whether it hits, and then t, u, v.
+__device__ __forceinline__ bool PairRay(const Ray& r, const Tri& tr,
+                                        float tnear, float tfar, float* t,
+                                        float* u, float* v) {
+    float e1[3], e2[3], s[3], p[3], q[3];
+    for (int k = 0; k < 3; ++k) {
+        e1[k] = tr.b[k] - tr.a[k];
+        e2[k] = tr.c[k] - tr.a[k];
+        s[k] = r.o[k] - tr.a[k];
+    }
+    Cross3(r.d, e2, p);
+    const float det = Dot3(e1, p);
+    if (det == 0.0f || det != det) return false;
+    const float inv = 1.0f / det;
+    *u = Dot3(s, p) * inv;
+    Cross3(s, e1, q);
+    *v = Dot3(r.d, q) * inv;
+    const float te = Dot3(e2, q) * inv;
+    if (!(*u >= 0.0f && *v >= 0.0f && *u + *v <= 1.0f)) return false;
+    float lo[3], hi[3], T0, T1;
+    TriBox(tr, lo, hi);
+    if (!Slab(r, lo, hi, tnear, tfar, &T0, &T1)) return false;
+    if (!(te > tnear && te <= tfar)) return false;
+    *t = fminf(fmaxf(te, T0), T1) + 0.0f;
+    return true;
+}
+
+enum RayPolicy { kPolicyClosest, kPolicyAny, kPolicyNext };
+
+struct RayBest {
+    float t;
+    uint32_t id;
+    int32_t pos;  // the winner's leaf, -1: none
+};
+
+struct RayVisits {
+    unsigned long long opened, tested;
+    bool overflow;
+};
+
+// One traversal of the tree for one ray, near child first (by T0), the far
+// child on this lane's stack (entry e at stack[e * kQueryBlock]).
+// kPolicyClosest: *best = the minimum (t, id) over the hitting pairs.
+// kPolicyNext: the same over the pairs with t > prev. kPolicyAny: returns at
+// the first hit, best->pos >= 0 then. *best comes in as {+inf, none, -1}.
+template <int POLICY, bool COUNT>
+__device__ __forceinline__ void TraverseRay(const MeshBvhView& bvh,
+                                            const Ray& r, float tnear,
+                                            float tfar, float prev,
+                                            int32_t* __restrict__ stack,
+                                            RayBest* best, RayVisits* vis) {
+    int sp = 0;
+    int32_t node = bvh.m == 1 ? ~0 : 0;
+    for (;;) {
+        bool pop = true;
+        if (node < 0) {
+            const int32_t pos = ~node;
+            const Tri tr = LoadLeaf(bvh.leaves, pos);
+            float t, u, v;
+            const bool hit = PairRay(r, tr, tnear, tfar, &t, &u, &v);
+            if (COUNT) ++vis->tested;
+            if (hit && (POLICY != kPolicyNext || t > prev)) {
+                if (POLICY == kPolicyAny) {
+                    best->pos = pos;
+                    return;
+                }
+                if (t < best->t || (t == best->t && tr.id < best->id)) {
+                    best->t = t;
+                    best->id = tr.id;
+                    best->pos = pos;
+                }
+            }
+        } else {
+            const float4* w = (const float4*)(bvh.nodes + node);
+            const float4 w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
+            const int32_t c0 = (int32_t)__float_as_uint(w0.x);
+            const int32_t c1 = (int32_t)__float_as_uint(w0.y);
+            const float lo0[3] = {w1.x, w1.y, w1.z};
+            const float hi0[3] = {w1.w, w2.x, w2.y};
+            const float lo1[3] = {w2.z, w2.w, w3.x};
+            const float hi1[3] = {w3.y, w3.z, w3.w};
+            float a0, a1, b0, b1;
+            bool go0 = Slab(r, lo0, hi0, tnear, tfar, &a0, &b0);
+            bool go1 = Slab(r, lo1, hi1, tnear, tfar, &a1, &b1);
+            if (COUNT) ++vis->opened;
+            if (POLICY != kPolicyAny) {
+                // skipped only when strictly farther than the best: a node
+                // at the best's t may hold a lower index
+                go0 = go0 && !(a0 > best->t);
+                go1 = go1 && !(a1 > best->t);
+            }
+            if (POLICY == kPolicyNext) {
+                go0 = go0 && b0 > prev;
+                go1 = go1 && b1 > prev;
+            }
+            if (go0 && go1) {
+                const bool near0 = a0 <= a1;
+                if (sp < kBvhStack) {
+                    stack[sp * kQueryBlock] = near0 ? c1 : c0;
+                    ++sp;
+                } else {
+                    vis->overflow = true;  // never, by the bound in mesh_bvh.h
+                }
+                node = near0 ? c0 : c1;
+                pop = false;
+            } else if (go0 || go1) {
+                node = go0 ? c0 : c1;
+                pop = false;
+            }
+        }
+        if (pop) {
+            if (sp == 0) return;
+            --sp;
+            node = stack[sp * kQueryBlock];
+        }
+    }
+}
+
+// The number of distinct t among the hitting pairs of r on (0, +inf].
+template <bool COUNT>
+__device__ __forceinline__ int CountRay(const MeshBvhView& bvh, const Ray& r,
+                                        int32_t* __restrict__ stack,
+                                        RayVisits* vis) {
+    int count = 0;
+    float prev = -INFINITY;
+    for (;;) {
+        RayBest best = {INFINITY, kBvhNoTriangle, -1};
+        TraverseRay<kPolicyNext, COUNT>(bvh, r, 0.0f, INFINITY, prev, stack,
+                                        &best, vis);
+        if (best.pos < 0) return count;
+        ++count;
+        prev = best.t;  // strictly above the last one: the loop ends
+    }
+}
+
+template <bool COUNT>
+__device__ __forceinline__ void FlushRayVisits(
+        const RayVisits& vis, int* __restrict__ status,
+        unsigned long long* __restrict__ visits) {
+    if (vis.overflow) atomicOr(status, 1);
+    if (COUNT) {
+        unsigned long long opened = vis.opened, tested = vis.tested;
+        for (int w = 32; w > 0; w >>= 1) {
+            opened += __shfl_xor(opened, w);
+            tested += __shfl_xor(tested, w);
+        }
+        if ((threadIdx.x & 63) == 0) {
+            atomicAdd(&visits[0], opened);
+            atomicAdd(&visits[1], tested);
+        }
+    }
+}
+
+__global__ void OriginCodesKernel(const float* __restrict__ rows, int stride,
+                                  int64_t q, MeshBvhView bvh,
+                                  uint32_t* __restrict__ keys,
+                                  uint32_t* __restrict__ vals) {
+    float scene[6];
+    for (int k = 0; k < 3; ++k) {
+        scene[k] = bvh.scene_lo[k];
+        scene[3 + k] = bvh.scene_hi[k];
+    }
+    O3DMI_GRID_STRIDE(i, q) {
+        const float p[3] = {rows[stride * i], rows[stride * i + 1],
+                            rows[stride * i + 2]};
+        keys[i] = Morton30(p, scene);
+        vals[i] = (uint32_t)i;
+    }
+}
+
+template <int KIND, bool COUNT>
+__global__ void __launch_bounds__(kQueryBlock)
+RayQueryKernel(MeshBvhView bvh, const float* __restrict__ rays,
+               const uint32_t* __restrict__ order, int64_t nq, float tnear,
+               float tfar, RayQueryOut out, int* __restrict__ status,
+               unsigned long long* __restrict__ visits) {
+    __shared__ int32_t stack_all[kBvhStack * kQueryBlock];
+    int32_t* stack = stack_all + threadIdx.x;
+    RayVisits vis = {0, 0, false};
+    O3DMI_GRID_STRIDE(slot, nq) {
+        const int64_t i = order ? (int64_t)order[slot] : slot;
+        const Ray r = LoadRay(rays, i);
+        if (KIND == kRayCount) {
+            const int count = CountRay<COUNT>(bvh, r, stack, &vis);
+            if (out.counts) out.counts[i] = count;
+            continue;
+        }
+        RayBest best = {INFINITY, kBvhNoTriangle, -1};
+        if (KIND == kRayAny) {
+            TraverseRay<kPolicyAny, COUNT>(bvh, r, tnear, tfar, 0.0f, stack,
+                                           &best, &vis);
+            if (out.occluded) out.occluded[i] = best.pos >= 0 ? 1 : 0;
+            continue;
+        }
+        TraverseRay<kPolicyClosest, COUNT>(bvh, r, tnear, tfar, 0.0f, stack,
+                                           &best, &vis);
+        float t = INFINITY, n[3] = {0, 0, 0}, u = 0, v = 0;
+        if (best.pos >= 0) {
+            const Tri tr = LoadLeaf(bvh.leaves, best.pos);
+            PairRay(r, tr, tnear, tfar, &t, &u, &v);
+            if (out.normals) {
+                // as ClosestPointKernel's
+                float e1[3], e2[3];
+                for (int k = 0; k < 3; ++k) {
+                    e1[k] = tr.b[k] - tr.a[k];
+                    e2[k] = tr.c[k] - tr.a[k];
+                }
+                Cross3(e1, e2, n);
+                const float norm = sqrtf((n[0] * n[0] + n[1] * n[1]) +
+                                         n[2] * n[2]);
+                if (norm > 0) {
+                    n[0] /= norm;
+                    n[1] /= norm;
+                    n[2] /= norm;
+                }
+            }
+        }
+        if (out.t_hit) out.t_hit[i] = t;
+        if (out.geometry_ids)
+            out.geometry_ids[i] = best.pos >= 0 ? 0u : kBvhNoTriangle;
+        if (out.primitive_ids) out.primitive_ids[i] = best.id;
+        if (out.uvs) {
+            out.uvs[2 * i] = u;
+            out.uvs[2 * i + 1] = v;
+        }
+        if (out.normals)
+            for (int k = 0; k < 3; ++k) out.normals[3 * i + k] = n[k];
+    }
+    FlushRayVisits<COUNT>(vis, status, visits);
+}
+
+__global__ void __launch_bounds__(kQueryBlock)
+RayListKernel(MeshBvhView bvh, const float* __restrict__ rays, int64_t nq,
+              const int64_t* __restrict__ splits, RayListOut out,
+              int* __restrict__ status) {
+    __shared__ int32_t stack_all[kBvhStack * kQueryBlock];
+    int32_t* stack = stack_all + threadIdx.x;
+    RayVisits vis = {0, 0, false};
+    O3DMI_GRID_STRIDE(i, nq) {
+        const Ray r = LoadRay(rays, i);
+        int64_t at = splits[i];
+        float prev = -INFINITY;
+        for (;;) {
+            RayBest best = {INFINITY, kBvhNoTriangle, -1};
+            TraverseRay<kPolicyNext, false>(bvh, r, 0.0f, INFINITY, prev,
+                                            stack, &best, &vis);
+            if (best.pos < 0) break;
+            if (out.ray_ids) out.ray_ids[at] = i;
+            if (out.t_hit) out.t_hit[at] = best.t;
+            if (out.geometry_ids) out.geometry_ids[at] = 0u;
+            if (out.primitive_ids) out.primitive_ids[at] = best.id;
+            if (out.uvs) {
+                const Tri tr = LoadLeaf(bvh.leaves, best.pos);
+                float t, u = 0, v = 0;
+                PairRay(r, tr, 0.0f, INFINITY, &t, &u, &v);
+                out.uvs[2 * at] = u;
+                out.uvs[2 * at + 1] = v;
+            }
+            ++at;
+            prev = best.t;
+        }
+    }
+    FlushRayVisits<false>(vis, status, nullptr);
+}
+
+// A point's rays go to `lanes` = min(nsamples, kVoteLanes) neighbouring lanes
+// of one wave (lane k of them takes the directions k, k + lanes, ...), and
+// the first of them adds up their odd counts by shuffles. The rays of a point
+// share their origin and nearly their direction, so the lanes walk the tree
+// together; one lane running them in turn took twice as long as a count
+// query over the {nsamples q, 6} ray tensor.
+constexpr int kVoteLanes = 8;
+constexpr int kVoteWaves = kQueryBlock / 64;
+
+// How many points one workgroup takes in a pass.
+inline __host__ __device__ int VotePointsPerBlock(int lanes) {
+    return kVoteWaves * (64 / lanes);
+}
+
+__global__ void __launch_bounds__(kQueryBlock)
+RayVoteKernel(MeshBvhView bvh, const float* __restrict__ points, int64_t nq,
+              const float* __restrict__ dirs, int nsamples, int lanes,
+              float* __restrict__ occupancy, float* __restrict__ distance,
+              int* __restrict__ status) {
+    __shared__ int32_t stack_all[kBvhStack * kQueryBlock];
+    int32_t* stack = stack_all + threadIdx.x;
+    RayVisits vis = {0, 0, false};
+    const int per_wave = 64 / lanes, per_block = VotePointsPerBlock(lanes);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int slot = lane / lanes, first = lane % lanes;
+    // every lane of a wave makes the same number of passes: the shuffles
+    // below see all of them
+    for (int64_t base = (int64_t)blockIdx.x * per_block; base < nq;
+         base += (int64_t)gridDim.x * per_block) {
+        const int64_t i = base + wave * per_wave + slot;
+        const bool mine = slot < per_wave && i < nq;
+        int odd = 0;
+        if (mine) {
+            Ray r;
+            for (int k = 0; k < 3; ++k) r.o[k] = points[3 * i + k];
+            for (int j = first; j < nsamples; j += lanes) {
+                for (int k = 0; k < 3; ++k) r.d[k] = dirs[3 * j + k];
+                odd += CountRay<false>(bvh, r, stack, &vis) & 1;
+            }
+        }
+        int votes = odd;
+        for (int k = 1; k < lanes; ++k) votes += __shfl_down(odd, k);
+        if (mine && first == 0) {
+            const bool inside = votes > nsamples / 2;
+            if (occupancy) occupancy[i] = inside ? 1.0f : 0.0f;
+            if (distance) distance[i] = distance[i] * (inside ? -1.0f : 1.0f);
+        }
+    }
+    FlushRayVisits<false>(vis, status, nullptr);
+}
+
+__global__ void PinholeRaysKernel(PinholeFrame f, int width, int64_t n,
+                                  float* __restrict__ rays) {
+    O3DMI_GRID_STRIDE(i, n) {
+        const float px = (float)(int)(i % width) + 0.5f;
+        const float py = (float)(int)(i / width) + 0.5f;
+        for (int k = 0; k < 3; ++k) {
+            rays[6 * i + k] = f.centre[k];
+            rays[6 * i + 3 + k] =
+                    (f.dir[3 * k] * px + f.dir[3 * k + 1] * py) +
+                    f.dir[3 * k + 2];
+        }
+    }
+}
+
 }  // namespace
 
 size_t MeshBvhBuildScratchBytes(int64_t m) {
@@ -577,6 +952,113 @@ int MeshBvhQueryAsync(const MeshBvhView& bvh, const float* queries_dev,
         hipLaunchKernelGGL(ClosestPointKernel<false>, grid, block, 0, s, bvh,
                            queries_dev, order, q, out, status_dev, visits_dev);
     O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
+namespace {
+
+inline dim3 RayGrid(int64_t q) {
+    return dim3((unsigned)GridFor(q, kQueryBlock, kCUs * 16));
+}
+
+template <int KIND>
+void LaunchRayQuery(const MeshBvhView& bvh, const float* rays,
+                    const uint32_t* order, int64_t q, float tnear, float tfar,
+                    const RayQueryOut& out, int* status,
+                    unsigned long long* visits, hipStream_t s) {
+    if (visits)
+        hipLaunchKernelGGL((RayQueryKernel<KIND, true>), RayGrid(q),
+                           dim3(kQueryBlock), 0, s, bvh, rays, order, q, tnear,
+                           tfar, out, status, visits);
+    else
+        hipLaunchKernelGGL((RayQueryKernel<KIND, false>), RayGrid(q),
+                           dim3(kQueryBlock), 0, s, bvh, rays, order, q, tnear,
+                           tfar, out, status, visits);
+}
+
+}  // namespace
+
+int MeshBvhRayQueryAsync(const MeshBvhView& bvh, RayQueryKind kind,
+                         const float* rays_dev, int64_t q, float tnear,
+                         float tfar, const RayQueryOut& out, bool sort_rays,
+                         void* scratch_dev, int* status_dev,
+                         unsigned long long* visits_dev, hipStream_t s) {
+    O3DMI_REQUIRE(bvh.leaves && bvh.m > 0 && (bvh.m == 1 || bvh.nodes) &&
+                          rays_dev && q > 0 && status_dev,
+                  "null argument");
+    O3DMI_REQUIRE(!sort_rays || scratch_dev, "null argument");
+    O3DMI_REQUIRE(tnear == tnear && tfar == tfar, "tnear / tfar is NaN");
+    const uint32_t* order = nullptr;
+    if (sort_rays) {
+        char* base = (char*)scratch_dev;
+        uint32_t* keys = (uint32_t*)base;
+        uint32_t* vals =
+                (uint32_t*)(base + Align256(sizeof(uint32_t) * (size_t)q));
+        void* sort_scratch =
+                base + 2 * Align256(sizeof(uint32_t) * (size_t)q);
+        O3DMI_LAUNCH(OriginCodesKernel, q, rays_dev, 6, q, bvh, keys, vals);
+        const int st =
+                SortPairsAsync(keys, vals, q, kBvhMortonBits, sort_scratch, s);
+        if (st) return st;
+        order = vals;
+    }
+    switch (kind) {
+        case kRayClosest:
+            LaunchRayQuery<kRayClosest>(bvh, rays_dev, order, q, tnear, tfar,
+                                        out, status_dev, visits_dev, s);
+            break;
+        case kRayAny:
+            LaunchRayQuery<kRayAny>(bvh, rays_dev, order, q, tnear, tfar, out,
+                                    status_dev, visits_dev, s);
+            break;
+        case kRayCount:
+            LaunchRayQuery<kRayCount>(bvh, rays_dev, order, q, 0.0f, INFINITY,
+                                      out, status_dev, visits_dev, s);
+            break;
+        default:
+            O3DMI_REQUIRE(false, "unknown ray query kind");
+    }
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
+int MeshBvhRayListAsync(const MeshBvhView& bvh, const float* rays_dev,
+                        int64_t q, const int64_t* splits_dev,
+                        const RayListOut& out, int* status_dev,
+                        hipStream_t s) {
+    O3DMI_REQUIRE(bvh.leaves && bvh.m > 0 && (bvh.m == 1 || bvh.nodes) &&
+                          rays_dev && q > 0 && splits_dev && status_dev,
+                  "null argument");
+    hipLaunchKernelGGL(RayListKernel, RayGrid(q), dim3(kQueryBlock), 0, s, bvh,
+                       rays_dev, q, splits_dev, out, status_dev);
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
+int MeshBvhVoteAsync(const MeshBvhView& bvh, const float* points_dev,
+                     int64_t q, const float* dirs_dev, int nsamples,
+                     float* occupancy_out_dev, float* distance_io_dev,
+                     int* status_dev, hipStream_t s) {
+    O3DMI_REQUIRE(bvh.leaves && bvh.m > 0 && (bvh.m == 1 || bvh.nodes) &&
+                          points_dev && q > 0 && dirs_dev && status_dev,
+                  "null argument");
+    O3DMI_REQUIRE(nsamples >= 1 && (nsamples & 1),
+                  "nsamples must be odd and >= 1");
+    const int lanes = nsamples < kVoteLanes ? nsamples : kVoteLanes;
+    const dim3 grid(
+            (unsigned)GridFor(q, VotePointsPerBlock(lanes), kCUs * 16));
+    hipLaunchKernelGGL(RayVoteKernel, grid, dim3(kQueryBlock), 0, s, bvh,
+                       points_dev, q, dirs_dev, nsamples, lanes,
+                       occupancy_out_dev, distance_io_dev, status_dev);
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
+int CreateRaysPinholeAsync(const PinholeFrame& frame, int width, int height,
+                           float* rays_out_dev, hipStream_t s) {
+    O3DMI_REQUIRE(width > 0 && height > 0 && rays_out_dev, "null argument");
+    const int64_t n = (int64_t)width * height;
+    O3DMI_LAUNCH(PinholeRaysKernel, n, frame, width, n, rays_out_dev);
     return O3DMI_OK;
 }
 

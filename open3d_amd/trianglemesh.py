@@ -2,8 +2,8 @@
 connectivity methods (t/geometry/TriangleMesh.cpp:198-404, 1221-1452,
 1826-1864), of legacy ClusterConnectedTriangles (geometry/TriangleMesh.cpp:
 1459-1528), of SamplePointsUniformly and ComputeMetrics (t/geometry/
-TriangleMesh.cpp:1866-1967) and of RaycastingScene's closest-point queries for
-one mesh (MeshBVH) on the HIP backend.
+TriangleMesh.cpp:1866-1967) and of RaycastingScene's closest-point and ray
+queries for one mesh (MeshBVH, create_rays_pinhole) on the HIP backend.
 
 A mesh is the dict VoxelBlockGrid.extract_triangle_mesh returns: "positions"
 ({V,3} Float32 or Float64) and "indices" ({M,3} Int32 or Int64) on the device,
@@ -342,10 +342,10 @@ def sample_points_uniformly(mesh, number_of_points, use_triangle_normal=False,
 
 
 class MeshBVH:
-    """The closest-point queries of RaycastingScene for one triangle mesh
-    (Float32): a linear BVH on the device that owns its copies of the mesh.
-    The answer to a query is the minimum over all triangles, the lowest index
-    on ties, whatever the tree."""
+    """The closest-point and ray queries of RaycastingScene for one triangle
+    mesh (Float32): a linear BVH on the device that owns its copies of the
+    mesh. The answer to a query is the minimum over all triangles, the lowest
+    index on ties, whatever the tree."""
 
     def __init__(self, mesh):
         p, t, args = _mesh_args(mesh)
@@ -405,6 +405,139 @@ class MeshBVH:
             self._handle, _lib.ptr(flat), q, TORCH_TO_O3DMI[flat.dtype], None,
             None, None, None, _lib.ptr(dist), stream()), "compute_distance")
         return dist.reshape(lead)
+
+    # ---- ray queries: pure functions of (mesh, ray), see the C header ------
+    def _rays(self, rays):
+        rays = require_cuda(rays, "rays")
+        if rays.dim() < 1 or rays.shape[-1] != 6:
+            raise ValueError("rays must have shape {..., 6}")
+        return rays.reshape(-1, 6).contiguous(), tuple(rays.shape[:-1])
+
+    def cast_rays(self, rays):
+        """RaycastingScene::CastRays -> dict(t_hit {..}, geometry_ids {..},
+        primitive_ids {..} uint32, primitive_uvs {..,2}, primitive_normals
+        {..,3}): the smallest t, the lowest triangle index among equals; a
+        miss is t_hit inf and INVALID_ID."""
+        flat, lead = self._rays(rays)
+        q, dev = flat.shape[0], flat.device
+        out = {
+            "t_hit": torch.empty(q, dtype=torch.float32, device=dev),
+            "geometry_ids": torch.empty(q, dtype=torch.uint32, device=dev),
+            "primitive_ids": torch.empty(q, dtype=torch.uint32, device=dev),
+            "primitive_uvs": torch.empty((q, 2), dtype=torch.float32,
+                                         device=dev),
+            "primitive_normals": torch.empty((q, 3), dtype=torch.float32,
+                                             device=dev),
+        }
+        _lib.check(_lib.lib().o3dmi_mesh_bvh_cast_rays(
+            self._handle, _lib.ptr(flat), q, TORCH_TO_O3DMI[flat.dtype],
+            _lib.ptr(out["t_hit"]), _lib.ptr(out["geometry_ids"]),
+            _lib.ptr(out["primitive_ids"]), _lib.ptr(out["primitive_uvs"]),
+            _lib.ptr(out["primitive_normals"]), stream()), "cast_rays")
+        return {k: v.reshape(lead + tuple(v.shape[1:]))
+                for k, v in out.items()}
+
+    def test_occlusions(self, rays, tnear=0.0, tfar=float("inf")):
+        """RaycastingScene::TestOcclusions -> {..} bool: whether anything is
+        hit on (tnear, tfar]."""
+        flat, lead = self._rays(rays)
+        q = flat.shape[0]
+        out = torch.empty(q, dtype=torch.uint8, device=flat.device)
+        _lib.check(_lib.lib().o3dmi_mesh_bvh_test_occlusions(
+            self._handle, _lib.ptr(flat), q, TORCH_TO_O3DMI[flat.dtype],
+            float(tnear), float(tfar), _lib.ptr(out), stream()),
+            "test_occlusions")
+        return out.to(torch.bool).reshape(lead)
+
+    def count_intersections(self, rays):
+        """RaycastingScene::CountIntersections -> {..} int32: the number of
+        distinct t at which the ray meets the mesh."""
+        flat, lead = self._rays(rays)
+        q = flat.shape[0]
+        out = torch.empty(q, dtype=torch.int32, device=flat.device)
+        _lib.check(_lib.lib().o3dmi_mesh_bvh_count_intersections(
+            self._handle, _lib.ptr(flat), q, TORCH_TO_O3DMI[flat.dtype],
+            _lib.ptr(out), stream()), "count_intersections")
+        return out.reshape(lead)
+
+    def list_intersections(self, rays):
+        """RaycastingScene::ListIntersections -> dict(ray_splits {R+1} int64,
+        ray_ids {N} int64, t_hit {N}, geometry_ids {N}, primitive_ids {N}
+        uint32, primitive_uvs {N,2}), the entries of a ray in ascending t."""
+        flat, _ = self._rays(rays)
+        q, dev = flat.shape[0], flat.device
+        splits = torch.empty(q + 1, dtype=torch.int64, device=dev)
+        total = C.c_int64(0)
+        head = (self._handle, _lib.ptr(flat), q, TORCH_TO_O3DMI[flat.dtype],
+                _lib.ptr(splits))
+        _lib.check(_lib.lib().o3dmi_mesh_bvh_list_intersections(
+            *head, -1, C.byref(total), None, None, None, None, None,
+            stream()), "list_intersections")
+        n = total.value
+        out = {
+            "ray_splits": splits,
+            "ray_ids": torch.empty(n, dtype=torch.int64, device=dev),
+            "t_hit": torch.empty(n, dtype=torch.float32, device=dev),
+            "geometry_ids": torch.empty(n, dtype=torch.uint32, device=dev),
+            "primitive_ids": torch.empty(n, dtype=torch.uint32, device=dev),
+            "primitive_uvs": torch.empty((n, 2), dtype=torch.float32,
+                                         device=dev),
+        }
+        if n:
+            _lib.check(_lib.lib().o3dmi_mesh_bvh_list_intersections(
+                *head, n, C.byref(total), _lib.ptr(out["ray_ids"]),
+                _lib.ptr(out["t_hit"]), _lib.ptr(out["geometry_ids"]),
+                _lib.ptr(out["primitive_ids"]),
+                _lib.ptr(out["primitive_uvs"]), stream()),
+                "list_intersections")
+        return out
+
+    def compute_occupancy(self, points, nsamples=1):
+        """RaycastingScene::ComputeOccupancy -> {..} Float32, 1 inside and 0
+        outside by the vote of nsamples (odd) rays per point."""
+        flat, lead = self._queries(points)
+        q = flat.shape[0]
+        out = torch.empty(q, dtype=torch.float32, device=flat.device)
+        _lib.check(_lib.lib().o3dmi_mesh_bvh_compute_occupancy(
+            self._handle, _lib.ptr(flat), q, TORCH_TO_O3DMI[flat.dtype],
+            int(nsamples), _lib.ptr(out), stream()), "compute_occupancy")
+        return out.reshape(lead)
+
+    def compute_signed_distance(self, points, nsamples=1):
+        """RaycastingScene::ComputeSignedDistance -> {..} Float32: the
+        distance, negative inside."""
+        flat, lead = self._queries(points)
+        q = flat.shape[0]
+        out = torch.empty(q, dtype=torch.float32, device=flat.device)
+        _lib.check(_lib.lib().o3dmi_mesh_bvh_compute_signed_distance(
+            self._handle, _lib.ptr(flat), q, TORCH_TO_O3DMI[flat.dtype],
+            int(nsamples), _lib.ptr(out), stream()),
+            "compute_signed_distance")
+        return out.reshape(lead)
+
+
+INVALID_ID = 0xFFFFFFFF  # RaycastingScene::INVALID_ID
+
+
+def create_rays_pinhole(intrinsic, extrinsic, width, height, device="cuda"):
+    """RaycastingScene::CreateRaysPinhole -> {height, width, 6} Float32 rays
+    on the device from a 3x3 intrinsic and a 4x4 extrinsic matrix (host
+    tensors or nested lists)."""
+    # nested lists of Python floats are doubles: not through torch's float32
+    k = torch.as_tensor(intrinsic, dtype=torch.float64).detach().cpu()
+    e = torch.as_tensor(extrinsic, dtype=torch.float64).detach().cpu()
+    if tuple(k.shape) != (3, 3) or tuple(e.shape) != (4, 4):
+        raise ValueError("intrinsic must be {3,3} and extrinsic {4,4}")
+    k, e = k.contiguous(), e.contiguous()
+    width, height = int(width), int(height)
+    if width <= 0 or height <= 0:
+        raise ValueError("width and height must be positive")
+    rays = torch.empty((height, width, 6), dtype=torch.float32, device=device)
+    _lib.check(_lib.lib().o3dmi_create_rays_pinhole(
+        C.cast(k.data_ptr(), C.POINTER(C.c_double)),
+        C.cast(e.data_ptr(), C.POINTER(C.c_double)), width, height,
+        _lib.ptr(rays), stream()), "create_rays_pinhole")
+    return rays
 
 
 def compute_metrics(mesh1, mesh2, metrics, fscore_radius=(0.01,),

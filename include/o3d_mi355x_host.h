@@ -2277,6 +2277,158 @@ int o3dmi_trianglemesh_compute_signed_distance(
         const void* points_dev, int64_t q, int nsamples,
         void* distance_out_dev, o3dmi_stream_t stream);
 
+/* ---- TriangleMesh clean-up, smoothing filters and vertex clustering ----------
+ * (legacy geometry/TriangleMesh.cpp:153-440 and 680-860, Smoothing.h:29-65,
+ * TriangleMeshSimplification.cpp:72-244. Upstream has these as sequential host
+ * loops of the legacy class only.) The rules of the TriangleMesh operators
+ * above hold: the triangle indices are range-checked on the device before
+ * anything is written, v < 2^31 (v < 2^30 where a vertex table is built:
+ * remove_duplicated_vertices, simplify_vertex_clustering), m <= 2^29, all
+ * synchronise. The filters and the clustering refuse a NaN / Inf position with
+ * O3DMI_ERR_INVALID_ARG and the outputs untouched. Vertex normals and colours,
+ * where taken, are {v,3} of attr_dtype, which must be the position dtype:
+ * another one is O3DMI_ERR_UNSUPPORTED.
+ *
+ * The de-duplications share one table: rep[i] = THE LOWEST INDEX j <= i WHOSE
+ * KEY EQUALS KEY i, a pure function of the input whatever the arrival order
+ * (equal keys meet in one slot of an open-addressing table of indices and keep
+ * the lowest with an integer atomic minimum). The first occurrence of a key is
+ * kept, as legacy's loops keep it. */
+
+/* Legacy RemoveDuplicatedVertices. The key is the coordinate triple by VALUE
+ * (std::tuple<double, double, double> equality; Float32 widens exactly): -0
+ * equals +0, and a row with a NaN coordinate equals nothing, itself included,
+ * so it is kept. vertex_mask_out_dev uint8 {v}: 1 = first occurrence (kept
+ * vertices keep ascending index; compact the attribute rows with
+ * o3dmi_pointcloud_select_by_mask). triangles_out_dev {m,3} in the index
+ * dtype: the triangles, in order, remapped through index_old_to_new[i] =
+ * rank(rep[i]). */
+int o3dmi_trianglemesh_remove_duplicated_vertices(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* triangles_dev, int64_t m, int index_dtype,
+        uint8_t* vertex_mask_out_dev, void* triangles_out_dev,
+        int64_t* n_vertices_out, o3dmi_stream_t stream);
+
+/* Legacy RemoveDuplicatedTriangles. The key is the index triple rotated by
+ * legacy's branch statements (TriangleMesh.cpp:744-760, ties included):
+ * t0 <= t1 ? (t0 <= t2 ? (t0,t1,t2) : (t2,t0,t1))
+ *          : (t1 <= t2 ? (t1,t2,t0) : (t2,t0,t1)).
+ * Orientation is kept: (0,1,2), (1,2,0), (2,0,1) are one key, (0,2,1) another.
+ * tri_mask_out_dev uint8 {m}: 1 = first occurrence; triangles_out_dev: the kept
+ * rows in input order, unchanged, in the index dtype. */
+int o3dmi_trianglemesh_remove_duplicated_triangles(
+        const void* triangles_dev, int64_t m, int index_dtype, int64_t v,
+        uint8_t* tri_mask_out_dev, void* triangles_out_dev,
+        int64_t* n_triangles_out, o3dmi_stream_t stream);
+
+/* Legacy RemoveDegenerateTriangles: keeps t0 != t1 && t1 != t2 && t2 != t0
+ * (indices only, as legacy). Outputs as above. */
+int o3dmi_trianglemesh_remove_degenerate_triangles(
+        const void* triangles_dev, int64_t m, int index_dtype, int64_t v,
+        uint8_t* tri_mask_out_dev, void* triangles_out_dev,
+        int64_t* n_triangles_out, o3dmi_stream_t stream);
+
+/* Legacy ComputeAdjacencyList as CSR: the neighbours of vertex u are
+ * neighbours_out_dev[row_splits[u] .. row_splits[u + 1]) in the index dtype,
+ * IN ASCENDING INDEX WITHOUT REPEATS (upstream: an unordered_set's order).
+ * The set is that of legacy's six inserts per triangle: a triangle (6,6,7)
+ * makes 6 its own neighbour. Built from the unique (lo, hi) runs of the edge
+ * table of o3dmi_trianglemesh_get_non_manifold_edges and one more pair sort
+ * by hi. row_splits_out_dev int64 {v + 1}. *n_entries_out is always set;
+ * capacity < 0 only counts and 0 <= capacity < the number is
+ * O3DMI_ERR_CAPACITY, both with nothing written. */
+int o3dmi_trianglemesh_compute_adjacency_list(
+        const void* triangles_dev, int64_t m, int index_dtype, int64_t v,
+        int64_t* row_splits_out_dev, void* neighbours_out_dev,
+        int64_t capacity, int64_t* n_entries_out, o3dmi_stream_t stream);
+
+/* The four filters share one driver. The arithmetic is legacy's, float64
+ * throughout: the inputs are widened on load, the buffers between passes are
+ * float64 and the result is narrowed once at the end, so a Float64 mesh
+ * reproduces the legacy statements bit for bit GIVEN THE NEIGHBOUR ORDER,
+ * which is pinned to ascending index: every sum is ((0 + x_a) + x_b) + ...
+ * over the adjacency list above, without contraction or float atomics.
+ *   sharpen    next = prev + strength * (prev * nb - sum)       (:192-233)
+ *   simple     next = (prev + sum) / (1 + nb)                   (:263-300)
+ *     with sum the neighbours' values and nb the list length as a double;
+ *   laplacian  per neighbour dist = sqrt((dx dx + dy dy) + dz dz) on the
+ *              CURRENT positions, w = 1.0 / (dist + 1e-12), total += w,
+ *              sum += w * x_nb (a multiply, then an add);
+ *              next = prev + factor * (sum / total - prev) when total > 0,
+ *              else prev                    (Smoothing.h:44-62, :336-342)
+ *   taubin     per iteration the laplacian pass with lambda, then with mu; the
+ *              second weighs with the positions the first one made.
+ * scope is upstream's FilterScope: 0 All, 1 Color, 2 Normal, 3 Vertex.
+ * normals_dev / colors_dev may be NULL (the mesh has none); an output is
+ * needed for every input given and may not overlap any input. DIFFERENCES
+ * FROM UPSTREAM: an attribute outside the scope is copied unchanged and the
+ * weights always use the current positions (upstream leaves such vectors
+ * unwritten and, for the Normal / Color scopes with several iterations, swaps
+ * them into the weight positions); iterations <= 0 returns a copy (upstream:
+ * unwritten vectors). */
+int o3dmi_trianglemesh_filter_sharpen(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* normals_dev, const void* colors_dev, int attr_dtype,
+        const void* triangles_dev, int64_t m, int index_dtype, int iterations,
+        double strength, int scope, void* positions_out_dev,
+        void* normals_out_dev, void* colors_out_dev, o3dmi_stream_t stream);
+int o3dmi_trianglemesh_filter_smooth_simple(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* normals_dev, const void* colors_dev, int attr_dtype,
+        const void* triangles_dev, int64_t m, int index_dtype, int iterations,
+        int scope, void* positions_out_dev, void* normals_out_dev,
+        void* colors_out_dev, o3dmi_stream_t stream);
+int o3dmi_trianglemesh_filter_smooth_laplacian(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* normals_dev, const void* colors_dev, int attr_dtype,
+        const void* triangles_dev, int64_t m, int index_dtype, int iterations,
+        double lambda_filter, int scope, void* positions_out_dev,
+        void* normals_out_dev, void* colors_out_dev, o3dmi_stream_t stream);
+int o3dmi_trianglemesh_filter_smooth_taubin(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* normals_dev, const void* colors_dev, int attr_dtype,
+        const void* triangles_dev, int64_t m, int index_dtype, int iterations,
+        double lambda_filter, double mu, int scope, void* positions_out_dev,
+        void* normals_out_dev, void* colors_out_dev, o3dmi_stream_t stream);
+
+/* Legacy SimplifyVertexClustering. min_bound = GetMinBound() - 0.5 *
+ * voxel_size in float64 from the positions widened; a vertex's voxel is
+ * int(floor((p - min_bound) / voxel_size)) per axis. voxel_size <= 0 (or not
+ * finite), or voxel_size * INT_MAX < the largest extent of the padded bounds
+ * (upstream's own check): O3DMI_ERR_INVALID_ARG. A cluster's new index is the
+ * rank of its first vertex in vertex order (legacy's voxel_vert_ind); its
+ * members are listed in ascending old index by a stable pair sort.
+ *   contraction 0 (Average): the float64 sum of the members in that order,
+ *     divided by their number, for positions, normals and colours (upstream:
+ *     its unordered_set's order; equal to rounding).
+ *   contraction 1 (Quadric): for each member in order, each triangle that
+ *     names it in ascending triangle index, once per member, adds
+ *     Quadric(plane, area): plane is ComputeTrianglePlane statement for
+ *     statement (TriangleMesh.cpp:1248-1262, every dot product (x x + y y) +
+ *     z z, the zero plane when the norm is 0), area the float64 triangle area
+ *     of o3dmi_trianglemesh_cluster_connected_triangles, A_ij += (w n_i) n_j,
+ *     b_i += (w d) n_i. With det = a00 (a11 a22 - a12 a21) - a01 (a10 a22 -
+ *     a12 a20) + a02 (a10 a21 - a11 a20) and C the cofactor matrix from the
+ *     same products, |det| > 1e-4 gives x_i = -((C_i0 b0 + C_i1 b1) + C_i2 b2)
+ *     / det (upstream: Eigen's pivoted LDLT; equal to rounding), else the
+ *     Average. Normals and colours are averaged either way.
+ * Triangles: the three vertices mapped; a triangle with two equal new indices
+ * is dropped; the rest is rotated by legacy's statements (:217-227) and the
+ * first occurrence of each triple is kept in input order (upstream: its
+ * unordered_set's order). Opposite orientations both stay. Outputs are sized
+ * by the input: positions_out_dev / normals_out_dev / colors_out_dev {v,3}
+ * (the first *n_vertices_out rows are written), triangles_out_dev {m,3} in the
+ * index dtype (the first *n_triangles_out rows). normals_dev / colors_dev may
+ * be NULL; an output is needed for every input given. */
+int o3dmi_trianglemesh_simplify_vertex_clustering(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* normals_dev, const void* colors_dev, int attr_dtype,
+        const void* triangles_dev, int64_t m, int index_dtype,
+        double voxel_size, int contraction, void* positions_out_dev,
+        void* normals_out_dev, void* colors_out_dev, void* triangles_out_dev,
+        int64_t* n_vertices_out, int64_t* n_triangles_out,
+        o3dmi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

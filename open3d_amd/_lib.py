@@ -606,6 +606,32 @@ PROTOTYPES.update({
                C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "o3dmi_trianglemesh_remove_unreferenced_vertices": (
         _i32, [_vp, _i64, _i32, _i64, _vp, _vp, C.POINTER(_i64), _vp]),
+    "o3dmi_trianglemesh_remove_duplicated_vertices": (
+        _i32, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp, C.POINTER(_i64),
+               _vp]),
+    "o3dmi_trianglemesh_remove_duplicated_triangles": (
+        _i32, [_vp, _i64, _i32, _i64, _vp, _vp, C.POINTER(_i64), _vp]),
+    "o3dmi_trianglemesh_remove_degenerate_triangles": (
+        _i32, [_vp, _i64, _i32, _i64, _vp, _vp, C.POINTER(_i64), _vp]),
+    "o3dmi_trianglemesh_compute_adjacency_list": (
+        _i32, [_vp, _i64, _i32, _i64, _vp, _vp, _i64, C.POINTER(_i64), _vp]),
+    # (positions, v, dtype, normals, colors, attr_dtype, triangles, m,
+    # index_dtype, iterations, ...)
+    "o3dmi_trianglemesh_filter_sharpen": (
+        _i32, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _d,
+               _i32, _vp, _vp, _vp, _vp]),
+    "o3dmi_trianglemesh_filter_smooth_simple": (
+        _i32, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _i32,
+               _vp, _vp, _vp, _vp]),
+    "o3dmi_trianglemesh_filter_smooth_laplacian": (
+        _i32, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _d,
+               _i32, _vp, _vp, _vp, _vp]),
+    "o3dmi_trianglemesh_filter_smooth_taubin": (
+        _i32, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _d, _d,
+               _i32, _vp, _vp, _vp, _vp]),
+    "o3dmi_trianglemesh_simplify_vertex_clustering": (
+        _i32, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _d, _i32,
+               _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "o3dmi_mesh_sample_draw": (
         _i32, [C.c_uint64, _i64, _dp, C.POINTER(_f), C.POINTER(_f)]),
     "o3dmi_trianglemesh_sample_points_uniformly": (

@@ -1,5 +1,6 @@
-// The call scaffold the TriangleMesh drivers (trianglemesh.cpp, mesh_bvh.cpp)
-// share: the size and dtype checks and the checked int32 triangle list.
+// The call scaffold the TriangleMesh drivers (trianglemesh.cpp, mesh_bvh.cpp,
+// trianglemesh_clean.cpp, trianglemesh_filter.cpp) share: the size and dtype
+// checks and the checked int32 triangle list.
 #pragma once
 
 #include "../trianglemesh.h"
@@ -42,6 +43,20 @@ inline int LoadTriangles(PoolScratch& pool, Words* w, const void* triangles_dev,
     O3DMI_HIP_CHECK(hipStreamSynchronize(pool.s));
     O3DMI_REQUIRE(!bad, "triangle index outside [0, v)");
     *tri = narrowed ? narrowed : (const int32_t*)triangles_dev;
+    return O3DMI_OK;
+}
+
+// The optional {v,3} attributes of the filters and the clustering.
+inline int CheckVertexAttrs(int dtype, int attr_dtype, const void* normals_dev,
+                     const void* colors_dev, const void* normals_out_dev,
+                     const void* colors_out_dev) {
+    if ((normals_dev || colors_dev) && attr_dtype != dtype)
+        return Unsupported(
+                "vertex normals and colours must have the position dtype");
+    O3DMI_REQUIRE(!normals_dev || normals_out_dev,
+                  "null argument: normals given, no output for them");
+    O3DMI_REQUIRE(!colors_dev || colors_out_dev,
+                  "null argument: colours given, no output for them");
     return O3DMI_OK;
 }
 

@@ -7,8 +7,8 @@
 //                  kept rows stay in input order (the scan decides the row, no
 //                  atomics), so the result is the same on every run
 //   non-finite     one pass
-//   duplicates     open-addressing table of point INDICES keyed by the bit
-//                  pattern of the point (the block hash holds keys within
+//   duplicates     rep_table.h: open-addressing table of point INDICES keyed by
+//                  the bit pattern of the point (the block hash holds keys within
 //                  +-2^20 only); equal keys meet in one slot and keep the
 //                  lowest index with atomicMin, so the survivor of a key does
 //                  not depend on which thread came first
@@ -25,6 +25,7 @@
 
 #include "common.h"
 #include "reduce_sums.h"
+#include "rep_table.h"
 #include "scan.h"
 
 namespace o3dmi {
@@ -94,72 +95,28 @@ struct NonFinitePred {
 };
 
 // ---- duplicates -----------------------------------------------------------------
-template <typename W> struct KeyOf;
-template <> struct KeyOf<float> { using word = uint32_t; };
-template <> struct KeyOf<double> { using word = uint64_t; };
-
-__device__ __forceinline__ uint32_t Fold(uint32_t w) { return w; }
-__device__ __forceinline__ uint32_t Fold(uint64_t w) {
-    return (uint32_t)w ^ ((uint32_t)(w >> 32) * 0x9E3779B1u);
-}
-
+// The bit pattern of the point as the key of rep_table.h's table.
 template <typename W>
-__device__ __forceinline__ uint32_t HashKey(W x, W y, W z) {
-    uint32_t h = Fold(x) * 0x9E3779B1u;
-    h ^= (Fold(y) * 0x85EBCA77u) + (h >> 15);
-    h ^= (Fold(z) * 0xC2B2AE3Du) + (h << 11);
-    h ^= h >> 16;
-    h *= 0x85EBCA6Bu;
-    h ^= h >> 13;
-    h *= 0xC2B2AE35u;
-    h ^= h >> 16;
-    return h;
-}
-
-// A slot's key never changes once it is claimed (atomicMin only swaps in
-// another point of the same key), so a probe sequence means the same on every
-// thread and in both launches.
-template <typename W>
-__global__ void DuplicateInsertKernel(const W* __restrict__ p, int64_t n,
-                                      int32_t* __restrict__ table,
-                                      uint32_t slot_mask) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        const W x = p[3 * i + 0], y = p[3 * i + 1], z = p[3 * i + 2];
-        uint32_t h = HashKey(x, y, z) & slot_mask;
-        for (;;) {
-            const int32_t prev = atomicCAS(&table[h], -1, (int32_t)i);
-            if (prev == -1) break;
-            const W* q = p + 3 * (int64_t)prev;
-            if (q[0] == x && q[1] == y && q[2] == z) {
-                atomicMin(&table[h], (int32_t)i);
-                break;
-            }
-            h = (h + 1) & slot_mask;
-        }
+struct PointBitKeys {
+    using Word = W;
+    const W* p;
+    __device__ __forceinline__ int operator()(int64_t i, W k[3]) const {
+        k[0] = p[3 * i + 0];
+        k[1] = p[3 * i + 1];
+        k[2] = p[3 * i + 2];
+        return kKeyed;
     }
-}
+};
 
 template <typename W>
 struct DuplicatePred {
-    const W* p;
+    PointBitKeys<W> keys;
     const int32_t* table;
     uint32_t slot_mask;
     __device__ __forceinline__ bool operator()(int64_t i) const {
-        const W x = p[3 * i + 0], y = p[3 * i + 1], z = p[3 * i + 2];
-        uint32_t h = HashKey(x, y, z) & slot_mask;
-        bool keep = false;
-        for (;;) {
-            const int32_t res = table[h];
-            if (res < 0) break;  // unreachable: i was inserted
-            const W* q = p + 3 * (int64_t)res;
-            if (q[0] == x && q[1] == y && q[2] == z) {
-                keep = res == (int32_t)i;
-                break;
-            }
-            h = (h + 1) & slot_mask;
-        }
-        return keep;
+        W k[3];
+        keys(i, k);
+        return RepFind(keys, i, k, table, slot_mask) == (int32_t)i;
     }
 };
 
@@ -326,19 +283,17 @@ int DuplicateMaskAsync(const void* points_dev, int64_t n, int dtype,
     const dim3 grid(GridFor(n, kBlock)), block(kBlock);
     const uint32_t slot_mask = (uint32_t)(slots - 1);
     if (dtype == O3DMI_F64) {
-        hipLaunchKernelGGL(DuplicateInsertKernel<uint64_t>, grid, block, 0, s,
-                           (const uint64_t*)points_dev, n, table_dev,
-                           slot_mask);
+        const PointBitKeys<uint64_t> keys = {(const uint64_t*)points_dev};
+        hipLaunchKernelGGL(RepInsertKernel<PointBitKeys<uint64_t>>, grid,
+                           block, 0, s, keys, n, table_dev, slot_mask);
         return LaunchMask(n,
-                          DuplicatePred<uint64_t>{(const uint64_t*)points_dev,
-                                                  table_dev, slot_mask},
+                          DuplicatePred<uint64_t>{keys, table_dev, slot_mask},
                           mask_dev, count_dev, s);
     }
-    hipLaunchKernelGGL(DuplicateInsertKernel<uint32_t>, grid, block, 0, s,
-                       (const uint32_t*)points_dev, n, table_dev, slot_mask);
-    return LaunchMask(n,
-                      DuplicatePred<uint32_t>{(const uint32_t*)points_dev,
-                                              table_dev, slot_mask},
+    const PointBitKeys<uint32_t> keys = {(const uint32_t*)points_dev};
+    hipLaunchKernelGGL(RepInsertKernel<PointBitKeys<uint32_t>>, grid, block, 0,
+                       s, keys, n, table_dev, slot_mask);
+    return LaunchMask(n, DuplicatePred<uint32_t>{keys, table_dev, slot_mask},
                       mask_dev, count_dev, s);
 }
 

@@ -2,8 +2,12 @@
 connectivity methods (t/geometry/TriangleMesh.cpp:198-404, 1221-1452,
 1826-1864), of legacy ClusterConnectedTriangles (geometry/TriangleMesh.cpp:
 1459-1528), of SamplePointsUniformly and ComputeMetrics (t/geometry/
-TriangleMesh.cpp:1866-1967) and of RaycastingScene's closest-point and ray
-queries for one mesh (MeshBVH, create_rays_pinhole) on the HIP backend.
+TriangleMesh.cpp:1866-1967), of RaycastingScene's closest-point and ray
+queries for one mesh (MeshBVH, create_rays_pinhole) and of the legacy clean-up,
+smoothing and clustering methods (RemoveDuplicatedVertices / Triangles,
+RemoveDegenerateTriangles, ComputeAdjacencyList, FilterSharpen, FilterSmooth*,
+SimplifyVertexClustering; geometry/TriangleMesh.cpp:153-440, 680-860,
+TriangleMeshSimplification.cpp:72-244) on the HIP backend.
 
 A mesh is the dict VoxelBlockGrid.extract_triangle_mesh returns: "positions"
 ({V,3} Float32 or Float64) and "indices" ({M,3} Int32 or Int64) on the device,
@@ -284,6 +288,195 @@ def cluster_connected_triangles(mesh):
         *args, _lib.ptr(labels), C.byref(n), _lib.ptr(counts),
         _lib.ptr(areas), m, stream()), "cluster_connected_triangles")
     return labels, counts[:n.value], areas[:n.value]
+
+
+# ---- clean-up, smoothing filters, vertex clustering ----------------------------
+
+class FilterScope:
+    """geometry::MeshBase::FilterScope."""
+    All, Color, Normal, Vertex = 0, 1, 2, 3
+
+
+class SimplificationContraction:
+    """geometry::MeshBase::SimplificationContraction."""
+    Average, Quadric = 0, 1
+
+
+def remove_duplicated_vertices(mesh):
+    """Legacy RemoveDuplicatedVertices: vertices with equal coordinates (by
+    value: -0 == +0, a NaN row equals nothing) collapse onto the first of
+    them; every vertex attribute keeps the first one's row and the triangles
+    are renumbered."""
+    p, t, args = _mesh_args(mesh)
+    vmask = torch.empty(p.shape[0], dtype=torch.uint8, device=p.device)
+    tris = torch.empty_like(t)
+    n = C.c_int64(0)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_remove_duplicated_vertices(
+        *args, _lib.ptr(vmask), _lib.ptr(tris), C.byref(n), stream()),
+        "remove_duplicated_vertices")
+    vertex, triangle = _split(mesh)
+    out = _select_rows(vertex, vmask)
+    out.update(triangle)
+    if "indices" in mesh:
+        out["indices"] = tris
+    return out
+
+
+def _remove_triangles(mesh, call, what):
+    p = _positions(mesh)
+    if "indices" not in mesh:
+        return dict(mesh)
+    t = _indices(mesh, p)
+    tmask = torch.empty(t.shape[0], dtype=torch.uint8, device=p.device)
+    tris = torch.empty_like(t)
+    n = C.c_int64(0)
+    _lib.check(call(*_index_args(p, t), _lib.ptr(tmask), _lib.ptr(tris),
+                    C.byref(n), stream()), what)
+    vertex, triangle = _split(mesh)
+    triangle.pop("indices")
+    out = dict(vertex)
+    out.update(_select_rows(triangle, tmask))
+    out["indices"] = tris[:n.value]
+    return out
+
+
+def remove_duplicated_triangles(mesh):
+    """Legacy RemoveDuplicatedTriangles: of the triangles that are rotations
+    of one another the first stays (the flipped one is another triangle);
+    triangle attributes follow."""
+    return _remove_triangles(
+        mesh, _lib.lib().o3dmi_trianglemesh_remove_duplicated_triangles,
+        "remove_duplicated_triangles")
+
+
+def remove_degenerate_triangles(mesh):
+    """Legacy RemoveDegenerateTriangles: a triangle that names a vertex twice
+    leaves; triangle attributes follow."""
+    return _remove_triangles(
+        mesh, _lib.lib().o3dmi_trianglemesh_remove_degenerate_triangles,
+        "remove_degenerate_triangles")
+
+
+def compute_adjacency_list(mesh):
+    """Legacy ComputeAdjacencyList as CSR -> (row_splits int64 {V+1},
+    neighbours in the index dtype): the neighbours of vertex u are
+    neighbours[row_splits[u]:row_splits[u + 1]], ascending, without
+    repeats."""
+    p = _positions(mesh)
+    t = _indices(mesh, p)
+    args = _index_args(p, t)
+    n = C.c_int64(0)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_compute_adjacency_list(
+        *args, None, None, -1, C.byref(n), stream()),
+        "compute_adjacency_list")
+    splits = torch.empty(p.shape[0] + 1, dtype=torch.int64, device=p.device)
+    nbrs = torch.empty(n.value, dtype=t.dtype, device=p.device)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_compute_adjacency_list(
+        *args, _lib.ptr(splits), _lib.ptr(nbrs), n.value, C.byref(n),
+        stream()), "compute_adjacency_list")
+    return splits, nbrs
+
+
+def _vertex_attr(mesh, name, p):
+    a = mesh.get(name)
+    if a is None:
+        return None
+    a = require_cuda(a, name).contiguous()
+    if a.shape != p.shape:
+        raise ValueError("%s must be {V,3}" % name)
+    return a
+
+
+def _attr_args(p, normals, colors):
+    """(normals, colors, attr_dtype) of a filter / clustering call."""
+    given = [a for a in (normals, colors) if a is not None]
+    dtypes = {a.dtype for a in given}
+    if len(dtypes) > 1 or any(d not in TORCH_TO_O3DMI for d in dtypes):
+        raise ValueError("normals and colors must have the position dtype")
+    code = TORCH_TO_O3DMI[given[0].dtype] if given else TORCH_TO_O3DMI[p.dtype]
+    return (_lib.ptr(normals), _lib.ptr(colors), code)
+
+
+def _filter(mesh, call, params, scope, what):
+    p, t, args = _mesh_args(mesh)
+    p = p.contiguous()
+    normals = _vertex_attr(mesh, "normals", p)
+    colors = _vertex_attr(mesh, "colors", p)
+    outs = [torch.empty_like(a) if a is not None else None
+            for a in (p, normals, colors)]
+    _lib.check(call(
+        _lib.ptr(p), p.shape[0], TORCH_TO_O3DMI[p.dtype],
+        *_attr_args(p, normals, colors), *args[3:], *params, int(scope),
+        *[_lib.ptr(o) for o in outs], stream()), what)
+    out = dict(mesh)
+    for name, o in zip(("positions", "normals", "colors"), outs):
+        if o is not None:
+            out[name] = o
+    return out
+
+
+def filter_sharpen(mesh, number_of_iterations=1, strength=1.0,
+                   filter_scope=FilterScope.All):
+    """Legacy FilterSharpen: v_o = v_i + strength (v_i |N| - sum_N v_n) per
+    iteration, in float64 over the neighbours in ascending index."""
+    return _filter(mesh, _lib.lib().o3dmi_trianglemesh_filter_sharpen,
+                   (int(number_of_iterations), float(strength)), filter_scope,
+                   "filter_sharpen")
+
+
+def filter_smooth_simple(mesh, number_of_iterations=1,
+                         filter_scope=FilterScope.All):
+    """Legacy FilterSmoothSimple: v_o = (v_i + sum_N v_n) / (|N| + 1)."""
+    return _filter(mesh, _lib.lib().o3dmi_trianglemesh_filter_smooth_simple,
+                   (int(number_of_iterations),), filter_scope,
+                   "filter_smooth_simple")
+
+
+def filter_smooth_laplacian(mesh, number_of_iterations=1, lambda_filter=0.5,
+                            filter_scope=FilterScope.All):
+    """Legacy FilterSmoothLaplacian with inverse-distance weights."""
+    return _filter(mesh, _lib.lib().o3dmi_trianglemesh_filter_smooth_laplacian,
+                   (int(number_of_iterations), float(lambda_filter)),
+                   filter_scope, "filter_smooth_laplacian")
+
+
+def filter_smooth_taubin(mesh, number_of_iterations=1, lambda_filter=0.5,
+                         mu=-0.53, filter_scope=FilterScope.All):
+    """Legacy FilterSmoothTaubin: a laplacian pass with lambda_filter, then
+    one with mu, per iteration."""
+    return _filter(mesh, _lib.lib().o3dmi_trianglemesh_filter_smooth_taubin,
+                   (int(number_of_iterations), float(lambda_filter),
+                    float(mu)), filter_scope, "filter_smooth_taubin")
+
+
+def simplify_vertex_clustering(
+        mesh, voxel_size, contraction=SimplificationContraction.Average):
+    """Legacy SimplifyVertexClustering -> a mesh with "positions", "indices",
+    "normals" / "colors" when the input has them, and "triangle_normals"
+    recomputed when it had them. Clusters are numbered by their first
+    vertex; the kept triangles stay in input order."""
+    p, t, args = _mesh_args(mesh)
+    p = p.contiguous()
+    normals = _vertex_attr(mesh, "normals", p)
+    colors = _vertex_attr(mesh, "colors", p)
+    outs = [torch.empty_like(a) if a is not None else None
+            for a in (p, normals, colors)]
+    tris = torch.empty_like(t)
+    n_v, n_t = C.c_int64(0), C.c_int64(0)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_simplify_vertex_clustering(
+        _lib.ptr(p), p.shape[0], TORCH_TO_O3DMI[p.dtype],
+        *_attr_args(p, normals, colors), *args[3:], float(voxel_size),
+        int(contraction), *[_lib.ptr(o) for o in outs], _lib.ptr(tris),
+        C.byref(n_v), C.byref(n_t), stream()), "simplify_vertex_clustering")
+    out = {}
+    for name, o in zip(("positions", "normals", "colors"), outs):
+        if o is not None:
+            out[name] = o[:n_v.value]
+    if "indices" in mesh:
+        out["indices"] = tris[:n_t.value]
+    if TRIANGLE_PREFIX + "normals" in mesh:
+        out = compute_triangle_normals(out, normalized=True)
+    return out
 
 
 # ---- sampling, closest points, metrics ----------------------------------------

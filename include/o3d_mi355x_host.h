@@ -2429,6 +2429,135 @@ int o3dmi_trianglemesh_simplify_vertex_clustering(
         int64_t* n_vertices_out, int64_t* n_triangles_out,
         o3dmi_stream_t stream);
 
+/* ---- mesh topology and intersection queries ---------------------------------
+ * Legacy geometry/TriangleMesh.cpp:1016-1135, 1212-1246, 1272-1457 and
+ * geometry/IntersectionTest.cpp:18-56. Every result is a pure function of the
+ * mesh: it depends on no tree shape, traversal order or launch shape, and
+ * lists come back in a stated order. The index calls take (triangles, m,
+ * index dtype, v) as o3dmi_trianglemesh_get_non_manifold_edges does, whose
+ * edge table (runs of equal (lo, hi) slots, a run's length the edge's
+ * multiplicity) and count / fill protocol they share. */
+
+/* EulerPoincareCharacteristic (:1272-1285): v + m - E, with E the number of
+ * runs of the edge table; a self edge (6,6) of a triangle (6,6,7) counts, as
+ * upstream's set counts it. m == 0: v. */
+int o3dmi_trianglemesh_euler_poincare_characteristic(
+        const void* triangles_dev, int64_t m, int index_dtype, int64_t v,
+        int64_t* characteristic_out, o3dmi_stream_t stream);
+
+/* IsEdgeManifold (:1301-1312): *manifold_out = 1 iff no edge has multiplicity
+ * > 2 (allow_boundary_edges) or != 2. m == 0: 1. */
+int o3dmi_trianglemesh_is_edge_manifold(const void* triangles_dev, int64_t m,
+                                        int index_dtype, int64_t v,
+                                        int allow_boundary_edges,
+                                        int* manifold_out,
+                                        o3dmi_stream_t stream);
+
+/* GetNonManifoldVertices (:1314-1368), upstream's loop read exactly: vertex x
+ * has a WEDGE in triangle t iff x occurs exactly once in t (what the three
+ * if / else if branches at :1334-1343 amount to), the wedge's link edge is
+ * t's other two vertices (they may be equal), and x is non-manifold iff the
+ * graph of its link edges has more than one connected component. The indices
+ * are written ASCENDING into vertices_out_dev {capacity} in the index dtype;
+ * capacity < 0 only counts, 0 <= capacity < the number is O3DMI_ERR_CAPACITY
+ * with nothing written (*n_vertices_out is still set). DIFFERENCE FROM
+ * UPSTREAM: a vertex that triangles name but that has no wedge (every such
+ * triangle names it twice) is not reported; upstream dereferences begin() of
+ * an empty map there, which is undefined. */
+int o3dmi_trianglemesh_get_non_manifold_vertices(
+        const void* triangles_dev, int64_t m, int index_dtype, int64_t v,
+        void* vertices_out_dev, int64_t capacity, int64_t* n_vertices_out,
+        o3dmi_stream_t stream);
+
+/* IsOrientable / OrientTriangles (:1016-1135). Slot 3 t + k runs FORWARD iff
+ * v_k < v_(k+1)%3; self edges are ignored. An edge of multiplicity 2 whose
+ * slots belong to two different triangles constrains them: run the same way,
+ * exactly one of the two must be flipped; run opposite ways, both or neither
+ * (two slots of one triangle constrain nothing). The mesh is orientable iff
+ * the constraints can all be met and no edge has multiplicity > 2.
+ * triangles_out_dev {m,3} in the index dtype (NULL: not wanted): when
+ * orientable, the LOWEST-INDEXED TRIANGLE OF EVERY CONNECTED COMPONENT KEEPS
+ * ITS WINDING, a flipped (a, b, c) is written (a, c, b) and the rest is
+ * copied; when not, a copy of the input. DIFFERENCES FROM UPSTREAM, whose
+ * breadth-first search starts at *unordered_set.begin() and is therefore no
+ * function of the mesh: an edge of multiplicity > 2 always makes the mesh not
+ * orientable (two of its triangles must run it the same way; upstream may say
+ * true, depending on its visiting order); the flip set is the canonical one
+ * above (upstream: that of its visiting order, a swap of the offending pair);
+ * a mesh that is not orientable is left as it was (upstream: half flipped).
+ * m == 0: orientable. */
+int o3dmi_trianglemesh_orient_triangles(const void* triangles_dev, int64_t m,
+                                        int index_dtype, int64_t v,
+                                        void* triangles_out_dev,
+                                        int* orientable_out,
+                                        o3dmi_stream_t stream);
+
+/* GetSelfIntersectingTriangles (:1374-1426). The per-pair function of
+ * triangles P (the lower index) and Q, in float64 on the positions widened,
+ * without contraction: the pair COUNTS iff box(P) and box(Q), the exact min /
+ * max of three doubles, overlap by IntersectionTest::AABBAABB's closed
+ * comparisons, and IntersectionTest::TriangleTriangle3d says so: per axis mu =
+ * the six points added left to right / 6, sigma = sqrt(the six squared
+ * deviations added left to right / 5) + 1e-12, every deviation / sigma, then
+ * Moeller's no-division test with its 1e-6 snap of the six plane distances,
+ * its interval test and its coplanar branch, operation for operation (IEEE
+ * sqrt and divide: the bits of an SSE2 build). The result is the set of (i,
+ * j), i < j, that share no vertex INDEX (upstream's nine comparisons) and
+ * count, written {n,2} in the index dtype in ASCENDING (i, j) (upstream: a
+ * concurrent_vector in arbitrary order); capacity as above, < 2^31. The pairs
+ * are found on the tree of o3dmi_mesh_bvh_create over the positions narrowed
+ * to float with round-to-nearest, which prunes exactly: rounding is monotone,
+ * so closed overlap in double implies closed overlap of the narrowed boxes,
+ * and the exact test at a leaf uses the doubles. A referenced coordinate that
+ * is not finite, as given or narrowed, is O3DMI_ERR_INVALID_ARG. */
+int o3dmi_trianglemesh_get_self_intersecting_triangles(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* triangles_dev, int64_t m, int index_dtype,
+        void* pairs_out_dev, int64_t capacity, int64_t* n_pairs_out,
+        o3dmi_stream_t stream);
+
+/* IsSelfIntersecting (:1428-1430): whether that set is non-empty. */
+int o3dmi_trianglemesh_is_self_intersecting(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* triangles_dev, int64_t m, int index_dtype,
+        int* intersecting_out, o3dmi_stream_t stream);
+
+/* IsIntersecting (:1432-1457): 0 unless the two meshes' bounding boxes
+ * (GetMinBound / GetMaxBound, over ALL vertices) overlap; then 1 iff some pair
+ * (triangle P of this mesh, triangle Q of the other) counts by the per-pair
+ * function above. DIFFERENCE FROM UPSTREAM, which applies no per-pair box
+ * test here: its 1e-6 snap can report two nearly coplanar triangles whose
+ * boxes are disjoint along the dropped axis; this call never does. Either
+ * mesh without triangles: 0. */
+int o3dmi_trianglemesh_is_intersecting(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* triangles_dev, int64_t m, int index_dtype,
+        const void* other_positions_dev, int64_t other_v, int other_dtype,
+        const void* other_triangles_dev, int64_t other_m,
+        int other_index_dtype, int* intersecting_out, o3dmi_stream_t stream);
+
+/* IsWatertight (:1126-1128): is_edge_manifold(0) && no non-manifold vertex &&
+ * !is_self_intersecting, in that order, stopping at the first that fails.
+ * m == 0: 1. */
+int o3dmi_trianglemesh_is_watertight(const void* positions_dev, int64_t v,
+                                     int dtype, const void* triangles_dev,
+                                     int64_t m, int index_dtype,
+                                     int* watertight_out,
+                                     o3dmi_stream_t stream);
+
+/* GetVolume (:1212-1246): O3DMI_ERR_INVALID_ARG with upstream's messages when
+ * the mesh is not watertight or not orientable (by the calls above). Each
+ * term is p0 . (p1 x p2) / 6 in float64 from the positions widened, every
+ * cross component a b - c d, the dot (x x + y y) + z z, with p0, p1, p2 the
+ * triangle's vertices in index order; the terms are added by the fixed tree
+ * of o3dmi_trianglemesh_surface_area (runs of 512 in index order, the run sums
+ * likewise; upstream: parallel_deterministic_reduce; equal to rounding) and
+ * the result is the absolute value. m == 0: 0. */
+int o3dmi_trianglemesh_get_volume(const void* positions_dev, int64_t v,
+                                  int dtype, const void* triangles_dev,
+                                  int64_t m, int index_dtype,
+                                  double* volume_out, o3dmi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -672,6 +672,28 @@ PROTOTYPES.update({
                _vp, _vp, _vp]),
     "o3dmi_trianglemesh_compute_signed_distance": (
         _i32, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp]),
+    # topology and intersection queries: (triangles, m, index dtype, v, ...)
+    # or (positions, v, dtype, triangles, m, index dtype, ...)
+    "o3dmi_trianglemesh_euler_poincare_characteristic": (
+        _i32, [_vp, _i64, _i32, _i64, C.POINTER(_i64), _vp]),
+    "o3dmi_trianglemesh_is_edge_manifold": (
+        _i32, [_vp, _i64, _i32, _i64, _i32, C.POINTER(_i32), _vp]),
+    "o3dmi_trianglemesh_get_non_manifold_vertices": (
+        _i32, [_vp, _i64, _i32, _i64, _vp, _i64, C.POINTER(_i64), _vp]),
+    "o3dmi_trianglemesh_orient_triangles": (
+        _i32, [_vp, _i64, _i32, _i64, _vp, C.POINTER(_i32), _vp]),
+    "o3dmi_trianglemesh_get_self_intersecting_triangles": (
+        _i32, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _i64, C.POINTER(_i64),
+               _vp]),
+    "o3dmi_trianglemesh_is_self_intersecting": (
+        _i32, [_vp, _i64, _i32, _vp, _i64, _i32, C.POINTER(_i32), _vp]),
+    "o3dmi_trianglemesh_is_intersecting": (
+        _i32, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _i64, _i32, _vp, _i64,
+               _i32, C.POINTER(_i32), _vp]),
+    "o3dmi_trianglemesh_is_watertight": (
+        _i32, [_vp, _i64, _i32, _vp, _i64, _i32, C.POINTER(_i32), _vp]),
+    "o3dmi_trianglemesh_get_volume": (
+        _i32, [_vp, _i64, _i32, _vp, _i64, _i32, _dp, _vp]),
 })
 
 # o3dmi_transport_t (include/o3d_mi355x_host.h): the caller-provided collectives
@@ -710,6 +732,11 @@ INTERNAL_PROTOTYPES = {
     "o3dmi_internal_mesh_bvh_ray_query": (
         _i32, [_vp, _i32, _vp, _i64, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp,
                _vp, _i32, C.POINTER(C.c_uint64), _vp]),
+    # csrc/trianglemesh_topology.h: (positions, v, dtype, triangles, m, index
+    # dtype, kind, n, visits[2], stream)
+    "o3dmi_internal_trianglemesh_self_intersections": (
+        _i32, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, C.POINTER(_i64),
+               C.POINTER(C.c_uint64), _vp]),
 }
 
 _lib = None

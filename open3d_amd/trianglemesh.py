@@ -7,7 +7,12 @@ queries for one mesh (MeshBVH, create_rays_pinhole) and of the legacy clean-up,
 smoothing and clustering methods (RemoveDuplicatedVertices / Triangles,
 RemoveDegenerateTriangles, ComputeAdjacencyList, FilterSharpen, FilterSmooth*,
 SimplifyVertexClustering; geometry/TriangleMesh.cpp:153-440, 680-860,
-TriangleMeshSimplification.cpp:72-244) on the HIP backend.
+TriangleMeshSimplification.cpp:72-244) and of the legacy topology and
+intersection queries (EulerPoincareCharacteristic, IsEdgeManifold,
+GetNonManifoldVertices / IsVertexManifold, IsOrientable / OrientTriangles,
+GetSelfIntersectingTriangles / IsSelfIntersecting, IsIntersecting,
+IsWatertight, GetVolume; geometry/TriangleMesh.cpp:1016-1135, 1212-1246,
+1272-1457) on the HIP backend.
 
 A mesh is the dict VoxelBlockGrid.extract_triangle_mesh returns: "positions"
 ({V,3} Float32 or Float64) and "indices" ({M,3} Int32 or Int64) on the device,
@@ -477,6 +482,153 @@ def simplify_vertex_clustering(
     if TRIANGLE_PREFIX + "normals" in mesh:
         out = compute_triangle_normals(out, normalized=True)
     return out
+
+
+# ---- topology and intersection queries -----------------------------------------
+
+def _contiguous_args(mesh):
+    p = _positions(mesh).contiguous()
+    t = _indices(mesh, p).contiguous()
+    return p, t, (_lib.ptr(p), p.shape[0], TORCH_TO_O3DMI[p.dtype],
+                  _lib.ptr(t), t.shape[0], TORCH_TO_O3DMI[t.dtype])
+
+
+def euler_poincare_characteristic(mesh):
+    """Legacy EulerPoincareCharacteristic: V + F - E, E the number of distinct
+    (lo, hi) edges (a self edge of a repeated-vertex triangle counts)."""
+    p, t, _ = _contiguous_args(mesh)
+    chi = C.c_int64(0)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_euler_poincare_characteristic(
+        *_index_args(p, t), C.byref(chi), stream()),
+        "euler_poincare_characteristic")
+    return chi.value
+
+
+def is_edge_manifold(mesh, allow_boundary_edges=True):
+    """Legacy IsEdgeManifold: no edge of multiplicity > 2
+    (allow_boundary_edges) or != 2."""
+    p, t, _ = _contiguous_args(mesh)
+    out = C.c_int(0)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_is_edge_manifold(
+        *_index_args(p, t), int(bool(allow_boundary_edges)), C.byref(out),
+        stream()), "is_edge_manifold")
+    return bool(out.value)
+
+
+def get_non_manifold_vertices(mesh):
+    """Legacy GetNonManifoldVertices -> {N} in the index dtype, ascending: the
+    vertices whose wedges' link edges form more than one connected component.
+    A vertex named only by triangles that name it twice is not reported
+    (upstream: undefined)."""
+    p, t, _ = _contiguous_args(mesh)
+    args = _index_args(p, t)
+    n = C.c_int64(0)
+    call = _lib.lib().o3dmi_trianglemesh_get_non_manifold_vertices
+    _lib.check(call(*args, None, -1, C.byref(n), stream()),
+               "get_non_manifold_vertices")
+    out = torch.empty(n.value, dtype=t.dtype, device=p.device)
+    if n.value:
+        _lib.check(call(*args, _lib.ptr(out), n.value, C.byref(n), stream()),
+                   "get_non_manifold_vertices")
+    return out
+
+
+def is_vertex_manifold(mesh):
+    """Legacy IsVertexManifold."""
+    p, t, _ = _contiguous_args(mesh)
+    n = C.c_int64(0)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_get_non_manifold_vertices(
+        *_index_args(p, t), None, -1, C.byref(n), stream()),
+        "is_vertex_manifold")
+    return n.value == 0
+
+
+def is_orientable(mesh):
+    """Legacy IsOrientable, as a function of the mesh: an edge of
+    multiplicity > 2 makes it false whatever the visiting order."""
+    p, t, _ = _contiguous_args(mesh)
+    ok = C.c_int(0)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_orient_triangles(
+        *_index_args(p, t), None, C.byref(ok), stream()), "is_orientable")
+    return bool(ok.value)
+
+
+def orient_triangles(mesh):
+    """Legacy OrientTriangles -> (mesh, orientable). When orientable, the
+    lowest-indexed triangle of every connected component keeps its winding
+    and a flipped (a, b, c) becomes (a, c, b); else "indices" is a copy.
+    Only "indices" changes: normals are left alone, as upstream leaves
+    them."""
+    p, t, _ = _contiguous_args(mesh)
+    out = dict(mesh)
+    tris = torch.empty_like(t)
+    ok = C.c_int(0)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_orient_triangles(
+        *_index_args(p, t), _lib.ptr(tris), C.byref(ok), stream()),
+        "orient_triangles")
+    if "indices" in mesh:
+        out["indices"] = tris
+    return out, bool(ok.value)
+
+
+def get_self_intersecting_triangles(mesh):
+    """Legacy GetSelfIntersectingTriangles -> {N,2} in the index dtype, in
+    ascending (i, j), i < j: the pairs that share no vertex index, whose
+    float64 boxes overlap and that IntersectionTest::TriangleTriangle3d
+    reports, found on the mesh BVH instead of upstream's all-pairs loop."""
+    p, t, args = _contiguous_args(mesh)
+    n = C.c_int64(0)
+    call = _lib.lib().o3dmi_trianglemesh_get_self_intersecting_triangles
+    _lib.check(call(*args, None, -1, C.byref(n), stream()),
+               "get_self_intersecting_triangles")
+    out = torch.empty((n.value, 2), dtype=t.dtype, device=p.device)
+    if n.value:
+        _lib.check(call(*args, _lib.ptr(out), n.value, C.byref(n), stream()),
+                   "get_self_intersecting_triangles")
+    return out
+
+
+def is_self_intersecting(mesh):
+    """Legacy IsSelfIntersecting."""
+    _, _, args = _contiguous_args(mesh)
+    out = C.c_int(0)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_is_self_intersecting(
+        *args, C.byref(out), stream()), "is_self_intersecting")
+    return bool(out.value)
+
+
+def is_intersecting(mesh, other):
+    """Legacy IsIntersecting: the bounding boxes of all vertices overlap and
+    some triangle of `mesh` meets one of `other`. Unlike upstream every pair
+    is box-tested first, so two nearly coplanar triangles with disjoint boxes
+    never count."""
+    _, _, args = _contiguous_args(mesh)
+    _, _, other_args = _contiguous_args(other)
+    out = C.c_int(0)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_is_intersecting(
+        *args, *other_args, C.byref(out), stream()), "is_intersecting")
+    return bool(out.value)
+
+
+def is_watertight(mesh):
+    """Legacy IsWatertight: edge manifold without boundary, vertex manifold
+    and not self-intersecting, tested in that order."""
+    _, _, args = _contiguous_args(mesh)
+    out = C.c_int(0)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_is_watertight(
+        *args, C.byref(out), stream()), "is_watertight")
+    return bool(out.value)
+
+
+def get_volume(mesh):
+    """Legacy GetVolume: |sum of p0 . (p1 x p2) / 6| as a float64 sum in a
+    fixed order; raises (upstream's messages) unless the mesh is watertight
+    and orientable."""
+    _, _, args = _contiguous_args(mesh)
+    out = C.c_double(0)
+    _lib.check(_lib.lib().o3dmi_trianglemesh_get_volume(
+        *args, C.byref(out), stream()), "get_volume")
+    return out.value
 
 
 # ---- sampling, closest points, metrics ----------------------------------------

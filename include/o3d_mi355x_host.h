@@ -2429,6 +2429,76 @@ int o3dmi_trianglemesh_simplify_vertex_clustering(
         int64_t* n_vertices_out, int64_t* n_triangles_out,
         o3dmi_stream_t stream);
 
+/* Legacy SubdivideMidpoint / SubdivideLoop (geometry/TriangleMeshSubdivide.cpp:
+ * 18-94, 96-357), statement for statement in float64 on the positions, normals
+ * and colours widened: a Float32 mesh is widened once, stays float64 across
+ * the iterations and is narrowed once at the end. No sum is contracted or
+ * atomic; each has the order stated here.
+ *   Numbering, per iteration: the old vertices keep their indices; the new
+ *     vertex of the unordered edge (lo, hi) is v_old + r, r the rank of the
+ *     edge's lowest slot e = 3 t + k (k = 0, 1, 2 for (v0, v1), (v1, v2),
+ *     (v2, v0)) among the lowest slots of all edges. That is upstream's
+ *     first-encounter order (:57-58, :236), exactly. The edge (a, a) of a
+ *     degenerate triangle is an edge like any other and gets a vertex, so
+ *     *n_vertices_out follows the walk, not E' = 2 E + 3 M.
+ *   Triangles: triangle t becomes rows 4 t .. 4 t + 3 = (v0, v01, v20), (v01,
+ *     v1, v12), (v12, v2, v20), (v01, v12, v20) (:77-84, :337-344);
+ *     *n_triangles_out = 4^n m.
+ *   Midpoint: the new vertex is 0.5 * (x[lo] + x[hi]) per component of every
+ *     attribute; the old ones are copied. Bit for bit upstream's result on a
+ *     Float64 mesh.
+ *   Loop, new vertex (:186-234): s = x[v0] + x[v1]; the edge's multiplicity n
+ *     is the number of DISTINCT triangles that name it (upstream's set of
+ *     triangle indices: (a, a, b) names (a, b) twice and counts once, a
+ *     triangle listed twice counts twice; o3dmi_trianglemesh_get_non_manifold_
+ *     edges counts slots instead). n < 2: s * 0.5. Else s * (3. / 8.), then
+ *     += (1. / (4. * n)) * x[opp] over the edge's triangles in ascending
+ *     triangle index (upstream: its unordered_set's order; equal to rounding),
+ *     opp the first of t0, t1, else t2, that differs from both ends.
+ *   Loop, old vertex (:119-176): nbs is the list of
+ *     o3dmi_trianglemesh_compute_adjacency_list (ascending, no repeats, the
+ *     vertex itself for (a, a, b)), the boundary ones those whose edge has
+ *     multiplicity 1. >= 2 boundary neighbours: beta = 1. / 8. over them;
+ *     else |nbs| == 3: beta = 3. / 16.; else beta = 3. / (8. * |nbs|), over
+ *     all; alpha = 1. - count * beta; alpha * x[v], then += beta * x[nb] in
+ *     ascending neighbour index (upstream: set order; equal to rounding).
+ *     A vertex WITHOUT neighbours is copied unchanged; upstream computes beta
+ *     = 3 / (8 * 0) = inf and alpha = NaN and turns every unreferenced vertex
+ *     into NaN. Upstream's two warnings (non-manifold edge, > 2 boundary
+ *     neighbours) are no errors; the statements run as written. The topology
+ *     is rebuilt from each iteration's triangle list.
+ * number_of_iterations <= 0 (or m == 0) copies the mesh. normals_dev /
+ * colors_dev may be NULL; given, they need the position dtype
+ * (O3DMI_ERR_UNSUPPORTED) and, unless only counting, an output. Refused with
+ * O3DMI_ERR_INVALID_ARG before anything is allocated: 4^n m > 2^29, or v +
+ * (4^n - 1) m >= 2^31 (the most vertices n iterations can add; vertex ids are
+ * int32 in the tables); before anything is written: a triangle index outside
+ * [0, v), a position, normal or colour that is not finite (referenced or
+ * not). The vertex count is data dependent, so the protocol is
+ * o3dmi_trianglemesh_compute_adjacency_list's: vertex_capacity < 0 only sets
+ * *n_vertices_out and *n_triangles_out (the outputs may be NULL; the index
+ * side runs, no attribute is touched beyond the finiteness check);
+ * vertex_capacity < *n_vertices_out sets both and is O3DMI_ERR_CAPACITY with
+ * the outputs untouched; else positions_out_dev / normals_out_dev /
+ * colors_out_dev {vertex_capacity,3} get *n_vertices_out rows and
+ * triangles_out_dev {4^n m,3} in the index dtype every row. */
+int o3dmi_trianglemesh_subdivide_midpoint(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* normals_dev, const void* colors_dev, int attr_dtype,
+        const void* triangles_dev, int64_t m, int index_dtype,
+        int number_of_iterations, void* positions_out_dev,
+        void* normals_out_dev, void* colors_out_dev, int64_t vertex_capacity,
+        void* triangles_out_dev, int64_t* n_vertices_out,
+        int64_t* n_triangles_out, o3dmi_stream_t stream);
+int o3dmi_trianglemesh_subdivide_loop(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* normals_dev, const void* colors_dev, int attr_dtype,
+        const void* triangles_dev, int64_t m, int index_dtype,
+        int number_of_iterations, void* positions_out_dev,
+        void* normals_out_dev, void* colors_out_dev, int64_t vertex_capacity,
+        void* triangles_out_dev, int64_t* n_vertices_out,
+        int64_t* n_triangles_out, o3dmi_stream_t stream);
+
 /* ---- mesh topology and intersection queries ---------------------------------
  * Legacy geometry/TriangleMesh.cpp:1016-1135, 1212-1246, 1272-1457 and
  * geometry/IntersectionTest.cpp:18-56. Every result is a pure function of the

@@ -632,6 +632,14 @@ PROTOTYPES.update({
     "o3dmi_trianglemesh_simplify_vertex_clustering": (
         _i32, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _d, _i32,
                _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), _vp]),
+    # (..., index_dtype, number_of_iterations, positions_out, normals_out,
+    # colors_out, vertex_capacity, triangles_out, n_vertices, n_triangles)
+    "o3dmi_trianglemesh_subdivide_midpoint": (
+        _i32, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _vp,
+               _vp, _vp, _i64, _vp, C.POINTER(_i64), C.POINTER(_i64), _vp]),
+    "o3dmi_trianglemesh_subdivide_loop": (
+        _i32, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _vp,
+               _vp, _vp, _i64, _vp, C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "o3dmi_mesh_sample_draw": (
         _i32, [C.c_uint64, _i64, _dp, C.POINTER(_f), C.POINTER(_f)]),
     "o3dmi_trianglemesh_sample_points_uniformly": (

@@ -12,7 +12,8 @@ intersection queries (EulerPoincareCharacteristic, IsEdgeManifold,
 GetNonManifoldVertices / IsVertexManifold, IsOrientable / OrientTriangles,
 GetSelfIntersectingTriangles / IsSelfIntersecting, IsIntersecting,
 IsWatertight, GetVolume; geometry/TriangleMesh.cpp:1016-1135, 1212-1246,
-1272-1457) on the HIP backend.
+1272-1457) and of legacy SubdivideMidpoint / SubdivideLoop (geometry/
+TriangleMeshSubdivide.cpp) on the HIP backend.
 
 A mesh is the dict VoxelBlockGrid.extract_triangle_mesh returns: "positions"
 ({V,3} Float32 or Float64) and "indices" ({M,3} Int32 or Int64) on the device,
@@ -482,6 +483,54 @@ def simplify_vertex_clustering(
     if TRIANGLE_PREFIX + "normals" in mesh:
         out = compute_triangle_normals(out, normalized=True)
     return out
+
+
+def _subdivide(mesh, call, number_of_iterations, what):
+    """The count call, the allocation, the call."""
+    p, t, _ = _mesh_args(mesh)
+    p = p.contiguous()
+    t = t.contiguous()
+    normals = _vertex_attr(mesh, "normals", p)
+    colors = _vertex_attr(mesh, "colors", p)
+    head = (_lib.ptr(p), p.shape[0], TORCH_TO_O3DMI[p.dtype],
+            *_attr_args(p, normals, colors), _lib.ptr(t), t.shape[0],
+            TORCH_TO_O3DMI[t.dtype], int(number_of_iterations))
+    n_v, n_t = C.c_int64(0), C.c_int64(0)
+    _lib.check(call(*head, None, None, None, -1, None, C.byref(n_v),
+                    C.byref(n_t), stream()), what)
+    outs = [torch.empty((n_v.value, 3), dtype=p.dtype, device=p.device)
+            if a is not None else None for a in (p, normals, colors)]
+    tris = torch.empty((n_t.value, 3), dtype=t.dtype, device=p.device)
+    _lib.check(call(*head, *[_lib.ptr(o) for o in outs], n_v.value,
+                    _lib.ptr(tris), C.byref(n_v), C.byref(n_t), stream()),
+               what)
+    out = {}
+    for name, o in zip(("positions", "normals", "colors"), outs):
+        if o is not None:
+            out[name] = o
+    if "indices" in mesh:
+        out["indices"] = tris
+    if TRIANGLE_PREFIX + "normals" in mesh:
+        out = compute_triangle_normals(out, normalized=True)
+    return out
+
+
+def subdivide_midpoint(mesh, number_of_iterations=1):
+    """Legacy SubdivideMidpoint -> a mesh with "positions", "indices",
+    "normals" / "colors" when the input has them, and "triangle_normals"
+    recomputed when it had them. Every triangle becomes four; the new vertex
+    of an edge is the midpoint of its ends and is numbered in the order in
+    which a walk over the triangles meets the edges first."""
+    return _subdivide(mesh, _lib.lib().o3dmi_trianglemesh_subdivide_midpoint,
+                      number_of_iterations, "subdivide_midpoint")
+
+
+def subdivide_loop(mesh, number_of_iterations=1):
+    """Legacy SubdivideLoop (Loop's masks with upstream's boundary rule), the
+    same outputs and numbering as subdivide_midpoint. A vertex no triangle
+    names is copied (upstream makes it NaN)."""
+    return _subdivide(mesh, _lib.lib().o3dmi_trianglemesh_subdivide_loop,
+                      number_of_iterations, "subdivide_loop")
 
 
 # ---- topology and intersection queries -----------------------------------------

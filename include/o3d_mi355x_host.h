@@ -2499,6 +2499,113 @@ int o3dmi_trianglemesh_subdivide_loop(
         void* triangles_out_dev, int64_t* n_vertices_out,
         int64_t* n_triangles_out, o3dmi_stream_t stream);
 
+/* ---- ClipPlane / SlicePlane ---------------------------------------------------
+ * t::geometry::TriangleMesh::ClipPlane / SlicePlane (t/geometry/
+ * TriangleMesh.cpp:649-716). Upstream hands both to VTK on a host copy
+ * (vtkClipPolyData + vtkCleanPolyData, vtkCutter), which cannot be matched bit
+ * for bit; here the result is a pure function of the input by the rules
+ * below. All arithmetic is float64 on the positions (normals, colours)
+ * widened, without contraction, narrowed once on the store. Float32 / Float64
+ * positions, Int32 / Int64 indices.
+ *   Signed value: s_i = ((n.x (x_i - o.x) + n.y (y_i - o.y)) + n.z (z_i -
+ *     o.z)), o = point and n = normal, host doubles {3}. The normal is NOT
+ *     normalised (vtkPlane::EvaluateFunction): a contour value is in units of
+ *     |n| times distance; upstream's "signed distance" holds for a unit normal.
+ *   Inside: vertex i is inside for the contour value c iff s_i >= c (VTK's
+ *     clip case index). Clip is the contour c = 0.
+ *   Cut point of an edge with one end u inside and the other outside: if s_u
+ *     == c it IS vertex u, no new point is made and all such edges at u share
+ *     it. Otherwise it belongs to the unordered edge (lo, hi), lo < hi by
+ *     index, whichever triangle names it and in whichever direction: t = (c -
+ *     s_lo) / (s_hi - s_lo), every attribute x_lo + t * (x_hi - x_lo)
+ *     (positions, and normals and colours if given; normals are not
+ *     renormalised). Two triangles sharing the edge get the same bits.
+ *   Rotation: a triangle keeps its winding; with one vertex inside it is
+ *     rotated so that this vertex is first, with two inside so that the
+ *     outside one is last: (a, b, c), and ab, bc, ca are the cut points of
+ *     those edges. Edge k of triangle t is (t_k, t_(k+1)%3) and its slot 3 t +
+ *     k, as in subdivision.
+ *   Coincident input vertices are NOT merged (upstream's vtkCleanPolyData
+ *     merges them): call o3dmi_trianglemesh_remove_duplicated_vertices first.
+ * Refused with O3DMI_ERR_INVALID_ARG, outputs untouched: from the sizes
+ * alone, before anything is allocated or read, clip m > 2^28 (up to 2 m output
+ * triangles), slice K m > 2^29, either v + 3 m >= 2^31; a non-finite point,
+ * normal or contour value; normal == (0, 0, 0); a triangle index outside [0,
+ * v); a position, given normal or colour that is not finite, referenced or
+ * not; an s_i that is not finite. Normals / colours of another dtype than the
+ * positions: O3DMI_ERR_UNSUPPORTED.
+ *
+ * o3dmi_trianglemesh_clip_plane keeps the part with s >= 0. Pieces per input
+ * triangle, in ascending triangle index: none inside, nothing; all inside,
+ * the triangle itself; one inside, (a, ab, ca); two inside, (a, b, bc), then
+ * (a, bc, ca) (upstream: VTK's case table picks the diagonal). Any output
+ * triangle that names a vertex twice is dropped, whatever its origin: a
+ * triangle touching the plane from the negative side with one vertex or one
+ * edge vanishes, a triangle lying in the plane stays, a degenerate input
+ * triangle vanishes (upstream's cleaner turns it into a line).
+ *   Vertices: first the old vertices that at least one output triangle names,
+ *     in ascending old index, copied bit for bit (unreferenced and outside
+ *     vertices are gone, as upstream); then the new cut vertices, in ascending
+ *     order of their edge's lowest slot among the slots whose cut point an
+ *     output triangle names. Every new vertex is named by an output triangle.
+ *   Outputs: positions_out_dev / normals_out_dev / colors_out_dev
+ *     {vertex_capacity,3}; triangles_out_dev {triangle_capacity,3} in the
+ *     index dtype; optional (may be NULL) triangle_source_out_dev
+ *     {triangle_capacity} in the index dtype, the input triangle of each
+ *     output triangle; optional vertex_source_out_dev {vertex_capacity,2} in
+ *     the index dtype together with vertex_t_out_dev {vertex_capacity}
+ *     Float64: (i, i) and 0 for an old vertex, (lo, hi) and t for a cut
+ *     vertex, from which a caller carries any other attribute.
+ *   Protocol (o3dmi_trianglemesh_subdivide_midpoint's): vertex_capacity < 0
+ *     only sets *n_vertices_out and *n_triangles_out; either capacity below
+ *     its count sets both and is O3DMI_ERR_CAPACITY with nothing written. An
+ *     empty mesh or one wholly outside gives 0 and 0. */
+int o3dmi_trianglemesh_clip_plane(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* normals_dev, const void* colors_dev, int attr_dtype,
+        const void* triangles_dev, int64_t m, int index_dtype,
+        const double* point, const double* normal, void* positions_out_dev,
+        void* normals_out_dev, void* colors_out_dev, int64_t vertex_capacity,
+        void* triangles_out_dev, int64_t triangle_capacity,
+        void* triangle_source_out_dev, void* vertex_source_out_dev,
+        double* vertex_t_out_dev, int64_t* n_vertices_out,
+        int64_t* n_triangles_out, o3dmi_stream_t stream);
+
+/* o3dmi_trianglemesh_slice_plane: the cross-sections at the n_contours values
+ * contour_values (a host array; 0 of them give an empty result). For each
+ * contour in the order given and each triangle in ascending index, one line
+ * from where the winding leaves the inside to where it re-enters: one inside,
+ * (ab, ca); two inside, (bc, ca); none or all inside, nothing. A line whose
+ * two ends are the same point is dropped and numbers nothing: a triangle
+ * touching the contour with one vertex from below gives nothing, a triangle
+ * in the contour plane gives nothing, an in-plane edge is emitted by each
+ * adjacent triangle whose third vertex is below (once for a surface crossing
+ * the plane there).
+ *   Points: a point is a vertex point (s_u == c) or an edge point, unique per
+ *     contour and not shared between contours (vtkCutter's per-contour merge).
+ *     Numbering is contour-major; within a contour a point's place is the
+ *     lowest slot 3 t + k among the kept lines' end uses, each end attached
+ *     to the edge slot it lies on. For c = 0 an edge point has the bits of
+ *     clip's cut vertex of the same edge.
+ *   Outputs: points_out_dev (normals_out_dev / colors_out_dev interpolated
+ *     when given) {point_capacity,3}; lines_out_dev {line_capacity,2} in the
+ *     index dtype; optional line_triangle_out_dev {line_capacity} in the index
+ *     dtype, line_contour_out_dev {line_capacity} Int32, and point_source_out_
+ *     dev {point_capacity,2} with point_t_out_dev as for clip. point_capacity
+ *     < 0 only counts; either capacity below its count sets both counts and
+ *     is O3DMI_ERR_CAPACITY with nothing written. */
+int o3dmi_trianglemesh_slice_plane(
+        const void* positions_dev, int64_t v, int dtype,
+        const void* normals_dev, const void* colors_dev, int attr_dtype,
+        const void* triangles_dev, int64_t m, int index_dtype,
+        const double* point, const double* normal,
+        const double* contour_values, int64_t n_contours, void* points_out_dev,
+        void* normals_out_dev, void* colors_out_dev, int64_t point_capacity,
+        void* lines_out_dev, int64_t line_capacity,
+        void* line_triangle_out_dev, int32_t* line_contour_out_dev,
+        void* point_source_out_dev, double* point_t_out_dev,
+        int64_t* n_points_out, int64_t* n_lines_out, o3dmi_stream_t stream);
+
 /* ---- mesh topology and intersection queries ---------------------------------
  * Legacy geometry/TriangleMesh.cpp:1016-1135, 1212-1246, 1272-1457 and
  * geometry/IntersectionTest.cpp:18-56. Every result is a pure function of the

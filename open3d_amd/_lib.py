@@ -640,6 +640,21 @@ PROTOTYPES.update({
     "o3dmi_trianglemesh_subdivide_loop": (
         _i32, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _vp,
                _vp, _vp, _i64, _vp, C.POINTER(_i64), C.POINTER(_i64), _vp]),
+    # (..., index_dtype, point, normal, positions_out, normals_out,
+    # colors_out, vertex_capacity, triangles_out, triangle_capacity,
+    # triangle_source, vertex_source, vertex_t, n_vertices, n_triangles)
+    "o3dmi_trianglemesh_clip_plane": (
+        _i32, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _dp, _dp,
+               _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+               C.POINTER(_i64), C.POINTER(_i64), _vp]),
+    # (..., index_dtype, point, normal, contour_values, n_contours,
+    # points_out, normals_out, colors_out, point_capacity, lines_out,
+    # line_capacity, line_triangle, line_contour, point_source, point_t,
+    # n_points, n_lines)
+    "o3dmi_trianglemesh_slice_plane": (
+        _i32, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _dp, _dp,
+               _dp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp,
+               C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "o3dmi_mesh_sample_draw": (
         _i32, [C.c_uint64, _i64, _dp, C.POINTER(_f), C.POINTER(_f)]),
     "o3dmi_trianglemesh_sample_points_uniformly": (

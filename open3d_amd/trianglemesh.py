@@ -12,8 +12,10 @@ intersection queries (EulerPoincareCharacteristic, IsEdgeManifold,
 GetNonManifoldVertices / IsVertexManifold, IsOrientable / OrientTriangles,
 GetSelfIntersectingTriangles / IsSelfIntersecting, IsIntersecting,
 IsWatertight, GetVolume; geometry/TriangleMesh.cpp:1016-1135, 1212-1246,
-1272-1457) and of legacy SubdivideMidpoint / SubdivideLoop (geometry/
-TriangleMeshSubdivide.cpp) on the HIP backend.
+1272-1457), of legacy SubdivideMidpoint / SubdivideLoop (geometry/
+TriangleMeshSubdivide.cpp) and of ClipPlane / SlicePlane (t/geometry/
+TriangleMesh.cpp:649-716; upstream: VTK on a host copy, here pinned rules on
+the device) on the HIP backend.
 
 A mesh is the dict VoxelBlockGrid.extract_triangle_mesh returns: "positions"
 ({V,3} Float32 or Float64) and "indices" ({M,3} Int32 or Int64) on the device,
@@ -531,6 +533,155 @@ def subdivide_loop(mesh, number_of_iterations=1):
     names is copied (upstream makes it NaN)."""
     return _subdivide(mesh, _lib.lib().o3dmi_trianglemesh_subdivide_loop,
                       number_of_iterations, "subdivide_loop")
+
+
+# ---- ClipPlane / SlicePlane -----------------------------------------------------
+
+def _vec3(x, name):
+    """A list, a tuple or an int / float tensor of shape {3} -> 3 doubles."""
+    if isinstance(x, torch.Tensor):
+        if x.dtype == torch.bool or x.is_complex():
+            raise ValueError("%s must be an int or float tensor" % name)
+        x = x.detach().to("cpu", torch.float64).tolist()
+    try:
+        values = [float(e) for e in x]
+    except TypeError:
+        raise ValueError("%s must have shape {3}" % name) from None
+    if len(values) != 3:
+        raise ValueError("%s must have shape {3}" % name)
+    return (C.c_double * 3)(*values)
+
+
+def _cut_inputs(mesh, what):
+    """-> positions, indices, the leading arguments of a clip / slice call, the
+    kernel's attributes {name: tensor or None}, the other vertex attributes
+    and the triangle attributes."""
+    p, t, _ = _mesh_args(mesh)
+    p = p.contiguous()
+    t = t.contiguous()
+    own = {"positions": p, "normals": _vertex_attr(mesh, "normals", p),
+           "colors": _vertex_attr(mesh, "colors", p)}
+    vertex, triangle = _split(mesh)
+    triangle.pop("indices", None)
+    extra = {}
+    for name, a in vertex.items():
+        if name in own:
+            continue
+        a = require_cuda(a, name)
+        if not a.dtype.is_floating_point:
+            raise ValueError(
+                "%s: vertex attribute %r is not floating point and cannot be "
+                "interpolated" % (what, name))
+        if a.dim() < 1 or a.shape[0] != p.shape[0]:
+            raise ValueError("attribute %r must have %d rows"
+                             % (name, p.shape[0]))
+        extra[name] = a
+    for name, a in triangle.items():
+        a = require_cuda(a, name)
+        if a.dim() < 1 or a.shape[0] != t.shape[0]:
+            raise ValueError("attribute %r must have %d rows"
+                             % (name, t.shape[0]))
+    head = (_lib.ptr(p), p.shape[0], TORCH_TO_O3DMI[p.dtype],
+            *_attr_args(p, own["normals"], own["colors"]), _lib.ptr(t),
+            t.shape[0], TORCH_TO_O3DMI[t.dtype])
+    return p, t, head, own, extra, triangle
+
+
+def _cut_outputs(own, rows):
+    return {name: torch.empty((rows, 3), dtype=a.dtype, device=a.device)
+            if a is not None else None for name, a in own.items()}
+
+
+def _interpolate(a, source, t):
+    """x_lo + t * (x_hi - x_lo) in float64 for the rows of a cut (two
+    roundings, no fused multiply-add: the kernel's statement), the row of an
+    old vertex as it is; narrowed to the attribute's dtype."""
+    lo, hi = source[:, 0].long(), source[:, 1].long()
+    w = a.to(torch.float64)
+    x_lo, x_hi = w[lo], w[hi]
+    tt = t.reshape((-1,) + (1,) * (a.dim() - 1))
+    mixed = x_lo + torch.mul(tt, x_hi - x_lo)
+    same = (lo == hi).reshape(tt.shape)
+    return torch.where(same, x_lo, mixed).to(a.dtype)
+
+
+def clip_plane(mesh, point, normal):
+    """TriangleMesh::ClipPlane -> the part of the mesh with normal . (x -
+    point) >= 0, as a pure function of the input (upstream: VTK). "positions",
+    "normals" and "colors" go through the kernel; every other floating vertex
+    attribute is interpolated by the same statement, x_lo + t (x_hi - x_lo) in
+    float64 (a non-floating one raises ValueError); every "triangle_"
+    attribute follows its input triangle. A triangle with one vertex inside
+    becomes (a, ab, ca), one with two (a, b, bc), (a, bc, ca); a vertex on the
+    plane is its own cut point; the kept old vertices come first, then the
+    cut vertices in the order a walk over the output meets their edges.
+    Coincident vertices are not merged (upstream merges them): call
+    remove_duplicated_vertices first. point / normal: lists, tuples or int /
+    float tensors of shape {3}; the normal is not normalised."""
+    p, t, head, own, extra, triangle = _cut_inputs(mesh, "clip_plane")
+    head += (_vec3(point, "point"), _vec3(normal, "normal"))
+    call = _lib.lib().o3dmi_trianglemesh_clip_plane
+    n_v, n_t = C.c_int64(0), C.c_int64(0)
+    _lib.check(call(*head, None, None, None, -1, None, 0, None, None, None,
+                    C.byref(n_v), C.byref(n_t), stream()), "clip_plane")
+    outs = _cut_outputs(own, n_v.value)
+    dev = p.device
+    tris = torch.empty((n_t.value, 3), dtype=t.dtype, device=dev)
+    tsrc = torch.empty(n_t.value, dtype=t.dtype, device=dev)
+    vsrc = torch.empty((n_v.value, 2), dtype=t.dtype, device=dev)
+    vt = torch.empty(n_v.value, dtype=torch.float64, device=dev)
+    _lib.check(call(*head, *[_lib.ptr(outs[k]) for k in own], n_v.value,
+                    _lib.ptr(tris), n_t.value, _lib.ptr(tsrc), _lib.ptr(vsrc),
+                    _lib.ptr(vt), C.byref(n_v), C.byref(n_t), stream()),
+               "clip_plane")
+    out = {k: o for k, o in outs.items() if o is not None}
+    for name, a in extra.items():
+        out[name] = _interpolate(a, vsrc, vt)
+    if "indices" in mesh:
+        out["indices"] = tris
+        rows = tsrc.long()
+        for name, a in triangle.items():
+            out[name] = a[rows]
+    return out
+
+
+def slice_plane(mesh, point, normal, contour_values=(0.0,)):
+    """TriangleMesh::SlicePlane -> a line set dict: "positions" {P,3},
+    "indices" {L,2}, the vertex attributes interpolated as in clip_plane,
+    "line_triangle" {L} (the triangle of every line) and "line_contour" {L}
+    int32. One line per crossed triangle and contour value c, from where the
+    winding leaves normal . (x - point) >= c to where it re-enters; points are
+    unique per contour, numbered contour after contour in the order a walk
+    over the lines meets them. The normal is not normalised: c is in units of
+    |normal| times distance. A triangle in the contour plane gives nothing;
+    an in-plane edge is emitted by the triangle below it."""
+    p, t, head, own, extra, _ = _cut_inputs(mesh, "slice_plane")
+    values = [float(c) for c in contour_values]
+    head += (_vec3(point, "point"), _vec3(normal, "normal"),
+             (C.c_double * max(len(values), 1))(*values), len(values))
+    call = _lib.lib().o3dmi_trianglemesh_slice_plane
+    n_p, n_l = C.c_int64(0), C.c_int64(0)
+    _lib.check(call(*head, None, None, None, -1, None, 0, None, None, None,
+                    None, C.byref(n_p), C.byref(n_l), stream()),
+               "slice_plane")
+    outs = _cut_outputs(own, n_p.value)
+    dev = p.device
+    lines = torch.empty((n_l.value, 2), dtype=t.dtype, device=dev)
+    ltri = torch.empty(n_l.value, dtype=t.dtype, device=dev)
+    lcon = torch.empty(n_l.value, dtype=torch.int32, device=dev)
+    psrc = torch.empty((n_p.value, 2), dtype=t.dtype, device=dev)
+    pt = torch.empty(n_p.value, dtype=torch.float64, device=dev)
+    _lib.check(call(*head, *[_lib.ptr(outs[k]) for k in own], n_p.value,
+                    _lib.ptr(lines), n_l.value, _lib.ptr(ltri),
+                    _lib.ptr(lcon), _lib.ptr(psrc), _lib.ptr(pt),
+                    C.byref(n_p), C.byref(n_l), stream()), "slice_plane")
+    out = {k: o for k, o in outs.items() if o is not None}
+    for name, a in extra.items():
+        out[name] = _interpolate(a, psrc, pt)
+    out["indices"] = lines
+    out["line_triangle"] = ltri
+    out["line_contour"] = lcon
+    return out
 
 
 # ---- topology and intersection queries -----------------------------------------

@@ -85,9 +85,8 @@ int CreateBvh(const void* positions_dev, int64_t v, const void* triangles_dev,
                                     bvh->nodes, bvh->leaves, scene, scratch,
                                     s)))
             return st;
-        O3DMI_HIP_CHECK(hipMemcpyAsync(bvh->scene, scene, 6 * sizeof(float),
-                                       hipMemcpyDeviceToHost, s));
-        O3DMI_HIP_CHECK(hipStreamSynchronize(s));
+        if ((st = Download(scene, bvh->scene, 6 * sizeof(float), s)))
+            return st;
     }
     *out = std::move(bvh);
     return O3DMI_OK;
@@ -205,9 +204,7 @@ int RunDirection(const o3dmi_mesh_bvh* bvh, const float* samples_dev,
     O3DMI_HIP_CHECK(hipMemcpyAsync(host.data(), words,
                                    sizeof(MetricsWords) * (size_t)groups,
                                    hipMemcpyDeviceToHost, s));
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&dir->sum, total, sizeof(double),
-                                   hipMemcpyDeviceToHost, s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
+    if ((st = Download(total, &dir->sum, sizeof(double), s))) return st;
     std::memcpy(&dir->max, &host[0].max_bits, sizeof(double));
     dir->counts.resize((size_t)n_radii);
     for (int r = 0; r < n_radii; ++r)
@@ -308,26 +305,20 @@ int RunRayList(const o3dmi_mesh_bvh* bvh, const void* rays_dev, int64_t q,
     O3DMI_HIP_CHECK(hipMemcpyAsync(splits + q, &w->total, sizeof(int64_t),
                                    hipMemcpyDeviceToDevice, s));
     Words host = {};
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&host, w, sizeof(Words),
-                                   hipMemcpyDeviceToHost, s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
+    if ((st = Download(w, &host, sizeof(host), s))) return st;
     if ((st = OverflowStatus(host.bad))) return st;
     const int64_t total = (int64_t)host.total;
     *total_out = total;
     if (total > 0x7FFFFFFFll)
         return Unsupported("list intersections: more than 2^31 - 1 entries");
     if (capacity < 0 || total == 0) return O3DMI_OK;
-    if (capacity < total) {
-        SetLastError("list intersections: capacity too small");
-        return O3DMI_ERR_CAPACITY;
-    }
+    if (capacity < total)
+        return CapacityError("list intersections: capacity too small");
     if ((st = MeshBvhRayListAsync(view, (const float*)rays_dev, q, splits, out,
                                   &w->bad, s)))
         return st;
     int overflow = 0;
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&overflow, &w->bad, sizeof(int),
-                                   hipMemcpyDeviceToHost, s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
+    if ((st = Download(&w->bad, &overflow, sizeof(overflow), s))) return st;
     return OverflowStatus(overflow);
 }
 
@@ -378,10 +369,8 @@ int RunVote(const o3dmi_mesh_bvh* bvh, const void* points_dev, int64_t q,
                                &w->bad, s)))
         return st;
     int overflow = 0;
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&overflow, &w->bad, sizeof(int),
-                                   hipMemcpyDeviceToHost, s));
     // host_dirs is pageable: the upload above was staged before it returned
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
+    if ((st = Download(&w->bad, &overflow, sizeof(overflow), s))) return st;
     return OverflowStatus(overflow);
 }
 

@@ -48,15 +48,23 @@ inline int AllocWords(PoolScratch& pool, Words** w_dev) {
     return O3DMI_OK;
 }
 
+// dst[0 .. bytes) = src_dev[0 .. bytes) once the stream has drained: one copy,
+// one wait.
+inline int Download(const void* src_dev, void* dst, size_t bytes,
+                    hipStream_t s) {
+    O3DMI_HIP_CHECK(hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost,
+                                   s));
+    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
+    return O3DMI_OK;
+}
+
 // Refuses a cloud with a NaN or Inf coordinate (one launch, one download).
 inline int RequireFinite(const void* points_dev, int64_t n, int dtype,
                          Words* w_dev, hipStream_t s) {
     int st = CheckFiniteAsync(points_dev, n, dtype, &w_dev->bad, s);
     if (st) return st;
     int bad = 0;
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&bad, &w_dev->bad, sizeof(int),
-                                   hipMemcpyDeviceToHost, s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
+    if ((st = Download(&w_dev->bad, &bad, sizeof(bad), s))) return st;
     O3DMI_REQUIRE(!bad,
                   "non-finite coordinate: run RemoveNonFinitePoints first");
     return O3DMI_OK;
@@ -65,9 +73,8 @@ inline int RequireFinite(const void* points_dev, int64_t n, int dtype,
 // *m_out = w_dev->count once the stream has drained.
 inline int DownloadCount(const Words* w_dev, int64_t* m_out, hipStream_t s) {
     unsigned long long c = 0;
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&c, &w_dev->count, sizeof(c),
-                                   hipMemcpyDeviceToHost, s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
+    const int st = Download(&w_dev->count, &c, sizeof(c), s);
+    if (st) return st;
     *m_out = (int64_t)c;
     return O3DMI_OK;
 }

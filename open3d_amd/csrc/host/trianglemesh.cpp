@@ -26,14 +26,6 @@ int CheckMesh(const void* positions_dev, int64_t v, int dtype,
     return O3DMI_OK;
 }
 
-int AllocEdgeTable(PoolScratch& pool, int64_t m, EdgeTable* tb) {
-    const size_t bytes = sizeof(uint32_t) * 3 * (size_t)m;
-    int st = pool.Alloc(&tb->lo, bytes);
-    if (!st) st = pool.Alloc(&tb->hi, bytes);
-    if (!st) st = pool.Alloc(&tb->slot, bytes);
-    return st;
-}
-
 // ComputeVertexNormalsCPU on checked triangles (m, v >= 1).
 int VertexNormalsOf(PoolScratch& pool, const int32_t* tri, int64_t m,
                     int64_t v, const void* tn_dev, int dtype, void* out_dev) {
@@ -41,14 +33,10 @@ int VertexNormalsOf(PoolScratch& pool, const int32_t* tri, int64_t m,
     CornerTable tb;
     int32_t* long_list = nullptr;
     void* scratch = nullptr;
-    int st = pool.Alloc(&tb.vertex, sizeof(uint32_t) * 3 * (size_t)m);
-    if (!st) st = pool.Alloc(&tb.corner, sizeof(uint32_t) * 3 * (size_t)m);
-    if (!st) st = pool.Alloc(&tb.count, sizeof(int32_t) * (size_t)v);
-    if (!st) st = pool.Alloc(&tb.start, sizeof(int64_t) * (size_t)v);
-    if (!st) st = pool.Alloc(&long_list, sizeof(int32_t) * ((size_t)v + 1));
+    int st = AllocCornerTable(pool, m, v, &tb);
     if (!st) st = pool.Alloc(&scratch, IncidenceScratchBytes(m, v));
+    if (!st) st = AllocLongList(pool, v, &long_list);
     if (st) return st;
-    O3DMI_HIP_CHECK(hipMemsetAsync(long_list + v, 0, sizeof(int32_t), s));
     if ((st = BuildCornerTableAsync(tri, m, v, tb, scratch, s))) return st;
     return VertexNormalSumAsync(tb, v, tn_dev, dtype, out_dev, long_list, s);
 }
@@ -80,9 +68,7 @@ int SelectChain(PoolScratch& pool, Words* w, const int32_t* tri, int64_t m,
         return st;
     if ((st = FlagsToMaskAsync(vflags, v, vertex_mask_out_dev, s))) return st;
     Words host;
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&host, w, sizeof(Words),
-                                   hipMemcpyDeviceToHost, s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
+    if ((st = Download(w, &host, sizeof(host), s))) return st;
     *n_vertices_out = (int64_t)host.count;
     *n_triangles_out = tflags ? (int64_t)host.total : m;
     return O3DMI_OK;
@@ -158,11 +144,10 @@ int SampleMeshChecked(const void* positions_dev, int64_t v, int dtype,
     double total = 0;
     O3DMI_HIP_CHECK(hipMemcpyAsync(&bad, &w->bad, sizeof(int),
                                    hipMemcpyDeviceToHost, s));
-    O3DMI_HIP_CHECK(hipMemcpyAsync(
-            &total,
-            tree.prefix[tree.levels - 1] + (tree.size[tree.levels - 1] - 1),
-            sizeof(double), hipMemcpyDeviceToHost, s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
+    if ((st = Download(
+                 tree.prefix[tree.levels - 1] + (tree.size[tree.levels - 1] - 1),
+                 &total, sizeof(total), s)))
+        return st;
     O3DMI_REQUIRE(!bad, "sample points: a triangle area is not finite");
     O3DMI_REQUIRE(total - total == 0 && total > 0,
                   "sample points: the surface area is not finite and > 0");
@@ -301,9 +286,7 @@ int o3dmi_trianglemesh_surface_area(const void* positions_dev, int64_t v,
     const double* total = nullptr;
     if ((st = RunSumTreeAsync(areas, m, dtype, sums, &total, s))) return st;
     double area = 0;
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&area, total, sizeof(double),
-                                   hipMemcpyDeviceToHost, s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
+    if ((st = Download(total, &area, sizeof(area), s))) return st;
     *area_out = area;
     return O3DMI_OK;
 }
@@ -412,7 +395,7 @@ int o3dmi_trianglemesh_get_non_manifold_edges(
     if ((st = AllocWords(pool, &w))) return st;
     if ((st = LoadTriangles(pool, w, triangles_dev, m, index_dtype, v, &tri)))
         return st;
-    if ((st = AllocEdgeTable(pool, m, &tb))) return st;
+    if ((st = AllocEdgeTable(pool, 3 * m, &tb))) return st;
     if ((st = pool.Alloc(&scratch, IncidenceScratchBytes(m, v)))) return st;
     if ((st = pool.Alloc(&flags, sizeof(int32_t) * 3 * (size_t)m))) return st;
     if ((st = pool.Alloc(&pos, sizeof(int64_t) * 3 * (size_t)m))) return st;
@@ -427,10 +410,8 @@ int o3dmi_trianglemesh_get_non_manifold_edges(
     if ((st = DownloadCount(w, &n_edges, s))) return st;
     *n_edges_out = n_edges;
     if (capacity < 0 || n_edges == 0) return O3DMI_OK;
-    if (capacity < n_edges) {
-        SetLastError("non-manifold edges: capacity too small");
-        return O3DMI_ERR_CAPACITY;
-    }
+    if (capacity < n_edges)
+        return CapacityError("non-manifold edges: capacity too small");
     if ((st = EmitEdgesAsync(tb, 3 * m, flags, pos, index_dtype,
                              edges_out_dev, s)))
         return st;
@@ -468,7 +449,7 @@ int o3dmi_trianglemesh_cluster_connected_triangles(
     if ((st = AllocWords(pool, &w))) return st;
     if ((st = LoadTriangles(pool, w, triangles_dev, m, index_dtype, v, &tri)))
         return st;
-    if ((st = AllocEdgeTable(pool, m, &tb))) return st;
+    if ((st = AllocEdgeTable(pool, 3 * m, &tb))) return st;
     if ((st = pool.Alloc(&scratch, IncidenceScratchBytes(m, v)))) return st;
     if ((st = pool.Alloc(&parent, sizeof(int) * (size_t)m))) return st;
     if ((st = pool.Alloc(&root, sizeof(int) * (size_t)m))) return st;
@@ -483,10 +464,8 @@ int o3dmi_trianglemesh_cluster_connected_triangles(
     if ((st = DownloadCount(w, &c, s))) return st;
     *n_clusters_out = c;
     if (capacity < 0) return O3DMI_OK;
-    if (capacity < c) {
-        SetLastError("cluster_connected_triangles: capacity too small");
-        return O3DMI_ERR_CAPACITY;
-    }
+    if (capacity < c)
+        return CapacityError("cluster_connected_triangles: capacity too small");
     int32_t* counts = nullptr;
     if ((st = pool.Alloc(&counts, sizeof(int32_t) * (size_t)c))) return st;
     O3DMI_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)c, s));

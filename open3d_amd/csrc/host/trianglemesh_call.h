@@ -1,6 +1,9 @@
 // The call scaffold the TriangleMesh drivers (trianglemesh.cpp, mesh_bvh.cpp,
-// trianglemesh_clean.cpp, trianglemesh_filter.cpp) share: the size and dtype
-// checks and the checked int32 triangle list.
+// trianglemesh_clean.cpp, trianglemesh_filter.cpp, trianglemesh_topology.cpp,
+// trianglemesh_subdivide.cpp, trianglemesh_clip.cpp) share: the size and dtype
+// checks, the checked int32 triangle list, the capacity refusal of the count /
+// fill protocol, and the allocation of the incidence tables and the long
+// lists. Download is pointcloud_call.h's.
 #pragma once
 
 #include "../trianglemesh.h"
@@ -38,9 +41,7 @@ inline int LoadTriangles(PoolScratch& pool, Words* w, const void* triangles_dev,
                              &w->bad, pool.s);
     if (st) return st;
     int bad = 0;
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&bad, &w->bad, sizeof(int),
-                                   hipMemcpyDeviceToHost, pool.s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(pool.s));
+    if ((st = Download(&w->bad, &bad, sizeof(bad), pool.s))) return st;
     O3DMI_REQUIRE(!bad, "triangle index outside [0, v)");
     *tri = narrowed ? narrowed : (const int32_t*)triangles_dev;
     return O3DMI_OK;
@@ -57,6 +58,43 @@ inline int CheckVertexAttrs(int dtype, int attr_dtype, const void* normals_dev,
                   "null argument: normals given, no output for them");
     O3DMI_REQUIRE(!colors_dev || colors_out_dev,
                   "null argument: colours given, no output for them");
+    return O3DMI_OK;
+}
+
+// The refusal of a fill call whose capacity is below the count.
+inline int CapacityError(const char* what) {
+    SetLastError(what);
+    return O3DMI_ERR_CAPACITY;
+}
+
+// The three arrays of an edge table of n_slots slots (3 m for a mesh's own).
+// The scratch of its build (IncidenceScratchBytes) stays with the caller, who
+// may share it with other steps.
+inline int AllocEdgeTable(PoolScratch& pool, int64_t n_slots, EdgeTable* tb) {
+    const size_t bytes = sizeof(uint32_t) * (size_t)n_slots;
+    int st = pool.Alloc(&tb->lo, bytes);
+    if (!st) st = pool.Alloc(&tb->hi, bytes);
+    if (!st) st = pool.Alloc(&tb->slot, bytes);
+    return st;
+}
+
+// The four arrays of the corner table of m triangles on v vertices.
+inline int AllocCornerTable(PoolScratch& pool, int64_t m, int64_t v,
+                            CornerTable* tb) {
+    const size_t corner_bytes = sizeof(uint32_t) * 3 * (size_t)m;
+    int st = pool.Alloc(&tb->vertex, corner_bytes);
+    if (!st) st = pool.Alloc(&tb->corner, corner_bytes);
+    if (!st) st = pool.Alloc(&tb->count, sizeof(int32_t) * (size_t)v);
+    if (!st) st = pool.Alloc(&tb->start, sizeof(int64_t) * (size_t)v);
+    return st;
+}
+
+// A long list over n items: n + 1 ints, the last one the counter, zeroed on
+// the pool's stream.
+inline int AllocLongList(PoolScratch& pool, int64_t n, int32_t** list) {
+    const int st = pool.Alloc(list, sizeof(int32_t) * ((size_t)n + 1));
+    if (st) return st;
+    O3DMI_HIP_CHECK(hipMemsetAsync(*list + n, 0, sizeof(int32_t), pool.s));
     return O3DMI_OK;
 }
 

@@ -118,9 +118,7 @@ int BuildAdjacency(PoolScratch& pool, const int32_t* tri, int64_t m, int64_t v,
     Counts* counts = nullptr;
     const size_t slot_bytes = sizeof(uint32_t) * (size_t)n3;
     const size_t vertex_ints = sizeof(int32_t) * (size_t)v;
-    int st = pool.Alloc(&tb.lo, slot_bytes);
-    if (!st) st = pool.Alloc(&tb.hi, slot_bytes);
-    if (!st) st = pool.Alloc(&tb.slot, slot_bytes);
+    int st = AllocEdgeTable(pool, n3, &tb);
     if (!st) st = pool.Alloc(&scratch, IncidenceScratchBytes(m, v));
     if (!st) st = pool.Alloc(&flags, sizeof(int32_t) * (size_t)n3);
     if (!st) st = pool.Alloc(&pos, sizeof(int64_t) * (size_t)n3);
@@ -152,9 +150,7 @@ int BuildAdjacency(PoolScratch& pool, const int32_t* tri, int64_t m, int64_t v,
                              s)))
         return st;
     Counts host;
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&host, counts, sizeof(Counts),
-                                   hipMemcpyDeviceToHost, s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
+    if ((st = Download(counts, &host, sizeof(host), s))) return st;
     const int64_t n_edges = (int64_t)host.n_edges;
     adj->n_entries = 2 * n_edges - (int64_t)host.n_self;
     adj->neighbours = nullptr;
@@ -172,10 +168,8 @@ int BuildAdjacency(PoolScratch& pool, const int32_t* tri, int64_t m, int64_t v,
         index_dtype = O3DMI_I32;
     } else {
         if (capacity < 0) return O3DMI_OK;
-        if (capacity < adj->n_entries) {
-            SetLastError("adjacency list: capacity too small");
-            return O3DMI_ERR_CAPACITY;
-        }
+        if (capacity < adj->n_entries)
+            return CapacityError("adjacency list: capacity too small");
     }
     if (n_edges == 0) return O3DMI_OK;
     if ((st = AdjacencyUpperAsync(lo, hi, n_edges, adj->row_splits, lower,
@@ -348,9 +342,7 @@ int o3dmi_trianglemesh_simplify_vertex_clustering(
     if ((st = MinMaxBoundAsync(positions_dev, v, dtype, bound_scratch,
                                &bound_dev, s)))
         return st;
-    O3DMI_HIP_CHECK(hipMemcpyAsync(bound, bound_dev, sizeof(bound),
-                                   hipMemcpyDeviceToHost, s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
+    if ((st = Download(bound_dev, bound, sizeof(bound), s))) return st;
     double min_bound[3], extent = 0;
     for (int k = 0; k < 3; ++k) {
         min_bound[k] = bound[k] - voxel_size * 0.5;
@@ -400,13 +392,9 @@ int o3dmi_trianglemesh_simplify_vertex_clustering(
         return st;
     if ((st = pool.Alloc(&start, sizeof(int64_t) * (size_t)n_clusters)))
         return st;
-    if ((st = pool.Alloc(&long_list,
-                         sizeof(int32_t) * ((size_t)n_clusters + 1))))
-        return st;
     O3DMI_HIP_CHECK(hipMemsetAsync(counts, 0,
                                    sizeof(int32_t) * (size_t)n_clusters, s));
-    O3DMI_HIP_CHECK(
-            hipMemsetAsync(long_list + n_clusters, 0, sizeof(int32_t), s));
+    if ((st = AllocLongList(pool, n_clusters, &long_list))) return st;
     if ((st = ClusterPairsAsync(vnew, v, keys, members, counts, s))) return st;
     if ((st = SortPairsAsync(keys, members, v, BitsFor(n_clusters), scratch,
                              s)))
@@ -427,14 +415,8 @@ int o3dmi_trianglemesh_simplify_vertex_clustering(
     io.colors_out = colors_out_dev;
     if (contraction == 1 && m > 0) {
         double *plane = nullptr, *area = nullptr;
-        const size_t corner_bytes = sizeof(uint32_t) * 3 * (size_t)m;
         io.quadric = true;
-        if ((st = pool.Alloc(&io.corners.vertex, corner_bytes))) return st;
-        if ((st = pool.Alloc(&io.corners.corner, corner_bytes))) return st;
-        if ((st = pool.Alloc(&io.corners.count, sizeof(int32_t) * (size_t)v)))
-            return st;
-        if ((st = pool.Alloc(&io.corners.start, sizeof(int64_t) * (size_t)v)))
-            return st;
+        if ((st = AllocCornerTable(pool, m, v, &io.corners))) return st;
         if ((st = pool.Alloc(&plane, sizeof(double) * 4 * (size_t)m)))
             return st;
         if ((st = pool.Alloc(&area, sizeof(double) * (size_t)m))) return st;

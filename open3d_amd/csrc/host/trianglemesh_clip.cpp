@@ -93,9 +93,7 @@ int LoadInput(PoolScratch& pool, const CutInput& c, const int32_t** tri,
                                &w->bad, s)))
         return st;
     int bad = 0;
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&bad, &w->bad, sizeof(int),
-                                   hipMemcpyDeviceToHost, s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
+    if ((st = Download(&w->bad, &bad, sizeof(bad), s))) return st;
     O3DMI_REQUIRE(!bad,
                   "non-finite position, normal, colour or signed value");
     return O3DMI_OK;
@@ -129,62 +127,27 @@ int RankPoints(PoolScratch& tmp, PoolScratch& keep, Totals* tot,
     hipStream_t s = tmp.s;
     *out = {};
     if (n_used == 0) return O3DMI_OK;
-    uint32_t *slot_of = nullptr, *lo = nullptr, *hi = nullptr,
-             *order = nullptr;
-    int32_t *head = nullptr, *by_pos = nullptr;
-    int64_t *q_incl = nullptr, *rank_by_pos = nullptr;
+    uint32_t* slot_of = nullptr;
+    EdgeTable table;  // a "slot" is a compact position
+    EdgeRunScans scans;
     void* scratch = nullptr;
-    const size_t words = sizeof(uint32_t) * (size_t)n_used;
-    const size_t scans = sizeof(int64_t) * (size_t)n_used;
-    int st = tmp.Alloc(&slot_of, words);
-    if (!st) st = tmp.Alloc(&lo, words);
-    if (!st) st = tmp.Alloc(&hi, words);
-    if (!st) st = tmp.Alloc(&order, words);
-    if (!st) st = tmp.Alloc(&head, words);
-    if (!st) st = tmp.Alloc(&by_pos, words);
-    if (!st) st = tmp.Alloc(&q_incl, scans);
-    if (!st) st = tmp.Alloc(&rank_by_pos, scans);
+    int st = tmp.Alloc(&slot_of, sizeof(uint32_t) * (size_t)n_used);
+    if (!st) st = AllocEdgeTable(tmp, n_used, &table);
     if (!st)
         st = tmp.Alloc(&scratch, std::max(SortPairsScratchBytes(n_used),
                                           ScanScratchBytes(n_used)));
     if (st) return st;
     if ((st = CompactSlotsAsync(slot_used, slot_pos, 3 * m, slot_of, s)))
         return st;
-    if ((st = SortSlotKeysAsync(tri, s_dev, c, slot_of, n_used, BitsFor(v), lo,
-                                hi, order, scratch, s)))
+    if ((st = SortSlotKeysAsync(tri, s_dev, c, slot_of, n_used, BitsFor(v),
+                                table.lo, table.hi, table.slot, scratch, s)))
         return st;
-    const EdgeTable table = {lo, hi, order};  // a "slot" is a compact position
-    if ((st = EdgeSlotFlagsAsync(table, n_used, head, by_pos, nullptr, s)))
+    if ((st = CountEdgeRuns(tmp, table, n_used, ids, false, scratch,
+                            &tot->points, &scans, &out->n_points)))
         return st;
-    if ((st = PrefixSumAsync(by_pos, n_used, false, rank_by_pos,
-                             (int64_t*)&tot->points, scratch, s)))
-        return st;
-    long long n_points = 0;
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&n_points, &tot->points, sizeof(n_points),
-                                   hipMemcpyDeviceToHost, s));
-    if (ids &&
-        (st = PrefixSumAsync(head, n_used, true, q_incl, nullptr, scratch, s)))
-        return st;
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
-    out->n_points = n_points;
     if (!ids) return O3DMI_OK;
-    const size_t recs = sizeof(uint32_t) * (size_t)n_points;
-    st = keep.Alloc(&out->points.lo, recs);
-    if (!st) st = keep.Alloc(&out->points.hi, recs);
-    if (!st) st = keep.Alloc(&out->points.rank, recs);
-    if (!st) st = keep.Alloc(&out->points.head, recs + sizeof(int32_t));
-    if (!st) st = tmp.Alloc(&out->id_by_pos, words);
-    if (st) return st;
-    if ((st = EdgeRecordsAsync(table, n_used, head, q_incl, rank_by_pos,
-                               n_points, out->points, s)))
-        return st;
-    return SlotVertexIdsAsync(table, n_used, q_incl, out->points, 0, nullptr,
-                              nullptr, out->id_by_pos, s);
-}
-
-int CapacityError(const char* what) {
-    SetLastError(what);
-    return O3DMI_ERR_CAPACITY;
+    return NumberEdgeRuns(tmp, keep, table, n_used, scans, out->n_points, 0,
+                          nullptr, &out->points, &out->id_by_pos);
 }
 
 // ---- clip ---------------------------------------------------------------------------
@@ -261,9 +224,7 @@ int ClipPlane(const CutInput& c, const ClipOutput& o, hipStream_t s) {
                              (int64_t*)&tot->used, scratch, s)))
         return st;
     Totals h = {};
-    O3DMI_HIP_CHECK(
-            hipMemcpyAsync(&h, tot, sizeof(h), hipMemcpyDeviceToHost, s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
+    if ((st = Download(tot, &h, sizeof(h), s))) return st;
 
     Ranked rk;
     if ((st = RankPoints(pool, pool, tot, tri, m, v, s_dev, 0., slot_used,
@@ -351,9 +312,7 @@ int SliceContour(PoolScratch& pool, const SliceTables& tb, const int32_t* tri,
                              (int64_t*)&tb.tot->used, tb.scratch, s)))
         return st;
     Totals h = {};
-    O3DMI_HIP_CHECK(
-            hipMemcpyAsync(&h, tb.tot, sizeof(h), hipMemcpyDeviceToHost, s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
+    if ((st = Download(tb.tot, &h, sizeof(h), s))) return st;
     Ranked rk;
     if ((st = RankPoints(tmp, pool, tb.tot, tri, m, v, s_dev, c, tb.slot_used,
                          tb.slot_pos, h.used, records, &rk)))

@@ -114,9 +114,7 @@ int RunFilter(const FilterCall& c, int kind, int64_t passes,
         if ((st = pool.Alloc(&adj.neighbours, sizeof(int32_t)))) return st;
         O3DMI_HIP_CHECK(hipMemsetAsync(adj.row_splits, 0, bytes, s));
     }
-    if ((st = pool.Alloc(&long_list, sizeof(int32_t) * ((size_t)v + 1))))
-        return st;
-    O3DMI_HIP_CHECK(hipMemsetAsync(long_list + v, 0, sizeof(int32_t), s));
+    if ((st = AllocLongList(pool, v, &long_list))) return st;
     if ((st = LongListsAsync(adj.row_splits, v, long_list, s))) return st;
 
     const size_t buf_bytes = sizeof(double) * 3 * (size_t)v;

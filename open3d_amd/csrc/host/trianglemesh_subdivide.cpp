@@ -18,6 +18,76 @@
 
 using namespace o3dmi;
 
+namespace o3dmi {
+
+// The numbering chain of trianglemesh_subdivide.h, shared with ClipPlane /
+// SlicePlane (host/trianglemesh_clip.cpp), whose "edges" are the distinct cut
+// points. The one wait of the chain is at the end of the first half, so a
+// caller can stop after the count or check a capacity before anything of its
+// own is written.
+int CountEdgeRuns(PoolScratch& tmp, const EdgeTable& table, int64_t n_slots,
+                  bool number, bool triangles, void* scratch_dev,
+                  long long* total_dev, EdgeRunScans* scans,
+                  int64_t* n_runs_out) {
+    hipStream_t s = tmp.s;
+    *scans = {};
+    int32_t* by_slot = nullptr;
+    const size_t slot_bytes = sizeof(uint32_t) * (size_t)n_slots;
+    const size_t scan_bytes = sizeof(int64_t) * (size_t)n_slots;
+    int st = tmp.Alloc(&scans->head, slot_bytes);
+    if (!st) st = tmp.Alloc(&by_slot, slot_bytes);
+    if (!st) st = tmp.Alloc(&scans->rank_by_slot, scan_bytes);
+    if (!st) st = tmp.Alloc(&scans->q_incl, scan_bytes);
+    if (!st && triangles) st = tmp.Alloc(&scans->distinct, slot_bytes);
+    if (!st && triangles) st = tmp.Alloc(&scans->distinct_incl, scan_bytes);
+    if (st) return st;
+    if ((st = EdgeSlotFlagsAsync(table, n_slots, scans->head, by_slot,
+                                 scans->distinct, s)))
+        return st;
+    if ((st = PrefixSumAsync(by_slot, n_slots, false, scans->rank_by_slot,
+                             (int64_t*)total_dev, scratch_dev, s)))
+        return st;
+    long long n_runs = 0;
+    O3DMI_HIP_CHECK(hipMemcpyAsync(&n_runs, total_dev, sizeof(n_runs),
+                                   hipMemcpyDeviceToHost, s));
+    if (number && (st = PrefixSumAsync(scans->head, n_slots, true,
+                                       scans->q_incl, nullptr, scratch_dev, s)))
+        return st;
+    if (number && triangles &&
+        (st = PrefixSumAsync(scans->distinct, n_slots, true,
+                             scans->distinct_incl, nullptr, scratch_dev, s)))
+        return st;
+    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
+    *n_runs_out = n_runs;
+    return O3DMI_OK;
+}
+
+int NumberEdgeRuns(PoolScratch& tmp, PoolScratch& keep, const EdgeTable& table,
+                   int64_t n_slots, const EdgeRunScans& scans, int64_t n_runs,
+                   int64_t id_base, const int32_t* tri, SubdivEdges* edges,
+                   int32_t** id_by_slot) {
+    hipStream_t s = tmp.s;
+    const bool triangles = scans.distinct != nullptr;
+    *edges = {};
+    const size_t run_bytes = sizeof(uint32_t) * (size_t)n_runs;
+    const size_t slot_bytes = sizeof(uint32_t) * (size_t)n_slots;
+    int st = keep.Alloc(&edges->lo, run_bytes);
+    if (!st) st = keep.Alloc(&edges->hi, run_bytes);
+    if (!st) st = keep.Alloc(&edges->rank, run_bytes);
+    if (!st) st = keep.Alloc(&edges->head, run_bytes + sizeof(int32_t));
+    if (!st && triangles) st = keep.Alloc(&edges->triangles, run_bytes);
+    if (!st && triangles) st = keep.Alloc(&edges->opposite, slot_bytes);
+    if (!st) st = tmp.Alloc(id_by_slot, slot_bytes);
+    if (st) return st;
+    if ((st = EdgeRecordsAsync(table, n_slots, scans.head, scans.q_incl,
+                               scans.rank_by_slot, n_runs, *edges, s)))
+        return st;
+    return SlotVertexIdsAsync(table, n_slots, scans.q_incl, *edges, id_base,
+                              scans.distinct, tri, *id_by_slot, s);
+}
+
+}  // namespace o3dmi
+
 namespace {
 
 struct SubdivideCall {
@@ -61,69 +131,32 @@ int RefineLevel(PoolScratch& pool, Words* w, const SubdivideCall& c, bool loop,
     PoolScratch tmp(s);
     EdgeTable tb;
     void* scratch = nullptr;
-    int32_t *head = nullptr, *by_slot = nullptr, *distinct = nullptr;
+    EdgeRunScans scans;
     int32_t* new_id = nullptr;
-    int64_t *rank_by_slot = nullptr, *q_incl = nullptr,
-            *distinct_incl = nullptr;
-    const size_t slot_bytes = sizeof(uint32_t) * (size_t)n3;
-    const size_t scan_bytes = sizeof(int64_t) * (size_t)n3;
-    int st = tmp.Alloc(&tb.lo, slot_bytes);
-    if (!st) st = tmp.Alloc(&tb.hi, slot_bytes);
-    if (!st) st = tmp.Alloc(&tb.slot, slot_bytes);
+    int st = AllocEdgeTable(tmp, n3, &tb);
     if (!st)
         st = tmp.Alloc(&scratch, std::max(IncidenceScratchBytes(m, v),
                                           ScanScratchBytes(n3)));
-    if (!st) st = tmp.Alloc(&head, slot_bytes);
-    if (!st) st = tmp.Alloc(&by_slot, slot_bytes);
-    if (!st) st = tmp.Alloc(&rank_by_slot, scan_bytes);
-    if (!st) st = tmp.Alloc(&q_incl, scan_bytes);
-    if (!st && loop) st = tmp.Alloc(&distinct, slot_bytes);
-    if (!st && loop) st = tmp.Alloc(&distinct_incl, scan_bytes);
     if (st) return st;
     if ((st = BuildEdgeTableAsync(lv->tri, m, v, tb, scratch, s))) return st;
-    if ((st = EdgeSlotFlagsAsync(tb, n3, head, by_slot, distinct, s)))
+    if ((st = CountEdgeRuns(tmp, tb, n3, true, loop, scratch, &w->total,
+                            &scans, &lv->n_edges)))
         return st;
-    if ((st = PrefixSumAsync(by_slot, n3, false, rank_by_slot,
-                             (int64_t*)&w->total, scratch, s)))
-        return st;
-    long long n_edges = 0;
-    O3DMI_HIP_CHECK(hipMemcpyAsync(&n_edges, &w->total, sizeof(n_edges),
-                                   hipMemcpyDeviceToHost, s));
-    if ((st = PrefixSumAsync(head, n3, true, q_incl, nullptr, scratch, s)))
-        return st;
-    if (loop && (st = PrefixSumAsync(distinct, n3, true, distinct_incl, nullptr,
-                                     scratch, s)))
-        return st;
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
-    lv->n_edges = n_edges;
+    const int64_t n_edges = lv->n_edges;
     if (last) {
         *c.n_vertices_out = v + n_edges;
         *c.n_triangles_out = 4 * m;
         if (c.vertex_capacity < 0) return O3DMI_OK;
-        if (c.vertex_capacity < v + n_edges) {
-            SetLastError("subdivide: vertex capacity too small");
-            return O3DMI_ERR_CAPACITY;
-        }
+        if (c.vertex_capacity < v + n_edges)
+            return CapacityError("subdivide: vertex capacity too small");
     }
 
     SubdivEdges& ed = lv->edges;
-    ed = {};
-    const size_t edge_bytes = sizeof(uint32_t) * (size_t)n_edges;
-    st = pool.Alloc(&ed.lo, edge_bytes);
-    if (!st) st = pool.Alloc(&ed.hi, edge_bytes);
-    if (!st) st = pool.Alloc(&ed.rank, edge_bytes);
-    if (!st) st = pool.Alloc(&ed.head, edge_bytes + sizeof(int32_t));
-    if (!st && loop) st = pool.Alloc(&ed.triangles, edge_bytes);
-    if (!st && loop) st = pool.Alloc(&ed.opposite, slot_bytes);
-    if (!st) st = tmp.Alloc(&new_id, slot_bytes);
-    if (st) return st;
-    if ((st = EdgeRecordsAsync(tb, n3, head, q_incl, rank_by_slot, n_edges, ed,
-                               s)))
+    if ((st = NumberEdgeRuns(tmp, pool, tb, n3, scans, n_edges, v, lv->tri,
+                             &ed, &new_id)))
         return st;
-    if ((st = SlotVertexIdsAsync(tb, n3, q_incl, ed, v, distinct, lv->tri,
-                                 new_id, s)))
-        return st;
-    if (loop && (st = EdgeTriangleCountsAsync(ed, n_edges, distinct_incl, s)))
+    if (loop &&
+        (st = EdgeTriangleCountsAsync(ed, n_edges, scans.distinct_incl, s)))
         return st;
     if (last)
         return EmitSubdividedAsync(lv->tri, m, new_id, c.index_dtype,
@@ -147,14 +180,9 @@ int LoopLevel(PoolScratch& pool, const Level& lv, const SubdivAttrs& attrs) {
     if (!st)
         st = tmp.Alloc(&boundary,
                        (size_t)std::max<int64_t>(adj.n_entries, 1));
-    if (!st)
-        st = tmp.Alloc(&long_vertices, sizeof(int32_t) * ((size_t)v + 1));
-    if (!st)
-        st = tmp.Alloc(&long_edges, sizeof(int32_t) * ((size_t)n_edges + 1));
+    if (!st) st = AllocLongList(tmp, v, &long_vertices);
+    if (!st) st = AllocLongList(tmp, n_edges, &long_edges);
     if (st) return st;
-    O3DMI_HIP_CHECK(hipMemsetAsync(long_vertices + v, 0, sizeof(int32_t), s));
-    O3DMI_HIP_CHECK(
-            hipMemsetAsync(long_edges + n_edges, 0, sizeof(int32_t), s));
     if ((st = BoundaryFlagsAsync(lv.edges, n_edges, adj.row_splits,
                                  adj.neighbours, boundary, s)))
         return st;
@@ -221,10 +249,8 @@ int Subdivide(const SubdivideCall& c, bool loop) {
         *c.n_vertices_out = v;
         *c.n_triangles_out = m;
         if (count_only) return O3DMI_OK;
-        if (c.vertex_capacity < v) {
-            SetLastError("subdivide: vertex capacity too small");
-            return O3DMI_ERR_CAPACITY;
-        }
+        if (c.vertex_capacity < v)
+            return CapacityError("subdivide: vertex capacity too small");
         const size_t row_bytes = 3 * ElemSize(c.dtype) * (size_t)v;
         for (int a = 0; a < 3; ++a)
             if (ins[a])

@@ -58,10 +58,7 @@ int Begin(Call* c) {
 // The edge table, built once a call.
 int NeedEdges(Call* c) {
     if (c->edges.lo) return O3DMI_OK;
-    const size_t bytes = sizeof(uint32_t) * 3 * (size_t)c->m;
-    int st = c->pool.Alloc(&c->edges.lo, bytes);
-    if (!st) st = c->pool.Alloc(&c->edges.hi, bytes);
-    if (!st) st = c->pool.Alloc(&c->edges.slot, bytes);
+    int st = AllocEdgeTable(c->pool, 3 * c->m, &c->edges);
     if (!st)
         st = c->pool.Alloc(&c->scratch, IncidenceScratchBytes(c->m, c->v));
     if (!st)
@@ -71,13 +68,6 @@ int NeedEdges(Call* c) {
     if (st) return st;
     return BuildEdgeTableAsync(c->tri, c->m, c->v, c->edges, c->scratch,
                                c->pool.s);
-}
-
-int Download(const void* src_dev, void* dst, size_t bytes, hipStream_t s) {
-    O3DMI_HIP_CHECK(hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost,
-                                   s));
-    O3DMI_HIP_CHECK(hipStreamSynchronize(s));
-    return O3DMI_OK;
 }
 
 // The number of (lo, hi) runs of the edge table. One wait.
@@ -117,22 +107,16 @@ int EdgeManifold(Call* c, bool allow_boundary, int* out) {
 int NonManifoldVertices(Call* c, int index_dtype, void* out_dev,
                         int64_t capacity, int64_t* n_out) {
     hipStream_t s = c->pool.s;
-    const size_t corner_bytes = sizeof(uint32_t) * 3 * (size_t)c->m;
     CornerTable corners;
     int* parent = nullptr;
     int32_t* long_list = nullptr;
     int64_t* pos = nullptr;
     int st = NeedEdges(c);
-    if (!st) st = c->pool.Alloc(&corners.vertex, corner_bytes);
-    if (!st) st = c->pool.Alloc(&corners.corner, corner_bytes);
-    if (!st) st = c->pool.Alloc(&corners.count, sizeof(int32_t) * (size_t)c->v);
-    if (!st) st = c->pool.Alloc(&corners.start, sizeof(int64_t) * (size_t)c->v);
+    if (!st) st = AllocCornerTable(c->pool, c->m, c->v, &corners);
     if (!st) st = c->pool.Alloc(&parent, sizeof(int) * 3 * (size_t)c->m);
-    if (!st)
-        st = c->pool.Alloc(&long_list, sizeof(int32_t) * ((size_t)c->v + 1));
     if (!st) st = c->pool.Alloc(&pos, sizeof(int64_t) * (size_t)c->v);
+    if (!st) st = AllocLongList(c->pool, c->v, &long_list);
     if (st) return st;
-    O3DMI_HIP_CHECK(hipMemsetAsync(long_list + c->v, 0, sizeof(int32_t), s));
     if ((st = BuildCornerTableAsync(c->tri, c->m, c->v, corners, c->scratch,
                                     s)))
         return st;
@@ -147,10 +131,8 @@ int NonManifoldVertices(Call* c, int index_dtype, void* out_dev,
     if ((st = Download(&c->cells->n_vertices, &n, sizeof(n), s))) return st;
     *n_out = (int64_t)n;
     if (capacity < 0 || n == 0) return O3DMI_OK;
-    if (capacity < n) {
-        SetLastError("non-manifold vertices: capacity too small");
-        return O3DMI_ERR_CAPACITY;
-    }
+    if (capacity < n)
+        return CapacityError("non-manifold vertices: capacity too small");
     if ((st = EmitFlaggedAsync(c->flags, pos, c->v, index_dtype, out_dev, s)))
         return st;
     O3DMI_HIP_CHECK(hipStreamSynchronize(s));
@@ -282,10 +264,8 @@ int SelfIntersections(Call* c, const void* positions_dev, int dtype,
     if ((st = TraversalResult(c, &n, visits_out))) return st;
     *n_out = kind == kIntersectAny ? (n != 0) : n;
     if (kind == kIntersectAny || capacity < 0 || n == 0) return O3DMI_OK;
-    if (capacity < n) {
-        SetLastError("self-intersecting triangles: capacity too small");
-        return O3DMI_ERR_CAPACITY;
-    }
+    if (capacity < n)
+        return CapacityError("self-intersecting triangles: capacity too small");
     // the pairs are distinct: stably by j, then by i, is ascending (i, j)
     const int bits = BitsFor(c->m);
     if ((st = SortPairsAsync(js, is, n, bits, sort_scratch, s))) return st;

@@ -8,24 +8,11 @@
 // and vote iterate the last). No result depends on the tree: see the header.
 #include "mesh_bvh.h"
 
-#include "common.h"
+#include "mesh_launch.h"
 #include "sort.h"
 
 namespace o3dmi {
 namespace {
-
-#define O3DMI_GRID_STRIDE(i, n)                                            \
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;       \
-         i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-inline dim3 Grid(int64_t n) { return dim3((unsigned)GridFor(n, kBlock)); }
-
-#define O3DMI_LAUNCH(kernel, n, ...)                                       \
-    do {                                                                   \
-        hipLaunchKernelGGL(kernel, Grid(n), dim3(kBlock), 0, s,            \
-                           __VA_ARGS__);                                   \
-        O3DMI_HIP_CHECK(hipGetLastError());                                \
-    } while (0)
 
 inline size_t Align256(size_t b) { return (b + 255) & ~(size_t)255; }
 

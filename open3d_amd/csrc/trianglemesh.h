@@ -165,6 +165,14 @@ struct EdgeTable {
     uint32_t* hi;
     uint32_t* slot;
 };
+__device__ __forceinline__ bool SameEdge(const EdgeTable& tb, int64_t a,
+                                         int64_t b) {
+    return tb.lo[a] == tb.lo[b] && tb.hi[a] == tb.hi[b];
+}
+// Entry j is the first one of its run.
+__device__ __forceinline__ bool FirstOfRun(const EdgeTable& tb, int64_t j) {
+    return j == 0 || !SameEdge(tb, j, j - 1);
+}
 int BuildEdgeTableAsync(const int32_t* tri, int64_t m, int64_t v,
                         const EdgeTable& table, void* scratch_dev,
                         hipStream_t s);
@@ -180,6 +188,8 @@ int EmitEdgesAsync(const EdgeTable& table, int64_t n_slots,
                    int index_dtype, void* edges_out_dev, hipStream_t s);
 
 // ---- connected components -----------------------------------------------------
+// p[i] = i: every element its own root, the start of a union-find.
+int IotaAsync(int* p_dev, int64_t n, hipStream_t s);
 // root[t] = the lowest triangle index of t's component (triangles that share
 // an edge of the table are adjacent), is_root[t] = (root[t] == t). parent:
 // {m} ints of scratch.

@@ -7,7 +7,7 @@
 // counts, flags and the union-find's CAS.
 #include "trianglemesh.h"
 
-#include "common.h"
+#include "mesh_launch.h"
 #include "scan.h"
 #include "sort.h"
 #include "union_find.h"
@@ -17,10 +17,6 @@ namespace {
 
 __device__ __forceinline__ float MeshSqrt(float x) { return sqrtf(x); }
 __device__ __forceinline__ double MeshSqrt(double x) { return sqrt(x); }
-
-#define O3DMI_GRID_STRIDE(i, n)                                            \
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;       \
-         i < (n); i += (int64_t)gridDim.x * blockDim.x)
 
 template <typename I>
 __global__ void CheckTrianglesKernel(const I* __restrict__ tri, int64_t n3,
@@ -252,17 +248,12 @@ __global__ void SlotKeysKernel(const int32_t* __restrict__ tri, int64_t n3,
     }
 }
 
-__device__ __forceinline__ bool SameEdge(const EdgeTable& tb, int64_t a,
-                                         int64_t b) {
-    return tb.lo[a] == tb.lo[b] && tb.hi[a] == tb.hi[b];
-}
-
 __global__ void NonManifoldFlagsKernel(EdgeTable tb, int64_t n3,
                                        bool allow_boundary,
                                        int32_t* __restrict__ flags) {
     O3DMI_GRID_STRIDE(j, n3) {
         int32_t flag = 0;
-        if (j == 0 || !SameEdge(tb, j, j - 1)) {
+        if (FirstOfRun(tb, j)) {
             // the first slot of an edge: nothing past the third slot changes
             // either rule
             int mult = 1;
@@ -297,7 +288,7 @@ __global__ void IotaKernel(int* __restrict__ p, int64_t n) {
 __global__ void EdgeUnionKernel(EdgeTable tb, int64_t n3,
                                 int* __restrict__ parent) {
     O3DMI_GRID_STRIDE(j, n3) {
-        if (j == 0 || !SameEdge(tb, j, j - 1)) continue;
+        if (FirstOfRun(tb, j)) continue;
         const int a = (int)(tb.slot[j] / 3u), b = (int)(tb.slot[j - 1] / 3u);
         if (a != b) DbscanUnite(parent, a, b);
     }
@@ -462,15 +453,6 @@ __global__ void RemapTrianglesKernel(const int32_t* __restrict__ tri, int64_t m,
     }
 }
 
-inline dim3 Grid(int64_t n) { return dim3((unsigned)GridFor(n, kBlock)); }
-
-#define O3DMI_LAUNCH(kernel, n, ...)                                       \
-    do {                                                                   \
-        hipLaunchKernelGGL(kernel, Grid(n), dim3(kBlock), 0, s,            \
-                           __VA_ARGS__);                                   \
-        O3DMI_HIP_CHECK(hipGetLastError());                                \
-    } while (0)
-
 inline size_t Align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -597,7 +579,7 @@ int VertexNormalSumAsync(const CornerTable& table, int64_t v,
                          const void* triangle_normals_dev, int dtype,
                          void* out_dev, int32_t* long_list_dev,
                          hipStream_t s) {
-    const dim3 waves((unsigned)GridFor(v, kBlock / 64, kCUs * 8));
+    const dim3 waves = WaveGrid(v);
     if (dtype == O3DMI_F64) {
         O3DMI_LAUNCH(VertexNormalThreadKernel<double>, v, table, v,
                      (const double*)triangle_normals_dev, (double*)out_dev,
@@ -652,9 +634,15 @@ int EmitEdgesAsync(const EdgeTable& table, int64_t n_slots,
     return O3DMI_OK;
 }
 
+int IotaAsync(int* p_dev, int64_t n, hipStream_t s) {
+    O3DMI_LAUNCH(IotaKernel, n, p_dev, n);
+    return O3DMI_OK;
+}
+
 int ClusterRootsAsync(const EdgeTable& table, int64_t m, int* parent_dev,
                       int* root_dev, int32_t* is_root_dev, hipStream_t s) {
-    O3DMI_LAUNCH(IotaKernel, m, parent_dev, m);
+    const int st = IotaAsync(parent_dev, m, s);
+    if (st) return st;
     O3DMI_LAUNCH(EdgeUnionKernel, 3 * m, table, 3 * m, parent_dev);
     O3DMI_LAUNCH(FlattenKernel, m, parent_dev, m, root_dev, is_root_dev);
     return O3DMI_OK;

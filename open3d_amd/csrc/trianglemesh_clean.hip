@@ -18,25 +18,13 @@
 // the table's CAS / min and the long-list counters.
 #include "trianglemesh_clean.h"
 
+#include "mesh_launch.h"
 #include "rep_table.h"
 #include "scan.h"
 #include "sort.h"
 
 namespace o3dmi {
 namespace {
-
-#define O3DMI_GRID_STRIDE(i, n)                                            \
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;       \
-         i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-inline dim3 Grid(int64_t n) { return dim3((unsigned)GridFor(n, kBlock)); }
-
-#define O3DMI_LAUNCH(kernel, n, ...)                                       \
-    do {                                                                   \
-        hipLaunchKernelGGL(kernel, Grid(n), dim3(kBlock), 0, s,            \
-                           __VA_ARGS__);                                   \
-        O3DMI_HIP_CHECK(hipGetLastError());                                \
-    } while (0)
 
 // ---- representative table ---------------------------------------------------------
 __device__ __forceinline__ uint32_t BitsOf(float x) {
@@ -154,8 +142,7 @@ __global__ void EdgeRunFlagsKernel(EdgeTable tb, int64_t n3,
                                    unsigned long long* n_self) {
     unsigned long long mine = 0;
     O3DMI_GRID_STRIDE(j, n3) {
-        const bool first = j == 0 || tb.lo[j] != tb.lo[j - 1] ||
-                           tb.hi[j] != tb.hi[j - 1];
+        const bool first = FirstOfRun(tb, j);
         flags[j] = first;
         mine += first && tb.lo[j] == tb.hi[j];
     }
@@ -652,7 +639,7 @@ int TrianglePlanesAsync(const void* positions_dev, int dtype,
 
 int ContractClustersAsync(const ClusterIO& io, int64_t n_clusters, int dtype,
                           int32_t* long_list_dev, hipStream_t s) {
-    const dim3 waves((unsigned)GridFor(n_clusters, kBlock / 64, kCUs * 8));
+    const dim3 waves = WaveGrid(n_clusters);
     if (dtype == O3DMI_F64) {
         O3DMI_LAUNCH(ContractThreadKernel<double>, n_clusters, io, n_clusters,
                      long_list_dev);

@@ -6,23 +6,12 @@
 // FMA contraction, so every result is a pure function of the input.
 #include "trianglemesh_clip.h"
 
+#define O3DMI_LAUNCH_BLOCK kClipBlock
+#include "mesh_launch.h"
 #include "sort.h"
 
 namespace o3dmi {
 namespace {
-
-#define O3DMI_GRID_STRIDE(i, n)                                            \
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;       \
-         i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-inline dim3 Grid(int64_t n) { return dim3((unsigned)GridFor(n, kClipBlock)); }
-
-#define O3DMI_LAUNCH(kernel, n, ...)                                       \
-    do {                                                                   \
-        hipLaunchKernelGGL(kernel, Grid(n), dim3(kClipBlock), 0, s,        \
-                           __VA_ARGS__);                                   \
-        O3DMI_HIP_CHECK(hipGetLastError());                                \
-    } while (0)
 
 // ---- the rules, shared by clip and slice ------------------------------------------
 __device__ __forceinline__ uint64_t PackPair(uint32_t lo, uint32_t hi) {

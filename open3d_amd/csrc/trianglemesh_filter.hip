@@ -12,21 +12,10 @@
 // marching-cubes order.
 #include "trianglemesh_clean.h"
 
+#include "mesh_launch.h"
+
 namespace o3dmi {
 namespace {
-
-#define O3DMI_GRID_STRIDE(i, n)                                            \
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;       \
-         i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-inline dim3 Grid(int64_t n) { return dim3((unsigned)GridFor(n, kBlock)); }
-
-#define O3DMI_LAUNCH(kernel, n, ...)                                       \
-    do {                                                                   \
-        hipLaunchKernelGGL(kernel, Grid(n), dim3(kBlock), 0, s,            \
-                           __VA_ARGS__);                                   \
-        O3DMI_HIP_CHECK(hipGetLastError());                                \
-    } while (0)
 
 template <typename T>
 __global__ void WidenKernel(const T* __restrict__ in, int64_t n,
@@ -200,8 +189,7 @@ int LaunchPass(const int64_t* row_splits_dev, const int32_t* neighbours_dev,
                hipStream_t s) {
     O3DMI_LAUNCH((FilterThreadKernel<kKind, kAttrs>), v, row_splits_dev,
                  neighbours_dev, v, pass);
-    hipLaunchKernelGGL((FilterWaveKernel<kKind, kAttrs>),
-                       dim3((unsigned)GridFor(v, kBlock / 64, kCUs * 8)),
+    hipLaunchKernelGGL((FilterWaveKernel<kKind, kAttrs>), WaveGrid(v),
                        dim3(kBlock), 0, s, row_splits_dev, neighbours_dev, v,
                        pass, long_list_dev);
     O3DMI_HIP_CHECK(hipGetLastError());

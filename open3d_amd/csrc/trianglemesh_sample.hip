@@ -4,7 +4,7 @@
 // of (seed, its index): no state, no atomics besides the error flag.
 #include "trianglemesh.h"
 
-#include "common.h"
+#include "mesh_launch.h"
 
 namespace o3dmi {
 namespace {
@@ -211,14 +211,12 @@ int MeshSamplePointsAsync(const MeshPrefixTree& tree, const void* areas_dev,
                   "sample points: normals wanted, none given");
     O3DMI_REQUIRE(!io.colors_out || io.vertex_colors,
                   "sample points: colours wanted, none given");
-    const dim3 grid((unsigned)GridFor(n, kBlock)), block(kBlock);
     if (dtype == O3DMI_F64)
-        hipLaunchKernelGGL(SamplePointsKernel<double>, grid, block, 0, s, tree,
-                           (const double*)areas_dev, io, n, seed);
+        O3DMI_LAUNCH(SamplePointsKernel<double>, n, tree,
+                     (const double*)areas_dev, io, n, seed);
     else
-        hipLaunchKernelGGL(SamplePointsKernel<float>, grid, block, 0, s, tree,
-                           (const float*)areas_dev, io, n, seed);
-    O3DMI_HIP_CHECK(hipGetLastError());
+        O3DMI_LAUNCH(SamplePointsKernel<float>, n, tree,
+                     (const float*)areas_dev, io, n, seed);
     return O3DMI_OK;
 }
 

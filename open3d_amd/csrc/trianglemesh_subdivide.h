@@ -44,6 +44,32 @@ struct SubdivEdges {
     int32_t* triangles;
     uint32_t* opposite;
 };
+// The numbering chain of a table's runs, in two halves around its one wait
+// (host/trianglemesh_subdivide.cpp). EdgeRunScans is what the first half
+// leaves for the second: {n_slots} arrays from `tmp`, distinct / distinct_incl
+// NULL unless `triangles`.
+struct EdgeRunScans {
+    int32_t* head;
+    int32_t* distinct;
+    int64_t* rank_by_slot;
+    int64_t* q_incl;
+    int64_t* distinct_incl;
+};
+// The flags, the exclusive scan of the per-slot flags into *total_dev, its
+// download, with `number` the inclusive scans of head (and of distinct), then
+// the wait: *n_runs_out. scratch_dev: ScanScratchBytes(n_slots).
+int CountEdgeRuns(PoolScratch& tmp, const EdgeTable& table, int64_t n_slots,
+                  bool number, bool triangles, void* scratch_dev,
+                  long long* total_dev, EdgeRunScans* scans,
+                  int64_t* n_runs_out);
+// After a first half with `number`: the records of the n_runs runs from `keep`
+// (triangles / opposite too when scans.distinct is there; `tri` is theirs) and
+// *id_by_slot {n_slots} from `tmp`, id_base + rank of every slot's run
+// (EdgeRecordsAsync, SlotVertexIdsAsync). Waits for nothing.
+int NumberEdgeRuns(PoolScratch& tmp, PoolScratch& keep, const EdgeTable& table,
+                   int64_t n_slots, const EdgeRunScans& scans, int64_t n_runs,
+                   int64_t id_base, const int32_t* tri, SubdivEdges* edges,
+                   int32_t** id_by_slot);
 // Fills lo / hi / rank / head from the run heads (q = q_incl[j] - 1, rank =
 // rank_by_slot[slot[j]]).
 int EdgeRecordsAsync(const EdgeTable& table, int64_t n_slots,

@@ -6,26 +6,10 @@
 // the library is built without FMA contraction.
 #include "trianglemesh_subdivide.h"
 
+#include "mesh_launch.h"
+
 namespace o3dmi {
 namespace {
-
-#define O3DMI_GRID_STRIDE(i, n)                                            \
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;       \
-         i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-inline dim3 Grid(int64_t n) { return dim3((unsigned)GridFor(n, kBlock)); }
-
-#define O3DMI_LAUNCH(kernel, n, ...)                                       \
-    do {                                                                   \
-        hipLaunchKernelGGL(kernel, Grid(n), dim3(kBlock), 0, s,            \
-                           __VA_ARGS__);                                   \
-        O3DMI_HIP_CHECK(hipGetLastError());                                \
-    } while (0)
-
-// A wave per listed item: the grid of the long-list kernels.
-inline dim3 WaveGrid(int64_t n) {
-    return dim3((unsigned)GridFor(n, kBlock / 64, kCUs * 8));
-}
 
 // ---- index side -------------------------------------------------------------------
 __global__ void EdgeSlotFlagsKernel(EdgeTable tb, int64_t n3,
@@ -33,8 +17,7 @@ __global__ void EdgeSlotFlagsKernel(EdgeTable tb, int64_t n3,
                                     int32_t* __restrict__ by_slot,
                                     int32_t* __restrict__ distinct) {
     O3DMI_GRID_STRIDE(j, n3) {
-        const bool first = j == 0 || tb.lo[j] != tb.lo[j - 1] ||
-                           tb.hi[j] != tb.hi[j - 1];
+        const bool first = FirstOfRun(tb, j);
         const uint32_t e = tb.slot[j];
         head[j] = first;
         by_slot[e] = first;

@@ -7,23 +7,11 @@
 
 #include <climits>
 
+#include "mesh_launch.h"
 #include "union_find.h"
 
 namespace o3dmi {
 namespace {
-
-#define O3DMI_GRID_STRIDE(i, n)                                            \
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;       \
-         i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-inline dim3 Grid(int64_t n) { return dim3((unsigned)GridFor(n, kBlock)); }
-
-#define O3DMI_LAUNCH(kernel, n, ...)                                       \
-    do {                                                                   \
-        hipLaunchKernelGGL(kernel, Grid(n), dim3(kBlock), 0, s,            \
-                           __VA_ARGS__);                                   \
-        O3DMI_HIP_CHECK(hipGetLastError());                                \
-    } while (0)
 
 // Coordinate k of vertex u, widened.
 __device__ __forceinline__ double Coord(const void* __restrict__ pos,
@@ -41,15 +29,6 @@ __global__ void CountFlagsKernel(const int32_t* __restrict__ flags, int64_t n,
     if ((threadIdx.x & 63) == 0 && sum) atomicAdd(count, sum);
 }
 
-__global__ void IotaKernel(int* __restrict__ p, int64_t n) {
-    O3DMI_GRID_STRIDE(i, n) p[i] = (int)i;
-}
-
-__device__ __forceinline__ bool SameEdge(const EdgeTable& tb, int64_t a,
-                                         int64_t b) {
-    return tb.lo[a] == tb.lo[b] && tb.hi[a] == tb.hi[b];
-}
-
 // ---- non-manifold vertices ----------------------------------------------------------
 // The corner of slot e's triangle that names x, one of the slot's two ends.
 __device__ __forceinline__ int CornerAt(const int32_t* __restrict__ tri,
@@ -64,7 +43,7 @@ __device__ __forceinline__ int CornerAt(const int32_t* __restrict__ tri,
 __global__ void WedgeUnionKernel(EdgeTable tb, const int32_t* __restrict__ tri,
                                  int64_t n3, int* __restrict__ parent) {
     O3DMI_GRID_STRIDE(j, n3) {
-        if (j == 0 || !SameEdge(tb, j, j - 1)) continue;
+        if (FirstOfRun(tb, j)) continue;
         const uint32_t lo = tb.lo[j], hi = tb.hi[j];
         if (lo == hi) continue;
         const uint32_t e = tb.slot[j], ep = tb.slot[j - 1];
@@ -161,7 +140,7 @@ __global__ void OrientUnionKernel(EdgeTable tb, const int32_t* __restrict__ tri,
                                   int64_t n3, int* __restrict__ parent,
                                   int* __restrict__ bad) {
     O3DMI_GRID_STRIDE(j, n3) {
-        if (j != 0 && SameEdge(tb, j, j - 1)) continue;
+        if (!FirstOfRun(tb, j)) continue;
         if (tb.lo[j] == tb.hi[j]) continue;
         int mult = 1;
         while (mult < 3 && j + mult < n3 && SameEdge(tb, j, j + mult)) ++mult;
@@ -666,17 +645,16 @@ int NonManifoldVertexFlagsAsync(const int32_t* tri, int64_t m, int64_t v,
                           flags_dev,
                   "null argument");
     const int64_t n3 = 3 * m;
-    O3DMI_LAUNCH(IotaKernel, n3, parent_dev, n3);
+    const int st = IotaAsync(parent_dev, n3, s);
+    if (st) return st;
     O3DMI_LAUNCH(WedgeUnionKernel, n3, edges, tri, n3, parent_dev);
     // the sorted corner keys are done with: they carry the wedge roots
     int* rootw = (int*)corners.vertex;
     O3DMI_LAUNCH(WedgeRootKernel, n3, tri, n3, parent_dev, rootw);
     O3DMI_LAUNCH(VertexFlagsThreadKernel, v, corners, v, rootw, long_list_dev,
                  flags_dev);
-    hipLaunchKernelGGL(VertexFlagsWaveKernel,
-                       dim3((unsigned)GridFor(v, kBlock / 64, kCUs * 8)),
-                       dim3(kBlock), 0, s, corners, v, rootw, long_list_dev,
-                       flags_dev);
+    hipLaunchKernelGGL(VertexFlagsWaveKernel, WaveGrid(v), dim3(kBlock), 0, s,
+                       corners, v, rootw, long_list_dev, flags_dev);
     O3DMI_HIP_CHECK(hipGetLastError());
     return O3DMI_OK;
 }
@@ -698,7 +676,8 @@ int OrientFlipsAsync(const int32_t* tri, int64_t m, const EdgeTable& edges,
                      hipStream_t s) {
     O3DMI_REQUIRE(tri && m > 0 && parent_dev && flip_dev && bad_dev,
                   "null argument");
-    O3DMI_LAUNCH(IotaKernel, 2 * m, parent_dev, 2 * m);
+    const int st = IotaAsync(parent_dev, 2 * m, s);
+    if (st) return st;
     O3DMI_LAUNCH(OrientUnionKernel, 3 * m, edges, tri, 3 * m, parent_dev,
                  bad_dev);
     O3DMI_LAUNCH(OrientFlattenKernel, m, parent_dev, m, flip_dev, bad_dev);

@@ -20,7 +20,7 @@
 namespace open3d {
 namespace core {
 
-/// Stand-in for core::TensorKey (slices only).
+/// Stand-in for core::TensorKey (unit-step slices and a single index).
 class TensorKey {
 public:
     static TensorKey Slice(int64_t start, int64_t stop, int64_t step) {
@@ -30,6 +30,15 @@ public:
         k.step = step;
         return k;
     }
+    /// Selects entry `i` of the leading dimension (which is dropped).
+    static TensorKey Index(int64_t i) {
+        TensorKey k;
+        k.is_index = true;
+        k.start = i;
+        k.stop = i + 1;
+        return k;
+    }
+    bool is_index = false;
     int64_t start = 0, stop = 0, step = 1;
 };
 
@@ -224,8 +233,18 @@ public:
         for (int64_t i = 0; i < n; ++i) SetDouble(i, (double)v);
         return *this;
     }
-    /// Unit-step slices of a 1-d or 2-d tensor, returned as a copy.
+    /// Unit-step slices of a 1-d or 2-d tensor, returned as a copy; a lone
+    /// TensorKey::Index is operator[] (a view of that row).
     Tensor GetItem(const std::vector<TensorKey>& keys) const {
+        if (keys.size() == 1 && keys[0].is_index) {
+            int64_t i = keys[0].start;
+            if (i < 0) i += GetLength();
+            if (i < 0 || i >= GetLength())
+                utility::LogError("shim GetItem: index out of range");
+            return (*this)[i];
+        }
+        for (const TensorKey& k : keys)
+            if (k.is_index) utility::LogError("shim GetItem: mixed index key");
         if (keys.size() == 1 && NumDims() == 1) {
             Tensor out({keys[0].stop - keys[0].start}, dtype_);
             for (int64_t i = keys[0].start; i < keys[0].stop; ++i)
@@ -290,6 +309,75 @@ public:
                 out.SetDouble(i * n + j, s);
             }
         return out;
+    }
+    /// Element-wise sum of two tensors with the same number of elements,
+    /// formed in the dtype (the result has this tensor's shape).
+    Tensor operator+(const Tensor& o) const {
+        if (o.NumElements() != NumElements() || o.dtype_ != dtype_)
+            utility::LogError("shim operator+: size or dtype mismatch");
+        Tensor t = Clone();
+        const int64_t n = NumElements();
+        if (dtype_ == core::Float32) {
+            float* d = t.GetDataPtr<float>();
+            const float* b = o.GetDataPtr<float>();
+            for (int64_t i = 0; i < n; ++i) d[i] = d[i] + b[i];
+        } else {
+            for (int64_t i = 0; i < n; ++i)
+                t.SetDouble(i, GetDouble(i) + o.GetDouble(i));
+        }
+        return t;
+    }
+    /// {1, k} Int64: the positions of the non-zero entries of a 1-d tensor,
+    /// ascending.
+    Tensor NonZero() const {
+        if (NumDims() != 1) utility::LogError("shim NonZero: 1-d only");
+        std::vector<int64_t> at;
+        for (int64_t i = 0; i < NumElements(); ++i)
+            if (GetDouble(i) != 0) at.push_back(i);
+        Tensor t({1, (int64_t)at.size()}, core::Int64);
+        if (!at.empty())
+            std::memcpy(t.data_, at.data(), sizeof(int64_t) * at.size());
+        return t;
+    }
+    /// start, start + step, ... below stop (step > 0).
+    static Tensor Arange(int64_t start, int64_t stop, int64_t step,
+                         Dtype dtype, const Device& d = Device("CPU:0")) {
+        if (step <= 0) utility::LogError("shim Arange: step must be positive");
+        const int64_t n = stop > start ? (stop - start + step - 1) / step : 0;
+        Tensor t({n}, dtype, d);
+        for (int64_t i = 0; i < n; ++i) t.SetDouble(i, (double)(start + i * step));
+        return t;
+    }
+    /// Advanced indexing with Int64 index tensors. One index tensor selects
+    /// entries of the leading dimension (whole rows); two of equal length
+    /// select elements (r[k], c[k]) of a 2-d tensor. Returned as a copy.
+    Tensor IndexGet(const std::vector<Tensor>& index_tensors) const {
+        const std::vector<int64_t> at = FlatOffsets(index_tensors);
+        const int64_t row = index_tensors.size() == 1 ? RowElements() : 1;
+        SizeVector shape{(int64_t)at.size()};
+        if (index_tensors.size() == 1)
+            shape.insert(shape.end(), shape_.begin() + 1, shape_.end());
+        Tensor out(shape, dtype_);
+        const size_t bytes = (size_t)(row * dtype_.ByteSize());
+        for (size_t k = 0; k < at.size(); ++k)
+            std::memcpy(static_cast<char*>(out.data_) + k * bytes,
+                        static_cast<const char*>(data_) + at[k] * bytes, bytes);
+        return out;
+    }
+    /// The assignment that matches IndexGet, in index order (a repeated
+    /// index keeps the last value).
+    void IndexSet(const std::vector<Tensor>& index_tensors,
+                  const Tensor& value) {
+        const std::vector<int64_t> at = FlatOffsets(index_tensors);
+        const int64_t row = index_tensors.size() == 1 ? RowElements() : 1;
+        if (value.NumElements() != (int64_t)at.size() * row ||
+            value.dtype_ != dtype_)
+            utility::LogError("shim IndexSet: size or dtype mismatch");
+        const size_t bytes = (size_t)(row * dtype_.ByteSize());
+        for (size_t k = 0; k < at.size(); ++k)
+            std::memcpy(static_cast<char*>(data_) + at[k] * bytes,
+                        static_cast<const char*>(value.data_) + k * bytes,
+                        bytes);
     }
     Tensor operator-(const Tensor& o) const {
         Tensor t = Clone();
@@ -363,6 +451,41 @@ public:
     }
 
 private:
+    int64_t RowElements() const {
+        int64_t row = 1;
+        for (size_t i = 1; i < shape_.size(); ++i) row *= shape_[i];
+        return row;
+    }
+    /// Offsets, in units of one row (one index tensor) or one element (two),
+    /// that a list of Int64 index tensors selects; range-checked.
+    std::vector<int64_t> FlatOffsets(const std::vector<Tensor>& idx) const {
+        if (idx.empty() || idx.size() > 2 || idx.size() > shape_.size() ||
+            (idx.size() == 2 && shape_.size() != 2))
+            utility::LogError("shim IndexGet/IndexSet: unsupported indices");
+        for (const Tensor& t : idx)
+            if (t.dtype_ != core::Int64 ||
+                t.NumElements() != idx[0].NumElements())
+                utility::LogError("shim IndexGet/IndexSet: index tensors "
+                                  "must be Int64 of one length");
+        const int64_t n = idx[0].NumElements();
+        std::vector<int64_t> at((size_t)n);
+        for (int64_t k = 0; k < n; ++k) {
+            int64_t r = idx[0].GetDataPtr<int64_t>()[k];
+            if (r < 0) r += shape_[0];
+            if (r < 0 || r >= shape_[0])
+                utility::LogError("shim IndexGet/IndexSet: index out of range");
+            if (idx.size() == 2) {
+                int64_t c = idx[1].GetDataPtr<int64_t>()[k];
+                if (c < 0) c += shape_[1];
+                if (c < 0 || c >= shape_[1])
+                    utility::LogError(
+                            "shim IndexGet/IndexSet: index out of range");
+                r = r * shape_[1] + c;
+            }
+            at[(size_t)k] = r;
+        }
+        return at;
+    }
     void Allocate() {
         size_t bytes = (size_t)(NumElements() * dtype_.ByteSize());
         blob_ = std::shared_ptr<void>(std::calloc(bytes ? bytes : 1, 1),

@@ -94,6 +94,8 @@ int Guard(F&& f) {
 extern "C" {
 
 const char* ref_last_error() { return g_err.c_str(); }
+// For the other translation units of this library (ref_entry_feature.cpp).
+void ref_set_last_error(const char* what) { g_err = what; }
 
 void ref_set_threads(int n) {
 #ifdef _OPENMP
@@ -904,6 +906,263 @@ int ref_odometry_information(int rows, int cols, const float* source_vertex,
                 Wrap(target_vertex, {rows, cols, 3}, core::Float32),
                 Mat(K, 3, 3), Mat(T, 4, 4), square_dist_thr, info);
         for (int i = 0; i < 36; ++i) info36[i] = info.GetDouble(i);
+    });
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Doppler ICP and the SLAC fill-ins: the reference's kernel bodies,
+// unmodified (RegistrationCPU.cpp is already included above). FPFH is a
+// translation unit of its own, ref_entry_feature.cpp.
+// ---------------------------------------------------------------------------
+#include "open3d/t/pipelines/kernel/FillInLinearSystemCPU.cpp"
+
+extern "C" {
+
+// PreComputeForDopplerICPKernelCPU, RegistrationCPU.cpp:416-424: v_s_in_S {3}
+// in the point dtype.
+int ref_doppler_precompute(const void* R_S_to_V9, const void* r_v_to_s_in_V3,
+                           const void* w_v_in_V3, const void* v_v_in_V3,
+                           int is_f64, void* v_s_in_S3) {
+    return Guard([&] {
+        if (is_f64)
+            pk::PreComputeForDopplerICPKernelCPU<double>(
+                    (const double*)R_S_to_V9, (const double*)r_v_to_s_in_V3,
+                    (const double*)w_v_in_V3, (const double*)v_v_in_V3,
+                    (double*)v_s_in_S3);
+        else
+            pk::PreComputeForDopplerICPKernelCPU<float>(
+                    (const float*)R_S_to_V9, (const float*)r_v_to_s_in_V3,
+                    (const float*)w_v_in_V3, (const float*)v_v_in_V3,
+                    (float*)v_s_in_S3);
+    });
+}
+
+// Whether DISPATCH_DUAL_ROBUST_KERNEL_FUNCTION (registration/
+// RobustKernelImpl.h:122-179), the dispatch of ComputePoseDopplerICPCPU,
+// accepts the pair of methods: 1 yes, 0 "Unsupported method.".
+int ref_doppler_dual_dispatch_accepts(int method_geometric,
+                                      int method_doppler) {
+    using reg::RobustKernelMethod;
+    int ran = 0;
+    int rc = Guard([&] {
+        using scalar_t = double;
+        DISPATCH_DUAL_ROBUST_KERNEL_FUNCTION(
+                scalar_t, (RobustKernelMethod)method_geometric, 1.0,
+                (RobustKernelMethod)method_doppler, 1.0, [&]() {
+                    (void)GetWeightFromRobustKernelFirst;
+                    (void)GetWeightFromRobustKernelSecond;
+                    ran = 1;
+                });
+    });
+    return rc == 0 && ran ? 1 : 0;
+}
+
+}  // extern "C"
+
+namespace {
+template <typename scalar_t>
+void DopplerPairTerms(const scalar_t* src, const scalar_t* dops,
+                      const scalar_t* dirs, const scalar_t* tgt,
+                      const scalar_t* tn, const int64_t* corr, int64_t n,
+                      const scalar_t* R, const scalar_t* r, const scalar_t* vs,
+                      bool reject, double threshold, double lambda_doppler,
+                      double period, int mg, double sg, double hg, int md,
+                      double sd, double hd, bool dual, scalar_t* out) {
+    using reg::RobustKernelMethod;
+    // ComputePoseDopplerICPCPU, RegistrationCPU.cpp:454-458.
+    const scalar_t slg = sqrt(1.0 - static_cast<scalar_t>(lambda_doppler));
+    const scalar_t sld = sqrt(lambda_doppler);
+    const scalar_t sld_dt = sld / static_cast<scalar_t>(period);
+    auto run = [&](auto first, auto second) {
+        for (int64_t w = 0; w < n; ++w)
+            pk::ComputePoseDopplerICPKernelCPU(
+                    src + 3 * w, dops + w, dirs + 3 * w, tgt, tn, corr + w, R,
+                    r, vs, reject, static_cast<scalar_t>(threshold), slg, sld,
+                    sld_dt, 1, out + 29 * w, first, second);
+    };
+    if (dual) {
+        DISPATCH_DUAL_ROBUST_KERNEL_FUNCTION(
+                scalar_t, (RobustKernelMethod)mg, sg, (RobustKernelMethod)md,
+                sd, [&]() {
+                    run(GetWeightFromRobustKernelFirst,
+                        GetWeightFromRobustKernelSecond);
+                });
+        return;
+    }
+    // The single-kernel dispatch (RobustKernelImpl.h:35-115), once per term.
+    DISPATCH_ROBUST_KERNEL_FUNCTION(
+            (RobustKernelMethod)mg, scalar_t, sg, hg, [&]() {
+                auto first = GetWeightFromRobustKernel;
+                DISPATCH_ROBUST_KERNEL_FUNCTION(
+                        (RobustKernelMethod)md, scalar_t, sd, hd, [&]() {
+                            run(first, GetWeightFromRobustKernel);
+                        });
+            });
+}
+}  // namespace
+
+extern "C" {
+
+// ComputePoseDopplerICPKernelCPU, RegistrationCPU.cpp:335-414 (with
+// GetJacobianDopplerICP, RegistrationImpl.h:555-643), called once per source
+// row with n = 1: out {n, 29} in the point dtype holds each row's 29 terms
+// (one pair summed into zeros). The weights come from the dual dispatch of
+// ComputePoseDopplerICPCPU (dual != 0), or from the single-kernel dispatch
+// applied to each term (the pairs the dual dispatch rejects).
+int ref_doppler_pair_terms(const void* src, const void* dopplers,
+                           const void* directions, const void* tgt,
+                           const void* tgt_n, const int64_t* corr, int64_t n,
+                           int is_f64, const void* R_S_to_V9,
+                           const void* r_v_to_s_in_V3, const void* v_s_in_S3,
+                           int reject, double threshold, double lambda_doppler,
+                           double period, int method_g, double scaling_g,
+                           double shape_g, int method_d, double scaling_d,
+                           double shape_d, int dual, void* out) {
+    return Guard([&] {
+        if (is_f64)
+            DopplerPairTerms<double>(
+                    (const double*)src, (const double*)dopplers,
+                    (const double*)directions, (const double*)tgt,
+                    (const double*)tgt_n, corr, n, (const double*)R_S_to_V9,
+                    (const double*)r_v_to_s_in_V3, (const double*)v_s_in_S3,
+                    reject != 0, threshold, lambda_doppler, period, method_g,
+                    scaling_g, shape_g, method_d, scaling_d, shape_d,
+                    dual != 0, (double*)out);
+        else
+            DopplerPairTerms<float>(
+                    (const float*)src, (const float*)dopplers,
+                    (const float*)directions, (const float*)tgt,
+                    (const float*)tgt_n, corr, n, (const float*)R_S_to_V9,
+                    (const float*)r_v_to_s_in_V3, (const float*)v_s_in_S3,
+                    reject != 0, threshold, lambda_doppler, period, method_g,
+                    scaling_g, shape_g, method_d, scaling_d, shape_d,
+                    dual != 0, (float*)out);
+    });
+}
+
+// FillInRigidAlignmentTermCPU, t/pipelines/kernel/FillInLinearSystemImpl.h:
+// 40-154: adds into AtA {n_vars, n_vars}, Atb {n_vars, 1}, residual {1}.
+int ref_fill_in_rigid_alignment_term(float* AtA, float* Atb, float* residual,
+                                     int64_t n_vars, const float* Ti_ps,
+                                     const float* Tj_qs,
+                                     const float* Ri_normal_ps, int64_t n,
+                                     int i, int j, float threshold) {
+    return Guard([&] {
+        Tensor A = Wrap(AtA, {n_vars, n_vars}, core::Float32);
+        Tensor b = Wrap(Atb, {n_vars, 1}, core::Float32);
+        Tensor r = Wrap(residual, {1}, core::Float32);
+        pk::FillInRigidAlignmentTermCPU(
+                A, b, r, Wrap(Ti_ps, {n, 3}, core::Float32),
+                Wrap(Tj_qs, {n, 3}, core::Float32),
+                Wrap(Ri_normal_ps, {n, 3}, core::Float32), i, j, threshold);
+    });
+}
+
+// The same, one call per pair with (i, j) = (0, 1) into a zeroed 12-unknown
+// system: out {n, 157} = the pair's 12x12 block, 12 rhs entries, residual.
+int ref_fill_in_rigid_alignment_pairs(const float* Ti_ps, const float* Tj_qs,
+                                      const float* Ri_normal_ps, int64_t n,
+                                      float threshold, float* out) {
+    return Guard([&] {
+        for (int64_t w = 0; w < n; ++w) {
+            float* o = out + 157 * w;
+            std::memset(o, 0, sizeof(float) * 157);
+            Tensor A = Wrap(o, {12, 12}, core::Float32);
+            Tensor b = Wrap(o + 144, {12, 1}, core::Float32);
+            Tensor r = Wrap(o + 156, {1}, core::Float32);
+            pk::FillInRigidAlignmentTermCPU(
+                    A, b, r, Wrap(Ti_ps + 3 * w, {1, 3}, core::Float32),
+                    Wrap(Tj_qs + 3 * w, {1, 3}, core::Float32),
+                    Wrap(Ri_normal_ps + 3 * w, {1, 3}, core::Float32), 0, 1,
+                    threshold);
+        }
+    });
+}
+
+// FillInSLACAlignmentTermCPU, FillInLinearSystemImpl.h:156-312: adds into AtA
+// {n_vars, n_vars}, Atb {n_vars}, residual {1}.
+int ref_fill_in_slac_alignment_term(
+        float* AtA, float* Atb, float* residual, int64_t n_vars,
+        const float* Ti_Cps, const float* Tj_Cqs, const float* Cnormal_ps,
+        const float* Ri_Cnormal_ps, const float* RjT_Ri_Cnormal_ps,
+        const int* cgrid_idx_ps, const int* cgrid_idx_qs,
+        const float* cgrid_ratio_ps, const float* cgrid_ratio_qs, int64_t n,
+        int i, int j, int n_frags, float threshold) {
+    return Guard([&] {
+        Tensor A = Wrap(AtA, {n_vars, n_vars}, core::Float32);
+        Tensor b = Wrap(Atb, {n_vars}, core::Float32);
+        Tensor r = Wrap(residual, {1}, core::Float32);
+        // the body's parameter order is (..., idx_ps, idx_qs, ratio_qs,
+        // ratio_ps): FillInLinearSystemImpl.h:169-172
+        pk::FillInSLACAlignmentTermCPU(
+                A, b, r, Wrap(Ti_Cps, {n, 3}, core::Float32),
+                Wrap(Tj_Cqs, {n, 3}, core::Float32),
+                Wrap(Cnormal_ps, {n, 3}, core::Float32),
+                Wrap(Ri_Cnormal_ps, {n, 3}, core::Float32),
+                Wrap(RjT_Ri_Cnormal_ps, {n, 3}, core::Float32),
+                Wrap(cgrid_idx_ps, {n, 8}, core::Int32),
+                Wrap(cgrid_idx_qs, {n, 8}, core::Int32),
+                Wrap(cgrid_ratio_qs, {n, 8}, core::Float32),
+                Wrap(cgrid_ratio_ps, {n, 8}, core::Float32), i, j, n_frags,
+                threshold);
+    });
+}
+
+// The same, one call per pair into a zeroed system of n_vars unknowns with
+// the node labels the caller gives for that pair (idx_ps / idx_qs {n, 8}):
+// out {n, n_vars * n_vars + n_vars + 1} = AtA, Atb, residual of each pair.
+int ref_fill_in_slac_alignment_pairs(
+        int64_t n_vars, const float* Ti_Cps, const float* Tj_Cqs,
+        const float* Cnormal_ps, const float* Ri_Cnormal_ps,
+        const float* RjT_Ri_Cnormal_ps, const int* cgrid_idx_ps,
+        const int* cgrid_idx_qs, const float* cgrid_ratio_ps,
+        const float* cgrid_ratio_qs, int64_t n, int i, int j, int n_frags,
+        float threshold, float* out) {
+    return Guard([&] {
+        const int64_t stride = n_vars * n_vars + n_vars + 1;
+        for (int64_t w = 0; w < n; ++w) {
+            float* o = out + stride * w;
+            std::memset(o, 0, sizeof(float) * (size_t)stride);
+            Tensor A = Wrap(o, {n_vars, n_vars}, core::Float32);
+            Tensor b = Wrap(o + n_vars * n_vars, {n_vars}, core::Float32);
+            Tensor r = Wrap(o + stride - 1, {1}, core::Float32);
+            pk::FillInSLACAlignmentTermCPU(
+                    A, b, r, Wrap(Ti_Cps + 3 * w, {1, 3}, core::Float32),
+                    Wrap(Tj_Cqs + 3 * w, {1, 3}, core::Float32),
+                    Wrap(Cnormal_ps + 3 * w, {1, 3}, core::Float32),
+                    Wrap(Ri_Cnormal_ps + 3 * w, {1, 3}, core::Float32),
+                    Wrap(RjT_Ri_Cnormal_ps + 3 * w, {1, 3}, core::Float32),
+                    Wrap(cgrid_idx_ps + 8 * w, {1, 8}, core::Int32),
+                    Wrap(cgrid_idx_qs + 8 * w, {1, 8}, core::Int32),
+                    Wrap(cgrid_ratio_qs + 8 * w, {1, 8}, core::Float32),
+                    Wrap(cgrid_ratio_ps + 8 * w, {1, 8}, core::Float32), i, j,
+                    n_frags, threshold);
+        }
+    });
+}
+
+// FillInSLACRegularizerTermCPU, FillInLinearSystemImpl.h:314-524 (its
+// rotation through the reference's float svd3x3): adds into AtA {n_vars,
+// n_vars}, Atb {n_vars}, residual {1}. grid_nbs_mask is Bool {n, 6}.
+int ref_fill_in_slac_regularizer_term(
+        float* AtA, float* Atb, float* residual, int64_t n_vars,
+        const int* grid_idx, const int* grid_nbs_idx,
+        const uint8_t* grid_nbs_mask, const float* positions_init,
+        const float* positions_curr, int64_t n, int64_t n_positions,
+        float weight, int n_frags, int anchor_idx) {
+    return Guard([&] {
+        Tensor A = Wrap(AtA, {n_vars, n_vars}, core::Float32);
+        Tensor b = Wrap(Atb, {n_vars}, core::Float32);
+        Tensor r = Wrap(residual, {1}, core::Float32);
+        pk::FillInSLACRegularizerTermCPU(
+                A, b, r, Wrap(grid_idx, {n}, core::Int32),
+                Wrap(grid_nbs_idx, {n, 6}, core::Int32),
+                Wrap(grid_nbs_mask, {n, 6}, core::Bool),
+                Wrap(positions_init, {n_positions, 3}, core::Float32),
+                Wrap(positions_curr, {n_positions, 3}, core::Float32), weight,
+                n_frags, anchor_idx);
     });
 }
 

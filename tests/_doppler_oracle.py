@@ -80,6 +80,17 @@ def robust_weight(kernel, r):
                      for x in r], dtype=r.dtype)
 
 
+def reference_accepts(method_geometric, method_doppler):
+    """DISPATCH_DUAL_ROBUST_KERNEL_FUNCTION (RobustKernelImpl.h:122-179), the
+    dispatch of ComputePoseDopplerICP{CPU,CUDA}, has branches for L2Loss and
+    TukeyLoss only and takes no shape parameter: any other pair of kernels,
+    GeneralizedLoss included, is "Unsupported method." in the reference. The
+    library (and robust_weight above) weighs each term with the single-kernel
+    dispatch instead, which gives the same bits on the four pairs the
+    reference runs."""
+    return (method_geometric in (L2, TUKEY)) and (method_doppler in (L2, TUKEY))
+
+
 def kernels_at(iteration, p):
     """The kernels and the rejection in force at `iteration` of a scale."""
     default = (L2, 1.0, 1.0)

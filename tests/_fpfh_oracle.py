@@ -110,6 +110,22 @@ def pair_features(p1, n1, p2, n2, dtype):
     return out
 
 
+def pair_angles(p1, n1, p2, n2, dtype):
+    """The two cosines ComputePairFeature's swap test compares (:44-46), over
+    arrays of pairs, in `dtype` (NaN for a coincident pair)."""
+    dt = np.dtype(dtype)
+    p1, n1, p2, n2 = (np.asarray(v, dt) for v in (p1, n1, p2, n2))
+
+    def dot(a, b):
+        return ((a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]).astype(dt) +
+                a[:, 2] * b[:, 2]).astype(dt)
+
+    dp = (p2 - p1).astype(dt)
+    f3 = np.sqrt(dot(dp, dp)).astype(dt)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (dot(n1, dp) / f3).astype(dt), (dot(n2, dp) / f3).astype(dt)
+
+
 def _bins(f):
     def clamp(h):
         return np.clip(h, 0, 10)

@@ -2,14 +2,18 @@
 
 libo3d_ref.so holds the reference's OWN hot-path kernel files
 (VoxelBlockGridCPU.cpp + VoxelBlockGridImpl.h, RegistrationCPU.cpp,
-TransformationConverter.cpp, TransformImpl.h, PointCloudCPU.cpp ...) compiled
+TransformationConverter.cpp, TransformImpl.h, PointCloudCPU.cpp,
+FeatureCPU.cpp + FeatureImpl.h, FillInLinearSystemCPU.cpp +
+FillInLinearSystemImpl.h ...) compiled
 from /root/reference through the stand-in headers in oracle/ref_shim
 (`make -C oracle ref`). It exists only where /root/reference exists (this build
 container) or where a prebuilt copy travelled with the tree (the GPU box).
 `available()` says whether it can be used; tests skip otherwise.
 
-Function names and argument order mirror tests/_oracle.py so the same inputs
-can be run through both.
+Function names and argument order mirror tests/_oracle.py (and, for FPFH,
+Doppler ICP and the SLAC fill-ins, tests/_fpfh_oracle.py,
+tests/_doppler_oracle.py, tests/_slac_oracle.py and
+tests/_slac_nonrigid_oracle.py) so the same inputs can be run through both.
 """
 import ctypes as C
 import os
@@ -589,3 +593,197 @@ def extract_triangle_mesh(indices, nb_indices, nb_masks, block_keys, tsdf,
     m, k = nv.value, nt.value
     assert m <= vcap and k <= tcap
     return pts[:m], nrm[:m], (None if col is None else col[:m]), tri[:k]
+
+
+# ---- FPFH (FeatureCPU.cpp + FeatureImpl.h) ---------------------------------
+
+def fpfh_float_math_is_float():
+    """Whether unqualified acos(float) is the float overload where the
+    reference's ComputePairFeature was compiled (it is the C function of
+    double when FeatureCPU.cpp is a translation unit of its own)."""
+    return bool(lib().ref_fpfh_float_math_is_float())
+
+
+def fpfh_pair_feature(p1, n1, p2, n2, dtype=np.float64):
+    """ComputePairFeature on one pair -> (f0, f1, f2, f3) of `dtype`."""
+    a = [np.ascontiguousarray(v, dtype=dtype) for v in (p1, n1, p2, n2)]
+    out = np.zeros(4, dtype)
+    _check(lib().ref_fpfh_pair_feature(
+        *[_p(v) for v in a], int(np.dtype(dtype) == np.float64), _p(out)),
+        "ComputePairFeature")
+    return tuple(out)
+
+
+def fpfh_from_lists(points, normals, idx, d2, counts=None, splits=None,
+                    list_points=None, mask=None, into=None):
+    """ComputeFPFHFeatureCPU, the arguments of _fpfh_oracle.fpfh_from_lists:
+    padded lists (idx / d2 {R, W} with counts) or CSR lists (idx / d2 1-d with
+    splits). The filtered form takes list_points (the body's
+    map_info_idx_to_point_idx) and mask (bool {n}); the output then has one
+    row per masked point. The body adds into `into` (default zeros)."""
+    points = np.ascontiguousarray(points)
+    dt = points.dtype
+    normals = np.ascontiguousarray(normals, dtype=dt)
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    d2 = np.ascontiguousarray(d2, dtype=dt)
+    n = points.shape[0]
+    if splits is not None:
+        splits = np.ascontiguousarray(splits, dtype=np.int64)
+        rows, width, counts = splits.shape[0] - 1, 0, None
+        assert idx.ndim == 1 and idx.shape[0] == d2.shape[0] == splits[-1]
+    else:
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        rows, width = idx.shape
+        assert d2.shape == idx.shape and counts.shape == (rows,)
+    assert (mask is None) == (list_points is None)
+    if mask is not None:
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        list_points = np.ascontiguousarray(list_points, dtype=np.int64)
+        n_out = int(mask.sum())
+    else:
+        n_out = n
+    out = (np.zeros((n_out, 33), dt) if into is None
+           else np.ascontiguousarray(into, dtype=dt).copy())
+    assert out.shape == (n_out, 33)
+    _check(lib().ref_fpfh_from_neighbors(
+        _p(points), _p(normals), C.c_int64(n), int(dt == np.float64), _p(idx),
+        _p(d2), _p(counts), _p(splits), int(width), C.c_int64(rows), _p(mask),
+        _p(list_points), _p(out), C.c_int64(n_out)), "ComputeFPFHFeatureCPU")
+    return out
+
+
+# ---- Doppler ICP (RegistrationCPU.cpp:335-493) -------------------------------
+
+def doppler_precompute(R, r, w, v):
+    """PreComputeForDopplerICPKernelCPU -> v_s_in_S {3} of the inputs' dtype."""
+    dt = np.asarray(R).dtype
+    a = [np.ascontiguousarray(x, dtype=dt) for x in (R, r, w, v)]
+    out = np.zeros(3, dt)
+    _check(lib().ref_doppler_precompute(*[_p(x) for x in a],
+                                        int(dt == np.float64), _p(out)),
+           "PreComputeForDopplerICPKernelCPU")
+    return out
+
+
+def doppler_dual_dispatch_accepts(method_geometric, method_doppler):
+    """Whether DISPATCH_DUAL_ROBUST_KERNEL_FUNCTION takes this pair."""
+    return bool(lib().ref_doppler_dual_dispatch_accepts(int(method_geometric),
+                                                        int(method_doppler)))
+
+
+def doppler_pair_terms(src, dopplers, directions, tgt, tgt_n, corr, R, r, w, v,
+                       period, reject, threshold, kernel_geometric,
+                       kernel_doppler, lambda_doppler, dual=None):
+    """The arguments of _doppler_oracle.pair_terms -> terms {n, 29} of the
+    point dtype, one row per SOURCE row (a row without a correspondence is
+    29 zeros). dual: weights from the reference's dual dispatch (default where
+    it accepts the pair) or from its single-kernel dispatch per term."""
+    src = np.ascontiguousarray(src)
+    dt = src.dtype
+    dopplers, directions, tgt, tgt_n = (
+        np.ascontiguousarray(a, dtype=dt)
+        for a in (dopplers, directions, tgt, tgt_n))
+    corr = np.ascontiguousarray(corr, dtype=np.int64).reshape(-1)
+    R, r = (np.ascontiguousarray(a, dtype=dt) for a in (R, r))
+    vs = doppler_precompute(R, r, np.asarray(w, dt), np.asarray(v, dt))
+    if dual is None:
+        dual = doppler_dual_dispatch_accepts(kernel_geometric[0],
+                                             kernel_doppler[0])
+    n = src.shape[0]
+    out = np.zeros((n, 29), dt)
+    _check(lib().ref_doppler_pair_terms(
+        _p(src), _p(dopplers), _p(directions), _p(tgt), _p(tgt_n), _p(corr),
+        C.c_int64(n), int(dt == np.float64), _p(R), _p(r), _p(vs),
+        int(bool(reject)), C.c_double(threshold), C.c_double(lambda_doppler),
+        C.c_double(period), int(kernel_geometric[0]),
+        C.c_double(kernel_geometric[1]), C.c_double(kernel_geometric[2]),
+        int(kernel_doppler[0]), C.c_double(kernel_doppler[1]),
+        C.c_double(kernel_doppler[2]), int(bool(dual)), _p(out)),
+        "ComputePoseDopplerICPKernelCPU")
+    return out
+
+
+# ---- SLAC fill-ins (FillInLinearSystemCPU.cpp + FillInLinearSystemImpl.h) ----
+
+def fill_in_rigid_alignment_term(AtA, Atb, residual, p, q, n, i, j, threshold):
+    """FillInRigidAlignmentTermCPU on copies of float32 AtA {V,V}, Atb {V},
+    residual {1} -> (AtA, Atb, residual)."""
+    AtA, Atb, residual = (np.ascontiguousarray(a, dtype=np.float32).copy()
+                          for a in (AtA, Atb, residual))
+    p, q, n = _f32(p), _f32(q), _f32(n)
+    _check(lib().ref_fill_in_rigid_alignment_term(
+        _p(AtA), _p(Atb), _p(residual), C.c_int64(Atb.shape[0]), _p(p), _p(q),
+        _p(n), C.c_int64(p.shape[0]), int(i), int(j), C.c_float(threshold)),
+        "FillInRigidAlignmentTermCPU")
+    return AtA, Atb, residual
+
+
+def fill_in_rigid_alignment_pairs(p, q, n, threshold):
+    """One call per pair, (i, j) = (0, 1), into zeros -> (A {m,12,12},
+    b {m,12}, r2 {m}) float32."""
+    p, q, n = _f32(p), _f32(q), _f32(n)
+    m = p.shape[0]
+    out = np.zeros((m, 157), np.float32)
+    _check(lib().ref_fill_in_rigid_alignment_pairs(
+        _p(p), _p(q), _p(n), C.c_int64(m), C.c_float(threshold), _p(out)),
+        "FillInRigidAlignmentTermCPU per pair")
+    return (out[:, :144].reshape(m, 12, 12).copy(), out[:, 144:156].copy(),
+            out[:, 156].copy())
+
+
+def _seam(arrays):
+    p, q, cn, n, v, ip, iq, rp, rq = arrays
+    f = [_f32(a) for a in (p, q, cn, n, v)]
+    ix = [np.ascontiguousarray(a, dtype=np.int32) for a in (ip, iq)]
+    rt = [_f32(a) for a in (rp, rq)]
+    return f + ix + rt
+
+
+def fill_in_slac_alignment_term(AtA, Atb, residual, arrays, i, j, n_frags,
+                                threshold):
+    """FillInSLACAlignmentTermCPU on copies; arrays as
+    _slac_nonrigid_oracle.pair_jacobians takes them (..., idx_ps, idx_qs,
+    ratio_ps, ratio_qs)."""
+    AtA, Atb, residual = (np.ascontiguousarray(a, dtype=np.float32).copy()
+                          for a in (AtA, Atb, residual))
+    a = _seam(arrays)
+    _check(lib().ref_fill_in_slac_alignment_term(
+        _p(AtA), _p(Atb), _p(residual), C.c_int64(Atb.shape[0]),
+        *[_p(x) for x in a], C.c_int64(a[0].shape[0]), int(i), int(j),
+        int(n_frags), C.c_float(threshold)), "FillInSLACAlignmentTermCPU")
+    return AtA, Atb, residual
+
+
+def fill_in_slac_alignment_pairs(arrays, i, j, n_frags, threshold, n_vars):
+    """One call per pair into a zeroed system of n_vars unknowns -> (A
+    {m,V,V}, b {m,V}, r2 {m}) float32."""
+    a = _seam(arrays)
+    m = a[0].shape[0]
+    stride = n_vars * n_vars + n_vars + 1
+    out = np.zeros((m, stride), np.float32)
+    _check(lib().ref_fill_in_slac_alignment_pairs(
+        C.c_int64(n_vars), *[_p(x) for x in a], C.c_int64(m), int(i), int(j),
+        int(n_frags), C.c_float(threshold), _p(out)),
+        "FillInSLACAlignmentTermCPU per pair")
+    V = n_vars
+    return (out[:, :V * V].reshape(m, V, V), out[:, V * V:V * V + V],
+            out[:, -1])
+
+
+def fill_in_slac_regularizer_term(grid_idx, nbs_idx, nbs_mask, init, curr,
+                                  weight, n_frags, anchor_idx, n):
+    """FillInSLACRegularizerTermCPU into zeros, the arguments of
+    _slac_nonrigid_oracle.regularizer -> dict(AtA, Atb, residual) float32."""
+    grid_idx = np.ascontiguousarray(grid_idx, dtype=np.int32)
+    nbs_idx = np.ascontiguousarray(nbs_idx, dtype=np.int32)
+    nbs_mask = np.ascontiguousarray(np.asarray(nbs_mask) != 0, dtype=np.uint8)
+    init, curr = _f32(init), _f32(curr)
+    AtA = np.zeros((n, n), np.float32)
+    Atb = np.zeros(n, np.float32)
+    res = np.zeros(1, np.float32)
+    _check(lib().ref_fill_in_slac_regularizer_term(
+        _p(AtA), _p(Atb), _p(res), C.c_int64(n), _p(grid_idx), _p(nbs_idx),
+        _p(nbs_mask), _p(init), _p(curr), C.c_int64(grid_idx.shape[0]),
+        C.c_int64(init.shape[0]), C.c_float(weight), int(n_frags),
+        int(anchor_idx)), "FillInSLACRegularizerTermCPU")
+    return dict(AtA=AtA, Atb=Atb, residual=float(res[0]))

@@ -8,6 +8,7 @@ import torch
 
 import _fpfh_oracle as fo
 import _oracle as orc
+from _seam_cases import surface as _surface
 
 pytestmark = pytest.mark.gpu
 
@@ -15,31 +16,6 @@ pytestmark = pytest.mark.gpu
 def _reg():
     from open3d_amd import registration
     return registration
-
-
-def _surface(n, seed, dtype):
-    """A bumpy closed-ish surface (sum of sines on a sphere): distinctive
-    neighbourhoods, analytic outward normals."""
-    rng = np.random.RandomState(seed)
-    v = rng.normal(size=(n, 3))
-    v /= np.linalg.norm(v, axis=1, keepdims=True)
-    th = np.arctan2(v[:, 1], v[:, 0])
-    ph = np.arccos(np.clip(v[:, 2], -1, 1))
-    r = 1.0 + 0.08 * np.sin(5 * th) * np.sin(4 * ph) + 0.05 * np.cos(7 * ph)
-    p = v * r[:, None]
-    # normals by finite differences of the parametrisation
-    e = 1e-6
-
-    def P(t, f):
-        rr = 1.0 + 0.08 * np.sin(5 * t) * np.sin(4 * f) + 0.05 * np.cos(7 * f)
-        return np.stack([np.sin(f) * np.cos(t), np.sin(f) * np.sin(t),
-                         np.cos(f)], 1) * rr[:, None]
-    dt_ = (P(th + e, ph) - P(th - e, ph)) / (2 * e)
-    dp_ = (P(th, ph + e) - P(th, ph - e)) / (2 * e)
-    nrm = np.cross(dp_, dt_)
-    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True) + 1e-300
-    nrm *= np.sign((nrm * p).sum(1))[:, None]
-    return p.astype(dtype), nrm.astype(dtype)
 
 
 def _cuda(a):

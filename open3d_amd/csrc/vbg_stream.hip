@@ -882,7 +882,22 @@ __device__ __forceinline__ unsigned PackU16(float lo, float hi) {
     return r;
 }
 
-// kP = voxel pairs per lane: 1 (2 x-consecutive voxels per lane, 72 registers,
+// Two lanes of a quad, j and j ^ 2, trade one value each: the lower lane's
+// slot 1 for the upper lane's slot 0 (DPP quad_perm [2,3,0,1]; every lane of
+// the wave must be active). With elements (2j, 2j + 1) of a run of 8 in lane j
+// before, the lanes 0, 2, 1, 3 hold elements (0, 4), (1, 5), (2, 6), (3, 7)
+// after: slot 0 the run's lower half, slot 1 the element 4 further on. The
+// trade is its own inverse. upper = the lane's bit 1.
+__device__ __forceinline__ void QuadTrade(float& s0, float& s1, bool upper) {
+    const float r0 = __int_as_float(__builtin_amdgcn_mov_dpp(
+            __float_as_int(s0), 0x4E, 0xF, 0xF, true));
+    const float r1 = __int_as_float(__builtin_amdgcn_mov_dpp(
+            __float_as_int(s1), 0x4E, 0xF, 0xF, true));
+    s0 = upper ? r1 : s0;
+    s1 = upper ? s1 : r0;
+}
+
+// kP = voxel pairs per lane: 1 (2 voxels of an x-row per lane, 72 registers,
 // 7 waves per SIMD; 4 voxels per lane -- kP = 2, ~127 registers -- measured 9 %
 // slower, profiles/r2q, and is no longer instantiated).
 // kRaw: depth and colour come from the frames' raw uint16 / uint8 images
@@ -1121,6 +1136,17 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
         int x0, yi, zi;
         int lin_s = 0;   // / kV
         unsigned lin_v;  // / kV
+        // kP = 1, cube map: the lane's two voxels are x0 and x0 + 4 of the
+        // wave's 8-voxel x-run, not x0 and x0 + 1 -- each of a frame's two
+        // gather instructions then covers a compact 4 x 4 x 4 cube (x-run of
+        // 3 voxel steps per row instead of 6) and the two touch mostly
+        // different lines. The state keeps its layout in memory: a lane loads
+        // and stores the contiguous pair (2j, 2j + 1) of its quad's run as
+        // before (lin_v is that pair's index) and the lanes j and j ^ 2 of a
+        // quad trade one value of each pair in registers (QuadTrade), after
+        // the load and again before the store: lane j then owns the elements
+        // r and r + 4 of the run, r = j's two bits swapped.
+        bool split = false;  // wave-uniform
         if (res_shift - kVShift >= 2 && ipi.cube) {
             // Lane -> voxel by a permutation of q's bits (q = part << 8 |
             // threadIdx.x): the 64 lanes of a wave take a compact
@@ -1153,8 +1179,10 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
             const unsigned qx_lo = tid & 3u;
             const unsigned y_lo = (tid >> 2) & 3u;
             const unsigned z_lo = (tid >> 4) & 3u;
+            split = kP == 1;
             x0 = (xb * res + (int)(qx_hi << (2 + kVShift))) +
-                 (int)(qx_lo << kVShift);
+                 (int)(kP == 1 ? ((qx_lo & 1u) << 1) | (qx_lo >> 1)
+                               : qx_lo << kVShift);
             yi = (yb * res + (int)(y_hi << 2)) + (int)y_lo;
             zi = (zb * res + (int)(rest << 2)) + (int)z_lo;
             lin_s = (int)(((((rest << 2) << rs) | (y_hi << 2)) << nx) |
@@ -1230,6 +1258,19 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
 #pragma unroll
                 for (int i = 0; i < 3; ++i) cf[v][i] = (float)c12.v[3 * v + i];
         }
+        if constexpr (kP == 1) {
+            if (split) {  // the loaded pair -> the lane's own voxels
+                const bool upper =
+                        ((threadIdx.x | (unsigned)opaque) & 2u) != 0u;
+                QuadTrade(ts[0], ts[1], upper);
+                QuadTrade(wf[0], wf[1], upper);
+                if constexpr (kColor) {
+#pragma unroll
+                    for (int i = 0; i < 3; ++i)
+                        QuadTrade(cf[0][i], cf[1][i], upper);
+                }
+            }
+        }
         // Facts of the whole work item, wave-uniform (one ballot each, kept
         // in scalar registers; apply takes ONE scalar branch on them per
         // round instead of paying vector instructions per voxel; kFold forms
@@ -1279,9 +1320,10 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
         // same for the lane's 4 voxels.
         const float ys = fy * vscale, zs = fz * vscale;
         f2 xs[kP];
+        const int dx = split ? 4 : 1;  // the pair's second voxel
 #pragma unroll
         for (int p = 0; p < kP; ++p)
-            xs[p] = f2{(float)(x0 + 2 * p), (float)(x0 + 2 * p + 1)} * vscale;
+            xs[p] = f2{(float)(x0 + 2 * p), (float)(x0 + 2 * p + dx)} * vscale;
         // (kChunk frames at a time: a group of up to kMaxGroup frames is
         // applied chunk after chunk to the same register-resident state; the
         // chunk loop is a real loop, so that the second chunk's gathers are
@@ -1636,6 +1678,26 @@ __device__ __forceinline__ void IntegrateRoleWide(const HashView& hv,
                 issue(c0, r);
                 apply(c0, r);
                 round_drained();
+            }
+        }
+        if constexpr (kP == 1) {
+            if (split) {
+                // the lane's own voxels -> the pair it stores. A lane stores
+                // values of its quad's other lanes: the whole wave stores if
+                // any of its lanes updated (the others write back what they
+                // loaded), and the moves run with every lane active.
+                touched = __builtin_amdgcn_ballot_w64(touched) != 0ull;
+                if (touched) {  // wave-uniform
+                    const bool upper =
+                            ((threadIdx.x | (unsigned)opaque) & 2u) != 0u;
+                    QuadTrade(ts[0], ts[1], upper);
+                    QuadTrade(wf[0], wf[1], upper);
+                    if constexpr (kColor) {
+#pragma unroll
+                        for (int i = 0; i < 3; ++i)
+                            QuadTrade(cf[0][i], cf[1][i], upper);
+                    }
+                }
             }
         }
         if (touched) {

@@ -2735,6 +2735,76 @@ int o3dmi_trianglemesh_get_volume(const void* positions_dev, int64_t v,
                                   int64_t m, int index_dtype,
                                   double* volume_out, o3dmi_stream_t stream);
 
+/* ---- ComputeConvexHull / HiddenPointRemoval ------------------------------------
+ * t::geometry::PointCloud::ComputeConvexHull / HiddenPointRemoval
+ * (t/geometry/PointCloud.cpp:1668, 1608; TriangleMesh::ComputeConvexHull is
+ * the hull of the vertex positions). Upstream copies the cloud to the host,
+ * widens it to float64 and runs Qhull; here a quickhull runs on the device and
+ * the result is a pure function of the input by the rules below
+ * (docs/pointcloud_convex_hull.md). All geometry is float64 on the widened
+ * coordinates, without contraction. Float32 / Float64 positions; the index
+ * dtype, Int32 or Int64, holds for triangles_out_dev and
+ * point_indices_out_dev alike.
+ *   Predicate: point p is outside facet (a, b, c), n = (b - a) x (c - a), iff
+ *     (n.x w.x + n.y w.y) + n.z w.z > eps |n| with w = p - a, eps =
+ *     O3DMI_HULL_EPS_ULPS * 2^-52 * E, E the largest extent of the bounding
+ *     box (o3dmi_pointcloud_min_max_bound). A point that is outside of no
+ *     facet it is tested against is inside for good; Qhull's joggle is not
+ *     reproduced, degenerate inputs are settled by this rule.
+ *   Initial simplex: the points of lowest and highest x, the point farthest
+ *     from their line, the point farthest from the plane of the three; ties go
+ *     to the lowest point index. If the fourth is not outside that plane by
+ *     more than eps on either side, the cloud is flat: O3DMI_ERR_SINGULAR
+ *     (Qhull's QH6154), nothing written. Collinear points and copies of one
+ *     point are flat.
+ *   Output (the one deliberate difference from upstream, whose order is
+ *     Qhull's facet traversal order and is specified nowhere): no trace of the
+ *     insertion order is left. Hull vertices come in ascending input point
+ *     index, point_indices_out_dev names them, positions_out_dev holds bit
+ *     copies of those input rows in the input dtype. Each triangle is wound
+ *     counter-clockwise seen from outside, rotated so that its lowest vertex
+ *     index is first, and the triangles are sorted by (v0, v1, v2). There are
+ *     2 V - 4 of them. Among coincident points only the lowest index can
+ *     become a vertex (the tie rule and the strict >). Points in the plane of
+ *     a facet within eps are not vertices, but an extreme point in a face of
+ *     the cloud may be: it may be picked by the initial simplex.
+ *   Protocol (o3dmi_trianglemesh_clip_plane's): vertex_capacity < 0 only sets
+ *     *n_vertices_out and *n_triangles_out; either capacity below its count
+ *     sets both and is O3DMI_ERR_CAPACITY with nothing written. V <= n and T
+ *     <= 2 n - 4 always suffice.
+ * Refused with O3DMI_ERR_INVALID_ARG before anything is allocated: n < 4
+ * (hidden-point removal: n < 3), n >= 2^31 - 1, a NULL argument, another
+ * dtype; after the finiteness gate: a NaN or Inf coordinate. Outputs are
+ * untouched by every refusal. The call waits once per round of insertions
+ * (the driver's comment has the list) and returns with the stream drained. */
+#define O3DMI_HULL_EPS_ULPS 256
+int o3dmi_pointcloud_convex_hull(
+        const void* points_dev, int64_t n, int dtype, void* positions_out_dev,
+        void* point_indices_out_dev, int64_t vertex_capacity,
+        void* triangles_out_dev, int64_t triangle_capacity, int index_dtype,
+        int64_t* n_vertices_out, int64_t* n_triangles_out,
+        o3dmi_stream_t stream);
+
+/* HiddenPointRemoval (Katz et al.; geometry/PointCloud.cpp:791-850): the
+ * spherical flip in float64 as upstream writes it, v = p - camera, norm =
+ * sqrt((v.x^2 + v.y^2) + v.z^2), f = v + ((2 (radius - norm)) v) / norm; the
+ * origin is added as point n, the hull of the n + 1 points is taken by the
+ * rules above, then the origin vertex and every triangle that names it are
+ * dropped. Vertices are the ORIGINAL rows of the kept points in ascending
+ * index and point_indices_out_dev is that index list; the triangles are
+ * numbered on it. camera_location: host doubles {3}. radius <= 0 or not
+ * finite, a camera location that is not finite, a point whose flip is not
+ * finite (a point at the camera location gives norm = 0; upstream feeds the
+ * NaN to Qhull): O3DMI_ERR_INVALID_ARG. V <= n and T <= 2 n - 4 suffice (the origin, when it
+ * is a vertex, takes at least three triangles with it). */
+int o3dmi_pointcloud_hidden_point_removal(
+        const void* points_dev, int64_t n, int dtype,
+        const double* camera_location, double radius, void* positions_out_dev,
+        void* point_indices_out_dev, int64_t vertex_capacity,
+        void* triangles_out_dev, int64_t triangle_capacity, int index_dtype,
+        int64_t* n_vertices_out, int64_t* n_triangles_out,
+        o3dmi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -717,6 +717,15 @@ PROTOTYPES.update({
         _i32, [_vp, _i64, _i32, _vp, _i64, _i32, C.POINTER(_i32), _vp]),
     "o3dmi_trianglemesh_get_volume": (
         _i32, [_vp, _i64, _i32, _vp, _i64, _i32, _dp, _vp]),
+    # (points, n, dtype, [camera_location, radius,] positions_out,
+    # point_indices_out, vertex_capacity, triangles_out, triangle_capacity,
+    # index_dtype, n_vertices, n_triangles, stream)
+    "o3dmi_pointcloud_convex_hull": (
+        _i32, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _i32,
+               C.POINTER(_i64), C.POINTER(_i64), _vp]),
+    "o3dmi_pointcloud_hidden_point_removal": (
+        _i32, [_vp, _i64, _i32, _dp, _d, _vp, _vp, _i64, _vp, _i64, _i32,
+               C.POINTER(_i64), C.POINTER(_i64), _vp]),
 })
 
 # o3dmi_transport_t (include/o3d_mi355x_host.h): the caller-provided collectives
@@ -760,6 +769,9 @@ INTERNAL_PROTOTYPES = {
     "o3dmi_internal_trianglemesh_self_intersections": (
         _i32, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, C.POINTER(_i64),
                C.POINTER(C.c_uint64), _vp]),
+    # csrc/pointcloud_hull.h: {rounds, sweep rounds, winners, refused} of the
+    # thread's last hull call
+    "o3dmi_internal_pointcloud_hull_stats": (_i32, [C.POINTER(_i64)]),
 }
 
 _lib = None

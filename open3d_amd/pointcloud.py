@@ -1,5 +1,6 @@
 """Mirror of t::geometry::PointCloud's selection, filter, sampling, cropping,
-smoothing, boundary, normal-orientation, segmentation and metrics methods
+smoothing, boundary, normal-orientation, segmentation, metrics, convex-hull
+and hidden-point-removal methods
 (t/geometry/PointCloud.cpp:435-494, 569-854, 986-1050, 1074-1203, 1634-1720,
 1805-1836) on the HIP backend.
 
@@ -607,3 +608,65 @@ def segment_plane(attrs, distance_threshold=0.01, ransac_n=3,
             final_break_iteration=info.final_break_iteration,
             fitness=info.fitness, inlier_rmse=info.inlier_rmse)
     return model, out
+
+
+def _hull_call(p, index_dtype, call, where):
+    """One native call at the bounds V <= n, T <= 2 n - 4, narrowed to the
+    counts -> (positions, point indices, triangles)."""
+    n = p.shape[0]
+    positions = torch.empty((n, 3), dtype=p.dtype, device=p.device)
+    indices = torch.empty(n, dtype=index_dtype, device=p.device)
+    n_tri = max(2 * n - 4, 0)
+    triangles = torch.empty((n_tri, 3), dtype=index_dtype, device=p.device)
+    n_v, n_t = C.c_int64(0), C.c_int64(0)
+    _lib.check(call(_lib.ptr(positions), _lib.ptr(indices), n,
+                    _lib.ptr(triangles), n_tri, TORCH_TO_O3DMI[index_dtype],
+                    C.byref(n_v), C.byref(n_t), stream()), where)
+    return (positions[:n_v.value], indices[:n_v.value],
+            triangles[:n_t.value])
+
+
+def compute_convex_hull(attrs, joggle_inputs=False):
+    """PointCloud::ComputeConvexHull -> the hull as a mesh dict: "positions"
+    (bit copies of the hull's points, in ascending point index), "indices"
+    Int32 {T,3} and the vertex attribute "point_indices" Int32 {V}. The hull
+    is a pure function of the input: triangles are wound counter-clockwise seen
+    from outside, rotated to their lowest vertex and sorted by rows (upstream:
+    Qhull's traversal order). joggle_inputs=True raises ValueError: Qhull's
+    random joggle is not reproduced; degenerate inputs are settled by the eps
+    rule of o3dmi_pointcloud_convex_hull instead. A flat cloud raises
+    O3DMIError (status 5), as Qhull's QH6154 does upstream."""
+    if joggle_inputs:
+        raise ValueError("joggle_inputs is not supported: the hull is "
+                         "deterministic, degenerate inputs go by the eps rule")
+    p = _positions(attrs)
+    call = _lib.lib().o3dmi_pointcloud_convex_hull
+    positions, indices, triangles = _hull_call(
+        p, torch.int32,
+        lambda *out: call(_lib.ptr(p), p.shape[0], TORCH_TO_O3DMI[p.dtype],
+                          *out),
+        "compute_convex_hull")
+    return {"positions": positions, "indices": triangles,
+            "point_indices": indices}
+
+
+def hidden_point_removal(attrs, camera_location, radius):
+    """PointCloud::HiddenPointRemoval (Katz et al.) -> (mesh dict of the
+    visible points with "positions" (the original rows) and "indices" Int64,
+    point indices Int64 {V} ascending). camera_location: 3 numbers or a tensor
+    of shape {3}; radius > 0."""
+    p = _positions(attrs)
+    if isinstance(camera_location, torch.Tensor):
+        camera_location = camera_location.detach().to(
+            "cpu", torch.float64).reshape(-1).tolist()
+    values = [float(e) for e in camera_location]
+    if len(values) != 3:
+        raise ValueError("camera_location must have shape {3}")
+    camera = (C.c_double * 3)(*values)
+    call = _lib.lib().o3dmi_pointcloud_hidden_point_removal
+    positions, indices, triangles = _hull_call(
+        p, torch.int64,
+        lambda *out: call(_lib.ptr(p), p.shape[0], TORCH_TO_O3DMI[p.dtype],
+                          camera, C.c_double(float(radius)), *out),
+        "hidden_point_removal")
+    return {"positions": positions, "indices": triangles}, indices

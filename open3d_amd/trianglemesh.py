@@ -15,7 +15,8 @@ IsWatertight, GetVolume; geometry/TriangleMesh.cpp:1016-1135, 1212-1246,
 1272-1457), of legacy SubdivideMidpoint / SubdivideLoop (geometry/
 TriangleMeshSubdivide.cpp) and of ClipPlane / SlicePlane (t/geometry/
 TriangleMesh.cpp:649-716; upstream: VTK on a host copy, here pinned rules on
-the device) on the HIP backend.
+the device) and of ComputeConvexHull (:644; upstream: Qhull on a host copy) on
+the HIP backend.
 
 A mesh is the dict VoxelBlockGrid.extract_triangle_mesh returns: "positions"
 ({V,3} Float32 or Float64) and "indices" ({M,3} Int32 or Int64) on the device,
@@ -1117,3 +1118,11 @@ def compute_metrics(mesh1, mesh2, metrics, fscore_radius=(0.01,),
     r = len(radii)
     return out, dict(sum=list(raw.sum), max=list(raw.max),
                      counts=[list(counts)[:r], list(counts)[r:2 * r]])
+
+
+def compute_convex_hull(mesh, joggle_inputs=False):
+    """TriangleMesh::ComputeConvexHull: the hull of the vertex positions, as
+    pointcloud.compute_convex_hull returns it (joggle_inputs=True raises
+    ValueError there)."""
+    return _pc.compute_convex_hull({"positions": _positions(mesh)},
+                                   joggle_inputs)

@@ -792,6 +792,113 @@ int o3dmi_ransac_score(const o3dmi_nns_t* nns, const void* source_dev,
                        int64_t* corres_inliers_dev, void* scratch_dev,
                        o3dmi_stream_t stream);
 
+/* ---- Fast Global Registration: the two kernel steps ------------------------
+ * The legacy (Eigen, float64) FastGlobalRegistrationBasedOnCorrespondence /
+ * ...BasedOnFeatureMatching (pipelines/registration/
+ * FastGlobalRegistration.cpp) has no tensor version. All arithmetic below is
+ * float64 on points widened on load, whatever the point dtype (Float32 or
+ * Float64); nothing is contracted to FMA. The contract:
+ *
+ * 1. Normalisation (NormalizePointCloud). Per cloud mean = sum / n, where the
+ *    sum of each coordinate is the TILE SUM TREE: a tile is 256 consecutive
+ *    rows; lane l (0..63) adds rows l, l + 64, l + 128, l + 192 of the tile in
+ *    that order to +0.0 (a row past the end adds +0.0); the 64 lane values are
+ *    added by the butterfly v[l] += v[l ^ o], o = 32, 16, 8, 4, 2, 1; the tile
+ *    sums form the next level's rows, until one row is left (at least one
+ *    level). Upstream adds in a sequential loop: equal to rounding.
+ *    max_scale = the largest sqrt((dx*dx + dy*dy) + dz*dz) of the points minus
+ *    the mean; scale = the larger of the two max_scale. use_absolute_scale:
+ *    scale_global = 1, scale_start = scale; otherwise scale_global = scale,
+ *    scale_start = 1. Both clouds become (p - mean) / scale_global.
+ *    scale_global <= 0 (upstream's LogError) and a non-finite coordinate in
+ *    either cloud are O3DMI_ERR_INVALID_ARG.
+ * 2. Initial matching (feature entry point; InitialMatching). ij[i] = nearest
+ *    row of the second feature set, ji[j] the reverse, both with the distance
+ *    and tie rule of o3dmi_registration_correspondences_from_features; the
+ *    pairs (i, ij[i]) with ji[ij[i]] == i are kept in ascending i. There is no
+ *    fall-back to all pairs.
+ * 3. Tuple test (AdvancedMatching) over the ORIGINAL points. ncorr <= 2 gives
+ *    an empty set. Trial t in [0, 100 * ncorr), counted in int64 (upstream's
+ *    int overflows above 21.4 M correspondences), draws
+ *    r_j = draw(seed, t, j, ncorr), j = 0, 1, 2: the sample function of rule 1
+ *    of "RANSAC on correspondences" above with i = t and n_corres = ncorr
+ *    (upstream draws from its global Mersenne engine). With (a_j, b_j) = pair
+ *    r_j: li0 = |A0 - A1|, li1 = |A1 - A2|, li2 = |A2 - A0| on the first
+ *    cloud, lj0..2 likewise on the second, each sqrt((dx*dx + dy*dy) + dz*dz).
+ *    The trial passes iff li_k * tuple_scale < lj_k && lj_k < li_k /
+ *    tuple_scale for k = 0, 1, 2 (all strict). The passing trials in ascending
+ *    t, the first maximum_tuple_count of them, each give their three pairs in
+ *    draw order: int64 {3 * count, 2}. Trials run in batches in trial order
+ *    (65536, doubling up to 2^22) until the cap is reached; what a batch
+ *    computed past the cap is discarded, so the output is bit exact whatever
+ *    the batching. n_trials = the trial index of the last kept tuple + 1 when
+ *    the cap was reached, else 100 * ncorr: what upstream's loop would have run.
+ * 4. Optimisation (OptimizePairwiseRegistration). Fewer than 10
+ *    correspondences: the identity. par starts at scale_global -- upstream's
+ *    call site hands scale_global to the parameter NAMED scale_start, and that
+ *    is reproduced -- not at scale_start. Per iteration and correspondence
+ *    (p, q), with q = (x, y, z): r = p - q, temp = par / (((r0*r0 + r1*r1) +
+ *    r2*r2) + par), s = temp * temp, the three rows
+ *        J0 = (0, -z, y, -1, 0, 0)   res r0
+ *        J1 = (z, 0, -x, 0, -1, 0)   res r1
+ *        J2 = (-y, x, 0, 0, 0, -1)   res r2
+ *    and the correspondence's terms JTJ_c[a][b] = ((J0[a]*J0[b])*s +
+ *    (J1[a]*J1[b])*s) + (J2[a]*J2[b])*s, JTr_c[a] = ((J0[a]*r0)*s +
+ *    (J1[a]*r1)*s) + (J2[a]*r2)*s. (Upstream adds row by row into the running
+ *    total: equal to rounding.) JTJ and JTr are the sums of the terms in a tree
+ *    that depends on the count alone: tiles of 256 correspondences in index
+ *    order, each added as the tile of rule 1 (lane l: l, l + 64, l + 128,
+ *    l + 192; butterfly), then the tile sums added to +0.0 in tile order.
+ *    JTJ = L L^T by the textbook Cholesky (column j: d = A[j][j] - sum_{k<j}
+ *    L[j][k]^2 with k ascending, L[j][j] = sqrt(d), L[i][j] = (A[i][j] -
+ *    sum_{k<j} L[i][k] L[j][k]) / L[j][j]); JTJ y = JTr by forward and back
+ *    substitution (k ascending), x = -y, which solves upstream's
+ *    -JTJ x = JTr. A pivot d that is not positive and finite, or a non-finite
+ *    x, leaves delta = identity and counts one failed solve (upstream ignores
+ *    the solver's flag). delta = TransformVector6dToMatrix4d(x): with
+ *    (sa, ca) = sincos(x0), (sb, cb) = sincos(x1), (sc, cc) = sincos(x2) the
+ *    rotation Rz Ry Rx =
+ *        cc*cb   (cc*sb)*sa - sc*ca   (cc*sb)*ca + sc*sa
+ *        sc*cb   (sc*sb)*sa + cc*ca   (sc*sb)*ca - cc*sa
+ *        -sb     cb*sa                cb*ca
+ *    and translation x[3..5]. trans = delta * trans; every q becomes
+ *    ((R0*x + R1*y) + R2*z) + t per row. Then, when decrease_mu && itr % 4 == 0
+ *    && par > maximum_correspondence_distance: par /= division_factor.
+ * 5. Result and 6. roles: see o3dmi_registration_fgr_correspondence
+ *    (o3d_mi355x_host.h).
+ *
+ * o3dmi_fgr_tuple_test: rule 3. corres_dev int64 {n_corres, 2} (first-cloud
+ * row, second-cloud row); a trial that draws a pair outside
+ * [0, ns) x [0, nt) never reads it and fails. tuples_dev must hold
+ * {3 * min(maximum_tuple_count, 100 * n_corres), 2}. *n_tuples = kept trials,
+ * *n_trials as above. Waits once per batch (for the batch's count).
+ *
+ * o3dmi_fgr_optimize: rule 4 on two normalised float64 clouds. out_dev
+ * float64 {18}: trans row-major 4x4, the final par, the number of failed
+ * solves. Up to 4096 correspondences ONE workgroup of 512 threads runs every
+ * iteration in one launch (the resident form: p and q in registers, two tiles
+ * per wave; docs/registration_fgr.md says why not 1024); above that, per iteration a partial-sums launch and a one-wave finish
+ * launch (the streamed form), with scratch_dev of
+ * o3dmi_fgr_optimize_scratch_bytes(n_corres) bytes (8-byte aligned; 0 bytes
+ * and NULL for the resident form), the caller's until the queued work has run.
+ * Both forms return the same bits. A pair outside the clouds is never read and
+ * adds zeros. Stream-ordered: queues its launches and returns without
+ * waiting. */
+int o3dmi_fgr_tuple_test(uint64_t seed, const void* source_dev, int64_t ns,
+                         const void* target_dev, int64_t nt, int dtype,
+                         const int64_t* corres_dev, int64_t n_corres,
+                         double tuple_scale, int64_t maximum_tuple_count,
+                         int64_t* tuples_dev, int64_t* n_tuples,
+                         int64_t* n_trials, o3dmi_stream_t stream);
+size_t o3dmi_fgr_optimize_scratch_bytes(int64_t n_corres);
+int o3dmi_fgr_optimize(const double* source_dev, int64_t ns,
+                       const double* target_dev, int64_t nt,
+                       const int64_t* corres_dev, int64_t n_corres, double par,
+                       double division_factor, int decrease_mu,
+                       double maximum_correspondence_distance,
+                       int iteration_number, void* scratch_dev,
+                       double* out_dev, o3dmi_stream_t stream);
+
 /* ---- SegmentPlane: the sample function and the scoring step ---------------
  * (legacy geometry/PointCloudSegmentation.cpp:157-279, run by ONE thread over
  * a stateless sample stream; the whole operator is

@@ -11,6 +11,8 @@
  *   o3dmi_registration_correspondences_from_features (Feature.cpp:23-333)
  *   o3dmi_registration_ransac_correspondence, <- legacy RegistrationRANSACBasedOnCorrespondence /
  *   o3dmi_registration_ransac_feature_matching   ...FeatureMatching (pipelines/registration/Registration.cpp:212-406)
+ *   o3dmi_registration_fgr_correspondence, <- legacy FastGlobalRegistrationBasedOnCorrespondence /
+ *   o3dmi_registration_fgr_feature_matching   ...FeatureMatching (pipelines/registration/FastGlobalRegistration.cpp)
  *   o3dmi_slac_correspondence_set,     <- t::pipelines::slac::RunRigidOptimizerForFragments
  *   o3dmi_slac_rigid_optimize             (t/pipelines/slac/SLACOptimizer.cpp:85-204,265-286,369-414)
  *   o3dmi_slac_optimize,               <- t::pipelines::slac::RunSLACOptimizerForFragments, kernel::FillInSLAC*Term
@@ -508,6 +510,80 @@ int o3dmi_registration_ransac_feature_matching(
         int with_scaling, int ransac_n, const o3dmi_ransac_options_t* options,
         int64_t* correspondences_dev, o3dmi_registration_result_t* result,
         o3dmi_ransac_info_t* info, o3dmi_stream_t stream);
+
+/* FastGlobalRegistrationBasedOnCorrespondence / ...BasedOnFeatureMatching
+ * (legacy pipelines/registration/FastGlobalRegistration.cpp; legacy only, like
+ * RANSAC above). Rules 1-4 are "Fast Global Registration" in o3d_mi355x.h;
+ * the rest:
+ *
+ * 5. Result. With trans of rule 4, the means m_s, m_t and scale_global of rule
+ *    1: G = [R | ((-(R m_t)) + t * scale_global) + m_s]
+ *    (GetTransformationOriginalScale; R m_t summed left to right), and
+ *    T = inverse(G) = [R^T | -(R^T g)], the rigid inverse, equal to rounding
+ *    to Eigen's general inverse. fitness, inlier_rmse and the optional
+ *    correspondences_dev (int64[ns]) are bit for bit what
+ *    o3dmi_registration_evaluate(source, target,
+ *    maximum_correspondence_distance, T) returns.
+ * 6. Roles (feature entry point with tuple_test). When ns < nt the target is
+ *    the query side of rules 2 and 3 (pairs (j, nearest i), the tuple test on
+ *    (target, source)) and the pairs are swapped back afterwards, as upstream;
+ *    the draws therefore index the swapped list. Without tuple_test the source
+ *    is always the query side.
+ *
+ * iteration_number == 0 or fewer than 10 correspondences run rule 5 on the
+ * identity. O3DMI_ERR_INVALID_ARG: maximum_tuple_count <= 0; division_factor,
+ * tuple_scale or maximum_correspondence_distance not finite or <= 0;
+ * iteration_number < 0; a correspondence outside [0, ns) x [0, nt); an empty
+ * cloud; a non-finite coordinate; scale_global <= 0. A refused call writes
+ * nothing. upstream defaults: 1.4, 0, 1, 0.025, 64, 0.95, 1000, 1. */
+typedef struct {
+    double division_factor;
+    int use_absolute_scale;
+    int decrease_mu;
+    double maximum_correspondence_distance;
+    int iteration_number;
+    double tuple_scale;
+    int maximum_tuple_count;
+    int tuple_test;
+    uint64_t seed;
+} o3dmi_fgr_options_t;
+
+/* What the reference only logs. */
+typedef struct {
+    int64_t n_initial;        /* pairs after rule 2 / pairs given            */
+    int64_t n_trials;         /* trials upstream's loop would have run       */
+    int64_t n_tuples;
+    int64_t n_used;           /* correspondences the optimisation saw        */
+    double scale_global;
+    double final_par;
+    int swapped;              /* rule 6                                      */
+    int failed_solves;
+    int form;                 /* 0 none (< 10), 1 resident, 2 streamed       */
+} o3dmi_fgr_info_t;
+
+/* corres_dev int64 {n_corres, 2} (source row, target row). info may be NULL.
+ * The host waits once for the gate (finiteness, range and scales of rule 1 in
+ * one download), once per batch of the tuple test, once for trans and in the
+ * final evaluate; no wait sits inside the iteration loop. */
+int o3dmi_registration_fgr_correspondence(
+        const void* source_dev, int64_t ns, const void* target_dev, int64_t nt,
+        int dtype, const int64_t* corres_dev, int64_t n_corres,
+        const o3dmi_fgr_options_t* options, int64_t* correspondences_dev,
+        o3dmi_registration_result_t* result, o3dmi_fgr_info_t* info,
+        o3dmi_stream_t stream);
+
+/* Features {ns, dim} / {nt, dim} of feature_dtype (Float32 / Float64), row r
+ * belonging to point r; rules 2 and 6, then as above (one more host wait, for
+ * the pair count of rule 2). With tuple_test off the
+ * result equals o3dmi_registration_fgr_correspondence on the pairs of rule 2,
+ * bit for bit. */
+int o3dmi_registration_fgr_feature_matching(
+        const void* source_dev, int64_t ns, const void* target_dev, int64_t nt,
+        int dtype, const void* source_features_dev,
+        const void* target_features_dev, int dim, int feature_dtype,
+        const o3dmi_fgr_options_t* options, int64_t* correspondences_dev,
+        o3dmi_registration_result_t* result, o3dmi_fgr_info_t* info,
+        o3dmi_stream_t stream);
 
 /* GetCorrespondenceSetForPointCloudPair (t/pipelines/slac/SLACOptimizer.cpp:
  * 85-204) for the edge (i, j) of a pose graph: fragment i moved by T_ij is

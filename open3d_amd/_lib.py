@@ -174,6 +174,21 @@ class RansacInfoC(C.Structure):
                 ("num_batches", _i64)]
 
 
+class FgrOptionsC(C.Structure):
+    _fields_ = [("division_factor", _d), ("use_absolute_scale", _i32),
+                ("decrease_mu", _i32),
+                ("maximum_correspondence_distance", _d),
+                ("iteration_number", _i32), ("tuple_scale", _d),
+                ("maximum_tuple_count", _i32), ("tuple_test", _i32),
+                ("seed", C.c_uint64)]
+
+
+class FgrInfoC(C.Structure):
+    _fields_ = [("n_initial", _i64), ("n_trials", _i64), ("n_tuples", _i64),
+                ("n_used", _i64), ("scale_global", _d), ("final_par", _d),
+                ("swapped", _i32), ("failed_solves", _i32), ("form", _i32)]
+
+
 class SegmentPlaneInfoC(C.Structure):
     _fields_ = [("best_iteration", _i64), ("iterations_counted", _i64),
                 ("final_break_iteration", _i64), ("fitness", _d),
@@ -313,6 +328,21 @@ PROTOTYPES.update({
         _i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _i32,
                _i32, _d, _i32, _i32, _i32, C.POINTER(RansacOptionsC), _vp,
                C.POINTER(RegistrationResultC), C.POINTER(RansacInfoC), _vp]),
+    "o3dmi_fgr_tuple_test": (
+        _i32, [C.c_uint64, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _d, _i64,
+               _vp, C.POINTER(_i64), C.POINTER(_i64), _vp]),
+    "o3dmi_fgr_optimize_scratch_bytes": (C.c_size_t, [_i64]),
+    "o3dmi_fgr_optimize": (
+        _i32, [_vp, _i64, _vp, _i64, _vp, _i64, _d, _d, _i32, _d, _i32, _vp,
+               _vp, _vp]),
+    "o3dmi_registration_fgr_correspondence": (
+        _i32, [_vp, _i64, _vp, _i64, _i32, _vp, _i64,
+               C.POINTER(FgrOptionsC), _vp, C.POINTER(RegistrationResultC),
+               C.POINTER(FgrInfoC), _vp]),
+    "o3dmi_registration_fgr_feature_matching": (
+        _i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _i32,
+               C.POINTER(FgrOptionsC), _vp, C.POINTER(RegistrationResultC),
+               C.POINTER(FgrInfoC), _vp]),
     "o3dmi_fill_in_rigid_alignment_term": (
         _i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _f,
                _vp]),
@@ -772,6 +802,22 @@ INTERNAL_PROTOTYPES = {
     # csrc/pointcloud_hull.h: {rounds, sweep rounds, winners, refused} of the
     # thread's last hull call
     "o3dmi_internal_pointcloud_hull_stats": (_i32, [C.POINTER(_i64)]),
+    # csrc/fgr.h: o3dmi_fgr_tuple_test with (first_batch) before the outputs
+    # and (n_batches) after them
+    "o3dmi_internal_fgr_tuple_test": (
+        _i32, [C.c_uint64, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _d, _i64,
+               _i64, _vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64),
+               _vp]),
+    # csrc/fgr.h: o3dmi_fgr_optimize with (form) before scratch and
+    # (form_out) after out
+    "o3dmi_internal_fgr_optimize": (
+        _i32, [_vp, _i64, _vp, _i64, _vp, _i64, _d, _d, _i32, _d, _i32, _i32,
+               _vp, _vp, C.POINTER(_i32), _vp]),
+    "o3dmi_internal_fgr_stream_scratch_bytes": (C.c_size_t, [_i64]),
+    "o3dmi_internal_fgr_resident_capacity": (_i64, []),
+    # csrc/feature.h: (a, na, b, nb, dim, dtype, nn, stream)
+    "o3dmi_internal_feature_nn1": (
+        _i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp]),
 }
 
 _lib = None

@@ -858,3 +858,104 @@ def registration_ransac_based_on_feature_matching(
         C.byref(res), C.byref(info), stream()),
         "registration_ransac_based_on_feature_matching")
     return _ransac_result(res, info, corr[:ns])
+
+
+class FastGlobalRegistrationOption:
+    """FastGlobalRegistration.h: upstream's fields and defaults, plus `seed`
+    (the tuple test draws from a stateless stream keyed by it, where upstream
+    uses its global Mersenne engine)."""
+    def __init__(self, division_factor=1.4, use_absolute_scale=False,
+                 decrease_mu=True, maximum_correspondence_distance=0.025,
+                 iteration_number=64, tuple_scale=0.95,
+                 maximum_tuple_count=1000, tuple_test=True, seed=0):
+        self.division_factor = division_factor
+        self.use_absolute_scale = use_absolute_scale
+        self.decrease_mu = decrease_mu
+        self.maximum_correspondence_distance = maximum_correspondence_distance
+        self.iteration_number = iteration_number
+        self.tuple_scale = tuple_scale
+        self.maximum_tuple_count = maximum_tuple_count
+        self.tuple_test = tuple_test
+        self.seed = seed
+
+
+def _fgr_options(option):
+    option = option or FastGlobalRegistrationOption()
+    opt = _lib.FgrOptionsC()
+    opt.division_factor = float(option.division_factor)
+    opt.use_absolute_scale = int(bool(option.use_absolute_scale))
+    opt.decrease_mu = int(bool(option.decrease_mu))
+    opt.maximum_correspondence_distance = float(
+        option.maximum_correspondence_distance)
+    opt.iteration_number = int(option.iteration_number)
+    opt.tuple_scale = float(option.tuple_scale)
+    opt.maximum_tuple_count = int(option.maximum_tuple_count)
+    opt.tuple_test = int(bool(option.tuple_test))
+    opt.seed = int(option.seed) & 0xFFFFFFFFFFFFFFFF
+    return opt
+
+
+def _fgr_result(res, info, corr):
+    out = RegistrationResult()
+    out.transformation = np.array(res.transformation[:]).reshape(4, 4)
+    out.inlier_rmse = res.inlier_rmse
+    out.fitness = res.fitness
+    out.correspondence_set = corr
+    names = [f for f, _ in _lib.FgrInfoC._fields_]
+    return out, {k: getattr(info, k) for k in names}
+
+
+def registration_fgr_based_on_correspondence(source, target, corres,
+                                             option=None):
+    """Legacy pipelines::registration::
+    FastGlobalRegistrationBasedOnCorrespondence on device tensors: `corres`
+    int64 {K,2} (source row, target row). Rules 1-6 of "Fast Global
+    Registration" in o3d_mi355x.h / o3d_mi355x_host.h. Returns
+    (RegistrationResult, info): info is a dict of o3dmi_fgr_info_t (n_initial,
+    n_trials, n_tuples, n_used, scale_global, final_par, swapped,
+    failed_solves, form)."""
+    source, target = _check_pair(source, target)
+    corres = require_cuda(corres, "corres")
+    if corres.dtype != torch.int64 or corres.dim() != 2 or \
+            corres.shape[1] != 2:
+        raise ValueError("corres must be int64 {K,2}")
+    opt = _fgr_options(option)
+    ns = source.shape[0]
+    corr = torch.full((max(ns, 1),), -1, dtype=torch.int64, device="cuda")
+    res = _lib.RegistrationResultC()
+    info = _lib.FgrInfoC()
+    _lib.check(_lib.lib().o3dmi_registration_fgr_correspondence(
+        _lib.ptr(source), ns, _lib.ptr(target), target.shape[0],
+        TORCH_TO_O3DMI[source.dtype], _lib.ptr(corres), corres.shape[0],
+        C.byref(opt), _lib.ptr(corr), C.byref(res), C.byref(info), stream()),
+        "registration_fgr_based_on_correspondence")
+    return _fgr_result(res, info, corr[:ns])
+
+
+def registration_fgr_based_on_feature_matching(source, target,
+                                               source_features,
+                                               target_features, option=None):
+    """Legacy FastGlobalRegistrationBasedOnFeatureMatching: the cross-checked
+    nearest feature rows (no fall-back to all pairs), the tuple test, then as
+    above. Features {N,D} / {M,D} of one dtype, row r of point r. Returns
+    (RegistrationResult, info)."""
+    source, target = _check_pair(source, target)
+    fs = require_cuda(source_features, "source_features")
+    ft = require_cuda(target_features, "target_features")
+    if fs.dtype != ft.dtype or fs.dim() != 2 or ft.dim() != 2 or \
+            fs.shape[1] != ft.shape[1] or fs.shape[0] != source.shape[0] or \
+            ft.shape[0] != target.shape[0]:
+        raise ValueError("features must be {N,D} / {M,D} of one dtype, one "
+                         "row per point")
+    opt = _fgr_options(option)
+    ns = source.shape[0]
+    corr = torch.full((max(ns, 1),), -1, dtype=torch.int64, device="cuda")
+    res = _lib.RegistrationResultC()
+    info = _lib.FgrInfoC()
+    _lib.check(_lib.lib().o3dmi_registration_fgr_feature_matching(
+        _lib.ptr(source), ns, _lib.ptr(target), target.shape[0],
+        TORCH_TO_O3DMI[source.dtype], _lib.ptr(fs), _lib.ptr(ft),
+        fs.shape[1], TORCH_TO_O3DMI[fs.dtype], C.byref(opt), _lib.ptr(corr),
+        C.byref(res), C.byref(info), stream()),
+        "registration_fgr_based_on_feature_matching")
+    return _fgr_result(res, info, corr[:ns])

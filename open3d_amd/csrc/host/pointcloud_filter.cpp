@@ -3,7 +3,7 @@
 // slac::PreprocessPointClouds' per-fragment step (t/pipelines/slac/
 // SLACOptimizer.cpp:25-64). Arguments are checked before anything is
 // allocated or launched; the kernels are in pointcloud_filter.hip, the
-// searches in nns.hip.
+// radius count in nns.hip.
 #include <cmath>
 
 #include "../pointcloud_filter.h"
@@ -14,7 +14,7 @@ using namespace o3dmi;
 
 namespace {
 
-constexpr int kMaxFilterKnn = 64;  // one wave's list (nns.hip kMaxKnn)
+constexpr int kMaxFilterKnn = 64;  // one wave's list (nns_wave.h kMaxKnn)
 
 int SelectByMaskImpl(int64_t n, const uint8_t* mask_dev, bool invert,
                      const SelectAttrs& attrs, int64_t* m_out, hipStream_t s) {

@@ -2,7 +2,7 @@
 // 1805-1836, t/geometry/kernel/Metrics.cpp) and of the per-point distances of
 // ComputePointCloudDistance (geometry/PointCloud.cpp:133-157). Arguments are
 // checked before anything is allocated or launched; the kernels are in
-// pointcloud_metrics.hip, the index and the second pass in nns.hip.
+// pointcloud_metrics.hip, the index build in nns.hip.
 #include <algorithm>
 #include <vector>
 
@@ -107,7 +107,7 @@ int RunDirection(const void* target_dev, int64_t n, const void* queries_dev,
     O3DMI_HIP_CHECK(hipMemsetAsync(words, 0,
                                    sizeof(MetricsWords) * (size_t)groups, s));
     st = NearestSearchRun(target_dev, n, queries_dev, q, dtype, d2, nullptr,
-                          NearestFirstPassAsync, &out->second_pass, s);
+                          &out->second_pass, s);
     if (st) return st;
     const double* total = nullptr;
     for (int g = 0; g < groups; ++g) {
@@ -179,7 +179,7 @@ int o3dmi_pointcloud_nearest_distance(const void* target_dev, int64_t n,
     if ((st = RequireFinite(queries_dev, q, dtype, w, s))) return st;
     // the squares land in the caller's array; the root is taken in place
     st = NearestSearchRun(target_dev, n, queries_dev, q, dtype, dist_out_dev,
-                          idx_out_dev, NearestFirstPassAsync, nullptr, s);
+                          idx_out_dev, nullptr, s);
     if (st) return st;
     st = MetricsReduceAsync(dist_out_dev, q, dtype, dist_out_dev, nullptr, 0,
                             false, words, nullptr, nullptr, s);

@@ -2,8 +2,7 @@
 // (legacy geometry/PointCloudCluster.cpp:21-97, geometry/PointCloud
 // Segmentation.cpp:157-279; t/geometry/PointCloud.cpp:1634-1666 converts to
 // the legacy cloud and calls them). Arguments are checked before anything is
-// allocated or launched; the kernels are in pointcloud_segment.hip, the two
-// neighbourhood sweeps in nns.hip.
+// allocated or launched; the kernels are in pointcloud_segment.hip.
 #include <cmath>
 #include <vector>
 

@@ -3,8 +3,8 @@
 // (t/geometry/PointCloud.cpp:762-854, 986-1050, 1074-1203; the device
 // drivers they call, t/geometry/kernel/PointCloudImpl.h:1410-1753).
 // Arguments are checked before anything is allocated, launched or written;
-// the kernels are in pointcloud_smooth.hip, the searches and their fused
-// output policies in nns.hip.
+// the kernels, the fused output policies of the searches among them, are in
+// pointcloud_smooth.hip; the index and the plain searches in nns.hip.
 #include <cmath>
 
 #include "../pointcloud_smooth.h"

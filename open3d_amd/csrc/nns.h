@@ -1,7 +1,8 @@
 // Private header shared by nns.hip (index build + searches), icp.hip (the
-// fused search + accumulate kernel) and ransac.hip (batched hypothesis
-// scoring): the bucketed uniform grid of the fixed-radius / KNN index and its
-// lane-per-query k = 1 search.
+// fused search + accumulate kernel), ransac.hip (batched hypothesis scoring)
+// and the host drivers: the bucketed uniform grid of the fixed-radius / KNN
+// index and its lane-per-query k = 1 search. The wave-per-query search that
+// .hip files build their own sinks and output policies on is nns_wave.h.
 //
 // Index design: cell edge = radius * (1 + 1e-3) (KNN: chosen from the measured
 // density). Target points are *reordered* by bucket into 16-byte (32-byte for
@@ -36,7 +37,8 @@ struct o3dmi_nns {
                                      // between launches
 };
 
-// Entry points of nns.hip for the host drivers and the other kernels' host
+// Entry points of nns.hip (o3dmi_internal_nns_knn_avg_distance:
+// pointcloud_filter.hip) for the host drivers and the other kernels' host
 // sides, not in the public header (each is described at its definition).
 extern "C" {
 int o3dmi_nns_set_normals(o3dmi_nns_t* nns, const void* normals_dev,
@@ -141,7 +143,7 @@ inline NnsView<T> MakeView(const o3dmi_nns* nns) {
 __device__ __forceinline__ float SqrtOf(float x) { return sqrtf(x); }
 __device__ __forceinline__ double SqrtOf(double x) { return sqrt(x); }
 
-// One level of the KNN index (nns.hip, "k nearest neighbours without a
+// One level of the KNN index (nns_wave.h, "k nearest neighbours without a
 // radius"): the bucketed grid, its cell edge and the occupied cell box.
 template <typename T>
 struct KnnGrid {
@@ -152,20 +154,6 @@ struct KnnGrid {
 
 // Shells a level is searched for before a query is left to a coarser one.
 constexpr int kKnnShells = 3;
-
-// ---- exact nearest point of every query (NearestSearchRun, nns.hip) ---------
-// What the first pass gets: the finest level of the KNN index as KnnSearchRun
-// builds it for k = 1. With `exhaustive` that level spans the whole cloud and
-// its box is searched in one step (no retry list then); else a query the level
-// cannot finish appends its id to retry_ids and is answered by the second pass.
-struct NearestFirstPass {
-    const o3dmi_nns* finest;
-    long long cmin[3], cmax[3];
-    int first_radius;
-    int exhaustive;
-    int* retry_ids;
-    int* retry_count;
-};
 
 template <typename T>
 inline KnnGrid<T> MakeKnnGrid(const o3dmi_nns* lv, const long long* cmin,
@@ -179,25 +167,6 @@ inline KnnGrid<T> MakeKnnGrid(const o3dmi_nns* lv, const long long* cmin,
     }
     return g;
 }
-
-// Launches the first pass over all q queries: d2_dev {q} in the point dtype
-// and idx_dev {q} (or NULL) get the slots of the queries it finishes.
-using NearestFirstPassFn = int (*)(const NearestFirstPass& fp, int dtype,
-                                   const void* queries_dev, int64_t q,
-                                   void* d2_dev, int32_t* idx_dev,
-                                   hipStream_t s);
-
-// d2_dev[i] = min over the n points of ((dx dx) + dy dy) + dz dz, dx = query -
-// point, in the point dtype; idx_dev[i] (optional) = the lowest original index
-// among the minima. Steps 1, 2 and 4 of KnnSearchRun (bounding box, cell size,
-// second-pass choice) with `first_pass` as step 3 and KnnSearchKernel with
-// knn = 1 over the retry ids as the second pass. Waits for the stream (twice
-// at least) and returns with the device drained; *second_pass_queries (optional) = the length of the retry list.
-// Size limits and their errors are o3dmi_nns_knn_search's.
-int NearestSearchRun(const void* points_dev, int64_t n, const void* queries_dev,
-                     int64_t q, int dtype, void* d2_dev, int32_t* idx_dev,
-                     NearestFirstPassFn first_pass,
-                     int64_t* second_pass_queries, hipStream_t s);
 
 // Nearest neighbour with d2 < r2 (strict), ties -> lowest original index.
 // Returns the position in the sorted array (or -1); idx/d2 by reference.

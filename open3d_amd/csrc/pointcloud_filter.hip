@@ -14,7 +14,7 @@
 //                  not depend on which thread came first
 //   radius         threshold on the counts of the fixed-radius count kernel
 //   statistical    mean and centred sum of the per-point average distances
-//                  (written by the KNN search's AvgDistanceOut policy, nns.hip)
+//                  (written by the KNN search through AvgDistanceOut below)
 //                  as float64 sums in the fixed tree of reduce_sums.h, then the
 //                  threshold and the mask in one launch
 //
@@ -24,6 +24,7 @@
 #include "pointcloud_filter.h"
 
 #include "common.h"
+#include "nns_wave.h"
 #include "reduce_sums.h"
 #include "rep_table.h"
 #include "scan.h"
@@ -130,6 +131,25 @@ struct CountThresholdPred {
 };
 
 // ---- statistical ------------------------------------------------------------------
+// AvgDistanceOut (KnnSearchKernel's output policy): only the mean distance to
+// the neighbours
+// (RemoveStatisticalOutliers: distance2.Sqrt().Mean({1}), t/geometry/
+// PointCloud.cpp:700) -- no {q, knn} array exists on this path. The sum runs
+// over the neighbours in list order (ascending by (d2, index)) in T and is
+// divided by the row width in T, so the value does not depend on how the
+// wave found the list.
+template <typename T>
+struct AvgDistanceOut {
+    T* avg;
+    __device__ __forceinline__ void Write(const WaveTopK<T>& list,
+                                          int64_t i) const {
+        T sum = T(0);
+        for (int j = 0; j < list.nbest; ++j)
+            sum += SqrtOf(__shfl(list.best_d, j));
+        if ((threadIdx.x & 63) == 0) avg[i] = sum / (T)list.knn;
+    }
+};
+
 // kCentred: sum of (avg_i - mean)^2 with mean = sum_in[0] / n, else sum of
 // avg_i. One partial per workgroup; the geometry depends on n alone.
 template <typename T, bool kCentred>
@@ -341,3 +361,22 @@ int StatisticalMaskAsync(const void* avg_dev, int64_t n, int dtype,
 }
 
 }  // namespace o3dmi
+
+// Internal (RemoveStatisticalOutliers): avg_dev[i] = mean over the
+// min(knn, n) nearest points of point i (itself included, at distance 0) of
+// sqrt(d2), in the point dtype; see AvgDistanceOut. Returns with the search
+// queued on the stream (its scratch is released after a wait).
+extern "C" int o3dmi_internal_nns_knn_avg_distance(const void* points_dev,
+                                                   int64_t n, int dtype,
+                                                   int knn, void* avg_dev,
+                                                   o3dmi_stream_t stream) {
+    using namespace o3dmi;
+    O3DMI_REQUIRE(avg_dev != nullptr, "null argument");
+    return KnnSearchRun(
+            points_dev, n, points_dev, n, dtype, knn,
+            [=](auto t) {
+                using T = decltype(t);
+                return AvgDistanceOut<T>{(T*)avg_dev};
+            },
+            (hipStream_t)stream);
+}

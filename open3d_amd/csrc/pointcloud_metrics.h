@@ -16,12 +16,17 @@ namespace o3dmi {
 // Lanes that share a query in the first pass of the nearest-point search.
 constexpr int kNearestGroup = 16;
 
-// The first pass of NearestSearchRun (nns.h): a group of kNearestGroup lanes
-// walks the finest level's growing cubes for a query and either writes its
-// slot of d2_dev / idx_dev or appends the query to the retry list.
-int NearestFirstPassAsync(const NearestFirstPass& fp, int dtype,
-                          const void* queries_dev, int64_t q, void* d2_dev,
-                          int32_t* idx_dev, hipStream_t s);
+// ---- exact nearest point of every query --------------------------------------
+// d2_dev[i] = min over the n points of ((dx dx) + dy dy) + dz dz, dx = query -
+// point, in the point dtype; idx_dev[i] (optional) = the lowest original index
+// among the minima. A KNN search with knn = 1 (KnnSearchRun, nns_wave.h) whose
+// first pass gives a group of kNearestGroup lanes to every query on the finest
+// level. Waits for the stream (twice at least) and returns with the device
+// drained; *second_pass_queries (optional) = the length of the retry list.
+// Size limits and their errors are o3dmi_nns_knn_search's.
+int NearestSearchRun(const void* points_dev, int64_t n, const void* queries_dev,
+                     int64_t q, int dtype, void* d2_dev, int32_t* idx_dev,
+                     int64_t* second_pass_queries, hipStream_t s);
 
 // ---- the reduction ----------------------------------------------------------
 constexpr int kMetricsRun = 512;       // values added in index order per run

@@ -5,11 +5,14 @@
 //
 // 1. NearestGroupKernel: the exact nearest target point of every query on the
 //    finest level of the KNN index (nns.h), a group of kNearestGroup lanes per
-//    query. It is the first pass of NearestSearchRun; what it cannot finish
-//    goes to that function's second pass (KnnSearchKernel, knn = 1).
+//    query. It is the first pass of NearestSearchRun (KnnSearchRun of
+//    nns_wave.h with knn = 1); what it cannot finish goes to the second pass
+//    (KnnSearchKernel with NearestOut).
 // 2. MetricsElementKernel / RunSumKernel: sqrt, the fixed-tree float64 sum,
 //    the maximum and the F-score counts of the {q} distances.
 #include "pointcloud_metrics.h"
+
+#include "nns_wave.h"
 
 namespace o3dmi {
 namespace {
@@ -272,15 +275,27 @@ int LaunchReduce(const void* d2_dev, int64_t q, void* dist_out_dev,
     return O3DMI_OK;
 }
 
-}  // namespace
+// NearestOut: the second pass of NearestSearchRun (knn = 1): the squared
+// distance to the nearest point into slot i and, when asked, its index.
+template <typename T>
+struct NearestOut {
+    T* d2;
+    int* idx;
+    __device__ __forceinline__ void Write(const WaveTopK<T>& list,
+                                          int64_t i) const {
+        if ((threadIdx.x & 63) == 0) {
+            d2[i] = list.best_d;
+            if (idx) idx[i] = list.best_i;
+        }
+    }
+};
 
-int NearestFirstPassAsync(const NearestFirstPass& fp, int dtype,
+// The first pass over all q queries: a group of kNearestGroup lanes walks the
+// finest level's growing cubes for a query and either writes its slot of
+// d2_dev / idx_dev or appends the query to the retry list.
+int NearestFirstPassAsync(const KnnFirstPass& fp, int dtype,
                           const void* queries_dev, int64_t q, void* d2_dev,
                           int32_t* idx_dev, hipStream_t s) {
-    O3DMI_REQUIRE(fp.finest && queries_dev && d2_dev && q > 0,
-                  "null argument");
-    O3DMI_REQUIRE(fp.exhaustive || (fp.retry_ids && fp.retry_count),
-                  "nearest search: no retry list");
     const dim3 grid(GridFor(q, kNearestBlock / kNearestGroup, kCUs * 16)),
             block(kNearestBlock);
     if (dtype == O3DMI_F64)
@@ -297,6 +312,27 @@ int NearestFirstPassAsync(const NearestFirstPass& fp, int dtype,
                            (float*)d2_dev, idx_dev);
     O3DMI_HIP_CHECK(hipGetLastError());
     return O3DMI_OK;
+}
+
+}  // namespace
+
+int NearestSearchRun(const void* points_dev, int64_t n, const void* queries_dev,
+                     int64_t q, int dtype, void* d2_dev, int32_t* idx_dev,
+                     int64_t* second_pass_queries, hipStream_t s) {
+    // (a missing d2_dev is reported where a missing queries_dev is: after the
+    // size checks, as "null argument")
+    return KnnSearchRun(
+            points_dev, n, d2_dev ? queries_dev : nullptr, q, dtype, 1,
+            [=](auto t) {
+                using T = decltype(t);
+                return NearestOut<T>{(T*)d2_dev, idx_dev};
+            },
+            s,
+            [=](const KnnFirstPass& fp) {
+                return NearestFirstPassAsync(fp, dtype, queries_dev, q, d2_dev,
+                                             idx_dev, s);
+            },
+            second_pass_queries);
 }
 
 size_t MetricsSumScratchDoubles(int64_t q) {

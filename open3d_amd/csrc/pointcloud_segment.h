@@ -1,6 +1,5 @@
 // Private seam between the kernels of PointCloud::ClusterDBSCAN /
-// SegmentPlane (pointcloud_segment.hip, and the two wave-per-point sweeps
-// beside the other output policies in nns.hip) and their C ABI in
+// SegmentPlane (pointcloud_segment.hip) and their C ABI in
 // host/pointcloud_segment.cpp. Every launcher is stream-ordered and waits for
 // nothing.
 #pragma once
@@ -23,7 +22,7 @@ namespace o3dmi {
 // parent[i] = i.
 int DbscanIdentityAsync(int32_t* parent_dev, int64_t n, hipStream_t s);
 
-// Union sweep (nns.hip): one wave per core point i; every core candidate
+// Union sweep: one wave per core point i; every core candidate
 // j < i within the index radius is united with i in parent[] (int32,
 // identity beforehand). Afterwards the root of every tree is the lowest core
 // index of its component.
@@ -37,7 +36,7 @@ int DbscanFlattenAsync(const int32_t* parent_dev, const int32_t* counts_dev,
                        int need, int64_t n, int32_t* root_dev,
                        int32_t* is_root_dev, hipStream_t s);
 
-// Label sweep (nns.hip). cluster_dev: exclusive prefix sum of is_root. Core
+// Label sweep. cluster_dev: exclusive prefix sum of is_root. Core
 // points take cluster[root]; the others the smallest cluster[root[j]] over
 // their core neighbours j, or -1. *noise_dev (zeroed by the caller) += the
 // number of -1 labels, one atomic per wave.

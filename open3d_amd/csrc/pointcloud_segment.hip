@@ -4,7 +4,8 @@
 // cloud and calls them, t/geometry/PointCloud.cpp:1634-1666).
 //
 //   DBSCAN        identity, flatten (pointer jump + root flags); the two
-//                 neighbourhood sweeps are wave-per-point kernels in nns.hip
+//                 neighbourhood sweeps are wave-per-point kernels: sinks of
+//                 the 27-cell gather of nns_wave.h
 //   hypotheses    one thread per RANSAC iteration: sample -> plane, float64
 //   score         lane = hypothesis, plane in registers; the workgroup walks a
 //                 tile of points that is the same for every lane, so the point
@@ -21,6 +22,8 @@
 #include "pointcloud_segment.h"
 
 #include "common.h"
+#include "nns_wave.h"
+#include "union_find.h"
 
 namespace o3dmi {
 namespace {
@@ -49,6 +52,91 @@ __global__ void FlattenKernel(const int* __restrict__ parent,
         root[i] = r;
         is_root[i] = r == (int)i ? 1 : 0;
     }
+}
+
+// ---- ClusterDBSCAN's two sweeps ------------------------------------------------
+// Point j is a core point when counts[j] >= need. parent[] is a forest over
+// the core points in which a non-root's parent is always a SMALLER index:
+// a root is only ever hooked under a smaller root, with one CAS, so the root
+// of a finished tree is the lowest core index of its component whatever order
+// the waves ran in.
+
+// DbscanFind / DbscanUnite: union_find.h.
+
+struct UnionSink {
+    const int* counts;
+    int* parent;
+    int need;
+    int self;
+    template <typename T>
+    __device__ __forceinline__ void Push(T, int j, T, T, T) {
+        if (j != kNoIndex && j < self && counts[j] >= need)
+            DbscanUnite(parent, self, j);
+    }
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kCoopBlock)
+DbscanUnionKernel(NnsView<T> nv, const T* __restrict__ q, int64_t nq,
+                  const int* __restrict__ counts, int need,
+                  int* __restrict__ parent) {
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t i = wave; i < nq; i += n_waves) {
+        if (counts[i] < need) continue;  // wave-uniform
+        const T qq[3] = {q[3 * i + 0], q[3 * i + 1], q[3 * i + 2]};
+        long long cx, cy, cz;
+        CellOf(qq, nv.inv_cell, cx, cy, cz);
+        UnionSink sink = {counts, parent, need, (int)i};
+        O3DMI_GATHER_BALL(T, nv, qq, cx, cy, cz, sink);
+    }
+}
+
+// The smallest cluster label among a lane's core candidates.
+struct MinLabelSink {
+    const int* counts;
+    const int* root;
+    const int64_t* cluster;
+    int need;
+    int best;
+    template <typename T>
+    __device__ __forceinline__ void Push(T, int j, T, T, T) {
+        if (j != kNoIndex && counts[j] >= need) {
+            const int l = (int)cluster[root[j]];
+            best = l < best ? l : best;
+        }
+    }
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kCoopBlock)
+DbscanLabelKernel(NnsView<T> nv, const T* __restrict__ q, int64_t nq,
+                  const int* __restrict__ counts, int need,
+                  const int* __restrict__ root,
+                  const int64_t* __restrict__ cluster, int* __restrict__ labels,
+                  unsigned long long* __restrict__ noise) {
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    unsigned long long n_noise = 0;  // wave-uniform
+    for (int64_t i = wave; i < nq; i += n_waves) {
+        const int c = counts[i];
+        int label = -1;
+        if (c >= need) {
+            label = (int)cluster[root[i]];
+        } else if (c > 1) {  // somebody besides the point itself is in range
+            const T qq[3] = {q[3 * i + 0], q[3 * i + 1], q[3 * i + 2]};
+            long long cx, cy, cz;
+            CellOf(qq, nv.inv_cell, cx, cy, cz);
+            MinLabelSink sink = {counts, root, cluster, need, kNoIndex};
+            O3DMI_GATHER_BALL(T, nv, qq, cx, cy, cz, sink);
+            int m = sink.best;
+            O3DMI_WAVE_MIN(m);
+            label = m == kNoIndex ? -1 : m;
+        }
+        if ((threadIdx.x & 63) == 0) labels[i] = label;
+        n_noise += label < 0 ? 1 : 0;
+    }
+    if ((threadIdx.x & 63) == 0 && n_noise) atomicAdd(noise, n_noise);
 }
 
 // ---- SegmentPlane ------------------------------------------------------------
@@ -262,6 +350,49 @@ int DbscanIdentityAsync(int32_t* parent_dev, int64_t n, hipStream_t s) {
     if (n <= 0) return O3DMI_OK;
     hipLaunchKernelGGL(IdentityKernel, dim3(GridFor(n, kBlock)), dim3(kBlock),
                        0, s, parent_dev, n);
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
+int DbscanUnionSweep(const o3dmi_nns* nns, const void* points_dev, int64_t n,
+                     const int32_t* counts_dev, int need, int32_t* parent_dev,
+                     hipStream_t s) {
+    O3DMI_REQUIRE(nns && points_dev && counts_dev && parent_dev,
+                  "null argument");
+    if (n <= 0) return O3DMI_OK;
+    const dim3 grid(GridFor(n, kCoopBlock / 64, kCUs * 16)), block(kCoopBlock);
+    if (nns->dtype == O3DMI_F64)
+        hipLaunchKernelGGL(DbscanUnionKernel<double>, grid, block, 0, s,
+                           MakeView<double>(nns), (const double*)points_dev, n,
+                           counts_dev, need, parent_dev);
+    else
+        hipLaunchKernelGGL(DbscanUnionKernel<float>, grid, block, 0, s,
+                           MakeView<float>(nns), (const float*)points_dev, n,
+                           counts_dev, need, parent_dev);
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
+int DbscanLabelSweep(const o3dmi_nns* nns, const void* points_dev, int64_t n,
+                     const int32_t* counts_dev, int need,
+                     const int32_t* root_dev, const int64_t* cluster_dev,
+                     int32_t* labels_dev, unsigned long long* noise_dev,
+                     hipStream_t s) {
+    O3DMI_REQUIRE(nns && points_dev && counts_dev && root_dev && cluster_dev &&
+                          labels_dev && noise_dev,
+                  "null argument");
+    if (n <= 0) return O3DMI_OK;
+    const dim3 grid(GridFor(n, kCoopBlock / 64, kCUs * 16)), block(kCoopBlock);
+    if (nns->dtype == O3DMI_F64)
+        hipLaunchKernelGGL(DbscanLabelKernel<double>, grid, block, 0, s,
+                           MakeView<double>(nns), (const double*)points_dev, n,
+                           counts_dev, need, root_dev, cluster_dev, labels_dev,
+                           noise_dev);
+    else
+        hipLaunchKernelGGL(DbscanLabelKernel<float>, grid, block, 0, s,
+                           MakeView<float>(nns), (const float*)points_dev, n,
+                           counts_dev, need, root_dev, cluster_dev, labels_dev,
+                           noise_dev);
     O3DMI_HIP_CHECK(hipGetLastError());
     return O3DMI_OK;
 }

@@ -1,7 +1,6 @@
 // Private seam between the kernels of PointCloud::Smooth* / ComputeBoundary
-// Points / the normal orientation calls (pointcloud_smooth.hip, and the fused
-// output policies of the searches in nns.hip) and their C ABI in
-// host/pointcloud_smooth.cpp. Every launcher is stream-ordered and waits for
+// Points / the normal orientation calls (pointcloud_smooth.hip) and their C
+// ABI in host/pointcloud_smooth.cpp. Every launcher is stream-ordered and waits for
 // nothing unless it says so.
 #pragma once
 
@@ -38,7 +37,7 @@ struct SmoothOp {
     double p0, p1;
 };
 
-// Fused forms (nns.hip): the search's output policy applies `op` to the list
+// Fused forms: the search's output policy applies `op` to the list
 // while it is in the wave's lanes; no {n, k} table exists.
 // KNN over the cloud itself, k = min(n, knn) <= 64. Waits for the stream
 // (the search's index is released on return).

@@ -8,11 +8,12 @@
 // The per-point bodies are in pointcloud_smooth_device.h. This file holds the
 // kernels that read a neighbour TABLE (fixed neighbourhoods, the radius-only
 // MLS mode, the boundary seam) -- one wave per point, 64 entries of the row
-// per step -- and the three elementwise kernels. The fused forms, where the
-// search's own wave reduces the list it has just found, are output policies
-// of the searches in nns.hip.
+// per step -- the three elementwise kernels, and the fused forms, where the
+// search's own wave reduces the list it has just found: output policies of
+// the searches of nns_wave.h.
 
 #include "common.h"
+#include "nns_wave.h"
 #include "pointcloud_rows.h"
 #include "pointcloud_smooth_device.h"
 
@@ -49,6 +50,51 @@ struct BoundaryBody {
         BoundaryPoint(a, i, nb);
     }
 };
+
+// LaplacianOut / MlsOut / BilateralOut / BoundaryOut: the smoothed point (or
+// the boundary flag) of query i straight from its list -- SmoothLaplacian /
+// SmoothTaubin with re-searched neighbourhoods, SmoothMLS, SmoothBilateral,
+// ComputeBoundaryPoints. Query i is point i of the cloud the index holds.
+template <typename T>
+struct LaplacianOut {
+    LaplacianArgs<T> a;
+    __device__ __forceinline__ void Write(const WaveTopK<T>& list,
+                                          int64_t i) const {
+        LaplacianPoint(a, i, ListOf(list));
+    }
+};
+template <typename T>
+struct MlsOut {
+    MlsArgs<T> a;
+    __device__ __forceinline__ void Write(const WaveTopK<T>& list,
+                                          int64_t i) const {
+        MlsPoint(a, i, ListOf(list));
+    }
+};
+template <typename T>
+struct BilateralOut {
+    BilateralArgs<T> a;
+    __device__ __forceinline__ void Write(const WaveTopK<T>& list,
+                                          int64_t i) const {
+        BilateralPoint(a, i, ListOf(list));
+    }
+};
+template <typename T>
+struct BoundaryOut {
+    BoundaryArgs<T> a;
+    __device__ __forceinline__ void Write(const WaveTopK<T>& list,
+                                          int64_t i) const {
+        BoundaryPoint(a, i, ListOf(list));
+    }
+};
+
+// The float64 smoothing policies keep three coordinates and a weight per lane
+// on top of the search's state: they get the register budget of three waves,
+// so that nothing of theirs goes to scratch memory.
+template <> struct KnnWaves<LaplacianOut<double>> {
+    static constexpr int value = 3;
+};
+template <> struct KnnWaves<MlsOut<double>> { static constexpr int value = 3; };
 
 template <typename T, typename Body>
 __global__ void __launch_bounds__(kTableBlock)
@@ -205,7 +251,70 @@ int LaunchTable(const SmoothOp& op, const int32_t* indices, const void* dist2,
     return O3DMI_OK;
 }
 
+template <typename T>
+int LaunchHybridSmoothOp(const o3dmi_nns* nns, const void* points_dev,
+                         int64_t n, int max_knn, const SmoothOp& op,
+                         hipStream_t s) {
+    const dim3 grid(GridFor(n, kCoopBlock / 64, kCUs * 16)), block(kCoopBlock);
+    const size_t lds = CoopLdsBytesPerWave<T>() * (kCoopBlock / 64);
+    const NnsView<T> nv = MakeView<T>(nns);
+    const T* q = (const T*)points_dev;
+    switch (op.kind) {
+        case kSmoothMls:
+            hipLaunchKernelGGL((HybridSearchKernel<T, MlsOut<T>>), grid, block,
+                               lds, s, nv, q, n, max_knn,
+                               MlsOut<T>{MakeMlsArgs<T>(op)});
+            break;
+        case kSmoothBilateral:
+            hipLaunchKernelGGL((HybridSearchKernel<T, BilateralOut<T>>), grid,
+                               block, lds, s, nv, q, n, max_knn,
+                               BilateralOut<T>{MakeBilateralArgs<T>(op)});
+            break;
+        case kSmoothBoundary:
+            hipLaunchKernelGGL((HybridSearchKernel<T, BoundaryOut<T>>), grid,
+                               block, lds, s, nv, q, n, max_knn,
+                               BoundaryOut<T>{MakeBoundaryArgs<T>(op)});
+            break;
+        default:
+            SetLastError("hybrid search: unknown output policy");
+            return O3DMI_ERR_INTERNAL;
+    }
+    O3DMI_HIP_CHECK(hipGetLastError());
+    return O3DMI_OK;
+}
+
 }  // namespace
+
+int HybridSearchSmoothOp(const o3dmi_nns* nns, const void* points_dev,
+                         int64_t n, int max_knn, const SmoothOp& op,
+                         hipStream_t s) {
+    O3DMI_REQUIRE(nns != nullptr && points_dev != nullptr, "null argument");
+    O3DMI_REQUIRE(max_knn >= 1 && max_knn <= kMaxKnn,
+                  "max_knn must be in [1, 64]");
+    if (n <= 0) return O3DMI_OK;
+    return nns->dtype == O3DMI_F64
+                   ? LaunchHybridSmoothOp<double>(nns, points_dev, n, max_knn,
+                                                  op, s)
+                   : LaunchHybridSmoothOp<float>(nns, points_dev, n, max_knn,
+                                                 op, s);
+}
+
+int KnnSearchSmoothOp(const void* points_dev, int64_t n, int dtype, int knn,
+                      const SmoothOp& op, hipStream_t s) {
+    O3DMI_REQUIRE(op.kind == kSmoothLaplacian || op.kind == kSmoothMls,
+                  "knn search: unknown output policy");
+    const auto run = [&](auto make_out) {
+        return KnnSearchRun(points_dev, n, points_dev, n, dtype, knn, make_out,
+                            s);
+    };
+    if (op.kind == kSmoothLaplacian)
+        return run([&](auto t) {
+            return LaplacianOut<decltype(t)>{MakeLaplacianArgs<decltype(t)>(op)};
+        });
+    return run([&](auto t) {
+        return MlsOut<decltype(t)>{MakeMlsArgs<decltype(t)>(op)};
+    });
+}
 
 int TableSmoothOpAsync(const SmoothOp& op, const int32_t* indices_dev,
                        const void* dist2_dev, const int32_t* counts_dev,

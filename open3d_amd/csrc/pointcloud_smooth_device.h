@@ -1,7 +1,7 @@
 // Per-point bodies of the PointCloud smoothing and boundary kernels: one wave
-// serves one point. They are shared by the output policies of the searches in
-// nns.hip (the neighbour list is in the wave's lanes when the search ends) and
-// by the table-reading kernels in pointcloud_smooth.hip, so both forms run the
+// serves one point. They are shared by the output policies of the searches
+// (the neighbour list is in the wave's lanes when the search ends) and by the
+// table-reading kernels, both in pointcloud_smooth.hip, so both forms run the
 // same statements in the same order.
 //
 // A neighbour source `Nb` hands lane l entry base + l of the point's list:

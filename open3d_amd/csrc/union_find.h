@@ -1,6 +1,6 @@
 // Lock-free union-find over an int parent[] array, shared by ClusterDBSCAN's
-// union sweep (nns.hip) and ClusterConnectedTriangles (trianglemesh.hip).
-// parent[] is a forest in which a non-root's parent is always a SMALLER
+// union sweep (pointcloud_segment.hip) and ClusterConnectedTriangles
+// (trianglemesh.hip). parent[] is a forest in which a non-root's parent is always a SMALLER
 // index: a root is only ever hooked under a smaller root, with one CAS, so
 // trees cannot form cycles and the root of a finished tree is the lowest
 // index of its component whatever order the waves ran in.

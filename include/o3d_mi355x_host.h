@@ -2881,6 +2881,99 @@ int o3dmi_pointcloud_hidden_point_removal(
         int64_t* n_vertices_out, int64_t* n_triangles_out,
         o3dmi_stream_t stream);
 
+/* ---- GetOrientedBoundingBox / GetOrientedBoundingEllipsoid ---------------------
+ * OrientedBoundingBox::CreateFromPoints(points, robust = false, method) and
+ * OrientedBoundingEllipsoid::CreateFromPoints, which is what t::geometry::
+ * PointCloud / TriangleMesh / LineSet::GetOrientedBoundingBox() and
+ * GetOrientedBoundingEllipsoid() return (docs/bounding_volumes.md). Both start
+ * from the convex hull of o3dmi_pointcloud_convex_hull, taken on the device:
+ * its vertices in ascending point index widened to float64, its triangles
+ * sorted by (v0, v1, v2). All arithmetic is float64 without contraction; every
+ * sum is taken in a fixed tree (runs of O3DMI_BV_TREE_RUN consecutive values in
+ * index order, the run sums likewise, level by level), so a result is a pure
+ * function of the input.
+ *   O3DMI_OBB_MINIMAL_APPROX (t/geometry/kernel/MinimumOBB.cpp:1250-1319): for
+ *     hull triangle (a, b, c): u = b - a, v = c - a, w = u x v, v = w x u,
+ *     each divided by its norm sqrt((x^2 + y^2) + z^2); the coordinates of hull
+ *     vertex x are ((d.x r.x + d.y r.y) + d.z r.z), d = x - a, r = u, v, w
+ *     (upstream multiplies by the inverse of [u v w]; the transpose is the same
+ *     matrix up to rounding). The candidate's volume is (e0 e1) e2, e = hi - lo.
+ *     Candidate -1 is the axis-aligned box of the hull vertices with the
+ *     identity rotation, its volume taken in float64 (upstream: from the
+ *     vertices cast to Float32). The smallest volume wins under a strict <, so
+ *     ties go to the lowest candidate index; a NaN volume (a degenerate frame)
+ *     never wins. The box: rotation = [u v w] as columns, extent = hi - lo,
+ *     center = a + R ((lo + hi) / 2).
+ *   O3DMI_OBB_PCA (geometry/BoundingVolume.cpp:232-286): the frame of
+ *     o3dmi_bounding_box_frame_from_moments on the nine sums of the hull
+ *     vertices, the minima and maxima of R^T (x - mean) by the same three-term
+ *     dot, center = R ((lo + hi) / 2) + mean, extent = hi - lo.
+ *   O3DMI_OBB_MINIMAL_JYLANKI: O3DMI_ERR_UNSUPPORTED. Upstream's traversal
+ *     order comes from std::random_device and its searches are seeded from one
+ *     edge to the next, so its result is not a function of the input.
+ *   The ellipsoid (t/geometry/kernel/MinimumOBE.cpp:108-272): Khachiyan's
+ *     iteration on the hull vertices with weights p_i = 1 / V: Lambda = sum p_i
+ *     [a_i; 1] [a_i; 1]^T (terms (p x) y), its inverse by an L D L^T in fixed
+ *     order without pivoting (a pivot <= 0 or not finite: O3DMI_ERR_SINGULAR),
+ *     M_i = [a_i; 1]^T Lambda^-1 [a_i; 1] (the diagonal only), its maximum with
+ *     ties to the lowest index, step = (max - 4) / (4 (max - 1)), p <- (1 -
+ *     step) p, p_j += step. The loop ends when sqrt(sum (new p_i - p_i)^2) <=
+ *     O3DMI_OBE_TOLERANCE or after O3DMI_OBE_MAX_ITERATIONS iterations; the rest
+ *     is o3dmi_bounding_ellipsoid_from_moments on the weighted sums.
+ * Outputs are HOST doubles; the rotation is row-major, as
+ * o3dmi_pointcloud_obb_mask takes it. Float32 / Float64 positions. A flat cloud
+ * is the hull's O3DMI_ERR_SINGULAR. Refused with O3DMI_ERR_INVALID_ARG before
+ * anything is allocated: n < 4, n >= 2^31 - 1, a NULL pointer other than
+ * iterations_out, another dtype, another method value; after the finiteness
+ * gate: a NaN or Inf coordinate. Every refusal leaves the outputs untouched.
+ * Waits: the hull's (once per round of insertions), then one for the box
+ * (MINIMAL_APPROX), two for PCA (the sums, the extents), one for the resident
+ * form of the ellipsoid's loop or one per batch of iterations for the streamed
+ * form (O3DMI_OBE_FORM, docs/switches.md; the resident form above its capacity
+ * is O3DMI_ERR_CAPACITY). Both return with the stream drained. */
+#define O3DMI_OBB_MINIMAL_APPROX 0 /* upstream's default */
+#define O3DMI_OBB_PCA 1
+#define O3DMI_OBB_MINIMAL_JYLANKI 2 /* O3DMI_ERR_UNSUPPORTED */
+#define O3DMI_BV_TREE_RUN 8
+#define O3DMI_OBE_TOLERANCE 1e-6
+#define O3DMI_OBE_MAX_ITERATIONS 1000
+int o3dmi_pointcloud_oriented_bounding_box(
+        const void* points_dev, int64_t n, int dtype, int method,
+        double center_out[3], double rotation_out[9], double extent_out[3],
+        o3dmi_stream_t stream);
+int o3dmi_pointcloud_oriented_bounding_ellipsoid(
+        const void* points_dev, int64_t n, int dtype, double center_out[3],
+        double rotation_out[9], double radii_out[3],
+        int32_t* iterations_out /* may be NULL */, o3dmi_stream_t stream);
+
+/* The host half of O3DMI_OBB_PCA, the companion of o3dmi_metrics_from_sums: no
+ * device, no stream. sums = the sums of {x, y, z, xx, xy, xz, yy, yz, zz} over
+ * n points. They are divided by n, mean = the first three, the covariance is
+ * E[xy] - E[x] E[y] entry by entry (utility/Eigen.cpp:391-403), diagonalised
+ * by this library's cyclic Jacobi iteration; the eigenvalues are put in
+ * descending order by upstream's three swaps, columns 0 and 1 are normalised
+ * and column 2 = column 0 x column 1. Eigen leaves the signs of columns 0 and
+ * 1 undefined; here each is negated if its component of largest magnitude is
+ * negative (lowest index on ties). rotation_out is row-major.
+ * O3DMI_ERR_INVALID_ARG: n < 1, a NULL pointer, a sum that is not finite. */
+int o3dmi_bounding_box_frame_from_moments(int64_t n, const double sums[9],
+                                          double mean_out[3],
+                                          double rotation_out[9]);
+
+/* The host half of the ellipsoid: sums = {sum p x, p y, p z, p xx, p xy, p xz,
+ * p yy, p yz, p zz} with weights that add up to 1. center = the first three,
+ * Q = (PN - c c^T)^-1 / 3 by an L D L^T in fixed order (a pivot <= 0 or not
+ * finite: O3DMI_ERR_SINGULAR), diagonalised by the same Jacobi iteration with
+ * the eigenvalues in ascending order, radii = 1 / sqrt(eigenvalue), then
+ * upstream's MapOBEToClosestIdentity: of the 48 signed permutations of the
+ * columns the one with the largest trace, strict >, the first best wins.
+ * rotation_out is row-major. O3DMI_ERR_INVALID_ARG: a NULL pointer, a sum that
+ * is not finite. */
+int o3dmi_bounding_ellipsoid_from_moments(const double sums[9],
+                                          double center_out[3],
+                                          double rotation_out[9],
+                                          double radii_out[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -756,6 +756,16 @@ PROTOTYPES.update({
     "o3dmi_pointcloud_hidden_point_removal": (
         _i32, [_vp, _i64, _i32, _dp, _d, _vp, _vp, _i64, _vp, _i64, _i32,
                C.POINTER(_i64), C.POINTER(_i64), _vp]),
+    # (points, n, dtype, method, center[3], rotation[9], extent[3], stream)
+    "o3dmi_pointcloud_oriented_bounding_box": (
+        _i32, [_vp, _i64, _i32, _i32, _dp, _dp, _dp, _vp]),
+    # (points, n, dtype, center[3], rotation[9], radii[3], iterations, stream)
+    "o3dmi_pointcloud_oriented_bounding_ellipsoid": (
+        _i32, [_vp, _i64, _i32, _dp, _dp, _dp, C.POINTER(_i32), _vp]),
+    # host-only: (n, sums[9], mean[3], rotation[9])
+    "o3dmi_bounding_box_frame_from_moments": (_i32, [_i64, _dp, _dp, _dp]),
+    # host-only: (sums[9], center[3], rotation[9], radii[3])
+    "o3dmi_bounding_ellipsoid_from_moments": (_i32, [_dp, _dp, _dp, _dp]),
 })
 
 # o3dmi_transport_t (include/o3d_mi355x_host.h): the caller-provided collectives
@@ -802,6 +812,16 @@ INTERNAL_PROTOTYPES = {
     # csrc/pointcloud_hull.h: {rounds, sweep rounds, winners, refused} of the
     # thread's last hull call
     "o3dmi_internal_pointcloud_hull_stats": (_i32, [C.POINTER(_i64)]),
+    # csrc/bounding_volume.h: the resident form's capacity; {hull vertices,
+    # hull triangles, iterations, form, winner} and 16 values of the thread's
+    # last bounding-volume call
+    # o3dmi_pointcloud_oriented_bounding_box's MINIMAL_APPROX with (split) in
+    # the place of (method)
+    "o3dmi_internal_pointcloud_obb_minimal_approx": (
+        _i32, [_vp, _i64, _i32, _i32, _dp, _dp, _dp, _vp]),
+    "o3dmi_internal_obe_resident_capacity": (_i64, []),
+    "o3dmi_internal_bounding_volume_stats": (
+        _i32, [C.POINTER(_i64), _dp]),
     # csrc/fgr.h: o3dmi_fgr_tuple_test with (first_batch) before the outputs
     # and (n_batches) after them
     "o3dmi_internal_fgr_tuple_test": (

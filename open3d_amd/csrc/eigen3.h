@@ -1,6 +1,8 @@
 // Symmetric 3x3 eigen-decomposition shared by the normal estimation
-// (normals.hip), the colour-gradient solve and the MLS projection
-// (pointcloud_smooth_device.h): device code only.
+// (normals.hip), the colour-gradient solve, the MLS projection
+// (pointcloud_smooth_device.h) and, on the host, the frames of the bounding
+// volumes (host/bounding_volume.cpp): the Jacobi iteration compiles for both
+// sides, everything below it is device code only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,10 +11,10 @@
 
 namespace o3dmi {
 
-__device__ __forceinline__ float Sqrt(float v) { return sqrtf(v); }
-__device__ __forceinline__ double Sqrt(double v) { return sqrt(v); }
-__device__ __forceinline__ float Abs(float v) { return fabsf(v); }
-__device__ __forceinline__ double Abs(double v) { return fabs(v); }
+__host__ __device__ __forceinline__ float Sqrt(float v) { return sqrtf(v); }
+__host__ __device__ __forceinline__ double Sqrt(double v) { return sqrt(v); }
+__host__ __device__ __forceinline__ float Abs(float v) { return fabsf(v); }
+__host__ __device__ __forceinline__ double Abs(double v) { return fabs(v); }
 
 // ---- symmetric 3x3 eigen-decomposition (this code base's own) -----------------
 // Cyclic Jacobi: rotations in the (0,1), (0,2), (1,2) planes, each chosen to
@@ -24,7 +26,8 @@ __device__ __forceinline__ double Abs(double v) { return fabs(v); }
 // the colour-gradient solve (pseudo-inverse).
 constexpr int kJacobiSweeps = 8;
 template <typename T>
-__device__ __forceinline__ void JacobiEigenSym3(T (&a)[3][3], T (&V)[3][3]) {
+__host__ __device__ __forceinline__ void JacobiEigenSym3(T (&a)[3][3],
+                                                         T (&V)[3][3]) {
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll

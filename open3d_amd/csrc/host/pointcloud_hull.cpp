@@ -17,6 +17,7 @@
 #include "../scan.h"
 #include "../sort.h"
 #include "o3d_mi355x_host.h"
+#include "pointcloud_hull_host.h"
 #include "trianglemesh_call.h"
 
 using namespace o3dmi;
@@ -24,17 +25,6 @@ using namespace o3dmi;
 namespace {
 
 thread_local int64_t g_stats[4] = {0, 0, 0, 0};
-
-struct HullOutput {
-    void* positions;
-    void* point_indices;
-    int64_t vertex_capacity;
-    void* triangles;
-    int64_t triangle_capacity;
-    int index_dtype;
-    int64_t* n_vertices;
-    int64_t* n_triangles;
-};
 
 // What both calls refuse from their arguments alone.
 int CheckCall(const void* points_dev, int64_t n, int64_t min_n, int dtype,
@@ -75,11 +65,13 @@ int AllocN(PoolScratch& pool, P** out, size_t count) {
     return pool.Alloc(out, sizeof(P) * std::max<size_t>(count, 1));
 }
 
+}  // namespace
+
 // The hull of the m widened points P_dev, written by the count / capacity
-// protocol. points_dev: the rows the output positions are copied from.
-// drop_last: point m - 1 and every triangle that names it are left out.
-int HullOf(PoolScratch& pool, const double* P_dev, int64_t m, bool drop_last,
-           const void* points_dev, int dtype, const HullOutput& o) {
+// protocol (pointcloud_hull_host.h).
+int o3dmi::HullOf(PoolScratch& pool, const double* P_dev, int64_t m,
+                  bool drop_last, const void* points_dev, int dtype,
+                  const HullOutput& o) {
     hipStream_t s = pool.s;
     const int64_t fc = 2 * m;
     HullDev d = {};
@@ -201,6 +193,8 @@ int HullOf(PoolScratch& pool, const double* P_dev, int64_t m, bool drop_last,
     O3DMI_HIP_CHECK(hipStreamSynchronize(s));
     return O3DMI_OK;
 }
+
+namespace {
 
 int ConvexHull(const void* points_dev, int64_t n, int dtype,
                const HullOutput& o, hipStream_t s) {

@@ -1,6 +1,6 @@
 """Mirror of t::geometry::PointCloud's selection, filter, sampling, cropping,
-smoothing, boundary, normal-orientation, segmentation, metrics, convex-hull
-and hidden-point-removal methods
+smoothing, boundary, normal-orientation, segmentation, metrics, convex-hull,
+hidden-point-removal and oriented bounding box / ellipsoid methods
 (t/geometry/PointCloud.cpp:435-494, 569-854, 986-1050, 1074-1203, 1634-1720,
 1805-1836) on the HIP backend.
 
@@ -670,3 +670,80 @@ def hidden_point_removal(attrs, camera_location, radius):
                           camera, C.c_double(float(radius)), *out),
         "hidden_point_removal")
     return {"positions": positions, "indices": triangles}, indices
+
+
+# ---- oriented bounding volumes -----------------------------------------------------
+OBB_METHODS = {"minimal_approx": 0, "pca": 1, "minimal_jylanki": 2}
+
+
+def _refuse_robust(robust):
+    if robust:
+        raise ValueError("robust is not supported: Qhull's joggle is not "
+                         "reproduced, degenerate inputs go by the hull's eps "
+                         "rule")
+
+
+def _volume_tensors(p, center, rotation, third):
+    return (torch.tensor(list(center), dtype=torch.float64).to(p.device,
+                                                               p.dtype),
+            torch.tensor(list(rotation), dtype=torch.float64).reshape(
+                3, 3).to(p.device, p.dtype),
+            torch.tensor(list(third), dtype=torch.float64).to(p.device,
+                                                              p.dtype))
+
+
+def get_oriented_bounding_box(attrs, robust=False, method="minimal_approx"):
+    """PointCloud::GetOrientedBoundingBox -> dict(center {3}, rotation {3,3},
+    extent {3}) as tensors of the cloud's dtype on its device. method:
+    "minimal_approx" (upstream's default) or "pca"; "minimal_jylanki" raises
+    O3DMIError (status 7): upstream's result depends on a random traversal
+    order. robust=True raises ValueError, a flat cloud O3DMIError (status 5).
+    The box goes straight into crop(center=, rotation=, extent=)."""
+    _refuse_robust(robust)
+    if method not in OBB_METHODS:
+        raise ValueError("method must be one of %s" % sorted(OBB_METHODS))
+    p = _positions(attrs)
+    center, rotation, extent = ((C.c_double * 3)(), (C.c_double * 9)(),
+                                (C.c_double * 3)())
+    _lib.check(_lib.lib().o3dmi_pointcloud_oriented_bounding_box(
+        _lib.ptr(p), p.shape[0], TORCH_TO_O3DMI[p.dtype], OBB_METHODS[method],
+        center, rotation, extent, stream()), "get_oriented_bounding_box")
+    c, r, e = _volume_tensors(p, center, rotation, extent)
+    return {"center": c, "rotation": r, "extent": e}
+
+
+def get_oriented_bounding_ellipsoid(attrs, robust=False):
+    """PointCloud::GetOrientedBoundingEllipsoid (Khachiyan's algorithm on the
+    hull's vertices) -> dict(center {3}, rotation {3,3}, radii {3}) as tensors
+    of the cloud's dtype on its device."""
+    _refuse_robust(robust)
+    p = _positions(attrs)
+    center, rotation, radii = ((C.c_double * 3)(), (C.c_double * 9)(),
+                               (C.c_double * 3)())
+    _lib.check(_lib.lib().o3dmi_pointcloud_oriented_bounding_ellipsoid(
+        _lib.ptr(p), p.shape[0], TORCH_TO_O3DMI[p.dtype], center, rotation,
+        radii, None, stream()), "get_oriented_bounding_ellipsoid")
+    c, r, e = _volume_tensors(p, center, rotation, radii)
+    return {"center": c, "rotation": r, "radii": e}
+
+
+_BOX_CORNERS = ((-1, -1, -1), (1, -1, -1), (-1, 1, -1), (-1, -1, 1),
+                (1, 1, 1), (-1, 1, 1), (1, -1, 1), (1, 1, -1))
+
+
+def box_points(box):
+    """OrientedBoundingBox::GetBoxPoints -> {8,3} in upstream's corner order
+    (geometry/BoundingVolume.cpp:190-204)."""
+    c, r, e = box["center"], box["rotation"], box["extent"]
+    axes = r * (e / 2)[None, :]  # column k = R (extent_k / 2) e_k
+    signs = torch.tensor(_BOX_CORNERS, dtype=c.dtype, device=c.device)
+    return c[None, :] + signs @ axes.T
+
+
+def ellipsoid_points(ellipsoid):
+    """OrientedBoundingEllipsoid::GetEllipsoidPoints -> {6,3}: center +/- each
+    axis scaled by its radius, the x pair first
+    (geometry/BoundingVolume.cpp:98-111)."""
+    c, r, e = ellipsoid["center"], ellipsoid["rotation"], ellipsoid["radii"]
+    axes = (r * e[None, :]).T  # row k = R radii_k e_k
+    return torch.stack([c + s * axes[k] for k in range(3) for s in (1, -1)])

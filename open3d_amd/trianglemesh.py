@@ -15,8 +15,8 @@ IsWatertight, GetVolume; geometry/TriangleMesh.cpp:1016-1135, 1212-1246,
 1272-1457), of legacy SubdivideMidpoint / SubdivideLoop (geometry/
 TriangleMeshSubdivide.cpp) and of ClipPlane / SlicePlane (t/geometry/
 TriangleMesh.cpp:649-716; upstream: VTK on a host copy, here pinned rules on
-the device) and of ComputeConvexHull (:644; upstream: Qhull on a host copy) on
-the HIP backend.
+the device), of ComputeConvexHull (:644; upstream: Qhull on a host copy) and
+of GetOrientedBoundingBox / GetOrientedBoundingEllipsoid on the HIP backend.
 
 A mesh is the dict VoxelBlockGrid.extract_triangle_mesh returns: "positions"
 ({V,3} Float32 or Float64) and "indices" ({M,3} Int32 or Int64) on the device,
@@ -1126,3 +1126,19 @@ def compute_convex_hull(mesh, joggle_inputs=False):
     ValueError there)."""
     return _pc.compute_convex_hull({"positions": _positions(mesh)},
                                    joggle_inputs)
+
+
+def get_oriented_bounding_box(mesh, robust=False, method="minimal_approx"):
+    """TriangleMesh::GetOrientedBoundingBox: the box of the vertex positions,
+    as pointcloud.get_oriented_bounding_box returns it."""
+    _pc._refuse_robust(robust)
+    return _pc.get_oriented_bounding_box({"positions": _positions(mesh)},
+                                         robust, method)
+
+
+def get_oriented_bounding_ellipsoid(mesh, robust=False):
+    """TriangleMesh::GetOrientedBoundingEllipsoid: the ellipsoid of the vertex
+    positions, as pointcloud.get_oriented_bounding_ellipsoid returns it."""
+    _pc._refuse_robust(robust)
+    return _pc.get_oriented_bounding_ellipsoid(
+        {"positions": _positions(mesh)}, robust)
